@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """Benchmark of the sampler hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c4] [--kappa 0.5]
+    python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c4] [--kappa 0.5] [--dump-outputs DIR] [--full]
+
+A plain run measures only the headline: set-up, the untimed pre-heat, W warm-up and K timed cold steps, then
+the result line (metric, value, unit, ms_per_step, ...).  ``--full`` adds every side measurement after the
+headline: the warm-plan step, the forward and backward rooflines, the deferred tile lists, the fwd + bwd
+steps and their hipGraph replays, two streams, kappa = 1.3, the reference's training sizes, BASELINE configs[1],
+unordered points and the CPU baseline (``--no-bwd`` / ``--no-extras`` / ``--no-cpu-baseline`` drop parts of it).
+``--dump-outputs DIR`` writes the outputs of the last timed step (u, grad u, Hessian of u, float32, as
+DIR/<name>.npy) after the timed steps; the inputs are seeded, so two builds can be compared output for output.
 
 One step = one pass of the hot path over one batch of synthetic input, through the reference's
 operator surface: ``GaussianSampler.preprocess(...)`` + one fused launch producing u, grad u and
@@ -18,10 +26,10 @@ scaling; one rank = all 16.8 M points).  The forward needs no collective; the ba
 the parameter gradients as ONE packed [N,6] buffer (RCCL over xGMI): for N > 1 the line also carries
 ``fwd_bwd.value`` = points/s of the whole preprocess + forward + backward + all-reduce step.
 
-Prints ONE JSON line on rank 0 (contract in the task description): metric, value (whole-job
-sample-points/s), roofline of the dominant kernel (HBM-bound designation of BASELINE.json) with the
-VALU-issue figure beside it, roofline_bwd, cpu_baseline (the reference's dense PyTorch algorithm on
-the host cores, bounded sample).
+Prints ONE JSON line on rank 0: metric, value (whole-job sample-points/s), ms_per_step; with ``--full``
+also roofline of the dominant kernel (HBM-bound designation of BASELINE.json) with the VALU-issue
+figure beside it, roofline_bwd, cpu_baseline (the reference's dense PyTorch algorithm on the host
+cores, bounded sample) and the other side records.
 """
 import argparse
 import gc
@@ -43,6 +51,7 @@ VALU_ISSUE_PEAK = 256 * 4 * 2.4e9 / 2       # wave-instructions/s: 1 024 SIMDs, 
 ROW_VALU_INSTR = 21.25     # VALU instructions per evaluated row (16 points x 1 Gaussian x 4 rows of a wave), ISA count
 ROW_NS_UBENCH = 30.8       # ns per wave-row per SIMD of the bare row loop at 8 waves/SIMD (tools/ubench/rowloop.hip)
 PREHEAT_S = 0.25
+DUMP_BYTES = 60 << 20      # --dump-outputs: at most this many bytes of arrays (a seeded sample of the points beyond it)
 
 
 def parse():
@@ -50,6 +59,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every side measurement (warm plan, rooflines, fwd + bwd, extras, "
+                         "CPU baseline); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32; rank 0's points; "
+                         f"a fixed seeded sample of the points if they exceed {DUMP_BYTES >> 20} MiB)")
     ap.add_argument("--workload", default="c3", choices=["c3", "c2", "c4"])
     ap.add_argument("--kappa", type=float, default=0.5)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -58,7 +73,27 @@ def parse():
     ap.add_argument("--backend", default="auto", choices=["auto", "dense", "binned"])
     # rehearsal of the N > 1 path on a box with fewer GPUs than ranks (gloo, ranks share devices)
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"])
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+def dump_outputs(outs, dirname):
+    """Write the timed step's outputs (u [M,1], grad u [M,2,1], Hessian [M,2,2,1]) as float32 .npy files.  Beyond
+    DUMP_BYTES, the same fixed seeded sample of points (rows) is taken from every array."""
+    import numpy as np
+    names = ("u", "grad_u", "hessian_u")
+    M = outs[0].shape[0]
+    per_point = sum(o[0].numel() for o in outs) * 4
+    idx = None
+    if M * per_point > DUMP_BYTES:
+        gen = torch.Generator().manual_seed(0)
+        idx = torch.randperm(M, generator=gen)[: DUMP_BYTES // per_point].sort().values.to(outs[0].device)
+    os.makedirs(dirname, exist_ok=True)
+    for name, o in zip(names, outs):
+        o = o if idx is None else o.index_select(0, idx)
+        np.save(os.path.join(dirname, name + ".npy"), o.detach().float().cpu().numpy())
 
 
 def measured_traffic(workload, kappa, binned, which="forward"):
@@ -334,8 +369,9 @@ def main():
 
     host_issue = [0.0]
 
-    def timed_steps(step, warmup, steps):
-        """W untimed + exactly K timed steps between barrier + synchronize pairs; max over the ranks."""
+    def timed_steps(step, warmup, steps, last=None):
+        """W untimed + exactly K timed steps between barrier + synchronize pairs; max over the ranks.  ``last``
+        (a list): receives what the last timed step returned."""
         for _ in range(warmup):
             step()
         barrier()
@@ -345,8 +381,12 @@ def main():
         gc_was_on = gc.isenabled()
         gc.disable()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             step()
+        out = step()
+        if last is not None:
+            last.append(out)
+        del out
         host_issue[0] = (time.perf_counter() - t0) / max(steps, 1)      # this rank's host: the loop before the device has drained
         barrier()
         dt = max_over_ranks(time.perf_counter() - t0)
@@ -381,17 +421,24 @@ def main():
             torch.cuda.synchronize(dev)
         preheat_ms = (time.perf_counter() - t0) * 1e3
         # ---------------- the headline: K cold steps ----------------
-        dt = timed_steps(step, a.warmup, a.steps)
+        last = []
+        dt = timed_steps(step, a.warmup, a.steps, last)
         host_cold = host_issue[0]
         ms_per_step = dt / a.steps * 1e3
         value = M * world / (dt / a.steps)
+        if a.dump_outputs and rank == 0:
+            dump_outputs(last[0], a.dump_outputs)
+        del last
         # ---------------- the same with the samples half of the plan reused ----------------
-        sampler_w, step_w = forward_only(t, pts_d, True)
-        settle(step_w)
-        dtw = timed_steps(step_w, a.warmup, a.steps)
-        warm = {"value": M * world / (dtw / a.steps), "ms_per_step": dtw / a.steps * 1e3,
-                "what": "the same K steps with preprocess() handed the same unmodified samples tensor every time: the "
-                        "sorted sample structure is reused, the Gaussians are re-binned and the tile lists rebuilt"}
+        if a.full:
+            sampler_w, step_w = forward_only(t, pts_d, True)
+            settle(step_w)
+            dtw = timed_steps(step_w, a.warmup, a.steps)
+            warm = {"value": M * world / (dtw / a.steps), "ms_per_step": dtw / a.steps * 1e3,
+                    "what": "the same K steps with preprocess() handed the same unmodified samples tensor every time: the "
+                            "sorted sample structure is reused, the Gaussians are re-binned and the tile lists rebuilt"}
+    binned = sampler._plan is not None
+    extras = a.full and not a.no_extras
 
     # ---------------- dominant kernel: HIP events on the launch stream ----------------
     def kernel_ms(fn, n):
@@ -466,18 +513,19 @@ def main():
                             "but the row loop's instructions at the 2-cycle issue peak (read it beside `frac`)"}
         return r
 
-    roofline = roofline_of(sampler, a.kappa, t, pts_d)
-    if sampler._plan is not None:
-        roofline["kernel_ms_how"] = ("mean over the timed kind of step (cold) of HIP events around the step's forward launch on its stream, "
-                                     "slowest quarter dropped (bench.py, kernel_in_step_ms)")
-    binned = sampler._plan is not None
+    roofline = None
+    if a.full:
+        roofline = roofline_of(sampler, a.kappa, t, pts_d)
+        if sampler._plan is not None:
+            roofline["kernel_ms_how"] = ("mean over the timed kind of step (cold) of HIP events around the step's forward launch on its stream, "
+                                         "slowest quarter dropped (bench.py, kernel_in_step_ms)")
 
     # ---------------- A/B: the tile lists deferred into the first forward's launch (round 4, an option) ----------------
     # GaussianSampler(defer_lists=True): preprocess() stops in front of the tile lists (PIGS_BUILD_DEFER_LISTS) and the
     # step's sample() builds them in the SAME launch as its evaluation (plan_lists_forward_kernel<1,7>).  Measured, not
     # the default: the cold step with it, and HIP events around that one launch.
     deferred = None
-    if binned and not a.no_extras:
+    if binned and extras:
         try:
             with torch.no_grad():
                 smp_d = GaussianSampler(False, fuse="all", backend=a.backend, reuse_samples=False, defer_lists=True)
@@ -509,7 +557,7 @@ def main():
 
     # ---------------- fwd + bwd step (second half of BASELINE.json's metric) ----------------
     fwd_bwd = roofline_bwd = None
-    if not a.no_bwd:
+    if a.full and not a.no_bwd:
         req = {k: t[k].clone().requires_grad_(True) for k in ("means", "values", "conics")}
         from pigs_amd.distributed import replicated
         gouts = None
@@ -585,7 +633,7 @@ def main():
                         "kernel": ("tile_backward_kernel<1,7> + plan_unpermute_kernel<1>" if plan is not None
                                    else "dense_backward_kernel"),
                         "kernel_ms": kb_ms, "algorithmic_bytes": bwd_bytes}
-        if dist is None and not a.no_extras:
+        if dist is None and extras:
             # the same two steps captured ONCE into a hipGraph and replayed (no entry point allocates or
             # synchronises): what a training loop pays when the host is taken out of the way
             try:
@@ -595,12 +643,12 @@ def main():
 
     # ---------------- extras ----------------
     two_streams = kappa13 = small = None
-    if not a.no_extras and dist is None:
+    if extras and dist is None:
         try:
             small = small_record(GaussianSampler, dev)
         except Exception as e:                # report, never lose the bench line over the extra figure
             small = {"error": f"{type(e).__name__}: {e}"[:200]}
-    if not a.no_extras:
+    if extras:
         # the same steps dealt round-robin to two HIP streams (extra figure, not `value`: independent evaluation
         # steps -- frames of a roll-out -- can overlap the latency-bound plan build of one with the forward of another)
         streams = [torch.cuda.Stream(dev) for _ in range(2)]
@@ -648,7 +696,7 @@ def main():
                 kappa13["bwd_frac"] = (48 * N + 36 * M) / (kappa13["bwd_kernel_ms"] * 1e-3) / HBM_PEAK
 
     c2 = None
-    if not a.no_extras and dist is None and a.workload == "c3":
+    if extras and dist is None and a.workload == "c3":
         # BASELINE configs[1]: 8k Gaussians x 256^2 grid, fwd + deriv + bwd on one GPU (same kappa)
         try:
             gs2 = synthetic.lattice_gaussians(128, 64, a.kappa, seed=0)
@@ -678,7 +726,7 @@ def main():
             c2 = {"error": f"{type(e).__name__}: {e}"[:200]}
 
     unordered = None
-    if not a.no_extras and dist is None and a.workload == "c3":
+    if extras and dist is None and a.workload == "c3":
         # the same Gaussians sampled at M uniform random points (torch.rand collocation points, main_pn.py:103): the
         # library switches to the coarse-bin samples build and to staged outputs / gradients once it has seen how a
         # point set of this size arrives -- extra figures, not `value`
@@ -717,13 +765,17 @@ def main():
                    "kappa": a.kappa, "path": "binned" if binned else "dense",
                    "step": "preprocess (cold: nothing reused) + fused forward (orders 0..2)"},
         "host_issue_ms_per_step": host_cold * 1e3,
-        "preheat_ms": preheat_ms, "value_warm_plan": warm["value"], "warm_plan": warm,
-        "roofline": roofline, "roofline_bwd": roofline_bwd, "deferred_lists": deferred, "fwd_bwd": fwd_bwd, "two_streams": two_streams,
-        "kappa_1_3": kappa13, "small": small, "c2": c2, "unordered_points": unordered, "host": sampler.host,
+        "preheat_ms": preheat_ms,
     }
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full:
+        line.update({
+            "value_warm_plan": warm["value"], "warm_plan": warm,
+            "roofline": roofline, "roofline_bwd": roofline_bwd, "deferred_lists": deferred, "fwd_bwd": fwd_bwd, "two_streams": two_streams,
+            "kappa_1_3": kappa13, "small": small, "c2": c2, "unordered_points": unordered})
+    line["host"] = sampler.host
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(gs, pts)
-    elif rank == 0:
+    elif a.full and rank == 0:
         line["cpu_baseline"] = None
     if rank == 0:
         print(json.dumps(line), flush=True)

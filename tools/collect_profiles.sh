@@ -24,7 +24,7 @@ pmc() {     # name, counters, prof_step args...
     echo "== pmc $name done"
 }
 if [ $part = stats ] || [ $part = all ]; then
-    stats bench $root/bench.py
+    stats bench $root/bench.py --full
     stats fwd $root/tools/prof_step.py fwd --steps 200
     stats cold $root/tools/prof_step.py cold --steps 200
     stats warm $root/tools/prof_step.py warm --steps 200
@@ -64,8 +64,8 @@ if [ $part = pmc ] || [ $part = all ]; then
 fi
 if [ $part = lines ] || [ $part = all ]; then
     cd $root
-    python3 bench.py > $out/${tag}_bench_c3_k0.5.json 2> $out/bench.err
-    python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/${tag}_bench_c3_k0.5_20steps.json 2>> $out/bench.err
+    python3 bench.py --full > $out/${tag}_bench_c3_k0.5.json 2> $out/bench.err
+    python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/${tag}_bench_c3_k0.5_20steps.json 2>> $out/bench.err
     python3 tools/size_sweep.py > $out/${tag}_size_sweep.txt 2>&1
     python3 tools/bench_aggregate.py 2>&1 | grep -v amdgpu.ids > $out/${tag}_aggregate.txt
     for c in grid random shuffled clustered clustered:0.5 clustered:0.3; do python3 tools/preprocess_cases.py $c 0.5 2>&1 | grep kappa; done > $out/${tag}_point_orders.txt
@@ -76,7 +76,7 @@ if [ $part = lines ] || [ $part = all ]; then
     (python3 tools/ab_defer.py 0.5 2>&1 | grep defer; python3 tools/ab_defer.py 0.5 90 256 2>&1 | grep defer | sed "s/^/c2 sizes: /"; \
      python3 tools/ab_defer.py 1.3 2>&1 | grep defer | sed "s/^/kappa 1.3: /") > $out/${tag}_ab_defer.txt
     # the N > 1 path of bench.py, two gloo ranks sharing the one GPU: a functional rehearsal, not a scaling number
-    python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2 \
+    python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 5 --warmup 2 \
         --dist-backend gloo --workload c4 --no-cpu-baseline 2> $out/rehearsal.err | grep '^{' > $out/${tag}_rehearsal_c4_gloo_world2.json
     echo "== lines done"
 fi
