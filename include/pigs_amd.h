@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define PIGS_ABI_VERSION 8
+#define PIGS_ABI_VERSION 9
 
 enum pigs_status {
     PIGS_OK = 0,
@@ -174,6 +174,15 @@ int pigs_samples_order_hint(int64_t M);
  * ordered behind the build, like any use of the plan.  PIGS_NO_FUSED_FIRST in the environment keeps the list
  * build in a launch of its own (A/B runs). */
 #define PIGS_BUILD_DEFER_LISTS 32
+/* ABI 9.  PIGS_BUILD_FORWARD_ONLY: the caller will not differentiate through this plan (grad mode off, or none of
+ * means / values / conics requires grad).  The plan then serves pigs_plan_forward and pigs_residual_forward only:
+ * the build sizes everything with ONE cut-off, q_max (q_max_backward is ignored), and writes the group lists the
+ * forward reads but no tile lists and no wide masks.  Forward results are those of a full plan (bit for bit where
+ * the Gaussians keep the caller's order, PlanParams::strips; the same sums in another order otherwise).
+ * The plan records the flag in its own workspace; pigs_plan_backward / pigs_residual_backward on such a plan write
+ * NaN gradients (the entry points cannot tell without waiting for the device, so they launch as ever; no list of
+ * the plan is read out of bounds).  Ignored together with PIGS_BUILD_DEFER_LISTS. */
+#define PIGS_BUILD_FORWARD_ONLY 64
 int pigs_plan_build(void* workspace, size_t workspace_bytes, void* samples_ws, size_t samples_ws_bytes,
                     int flags, int64_t N, int64_t M, int c, float q_max, float q_max_backward,
                     const void* means, const void* conics, const void* values, const void* samples, void* stream);

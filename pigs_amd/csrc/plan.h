@@ -191,6 +191,8 @@ struct PlanParams {
     uint32_t points_wanted;         // ... and met this many blocks / tiles of far-apart points, which a build through the
                                     // cells would have left to the per-point walk (TILE_MODE_POINTS needs the grid): the
                                     // library then goes back to the cells
+    uint32_t fwd_only;              // PIGS_BUILD_FORWARD_ONLY: one cut-off, group lists only (no tile lists, no wide masks);
+                                    // a backward on such a plan writes NaN gradients (plan_unpermute_kernel)
 };
 constexpr uint32_t STRIP = 16;                      // Gaussians per strip = a row of 16 lanes of the wave that packs it
 constexpr uint32_t SUPER_STRIPS = 16;               // strips per super-strip

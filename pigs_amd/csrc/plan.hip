@@ -132,6 +132,7 @@ struct BuildArgs {
     // STRIPS (plan.h, PlanParams::strips): the Gaussians keep the caller's order -- gauss_pack_part instead of count,
     // scan and scatter; `parea` is written by builds of either kind (the statistic the library decides from)
     int strips;
+    int fwd_only;         // PIGS_BUILD_FORWARD_ONLY (PlanParams::fwd_only): q_max = q_f = q_b
     float4* pbox;
     float4* sbox;
     float* parea;
@@ -537,6 +538,7 @@ __device__ __forceinline__ void gauss_count_part(const BuildArgs& a, uint32_t bi
         a.params->n_points = 0u;
         a.params->strips = a.strips ? 1u : 0u;
         a.params->points_wanted = 0u;
+        a.params->fwd_only = a.fwd_only ? 1u : 0u;
         if (a.strips) a.params->level_mask = 0u;
 #pragma unroll
         for (int l = 0; l <= PLAN_MAX_LEVELS; ++l) a.params->level_off[l] = a.level_off[l];
@@ -1215,6 +1217,7 @@ __global__ __launch_bounds__(256) void plan_gauss_build_kernel(BuildArgs a) {
         a.params->n_points = 0u;
         a.params->strips = 0u;
         a.params->points_wanted = 0u;
+        a.params->fwd_only = a.fwd_only ? 1u : 0u;
 #pragma unroll
         for (int l = 0; l <= PLAN_MAX_LEVELS; ++l) a.params->level_off[l] = a.level_off[l];
     }
@@ -1344,7 +1347,10 @@ struct ListArgs {
 // shared by four tiles) where the launch fills the chip; TPW = 1 for small point sets (LISTS_SMALL_TILES): the launch's
 // time is the serial life of ONE wave there (21 us at 65 536 points with four tiles per wave, the chip nearly idle), and
 // a wave with a quarter of the work has a shorter life.
-template <int TPW, bool STRIPS = false>
+// FWD_ONLY (PIGS_BUILD_FORWARD_ONLY; pv.q_max == q_f then): the forward reads the group lists alone, so the tile list
+// and its wide masks are not written, one cut-off is tested per group, and a tile whose group lists fit is LIST with a
+// count of zero (no tile list a backward could read; there is no TILE_MODE_GROUPS rebuild either).
+template <int TPW, bool STRIPS = false, bool FWD_ONLY = false>
 __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TPW>& lds, uint32_t tile0, int lane) {
     const PlanView& pv = a.pv;
     const uint32_t ntiles = a.sv.ntiles;
@@ -1467,24 +1473,26 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
                     // a group without a point (the ragged last tile) has an inverted box: never needed
                     const float qmin = ellipse_min_q_rect(e, gb[g].x, gb[g].y, gb[g].z, gb[g].w);
                     if (gb[g].x <= gb[g].z) {
-                        if (!(qmin > pv.q_max)) gm |= 1u << g;
+                        if (!FWD_ONLY && !(qmin > pv.q_max)) gm |= 1u << g;
                         if (!(qmin > a.q_f)) gf |= 1u << g;
                     }
                 }
                 if (s0 + lane >= sel) gm = gf = 0u;
-                const uint64_t km = __ballot(gm != 0u);
-                const uint32_t cnt = (uint32_t)__builtin_popcountll(km);
+                if constexpr (!FWD_ONLY) {
+                    const uint64_t km = __ballot(gm != 0u);
+                    const uint32_t cnt = (uint32_t)__builtin_popcountll(km);
 #if PIGS_BWD_BLOCK
-                (void)tl;
-                if (gm != 0u) lds.bmask[k] |= ((gm << 4) | gf) << (8 * t);      // one lane per survivor k in this pass
+                    (void)tl;
+                    if (gm != 0u) lds.bmask[k] |= ((gm << 4) | gf) << (8 * t);      // one lane per survivor k in this pass
 #else
-                if (n[t] + cnt <= cap) {
-                    if (gm != 0u) tl[n[t] + (uint32_t)lanes_below(km)] = j | (gm << LIST_WIDE_SHIFT) | (gf << LIST_NARROW_SHIFT);
-                } else {
-                    overflow[t] = true;
-                }
+                    if (n[t] + cnt <= cap) {
+                        if (gm != 0u) tl[n[t] + (uint32_t)lanes_below(km)] = j | (gm << LIST_WIDE_SHIFT) | (gf << LIST_NARROW_SHIFT);
+                    } else {
+                        overflow[t] = true;
+                    }
 #endif
-                n[t] += cnt;
+                    n[t] += cnt;
+                }
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const uint64_t mg = __ballot(gf >> g & 1u);
@@ -1550,7 +1558,7 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
     // region share few Gaussians: up to 4 x cap distinct ones) is no reason to give the lists up: the
     // forward reads the group lists only, and the backward walks them as four single-group lists
     // (TILE_MODE_GROUPS) -- which must then hold the WIDE set: they are rebuilt below.
-    const bool two_cuts = pv.q_max > a.q_f;
+    const bool two_cuts = !FWD_ONLY && pv.q_max > a.q_f;
     bool any_rare = false;
     bool rebuild[TPW];
 #if PIGS_BWD_BLOCK
@@ -1568,7 +1576,7 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
     for (int t = 0; t < TPW; ++t) {
         rebuild[t] = false;
         if (tile0 + (uint32_t)t >= ntiles) { overflow[t] = false; continue; }
-        const bool tl_over = overflow[t];
+        const bool tl_over = FWD_ONLY ? goverflow[t] : overflow[t];      // (no tile list: its group lists decide)
         overflow[t] = tl_over && goverflow[t];            // from here on: the tile needs the ranges fallback
         rebuild[t] = tl_over && !goverflow[t] && two_cuts;
         // spread-out points with long lists: the per-point walk is cheaper than the lists (plan.h)
@@ -1722,7 +1730,7 @@ __device__ __forceinline__ void lists_strip_cover(const ListArgs& a) {
     if (threadIdx.x == 0) a.strip_cover[0] = cover_sh[0] + cover_sh[1] + cover_sh[2] + cover_sh[3];
 }
 
-template <int TPW, bool STRIPS>
+template <int TPW, bool STRIPS, bool FWD_ONLY = false>
 __global__ __launch_bounds__(256) void plan_lists_kernel(ListArgs a) {
     __shared__ ListsLds<TPW> lds_all[4];
     const int lane = threadIdx.x & 63;
@@ -1730,7 +1738,7 @@ __global__ __launch_bounds__(256) void plan_lists_kernel(ListArgs a) {
     lists_strip_cover(a);
     const uint32_t tile0 = lists_tile0<TPW>(wave);
     if (tile0 >= a.sv.ntiles) return;
-    build_block_lists<TPW, STRIPS>(a, lds_all[wave], tile0, lane);
+    build_block_lists<TPW, STRIPS, FWD_ONLY>(a, lds_all[wave], tile0, lane);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2771,6 +2779,13 @@ __global__ __launch_bounds__(256) void plan_unpermute_kernel(PlanView pv, float*
 #pragma unroll
         for (int k = 0; k < 3; ++k) v[BL::CON + k] *= val;
     }
+    // PIGS_BUILD_FORWARD_ONLY: the plan has no tile lists for the backward -- NaN, not a gradient with terms missing.  (The
+    // host entry cannot refuse such a plan without reading the flag back, i.e. waiting for the device: measured, a
+    // stream query and that read in every backward entry cost the sampler-only training step 2.5 us.)
+    if (pv.params->fwd_only) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = __builtin_nanf("");
+    }
     g_means[2 * n] = v[BL::MU + 0];
     g_means[2 * n + 1] = v[BL::MU + 1];
 #pragma unroll
@@ -3272,9 +3287,17 @@ static ListArgs make_list_args(const PlanLayout& p, const SamplesLayout& s, void
 // Small point sets (a list launch of fewer tiles than this is one sparse generation of waves): one tile per wave.
 // PIGS_BWD_BLOCK builds keep four (the block lists are per four tiles).
 constexpr uint32_t LISTS_SMALL_TILES = 4096;
-static void launch_lists(uint32_t ntiles, const ListArgs& la, hipStream_t stream, bool strips = false) {
+// fwd_only: PIGS_BUILD_FORWARD_ONLY (build_block_lists<..., FWD_ONLY>)
+static void launch_lists(uint32_t ntiles, const ListArgs& la, hipStream_t stream, bool strips = false, bool fwd_only = false) {
     const bool small = ntiles <= LISTS_SMALL_TILES && !PIGS_BWD_BLOCK && LISTS_TPW != 1;
     const dim3 grid(small ? (ntiles + 3) / 4 : (ntiles + 4 * LISTS_TPW - 1) / (4 * LISTS_TPW));
+    if (fwd_only) {
+        if (small && strips) hipLaunchKernelGGL((plan_lists_kernel<1, true, true>), grid, dim3(256), 0, stream, la);
+        else if (small) hipLaunchKernelGGL((plan_lists_kernel<1, false, true>), grid, dim3(256), 0, stream, la);
+        else if (strips) hipLaunchKernelGGL((plan_lists_kernel<LISTS_TPW, true, true>), grid, dim3(256), 0, stream, la);
+        else hipLaunchKernelGGL((plan_lists_kernel<LISTS_TPW, false, true>), grid, dim3(256), 0, stream, la);
+        return;
+    }
     if (small && strips) hipLaunchKernelGGL((plan_lists_kernel<1, true>), grid, dim3(256), 0, stream, la);
     else if (small) hipLaunchKernelGGL((plan_lists_kernel<1, false>), grid, dim3(256), 0, stream, la);
     else if (strips) hipLaunchKernelGGL((plan_lists_kernel<LISTS_TPW, true>), grid, dim3(256), 0, stream, la);
@@ -3285,7 +3308,8 @@ static void launch_lists(uint32_t ntiles, const ListArgs& la, hipStream_t stream
 // (build_plan) or both in the same four launches, then the tile lists.
 static int run_build(bool do_samples, bool do_plan, bool plan_ws_clean, bool no_lookback, void* sws, size_t sws_bytes, void* ws, size_t ws_bytes, int64_t N,
                      int64_t M, int c, float q_max, float q_max_b, const void* means, const void* conics, const void* values,
-                     const void* samples, hipStream_t stream, bool build_lists = true, int order = 0, bool defer_lists = false) {
+                     const void* samples, hipStream_t stream, bool build_lists = true, int order = 0, bool defer_lists = false,
+                     bool fwd_only = false) {
     if (!samples_supported(M)) return PIGS_ERR_UNSUPPORTED;
     const SamplesLayout s = make_samples_layout(M);
     if (!sws || sws_bytes < s.total_bytes) return PIGS_ERR_WORKSPACE;
@@ -3307,9 +3331,13 @@ static int run_build(bool do_samples, bool do_plan, bool plan_ws_clean, bool no_
         if (!plan_supported(N, M, c)) return PIGS_ERR_UNSUPPORTED;
         if (!(q_max > 0.f)) return PIGS_ERR_INVALID;
         if (!(q_max_b >= q_max)) q_max_b = q_max;      // <= 0 / NaN: one cut-off
+        // a plan for the forward alone is sized with the forward's cut-off throughout (boxes, levels, strips, the walk)
+        fwd_only = fwd_only && build_lists && !defer_lists && !PIGS_BWD_BLOCK;
+        if (fwd_only) q_max_b = q_max;
         p = make_plan_layout(N, M, c);
         if (!ws || ws_bytes < p.total_bytes) return PIGS_ERR_WORKSPACE;
         fill_plan_args(a, p, ws, q_max, q_max_b, means, conics, values);
+        a.fwd_only = fwd_only;
     }
     clear_hip_error();
     const uint32_t gb = do_plan ? (uint32_t)((N + 255) / 256) : 0u;
@@ -3368,7 +3396,7 @@ static int run_build(bool do_samples, bool do_plan, bool plan_ws_clean, bool no_
         }
     }
     if (do_plan && build_lists && !defer_lists)
-        launch_lists(s.ntiles, make_list_args(p, s, ws, sws, q_max, a.q_max), stream, strips);
+        launch_lists(s.ntiles, make_list_args(p, s, ws, sws, q_max, a.q_max), stream, strips, fwd_only);
     const int rc = launch_status();
     if (do_plan) defer_set(ws, build_lists && defer_lists && rc == PIGS_OK, q_max, a.q_max);
     if (do_plan && build_lists && !defer_lists && rc == PIGS_OK) plan_note_points(p, ws, stream);
@@ -3407,7 +3435,8 @@ int plan_build(void* ws, size_t ws_bytes, void* sws, size_t sws_bytes, int flags
                float q_max, float q_max_backward, const void* means, const void* conics, const void* values, const void* samples,
                hipStream_t stream) {
     return run_build((flags & 1) != 0, true, (flags & 2) != 0, (flags & 4) != 0, sws, sws_bytes, ws, ws_bytes, N, M, c, q_max, q_max_backward, means, conics, values,
-                     samples, stream, true, (flags & 8) ? 1 : (flags & 16) ? 2 : 0, (flags & PIGS_BUILD_DEFER_LISTS) != 0);
+                     samples, stream, true, (flags & 8) ? 1 : (flags & 16) ? 2 : 0, (flags & PIGS_BUILD_DEFER_LISTS) != 0,
+                     (flags & PIGS_BUILD_FORWARD_ONLY) != 0);
 }
 
 // the masks the fused first forward is compiled for (the rest: the list launch, then the forward launch)

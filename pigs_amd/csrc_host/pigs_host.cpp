@@ -166,6 +166,8 @@ struct Plan {
     hipStream_t build_stream = nullptr;
     bool other_stream_used = false;      // a launch on another stream read the workspace: stream order no longer covers a reuse
     bool recorded_only = false;          // built inside a hipGraph capture: it has run only if (and when) that graph was replayed
+    bool forward_only = false;           // PIGS_BUILD_FORWARD_ONLY: no backward can follow (group lists under q_max alone)
+    std::shared_ptr<Plan> full;          // forward_only: the full plan a raw backward on this one was given (full_for_backward)
 
     ~Plan() {
         if (pool && !other_stream_used && workspace.defined()) pool->give(key, std::move(workspace));
@@ -186,7 +188,7 @@ struct Plan {
 std::shared_ptr<Plan> build_plan(const at::Tensor& means, const at::Tensor& values, const at::Tensor& conics,
                                  const at::Tensor& samples, float q_max, float q_max_backward,
                                  std::shared_ptr<SamplePlan> sp, const at::Tensor& source,
-                                 const std::shared_ptr<PlanPool>& pool_or_null, bool defer_lists) {
+                                 const std::shared_ptr<PlanPool>& pool_or_null, bool defer_lists, bool forward_only) {
     auto plan = std::make_shared<Plan>();
     plan->N = means.size(0); plan->M = samples.size(0); plan->c = (int)values.size(1); plan->q_max = q_max;
     plan->q_max_backward = q_max_backward > q_max ? q_max_backward : q_max;
@@ -203,6 +205,8 @@ std::shared_ptr<Plan> build_plan(const at::Tensor& means, const at::Tensor& valu
     int flags = sp->built ? 0 : PIGS_BUILD_SAMPLES;
     // the tile lists are built by the plan's first sampling call, a forward in the same launch (pigs_amd.h)
     if (defer_lists) flags |= PIGS_BUILD_DEFER_LISTS;
+    plan->forward_only = forward_only && !defer_lists;
+    if (plan->forward_only) flags |= PIGS_BUILD_FORWARD_ONLY;
     if (pool_or_null) plan->workspace = pool_or_null->take(plan->key);
     if (plan->workspace.defined()) flags |= PIGS_BUILD_PLAN_WS_CLEAN;
     else plan->workspace = at::empty({(int64_t)nbytes}, means.options().dtype(at::kByte));
@@ -327,6 +331,7 @@ struct SampleBackward : public torch::autograd::Node {
             gmask |= 1 << orders[i];
         }
         if (gmask == 0) return {at::Tensor(), at::Tensor(), at::Tensor()};
+        if (debug && plan && plan->forward_only) throw std::logic_error("a sample_*() node holds a forward-only plan");
         auto g = backward_raw(means, values, conics, samples, gouts, gmask, plan.get());
         if (debug) device_sync(means);
         return {g[0], g[1], g[2]};
@@ -389,6 +394,7 @@ struct ResidualBackward : public torch::autograd::Node {
         if (grads.empty() || !grads[0].defined()) return res;
         at::AutoGradMode no_grad(false);
         if (grads[0].requires_grad()) throw std::runtime_error("GaussianSampler.residual() is differentiable once");
+        if (debug && plan && plan->forward_only) throw std::logic_error("a residual() node holds a forward-only plan");
         const at::Tensor gout = grads[0].contiguous();
         const int64_t N = means.size(0), d = means.size(1), c = values.size(1), M = samples.size(0);
         auto gv3 = gradient_views(means, values, conics);
@@ -694,20 +700,30 @@ struct Core {
             raise_py(PyExc_NotImplementedError, "backend='binned' needs float32, d = 2, c <= 2");
     }
 
+    // Can a backward follow a launch made now (grad mode on and an input that requires grad)?  Plans built when it
+    // cannot are forward-only (PIGS_BUILD_FORWARD_ONLY).
+    bool needs_backward(const c10::optional<at::Tensor>& target = c10::nullopt) const {
+        if (!at::GradMode::is_enabled()) return false;
+        return means.requires_grad() || values.requires_grad() || conics.requires_grad() ||
+               (target.has_value() && target->requires_grad());
+    }
+
     // A plan for the bound inputs; the samples half is reused when preprocess was handed an unmodified
     // samples tensor it remembers.  While a hipGraph is being captured nothing is looked up and nothing
     // is remembered: the capture must record the samples build itself (a replay after an in-place
     // update of the static samples input has to re-sort them), its workspaces belong to the graph (they
     // neither come from the pool nor go back to it), and a SamplePlan that was only RECORDED has not
     // been built as far as later eager calls are concerned.
-    std::shared_ptr<Plan> make_plan(float q, std::shared_ptr<SamplePlan> sp) {
+    // forward_only: -1 = by the rule of needs_backward()
+    std::shared_ptr<Plan> make_plan(float q, std::shared_ptr<SamplePlan> sp, int forward_only = -1) {
+        const bool fwd_only = forward_only < 0 ? !needs_backward() : forward_only != 0;
         at::AutoGradMode no_grad(false);
         const bool cap = capturing(current_stream(means));
         if (!sp && (!cap || static_samples) && reuse > 0)
             for (auto& p : sample_plans)
                 if (p->built && p->matches(samples_source)) { sp = p; break; }
         auto pl = build_plan(means.detach(), values.detach(), conics.detach(), samples, q, q_max_b > q ? q_max_b : q, sp,
-                             samples_source, cap ? nullptr : pool, defer_lists);
+                             samples_source, cap ? nullptr : pool, defer_lists, fwd_only);
         if (reuse > 0 && !cap) {
             std::vector<std::shared_ptr<SamplePlan>> next{pl->samples};
             for (auto& p : sample_plans)
@@ -722,7 +738,7 @@ struct Core {
         if (!bound) raise_py(PyExc_RuntimeError, "preprocess() must be called before sampling");
     }
 
-    std::shared_ptr<Plan> plan_for(int mask) {
+    std::shared_ptr<Plan> plan_for(int mask, const c10::optional<at::Tensor>& target = c10::nullopt) {
         if (!plan) return plan;
         const bool cap = capturing(current_stream(means));
         // An eager call behind a capture (no preprocess in between) must not sample what the capture only RECORDED:
@@ -732,8 +748,16 @@ struct Core {
             plan = make_plan(q_max, nullptr);
             plan3.reset();
         }
+        // a differentiable call on a plan preprocess built for the forward alone (no_grad): the plan is rebuilt in
+        // full first, on the same samples half; an autograd node never holds a forward-only plan
+        const bool need_bwd = needs_backward(target);
+        if (need_bwd && plan->forward_only) {
+            plan = make_plan(q_max, plan->samples, 0);
+            plan3.reset();
+        }
         if (!(mask & 8) || q_max3 == q_max) return plan;
         if (plan3 && plan3->recorded_only && !cap) plan3.reset();
+        if (plan3 && need_bwd && plan3->forward_only) plan3.reset();
         if (!plan3) plan3 = make_plan(q_max3, plan->samples);      // same points: the sorted samples are shared
         return plan3;
     }
@@ -784,7 +808,7 @@ struct Core {
 
     at::Tensor residual(const std::array<double, 4>& coeffs, const c10::optional<at::Tensor>& target) {
         require_inputs();
-        return residual_apply(means, values, conics, samples, coeffs, target, debug, plan_for(0));
+        return residual_apply(means, values, conics, samples, coeffs, target, debug, plan_for(0, target));
     }
 
     void preprocess_aggregate(int64_t cap) {
@@ -816,11 +840,25 @@ py::list py_forward_raw(const at::Tensor& means, const at::Tensor& values, const
     return l;
 }
 
+// A raw backward (backward_raw here and in sampler.py: tools, bench) on a forward-only plan runs on a full plan of the
+// same inputs and samples half, built on the first such call and kept with the forward-only one.
+std::shared_ptr<Plan> full_for_backward(const std::shared_ptr<Plan>& plan, const at::Tensor& means, const at::Tensor& values,
+                                        const at::Tensor& conics, const at::Tensor& samples) {
+    if (!plan || !plan->forward_only) return plan;
+    if (!plan->full) {
+        at::AutoGradMode no_grad(false);
+        plan->full = build_plan(means.detach(), values.detach(), conics.detach(), samples, plan->q_max, plan->q_max_backward,
+                                plan->samples, samples, nullptr, false, false);
+    }
+    return plan->full;
+}
+
 py::tuple py_backward_raw(const at::Tensor& means, const at::Tensor& values, const at::Tensor& conics, const at::Tensor& samples,
                           const std::vector<c10::optional<at::Tensor>>& gouts, int mask, std::shared_ptr<Plan> plan) {
     Outs g;
     for (size_t k = 0; k < 5 && k < gouts.size(); ++k)
         if (gouts[k].has_value()) g[k] = *gouts[k];
+    if (samples.size(0) > 0) plan = full_for_backward(plan, means, values, conics, samples);
     auto r = backward_raw(means, values, conics, samples, g, mask, plan.get());
     return py::make_tuple(r[0], r[1], r[2]);
 }
@@ -865,6 +903,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def_readonly("q_max_backward", &Plan::q_max_backward)
         .def_readonly("other_stream_used", &Plan::other_stream_used)
         .def_readonly("recorded_only", &Plan::recorded_only)
+        .def_readonly("forward_only", &Plan::forward_only)
+        .def("full_for_backward", &full_for_backward)
         .def("scan_took_slow_path", [](const Plan& p) {
             return error_flag(p.samples->workspace, pigs_samples_error_offset()) != 0 ||
                    error_flag(p.workspace, pigs_plan_error_offset()) != 0;

@@ -171,18 +171,22 @@ class Plan:
     pending backward."""
 
     __slots__ = ("workspace", "samples", "N", "M", "c", "q_max", "q_max_backward", "_pool", "_pool_key",
-                 "build_stream", "other_stream_used", "recorded_only")
+                 "build_stream", "other_stream_used", "recorded_only", "forward_only", "_full")
 
-    BUILD_SAMPLES, WS_CLEAN, DEFER_LISTS = 1, 2, 32      # pigs_amd.h: PIGS_BUILD_SAMPLES, _PLAN_WS_CLEAN, _DEFER_LISTS
+    # pigs_amd.h: PIGS_BUILD_SAMPLES, _PLAN_WS_CLEAN, _DEFER_LISTS, _FORWARD_ONLY
+    BUILD_SAMPLES, WS_CLEAN, DEFER_LISTS, FORWARD_ONLY = 1, 2, 32, 64
 
     def __init__(self, means, values, conics, samples, q_max, sample_plan=None, source=None, pool=None,
-                 recorded_only=False, q_max_backward=None, defer_lists=False):
+                 recorded_only=False, q_max_backward=None, defer_lists=False, forward_only=False):
         lib = _lib.load()
         self.N, self.M, self.c, self.q_max = means.shape[0], samples.shape[0], values.shape[1], float(q_max)
         self.q_max_backward = max(self.q_max, float(q_max_backward if q_max_backward is not None else q_max))
         self._pool = None
         self.other_stream_used = False
         self.recorded_only = bool(recorded_only)      # built inside a capture: has run only if that graph was replayed
+        # no backward can follow (PIGS_BUILD_FORWARD_ONLY): group lists under the one cut-off q_max, no tile lists
+        self.forward_only = bool(forward_only) and not defer_lists
+        self._full = None
         key = (self.N, self.M, self.c)
         nbytes = _WORKSPACE_BYTES.get(key)
         if nbytes is None:
@@ -200,6 +204,8 @@ class Plan:
             flags = 0 if sample_plan.built else self.BUILD_SAMPLES
             if defer_lists:       # the tile lists are built by the plan's first sampling call, a forward in the same launch
                 flags |= self.DEFER_LISTS
+            if self.forward_only:
+                flags |= self.FORWARD_ONLY
             if self.workspace is not None:
                 flags |= self.WS_CLEAN
             else:
@@ -232,6 +238,17 @@ class Plan:
                 self._pool.give(self._pool_key, self.workspace)
         except Exception:            # interpreter shutdown: nothing to keep
             pass
+
+    def full_for_backward(self, means, values, conics, samples):
+        """A raw backward (:func:`backward_raw`: tools, bench) on a forward-only plan runs on a full plan of the same
+        inputs and samples half, built on the first such call and kept with this one."""
+        if not self.forward_only:
+            return self
+        if self._full is None:
+            with torch.no_grad():
+                self._full = Plan(means.detach(), values.detach(), conics.detach(), samples, self.q_max, self.samples,
+                                  q_max_backward=self.q_max_backward)
+        return self._full
 
     def scan_took_slow_path(self):
         """Diagnostic (synchronises): see :meth:`SamplePlan.scan_took_slow_path`."""
@@ -291,6 +308,8 @@ def backward_raw(means, values, conics, samples, gouts, mask, plan=None):
     c = values.shape[1]
     M = samples.shape[0]
     g_means, g_values, g_conics = _gradient_views(means, values, conics)
+    if plan is not None and M > 0 and getattr(plan, "forward_only", False):
+        plan = plan.full_for_backward(means, values, conics, samples)
     if N > 0:
         with _on_device(means.device):
             if plan is not None and M > 0:
@@ -319,6 +338,8 @@ def _residual_call(backward, means, values, conics, samples, coeffs, plan, targe
     c = values.shape[1]
     M = samples.shape[0]
     cf = (ctypes.c_double * 4)(*coeffs)
+    if backward and plan is not None and M > 0 and getattr(plan, "forward_only", False):
+        plan = plan.full_for_backward(means, values, conics, samples)
     pw = (_ptr(plan.workspace), plan.workspace.numel(), _ptr(plan.samples.workspace), plan.samples.workspace.numel()) \
         if plan is not None else (ctypes.c_void_p(0), 0, ctypes.c_void_p(0), 0)
     with _on_device(means.device):
@@ -369,6 +390,8 @@ class _ResidualFunction(torch.autograd.Function):
             raise RuntimeError("one of the tensors handed to GaussianSampler.preprocess() has been modified in place "
                                "before the backward of a residual() output that was computed from it")
         gout = gout.contiguous()
+        if ctx.debug:
+            assert ctx.plan is None or not ctx.plan.forward_only, "a residual() node holds a forward-only plan"
         g_means, g_values, g_conics = _residual_call(True, means, values, conics, samples, ctx.coeffs, ctx.plan, gout=gout)
         if ctx.debug:
             torch.cuda.synchronize(means.device)
@@ -417,6 +440,8 @@ class _SampleFunction(torch.autograd.Function):
                 mask |= 1 << k
         if mask == 0:
             return None, None, None, None, None, None, None
+        if ctx.debug:
+            assert ctx.plan is None or not ctx.plan.forward_only, "a sample_*() node holds a forward-only plan"
         g_means, g_values, g_conics = backward_raw(means, values, conics, samples, gouts, mask, ctx.plan)
         if ctx.debug:
             torch.cuda.synchronize(means.device)
@@ -672,7 +697,15 @@ class GaussianSampler:
         elif self.backend == "binned" and N > 0 and sc.shape[0] > 0:
             raise NotImplementedError("backend='binned' needs float32, d = 2, c <= 2")
 
-    def _build_plan(self, q_max, sample_plan=None):
+    def _needs_backward(self, target=None):
+        """Can a backward follow a launch made now (grad mode on and an input that requires grad)?  Plans built when
+        it cannot are forward-only (PIGS_BUILD_FORWARD_ONLY)."""
+        if not torch.is_grad_enabled() or self._st_inputs is None:
+            return False
+        mc, vc, cc, _ = self._st_inputs
+        return mc.requires_grad or vc.requires_grad or cc.requires_grad or (target is not None and target.requires_grad)
+
+    def _build_plan(self, q_max, sample_plan=None, forward_only=None):
         """A plan for the bound inputs; the samples half is reused when ``preprocess`` was handed an
         unmodified samples tensor it remembers (``reuse_samples``).  While a hipGraph is being captured
         nothing is looked up and nothing is remembered: the capture has to record the samples build
@@ -685,10 +718,12 @@ class GaussianSampler:
         if sp is None and (not capturing or self.static_samples):
             sp = next((p for p in self._st_sample_plans if p.built and p.matches(self._samples_source)), None)
         pool = None if capturing else self._plan_pool
+        if forward_only is None:
+            forward_only = not self._needs_backward()
         with torch.no_grad():
             plan = Plan(mc.detach(), vc.detach(), cc.detach(), sc, q_max, sp, self._samples_source, pool,
                         recorded_only=capturing, q_max_backward=max(q_max, self.q_max_backward),
-                        defer_lists=self.defer_lists)
+                        defer_lists=self.defer_lists, forward_only=forward_only)
         if self.reuse_samples and not capturing:
             self._st_sample_plans = [plan.samples] + [p for p in self._st_sample_plans if p is not plan.samples]
             del self._st_sample_plans[self.reuse_samples:]
@@ -703,7 +738,7 @@ class GaussianSampler:
             raise RuntimeError("preprocess() must be called before sampling")
         return inputs
 
-    def _plan_for(self, mask):
+    def _plan_for(self, mask, target=None):
         """The plan a launch with this order mask runs on: third derivatives get the wider cut-off."""
         if self._st_plan is None:
             return None
@@ -714,9 +749,17 @@ class GaussianSampler:
         if self._st_plan.recorded_only and not capturing:
             self._st_plan = self._build_plan(self.q_max)
             self._st_plan3 = None
+        # a differentiable call on a plan preprocess built for the forward alone (no_grad): the plan is rebuilt in
+        # full first, on the same samples half; an autograd node never holds a forward-only plan
+        needs_backward = self._needs_backward(target)
+        if needs_backward and self._st_plan.forward_only:
+            self._st_plan = self._build_plan(self.q_max, self._st_plan.samples, forward_only=False)
+            self._st_plan3 = None
         if not mask & 8 or self.q_max_order3 == self.q_max:
             return self._st_plan
         if self._st_plan3 is not None and self._st_plan3.recorded_only and not capturing:
+            self._st_plan3 = None
+        if self._st_plan3 is not None and needs_backward and self._st_plan3.forward_only:
             self._st_plan3 = None
         if self._st_plan3 is None:
             self._st_plan3 = self._build_plan(self.q_max_order3, self._st_plan.samples)     # same points: the sorted samples are shared
@@ -788,7 +831,7 @@ class GaussianSampler:
             target = target.reshape(M, c)
         if self._core is not None:
             return self._core.residual(coeffs, target)
-        return _ResidualFunction.apply(means, values, conics, samples, target, coeffs, self.debug, self._plan_for(0))
+        return _ResidualFunction.apply(means, values, conics, samples, target, coeffs, self.debug, self._plan_for(0, target))
 
     def sample_gaussians(self):
         """u [M, c]"""
