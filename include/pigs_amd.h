@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define PIGS_ABI_VERSION 9
+#define PIGS_ABI_VERSION 10
 
 enum pigs_status {
     PIGS_OK = 0,
@@ -263,6 +263,37 @@ size_t pigs_plan_strips_offset(void);
  * offset of the group-list slabs (uint32[tiles][4][slab], sorted Gaussian indices).
  * Returns PIGS_ERR_UNSUPPORTED for sizes the binned path does not take (N >= 2^24 among them). */
 int pigs_plan_layout_info(int64_t N, int64_t M, int c, int64_t info[6]);
+
+/*
+ * ABI 10.  Periodic domain [lo, lo + period)^2, d = 2, f32 / f64, c in 1..4.  A periodic sampler sums, for every
+ * point x, the 3 x 3 images of every Gaussian:
+ *     u(x) = sum_n sum_{k in {-1,0,1}^2} v_n exp(-1/2 (x - mu'_n - k period)^T C_n (x - mu'_n - k period)),
+ *     mu'_n = lo + (mu_n - lo) - period floor((mu_n - lo) / period)     (the mean wrapped into the box; d mu'/d mu = 1).
+ * Sample points are not wrapped.  For x in the closed box this is the periodic field exactly (up to the cut-off)
+ * when every Gaussian's q <= q_cut ellipse spans less than one period on each axis: q_cut Sigma_ii < period^2,
+ * Sigma = C^-1, with q_cut the widest cut-off the caller samples with.
+ *
+ * pigs_periodic_images: means [N][2], conics [N][3], values [N][c] -> img_means [9N][2], img_conics [9N][3],
+ *   img_values [9N][c], the arrays the caller then binds (pigs_sample_*, pigs_plan_build, pigs_residual_*) in place
+ *   of the originals.  Image j of Gaussian n is row j*N + n.  Block j = 0 holds the wrapped originals; blocks 1..8
+ *   the shifts k = (kx, ky) = (-1,-1) (0,-1) (1,-1) (-1,0) (1,0) (-1,1) (0,1) (1,1).  Every block keeps the
+ *   caller's order, so Gaussians laid out on a lattice stay in spatial strips (pigs_plan_strips_offset) in each.
+ *   A Gaussian whose ellipse reaches one period (or whose conic is not positive definite, or whose mean is not
+ *   finite) sets *flag (uint32, zeroed by the caller; one atomic OR per wave at most) to non-zero; the images are
+ *   written as ever.  flag may be NULL.
+ * pigs_periodic_images_backward: the fold -- g_means[n] = sum_j g_img_means[j*N + n], likewise for conics and values,
+ *   summed over j = 0..8 in order without atomics (bitwise reproducible).  A NULL incoming array reads as zero; the
+ *   three outputs are overwritten.
+ * Arguments are checked before any HIP call: a bad dtype or c is PIGS_ERR_UNSUPPORTED; a negative N, null arrays
+ * with N > 0, a period that is not finite and positive, a non-finite lo or a q_cut that is not finite and positive
+ * are PIGS_ERR_INVALID.
+ */
+int pigs_periodic_images(int dtype, int c, int64_t N, double lo, double period, double q_cut,
+                         const void* means, const void* conics, const void* values,
+                         void* img_means, void* img_conics, void* img_values, uint32_t* flag, void* stream);
+int pigs_periodic_images_backward(int dtype, int c, int64_t N,
+                                  const void* g_img_means, const void* g_img_conics, const void* g_img_values,
+                                  void* g_means, void* g_conics, void* g_values, void* stream);
 
 /*
  * preprocess_aggregate() / aggregate_neighbors() -- GaussianSampler methods of the reference

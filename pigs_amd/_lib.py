@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PIGS_AMD_LIB") or os.path.join(HERE, "libpigs_amd.so")
 
 PIGS_F32, PIGS_F64 = 0, 1
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -49,6 +49,9 @@ SIGNATURES = {
                               + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
     "pigs_residual_backward": (_i, [_i, _i, _i, _i64, _i64] + [_vp] * 4 + [ctypes.POINTER(ctypes.c_double), _vp] + [_vp] * 3
                                + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
+    "pigs_periodic_images": (_i, [_i, _i, _i64, ctypes.c_double, ctypes.c_double, ctypes.c_double] + [_vp] * 6
+                             + [_vp, _vp]),
+    "pigs_periodic_images_backward": (_i, [_i, _i, _i64] + [_vp] * 6 + [_vp]),
     "pigs_aggregate_workspace_bytes": (ctypes.c_size_t, [_i, _i64]),
     "pigs_aggregate_lists": (_i, [_i, _i64, _i64, _vp, _vp, ctypes.c_double, _vp, ctypes.c_size_t, _i] + [_vp] * 5 + [_vp]),
     "pigs_aggregate_forward": (_i, [_i, _i64, _i64, _i, _i, _i] + [_vp] * 4 + [_vp] * 6 + [_vp] * 3 + [_vp]),

@@ -1,4 +1,6 @@
 // extern "C" entry points declared in include/pigs_amd.h: argument checks + dispatch.
+#include <cmath>
+
 #include "launch.h"
 
 using namespace pigs;
@@ -178,6 +180,30 @@ int pigs_residual_backward(int dtype, int d, int c, int64_t N, int64_t M, const 
     a.g_means = g_means; a.g_conics = g_conics; a.g_values = g_values;
     for (int k = 0; k < 4; ++k) a.resid[k] = coeffs[k];
     return dense_dispatch(true, a, (hipStream_t)stream);
+}
+
+// ---- periodic domain (ABI 10): the 3 x 3 images of every Gaussian and the fold of their gradients (periodic.hip)
+int pigs_periodic_images(int dtype, int c, int64_t N, double lo, double period, double q_cut, const void* means,
+                         const void* conics, const void* values, void* img_means, void* img_conics, void* img_values,
+                         uint32_t* flag, void* stream) {
+    if (dtype != PIGS_F32 && dtype != PIGS_F64) return PIGS_ERR_UNSUPPORTED;
+    if (c < 1 || c > 4) return PIGS_ERR_UNSUPPORTED;
+    if (N < 0 || !std::isfinite(lo) || !std::isfinite(period) || !(period > 0) || !std::isfinite(lo + period) ||
+        !(q_cut > 0) || !std::isfinite(q_cut))
+        return PIGS_ERR_INVALID;
+    if (N > 0 && (!means || !conics || !values || !img_means || !img_conics || !img_values)) return PIGS_ERR_INVALID;
+    return periodic_dispatch(false, dtype, c, N, lo, period, q_cut, means, conics, values, img_means, img_conics,
+                             img_values, flag, (hipStream_t)stream);
+}
+
+int pigs_periodic_images_backward(int dtype, int c, int64_t N, const void* g_img_means, const void* g_img_conics,
+                                  const void* g_img_values, void* g_means, void* g_conics, void* g_values, void* stream) {
+    if (dtype != PIGS_F32 && dtype != PIGS_F64) return PIGS_ERR_UNSUPPORTED;
+    if (c < 1 || c > 4) return PIGS_ERR_UNSUPPORTED;
+    if (N < 0) return PIGS_ERR_INVALID;
+    if (N > 0 && (!g_means || !g_conics || !g_values)) return PIGS_ERR_INVALID;
+    return periodic_dispatch(true, dtype, c, N, 0.0, 1.0, 1.0, g_img_means, g_img_conics, g_img_values, g_means,
+                             g_conics, g_values, nullptr, (hipStream_t)stream);
 }
 
 static int aggregate_sizes_ok(int dtype, int64_t N, int64_t cap, int L, int K, int F) {

@@ -24,6 +24,11 @@ int dense_dispatch(bool backward, const SampleArgs& a, hipStream_t stream);
 int covariances_dispatch(bool backward, int dtype, int64_t N, const void* scaling, const void* transform,
                          const void* a, const void* b, void* o0, void* o1, hipStream_t stream);
 
+// periodic.hip: images (fold = false; a = means, conics, values; o = image arrays) or the fold of their gradients
+// (fold = true; a = image gradients, null = zero; o = gradients)
+int periodic_dispatch(bool fold, int dtype, int c, int64_t N, double lo, double period, double q_cut, const void* a0,
+                      const void* a1, const void* a2, void* o0, void* o1, void* o2, uint32_t* flag, hipStream_t stream);
+
 // aggregate.hip
 struct AggregateArgs {
     int dtype;

@@ -22,11 +22,14 @@
 #include <c10/core/DeviceGuard.h>
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <array>
 #include <list>
 #include <map>
 #include <memory>
 #include <mutex>
+#include <optional>
+#include <sstream>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -359,6 +362,67 @@ Outs sample_apply(const at::Tensor& means, const at::Tensor& values, const at::T
 }
 
 // ---------------------------------------------------------------------------------------------
+// Periodic domain (pigs_periodic_images*, ABI 10): the 3 x 3 images of every Gaussian, bound by preprocess in place of
+// the N originals; the node's backward folds the image gradients back onto them.  The fold reads nothing but the
+// incoming gradients, so the node keeps no tensors.  Mirrors _PeriodicImages in pigs_amd/sampler.py.
+// ---------------------------------------------------------------------------------------------
+struct PeriodicImagesBackward : public torch::autograd::Node {
+    int64_t N = 0;
+    int c = 1;
+    at::TensorOptions options;
+
+    std::string name() const override { return "PigsPeriodicImagesBackward"; }
+
+    torch::autograd::variable_list apply(torch::autograd::variable_list&& grads) override {
+        torch::autograd::variable_list res(3);
+        at::Tensor g[3];
+        bool any = false;
+        for (size_t i = 0; i < 3 && i < grads.size(); ++i) {
+            if (!grads[i].defined()) continue;
+            if (grads[i].requires_grad()) throw std::runtime_error("GaussianSampler: the periodic images are differentiable once");
+            g[i] = grads[i].contiguous();
+            any = true;
+        }
+        if (!any) return res;
+        at::AutoGradMode no_grad(false);
+        // one flat allocation [means | values | conics] like every gradient of the sampler (gradient_views)
+        at::Tensor flat = at::empty({N * (5 + c)}, options);
+        res[0] = flat.narrow(0, 0, 2 * N).view({N, 2});
+        res[1] = flat.narrow(0, 2 * N, c * N).view({N, (int64_t)c});
+        res[2] = flat.narrow(0, (2 + c) * N, 3 * N).view({N, 3});
+        c10::DeviceGuard guard(flat.device());
+        check(pigs_periodic_images_backward(dtype_code(flat), c, N, ptr(g[0]), ptr(g[2]), ptr(g[1]), ptr(res[0]), ptr(res[2]),
+                                            ptr(res[1]), current_stream(flat)),
+              "pigs_periodic_images_backward");
+        return res;
+    }
+};
+
+// the images [9N, 2], [9N, c], [9N, 3] (image j of Gaussian n in row j*N + n); tracked whenever an input requires grad,
+// also under no_grad (a later differentiable sample_*() call must reach the caller's tensors, as without periodic)
+std::array<at::Tensor, 3> periodic_images_apply(const at::Tensor& means, const at::Tensor& values, const at::Tensor& conics,
+                                                double lo, double period, double q_cut, uint32_t* flag) {
+    const int64_t N = means.size(0), c = values.size(1);
+    at::Tensor img_m = at::empty({9 * N, 2}, means.options()), img_v = at::empty({9 * N, c}, means.options()),
+               img_c = at::empty({9 * N, 3}, means.options());
+    {
+        c10::DeviceGuard guard(means.device());
+        check(pigs_periodic_images(dtype_code(means), (int)c, N, lo, period, q_cut, ptr(means), ptr(conics), ptr(values),
+                                   ptr(img_m), ptr(img_c), ptr(img_v), flag, current_stream(means)),
+              "pigs_periodic_images");
+    }
+    if (means.requires_grad() || values.requires_grad() || conics.requires_grad()) {
+        std::shared_ptr<PeriodicImagesBackward> node(new PeriodicImagesBackward(), torch::autograd::deleteNode);
+        node->set_next_edges(torch::autograd::collect_next_edges(means, values, conics));
+        node->N = N; node->c = (int)c; node->options = means.options();
+        torch::autograd::create_gradient_edge(img_m, node);
+        torch::autograd::create_gradient_edge(img_v, node);
+        torch::autograd::create_gradient_edge(img_c, node);
+    }
+    return {img_m, img_v, img_c};
+}
+
+// ---------------------------------------------------------------------------------------------
 // residual(): r = a0 u + a1 . grad u + aL lap u - target in one launch (pigs_residual_*); the node owns its
 // inputs and plan like SampleBackward.
 // ---------------------------------------------------------------------------------------------
@@ -620,8 +684,11 @@ struct Core {
     bool defer_lists = false;         // PIGS_BUILD_DEFER_LISTS (measured: the one-launch lists + forward is not faster; an option)
     bool static_samples = false;      // a capture may reuse a remembered (eagerly built) SamplePlan: the caller promises
                                       // not to modify the samples tensor between replays (GraphedStep(static_samples=True))
+    // periodic box (lo, hi), or none; set by the Python wrapper after construction, like defer_lists
+    std::optional<std::pair<double, double>> periodic;
     bool bound = false;
     at::Tensor means, values, conics, samples, samples_source;
+    at::Tensor caller_means, caller_conics;      // the caller's N Gaussians (periodic: the bound arrays are their images)
     std::shared_ptr<Plan> plan, plan3;
     std::vector<std::shared_ptr<SamplePlan>> sample_plans;      // most recently used first
     std::shared_ptr<PlanPool> pool = std::make_shared<PlanPool>();
@@ -686,6 +753,13 @@ struct Core {
         means = means_in.contiguous();
         values = values_in.contiguous();
         conics = conics_in.contiguous();
+        caller_means = means;
+        caller_conics = conics;
+        if (periodic) {
+            bound = false;      // a preprocess that raises leaves nothing bound
+            if (d != 2) raise_py(PyExc_NotImplementedError, "periodic=(lo, hi) is implemented for d = 2");
+            bind_periodic_images();
+        }
         samples = samples_in.detach().contiguous();
         samples_source = samples_in;
         bound = true;
@@ -693,11 +767,34 @@ struct Core {
         plan.reset();
         plan3.reset();
         neighbors.reset();
-        const bool use_plan = backend == BACKEND_BINNED || (backend == BACKEND_AUTO && N * samples.size(0) >= BINNED_AUTO_MIN_PAIRS);
+        // the pairs the launches will evaluate: with a periodic box the bound rows are the 9N images
+        const bool use_plan =
+            backend == BACKEND_BINNED || (backend == BACKEND_AUTO && means.size(0) * samples.size(0) >= BINNED_AUTO_MIN_PAIRS);
         if (use_plan && plan_supported(means, values, samples))
             plan = make_plan(q_max, nullptr);
         else if (backend == BACKEND_BINNED && N > 0 && samples.size(0) > 0)
             raise_py(PyExc_NotImplementedError, "backend='binned' needs float32, d = 2, c <= 2");
+    }
+
+    // the widest cut-off any launch samples with: the extent condition of the periodic images is checked against it
+    double q_cut() const { return std::max({(double)q_max, (double)q_max3, (double)q_max_b}); }
+
+    void bind_periodic_images() {
+        const double lo = periodic->first, hi = periodic->second;
+        const bool check_flag = debug && means.size(0) > 0 && !capturing(current_stream(means));
+        at::Tensor flag;
+        if (check_flag) flag = at::zeros({1}, means.options().dtype(at::kInt));
+        auto imgs = periodic_images_apply(means, values, conics, lo, hi - lo, q_cut(), check_flag ? (uint32_t*)flag.data_ptr() : nullptr);
+        if (check_flag && flag.item<int32_t>() != 0) {
+            std::ostringstream msg;
+            msg << "periodic=(" << lo << ", " << hi << "): a Gaussian's cut-off ellipse (q <= " << q_cut() << ") spans one period L = "
+                << hi - lo << " or more on an axis (sqrt(q_cut Sigma_ii) >= L), or its conic is not positive definite, or its mean is "
+                << "not finite: the 3 x 3 images do not give the periodic field";
+            raise_py(PyExc_ValueError, msg.str());
+        }
+        means = imgs[0];
+        values = imgs[1];
+        conics = imgs[2];
     }
 
     // Can a backward follow a launch made now (grad mode on and an input that requires grad)?  Plans built when it
@@ -814,7 +911,8 @@ struct Core {
     void preprocess_aggregate(int64_t cap) {
         require_inputs();
         if (means.size(1) != 2) raise_py(PyExc_NotImplementedError, "aggregate_neighbors is implemented for d = 2");
-        neighbors = std::make_shared<NeighborLists>(means, conics, (double)q_max, cap);
+        // the caller's N Gaussians, not the periodic images: the neighbour lists are not periodic
+        neighbors = std::make_shared<NeighborLists>(caller_means, caller_conics, (double)q_max, cap);
         if (debug) neighbors->check_overflow();
     }
 
@@ -932,6 +1030,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def_readonly("plan", &Core::plan)
         .def_readonly("plan3", &Core::plan3)
         .def_readwrite("defer_lists", &Core::defer_lists)
+        .def_readwrite("periodic", &Core::periodic)
         .def_readwrite("static_samples", &Core::static_samples)
         .def_property_readonly("sample_plans", [](const Core& c) { return c.sample_plans; })
         .def_property_readonly("pool_size", [](const Core& c) { return c.pool->size(); })

@@ -20,6 +20,7 @@ All arithmetic runs in the HIP library behind the C ABI of include/pigs_amd.h; t
 or PyTorch fallback -- CPU tensors are rejected.
 """
 import ctypes
+import math
 import os
 import threading
 
@@ -300,6 +301,59 @@ def _gradient_views(means, values, conics):
     return flat[:nm].view(means.shape), flat[nm:nm + nv].view(values.shape), flat[nm + nv:].view(conics.shape)
 
 
+def periodic_images_raw(means, values, conics, lo, period, q_cut, flag=None):
+    """pigs_periodic_images on contiguous device tensors [N, 2], [N, c], [N, 3]: the image arrays [9N, 2], [9N, c],
+    [9N, 3] (image j of Gaussian n in row j*N + n; include/pigs_amd.h, ABI 10).  ``flag``: None or a zeroed int32
+    tensor of one element that the launch sets when a Gaussian's cut-off ellipse reaches one period."""
+    lib = _lib.load()
+    N, c = means.shape[0], values.shape[1]
+    img_m = torch.empty((9 * N, 2), dtype=means.dtype, device=means.device)
+    img_v = torch.empty((9 * N, c), dtype=means.dtype, device=means.device)
+    img_c = torch.empty((9 * N, 3), dtype=means.dtype, device=means.device)
+    with _on_device(means.device):
+        rc = lib.pigs_periodic_images(_DTYPES[means.dtype], c, N, lo, period, q_cut, _ptr(means), _ptr(conics),
+                                      _ptr(values), _ptr(img_m), _ptr(img_c), _ptr(img_v), _ptr(flag),
+                                      _stream(means.device))
+    _lib.check(rc, "pigs_periodic_images")
+    return img_m, img_v, img_c
+
+
+def periodic_fold_raw(g_img_means, g_img_values, g_img_conics, N, c, dtype, device):
+    """pigs_periodic_images_backward: the gradients [N, 2], [N, c], [N, 3] of the originals, g[n] = sum over the nine
+    images (None reads as zero), as views of ONE flat allocation like every gradient of the sampler
+    (:func:`_gradient_views`)."""
+    lib = _lib.load()
+    flat = torch.empty(N * (5 + c), dtype=dtype, device=device)
+    g_means, g_values, g_conics = flat[:2 * N].view(N, 2), flat[2 * N:(2 + c) * N].view(N, c), flat[(2 + c) * N:].view(N, 3)
+    with _on_device(device):
+        rc = lib.pigs_periodic_images_backward(_DTYPES[dtype], c, N, _ptr(g_img_means), _ptr(g_img_conics),
+                                               _ptr(g_img_values), _ptr(g_means), _ptr(g_conics), _ptr(g_values),
+                                               _stream(device))
+    _lib.check(rc, "pigs_periodic_images_backward")
+    return g_means, g_values, g_conics
+
+
+class _PeriodicImages(torch.autograd.Function):
+    """The 3 x 3 images of every Gaussian on the torus (one launch); the backward folds the image gradients back onto
+    the originals (one launch, no atomics).  The fold reads nothing but the incoming gradients: the node keeps no
+    tensors."""
+
+    @staticmethod
+    def forward(ctx, means, values, conics, lo, period, q_cut, flag):
+        ctx.sizes = (means.shape[0], values.shape[1], means.dtype, means.device)
+        ctx.set_materialize_grads(False)
+        return periodic_images_raw(means, values, conics, lo, period, q_cut, flag)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_means, g_values, g_conics):
+        if g_means is None and g_values is None and g_conics is None:
+            return None, None, None, None, None, None, None
+        gs = [None if g is None else g.contiguous() for g in (g_means, g_values, g_conics)]
+        gm, gv, gc = periodic_fold_raw(*gs, *ctx.sizes)
+        return gm, gv, gc, None, None, None, None
+
+
 def backward_raw(means, values, conics, samples, gouts, mask, plan=None):
     """Launch the backward; ``gouts`` has 5 entries (contiguous tensor or None: orders 0..3 and the
     trace), ``mask`` marks the non-None ones.  Returns (g_means, g_values, g_conics)."""
@@ -448,6 +502,28 @@ class _SampleFunction(torch.autograd.Function):
         return g_means, g_values, g_conics, None, None, None, None
 
 
+def _periodic_box(periodic):
+    """None, or the box (lo, hi) as two finite floats with hi > lo."""
+    if periodic is None:
+        return None
+    try:
+        lo, hi = periodic
+        lo, hi = float(lo), float(hi)
+    except (TypeError, ValueError):
+        raise ValueError(f"periodic must be None or (lo, hi), got {periodic!r}") from None
+    if not (math.isfinite(lo) and math.isfinite(hi) and math.isfinite(hi - lo) and hi > lo):
+        raise ValueError(f"periodic=(lo, hi) needs finite lo < hi, got {periodic!r}")
+    return lo, hi
+
+
+def _check_periodic_flag(flag, box, q_cut):
+    if flag:
+        lo, hi = box
+        raise ValueError(f"periodic=({lo}, {hi}): a Gaussian's cut-off ellipse (q <= {q_cut}) spans one period "
+                         f"L = {hi - lo} or more on an axis (sqrt(q_cut Sigma_ii) >= L), or its conic is not positive "
+                         "definite, or its mean is not finite: the 3 x 3 images do not give the periodic field")
+
+
 _FUSE_CODES = {"auto": 0, "all": 1, "none": 2}
 _BACKEND_CODES = {"auto": 0, "dense": 1, "binned": 2}
 
@@ -527,6 +603,18 @@ class GaussianSampler:
     first and evaluates afterwards, in step with all the others -- DESIGN.md section 3.3), so it is an option, not
     the default.
 
+    ``periodic`` (extension, keyword only; default None; settable, the next ``preprocess`` uses it): ``(lo, hi)`` declares the periodic box [lo, hi)^2 with period
+    L = hi - lo on both axes -- the reference's Navier-Stokes problem, whose model wraps its means back into the box
+    after every update (model_pn.py:689-693).  ``preprocess`` then wraps every mean into the box (the gradient flows to
+    the caller's mean unchanged) and binds the 3 x 3 images of every Gaussian, shifted by -L, 0, +L on each axis, in
+    place of the N originals: every ``sample_*`` output, ``residual()`` and every gradient is that of the periodic
+    field.  Sample points are not wrapped; for points in the closed box the sum is the periodic field exactly (up to
+    the cut-off) when every Gaussian's q <= q_cut ellipse spans less than one period on each axis, sqrt(q_cut
+    Sigma_ii) < L with q_cut = max(q_max, q_max_backward, q_max_order3) -- debug mode (``flag``) checks this and
+    raises ``ValueError``.  d = 2 only (d = 1 raises ``NotImplementedError``); dense and binned alike, the ``auto``
+    rule counting the 9N images.  ``preprocess_aggregate`` / ``aggregate_neighbors`` keep working on the caller's N
+    Gaussians with the non-periodic neighbour definition: periodic neighbour lists are not implemented.
+
     ``host`` (extension, keyword only): ``"native"`` (default; environment override PIGS_AMD_HOST) keeps
     the sampler's state and its autograd node in the C++ torch extension ``pigs_amd/_pigs_host.so``
     (csrc_host/pigs_host.cpp) -- what the reference's own boundary is (a compiled torch extension,
@@ -549,7 +637,7 @@ class GaussianSampler:
 
     def __init__(self, flag=False, *, fuse="auto", backend="auto", q_max=36.0, q_max_order3=None,
                  q_max_backward=None, reuse_samples=True, unpinned_aggregate=False, aggregate_cap=None, host=None,
-                 defer_lists=False):
+                 defer_lists=False, periodic=None):
         if fuse not in ("auto", "all", "none"):
             raise ValueError("fuse must be 'auto', 'all' or 'none'")
         if backend not in ("auto", "dense", "binned"):
@@ -573,6 +661,8 @@ class GaussianSampler:
             raise ValueError("q_max_backward must not be below q_max")
         self.reuse_samples = 4 if reuse_samples is True else max(0, int(reuse_samples))
         self.defer_lists = bool(defer_lists)
+        self._periodic = _periodic_box(periodic)
+        self._st_caller = None
         self._static_samples = False
         self.unpinned_aggregate = bool(unpinned_aggregate)
         self.aggregate_cap = None if aggregate_cap is None else int(aggregate_cap)
@@ -591,6 +681,25 @@ class GaussianSampler:
                                                          self.q_max, self.q_max_order3, self.q_max_backward,
                                                          self.reuse_samples)
             self._core.defer_lists = self.defer_lists
+            self._core.periodic = self._periodic
+
+    @property
+    def periodic(self):
+        """Settable: None or the box (lo, hi) (class docstring); a new value takes effect at the next ``preprocess``,
+        on both hosts."""
+        return self._periodic
+
+    @periodic.setter
+    def periodic(self, value):
+        self._periodic = _periodic_box(value)
+        if self._core is not None:
+            self._core.periodic = self._periodic
+
+    @property
+    def q_cut(self):
+        """The widest cut-off any launch samples with: the extent condition of the periodic images is checked against
+        it."""
+        return max(self.q_max, self.q_max_backward, self.q_max_order3)
 
     @property
     def static_samples(self):
@@ -682,20 +791,40 @@ class GaussianSampler:
             warnings.warn("GaussianSampler: samples.requires_grad is set, but the sampler returns no gradient "
                           "with respect to the sample points (as the reference, whose tests ask for the gradients "
                           "of means, values and conics only); use the derivative outputs instead", stacklevel=2)
-        self._st_inputs = (means.contiguous(), values.contiguous(), conics.contiguous(),
-                           samples.detach().contiguous())
+        means, values, conics = means.contiguous(), values.contiguous(), conics.contiguous()
+        self._st_caller = (means, conics)
+        if self.periodic is not None:
+            self._st_inputs = None          # a preprocess that raises leaves nothing bound
+            if d != 2:
+                raise NotImplementedError("periodic=(lo, hi) is implemented for d = 2")
+            means, values, conics = self._periodic_images(means, values, conics)
+        self._st_inputs = (means, values, conics, samples.detach().contiguous())
         self._samples_source = samples
         self._cache = {}
         self._st_plan = None
         self._st_plan3 = None
         self._neighbors = None
         mc, vc, cc, sc = self._st_inputs
+        # the pairs the launches will evaluate: with periodic=... the bound rows are the 9N images
         use_plan = self.backend == "binned" or (
-            self.backend == "auto" and N * sc.shape[0] >= self.BINNED_AUTO_MIN_PAIRS)
+            self.backend == "auto" and mc.shape[0] * sc.shape[0] >= self.BINNED_AUTO_MIN_PAIRS)
         if use_plan and Plan.supported(mc, vc, sc):
             self._st_plan = self._build_plan(self.q_max)
         elif self.backend == "binned" and N > 0 and sc.shape[0] > 0:
             raise NotImplementedError("backend='binned' needs float32, d = 2, c <= 2")
+
+    def _periodic_images(self, means, values, conics):
+        """The 9N images, an autograd-tracked launch (also when preprocess runs under no_grad: the outputs of a later
+        differentiable sample_*() call must reach the caller's tensors, as without periodic).  Debug mode reads the
+        extent flag back (one synchronisation); otherwise it is never read and not even allocated."""
+        lo, hi = self.periodic
+        check = self.debug and means.shape[0] > 0 and not torch.cuda.is_current_stream_capturing()
+        flag = torch.zeros(1, dtype=torch.int32, device=means.device) if check else None
+        with torch.enable_grad():
+            imgs = _PeriodicImages.apply(means, values, conics, lo, hi - lo, self.q_cut, flag)
+        if check:
+            _check_periodic_flag(int(flag.item()), self.periodic, self.q_cut)
+        return imgs
 
     def _needs_backward(self, target=None):
         """Can a backward follow a launch made now (grad mode on and an input that requires grad)?  Plans built when
@@ -871,7 +1000,8 @@ class GaussianSampler:
             self._core.preprocess_aggregate(-1 if self.aggregate_cap is None else self.aggregate_cap)
             self._neighbors = self._core.neighbors
             return
-        means, _, conics, _ = self._require_inputs()
+        self._require_inputs()
+        means, conics = self._st_caller          # the caller's N Gaussians, not the periodic images
         if means.shape[1] != 2:
             raise NotImplementedError("aggregate_neighbors is implemented for d = 2")
         self._neighbors = aggregate.NeighborLists(means, conics, self.q_max, cap=self.aggregate_cap)
