@@ -370,6 +370,36 @@ __device__ inline PointOrder point_order(const SamplesView& sv) {
     po.src = (const float2*)(uintptr_t)sv.params->src;
     return po;
 }
+// The same in two steps, for the forward (plan.hip, forward_tile): first the three words as loaded -- through the
+// constant address space (the sampling kernels never write SampleParams), which makes them ONE scalar load beside the
+// wave's vector loads instead of a vector load + v_readfirstlane in their queue; nothing is derived from them here, or
+// the wave would wait for them here -- then, where the first point is addressed, the order they spell.
+struct PointOrderWords {
+    uint32_t rf, rs;
+    uint64_t src;
+};
+__device__ inline PointOrderWords point_order_words(const SamplesView& sv) {
+    // (one 16-byte load: taken word by word, the address is fetched only once the row length is known to be non-zero,
+    // a second round trip)
+    static_assert(offsetof(SampleParams, src) == offsetof(SampleParams, lat) + 8, "lat[0], lat[1], src: 16 consecutive bytes");
+    typedef uint32_t Words4 __attribute__((ext_vector_type(4)));
+    typedef const Words4 __attribute__((address_space(4))) * ConstWords;
+    const Words4 v = *(ConstWords)&sv.params->lat[0];
+    PointOrderWords w;
+    w.rf = v.x; w.rs = v.y; w.src = (uint64_t)v.z | (uint64_t)v.w << 32;
+    return w;
+}
+__device__ inline PointOrder point_order(const PointOrderWords& w) {
+    PointOrder po;
+    po.rf = w.rf;
+    po.ntx = w.rf >> 3;
+    po.nty = w.rs >> 3;
+    // (a device array: said so, the points come by global loads; a flat load also counts as an LDS access, and the wait
+    // for the list lengths in front of it would wait for the point as well)
+    typedef const float2 __attribute__((address_space(1))) * GlobalPoints;
+    po.src = (const float2*)(GlobalPoints)(uintptr_t)w.src;
+    return po;
+}
 // the point at position `lane` of tile `tile` (tile wave-uniform in the tile kernels: its (tx, ty) stay scalar); a
 // position behind the last point repeats the last one (never stored)
 __device__ inline SPoint tile_point(const SamplesView& sv, const PointOrder& po, uint32_t tile, uint32_t lane) {

@@ -2029,20 +2029,39 @@ __device__ __forceinline__ void forward_tile(const PlanView& pv, const SamplesVi
     char* const qbase = (char*)lds.rec;
     const uint32_t m = tile * TILE_POINTS + (uint32_t)lane;
     const bool valid = m < sv.M;
-    const SPoint sp = tile_point(sv, point_order(sv), tile, (uint32_t)lane);      // lanes behind the last point repeat it (never stored)
+    // The head of a wave: the point's address waits for the order of the points, which is in memory; the
+    // tile header and the first chunk's list entries wait for nothing but kernel arguments.  So the question for the
+    // order leaves first (one scalar load), header and entries leave behind it, and only then is the order used: the
+    // wave's first wait covers all three, and the records are its second round trip.  (Scalar loads return in no
+    // order -- a wait for one is a wait for all -- so the arguments that header and entries are addressed by are in
+    // registers before the question leaves: the empty asm.  Checked in the ISA of hipcc 7.2.26015, clang 22.0.0git
+    // roc-7.2.0: the four global loads and the s_load_dwordx4 of lat / src, then s_waitcnt lgkmcnt(0).)
+    const int g = lane >> 4, i = lane & 15;
+    asm volatile("" ::"s"(sv.params), "s"(sv.M), "s"(pv.hdr), "s"(pv.glist), "s"(pv.list_cap));
+    const PointOrderWords pw = point_order_words(sv);
+    // (word 0 through a lane index the compiler cannot see through: a load it knows to be uniform is followed by its
+    // v_readfirstlane, and the wait for the header would stand in front of the point's load)
+    const uint32_t* hd = pv.hdr + (size_t)tile * TILE_HDR_WORDS;
+    uint32_t zero = 0u;
+    asm("" : "+v"(zero));
+    const uint32_t h0v = hd[zero];
+    const uint32_t ngv = hd[1 + g];           // this row's list length (a tile without group lists: not used)
+    // the first chunk's entries are loaded whether or not they lie inside the list -- or the tile has group lists at all
+    // (every tile has the slab, and list_cap is a multiple of 16: in bounds)
+    const uint32_t* gl = pv.glist + ((size_t)tile * 4 + g) * pv.list_cap;
+    uint32_t e0 = gl[(uint32_t)i < pv.list_cap ? i : 0], e1 = gl[16u + (uint32_t)i < pv.list_cap ? 16 + i : 0];
+    const SPoint sp = tile_point(sv, point_order(pw), tile, (uint32_t)lane);      // lanes behind the last point repeat it (never stored)
+    const uint32_t h0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)h0v);
     const float s[2] = {sp.x, sp.y};
     float acc[L::N];
 #pragma unroll
     for (int k = 0; k < L::N; ++k) acc[k] = 0.f;
-    const int g = lane >> 4, i = lane & 15;
-    const uint32_t* hd = pv.hdr + (size_t)tile * TILE_HDR_WORDS;
-    const uint32_t h0 = hd[0];
     // one chunk: every row fills its queue with `rows` records (its own list's, or the all-zero record
     // behind the list's end), two rounds of 16 in flight together, and the rows are evaluated
     auto chunk = [&](int rows, auto&& index_of) {
         static_assert(GROUP_CAP == 32, "two rounds of 16 records per chunk");
         rows = __builtin_amdgcn_readfirstlane((rows + U - 1) / U * U);
-        const uint32_t j0 = index_of(i), j1 = index_of(16 + i);
+        const uint32_t j0 = index_of(0, i), j1 = index_of(1, 16 + i);      // (round of the chunk, position in it)
         const float4 A0 = pv.rec[2 * (size_t)j0], B0 = pv.rec[2 * (size_t)j0 + 1];
         float4 A1 = A0, B1 = B0;
         if (rows > 16) { A1 = pv.rec[2 * (size_t)j1]; B1 = pv.rec[2 * (size_t)j1 + 1]; }
@@ -2070,19 +2089,22 @@ __device__ __forceinline__ void forward_tile(const PlanView& pv, const SamplesVi
     if ((h0 >> TILE_MODE_SHIFT) == TILE_MODE_POINTS) {
         return;                                   // scattered points: the caller's (helper workgroups / the fused launch's own walk)
     } else if ((h0 >> TILE_MODE_SHIFT) != TILE_MODE_RANGES) {            // LIST or GROUPS: the group lists are there
-        const uint32_t ng = hd[1 + g];                                    // this row's list length
-        const uint32_t* gl = pv.glist + ((size_t)tile * 4 + g) * pv.list_cap;
-        uint32_t nmax = hd[1] > hd[2] ? hd[1] : hd[2];
-        nmax = hd[3] > nmax ? hd[3] : nmax;
-        nmax = hd[4] > nmax ? hd[4] : nmax;
+        const uint32_t ng = ngv;
+        const uint32_t n0 = (uint32_t)__builtin_amdgcn_readlane((int)ngv, 0), n1 = (uint32_t)__builtin_amdgcn_readlane((int)ngv, 16);
+        const uint32_t n2 = (uint32_t)__builtin_amdgcn_readlane((int)ngv, 32), n3 = (uint32_t)__builtin_amdgcn_readlane((int)ngv, 48);
+        uint32_t nmax = n0 > n1 ? n0 : n1;
+        nmax = n2 > nmax ? n2 : nmax;
+        nmax = n3 > nmax ? n3 : nmax;
         for (uint32_t base = 0; base < nmax; base += GROUP_CAP) {
             const int rows = (int)(nmax - base < GROUP_CAP ? nmax - base : GROUP_CAP);
             // the entry is loaded whether or not it lies inside the list (the slab has the room, and
             // the load then does not wait for the header): one dependent round trip less per tile
-            chunk(rows, [&](int p) {
-                const uint32_t e = gl[base + p < pv.list_cap ? base + p : 0u];
-                return base + p < ng ? e : pv.N;
-            });
+            chunk(rows, [&](int round, int p) { return base + p < ng ? (round == 0 ? e0 : e1) : pv.N; });
+            if (base + GROUP_CAP < nmax) {                  // the next chunk's (where the parent's loop loaded them: behind this chunk's rows)
+                const uint32_t p0 = base + GROUP_CAP + (uint32_t)i, p1 = p0 + 16u;
+                e0 = gl[p0 < pv.list_cap ? p0 : 0u];
+                e1 = gl[p1 < pv.list_cap ? p1 : 0u];
+            }
         }
     } else {
         // Record ranges (a group list did not fit): the ranges hold every Gaussian near the tile.  Every
