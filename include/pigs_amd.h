@@ -350,6 +350,45 @@ int pigs_aggregate_backward(int dtype, int64_t N, int64_t cap, int L, int K, int
                             void* g_features, void* g_transform, void* g_queries, void* g_keys, void* g_frequencies,
                             void* g_distance_transform, void* stream);
 
+/*
+ * The same on the torus [lo, lo + period)^2 of pigs_periodic_images (additive to ABI 10: the number does not change).
+ * The neighbours of i are the PAIRS (j, k), image k = 0..8 of Gaussian j in the block order of pigs_periodic_images
+ * (k = 0: no shift), with (mu'_i - mu'_j - s_k L)^T C_j (mu'_i - mu'_j - s_k L) <= q_max, L = period: every pair is
+ * a neighbour of its own (offset mu'_j + s_k L - mu'_i, its own density and softmax entry, keys and features of j),
+ * i.e. the definition above applied to the 9N images, rows of block 0.  One j may appear through several images
+ * (half extents between L/2 and L), so a list can be LONGER THAN N: `cap` = N is not safe here, take the counting
+ * pass (lists == NULL) or check *overflow.
+ * PRECONDITIONS, neither of which is checked here: (1) `means` are already wrapped into [lo, lo + period) -- block 0
+ * of pigs_periodic_images (with its conics); nothing is wrapped here.  (2) Every Gaussian's q <= q_max ellipse spans
+ * less than one period on each axis, sqrt(q_max Sigma_ii) < period -- what the flag of pigs_periodic_images reports
+ * for q_cut >= q_max.  The all-pairs build (N <= 2048) relies on both: it tests only the four shifts that can then
+ * reach.  With unwrapped means or a wider Gaussian it drops pairs silently, while the grid build (N > 2048), which
+ * tries all nine shifts, would still find them: the two builds then differ, and neither gives the periodic relation
+ * (a second-neighbour image would be needed).  A list entry is j | k << 28 (row lists: (j, k); column lists: (i, k) with the k
+ * of the row entry of that pair; sum of col_counts = sum of row_counts); N >= 2^28 is PIGS_ERR_UNSUPPORTED.  Lists
+ * built here are read by the two _periodic sampling entries only, and those read no others.  Up to N = 2048 a
+ * pair costs four tests (only the shifts towards each other can reach) and lists ascend in (j, k); beyond, the grid
+ * of the wrapped centres is walked once per shift that can reach.  A period that is not finite and positive or a
+ * non-finite lo is PIGS_ERR_INVALID (checked before any HIP call).  The means are constants: no gradient.
+ */
+int pigs_aggregate_lists_periodic(int dtype, int64_t N, int64_t cap, const void* means, const void* conics, double q_max,
+                                  double lo, double period, void* workspace, size_t workspace_bytes, int flags,
+                                  int32_t* row_counts, int32_t* row_lists, int32_t* col_counts, int32_t* col_lists,
+                                  int32_t* overflow, void* stream);
+int pigs_aggregate_forward_periodic(int dtype, int64_t N, int64_t cap, int L, int K, int F, double period,
+                                    const void* means, const void* conics, const int32_t* row_counts,
+                                    const int32_t* row_lists, const void* features, const void* transform,
+                                    const void* queries, const void* keys, const void* frequencies,
+                                    const void* distance_transform, void* out, void* lse, void* acc, void* stream);
+int pigs_aggregate_backward_periodic(int dtype, int64_t N, int64_t cap, int L, int K, int F, double period,
+                                     const void* means, const void* conics, const int32_t* row_counts,
+                                     const int32_t* row_lists, const int32_t* col_counts, const int32_t* col_lists,
+                                     const void* features, const void* transform, const void* queries, const void* keys,
+                                     const void* frequencies, const void* distance_transform, const void* lse,
+                                     const void* acc, const void* gout, void* scratch, size_t scratch_bytes,
+                                     void* g_features, void* g_transform, void* g_queries, void* g_keys,
+                                     void* g_frequencies, void* g_distance_transform, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,6 +58,13 @@ SIGNATURES = {
     "pigs_aggregate_backward_scratch_bytes": (ctypes.c_size_t, [_i, _i64, _i, _i]),
     "pigs_aggregate_backward": (_i, [_i, _i64, _i64, _i, _i, _i] + [_vp] * 6 + [_vp] * 6 + [_vp] * 3 + [_vp, ctypes.c_size_t]
                                 + [_vp] * 6 + [_vp]),
+    # the same on the torus of pigs_periodic_images (additive to ABI 10): + lo, period / + period
+    "pigs_aggregate_lists_periodic": (_i, [_i, _i64, _i64, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                           _vp, ctypes.c_size_t, _i] + [_vp] * 5 + [_vp]),
+    "pigs_aggregate_forward_periodic": (_i, [_i, _i64, _i64, _i, _i, _i, ctypes.c_double] + [_vp] * 4 + [_vp] * 6 + [_vp] * 3
+                                        + [_vp]),
+    "pigs_aggregate_backward_periodic": (_i, [_i, _i64, _i64, _i, _i, _i, ctypes.c_double] + [_vp] * 6 + [_vp] * 6 + [_vp] * 3
+                                         + [_vp, ctypes.c_size_t] + [_vp] * 6 + [_vp]),
 }
 
 _lib = None
@@ -78,7 +85,11 @@ def load():
             "pigs_amd has no CPU or PyTorch fallback.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the symbol is not exported
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise ImportError(f"{LIB_PATH} does not export {name}: it was built from older sources; rebuild "
+                              "(python -m pigs_amd.build)") from None
         fn.restype = res
         fn.argtypes = args
     if lib.pigs_abi_version() != ABI_VERSION:

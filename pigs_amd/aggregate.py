@@ -18,6 +18,13 @@ oracle/aggregate_torch.py):
 The neighbour relation lives in index lists (``NeighborLists``: [N, cap] with cap = the longest list,
 found by a counting pass).  Forward = one launch, backward = four (the three small GEMMs
 gout @ [transform | distance_transform], gout^T @ acc included).  d = 2, float32 / float64.
+
+Periodic lists (``NeighborLists(..., periodic=(lo, period))``; ``GaussianSampler(periodic=...,
+periodic_aggregate=True)``): the same definition on the torus [lo, lo + period)^2 -- the neighbours of i are the
+pairs (j, k), image k of Gaussian j, each with its own offset mu'_j + s_k L - mu'_i, density and softmax entry;
+equivalently the definition above on the 9N images of pigs_periodic_images, rows of block 0.  ``means`` must already
+be wrapped into the box (block 0 of the image arrays).  One j can appear through several images, so a list can be
+longer than N and ``cap`` always comes from the counting pass unless given.
 """
 import ctypes
 
@@ -46,10 +53,17 @@ class NeighborLists:
     a counting pass, then -- with ``cap`` = the longest list rounded up to 64, read back ONCE (the only
     host synchronisation of ``preprocess_aggregate``) -- the lists themselves.  ``cap`` given (or a hipGraph
     being captured, where nothing may be read back): one pass into slabs of that size, and a list that does
-    not fit sets ``overflow`` (checked by :meth:`check`; debug mode calls it)."""
+    not fit sets ``overflow`` (checked by :meth:`check`; debug mode calls it).
 
-    def __init__(self, means, conics, q_max, cap=None):
+    ``periodic=(lo, period)``: the lists of the torus (module docstring; entries j | k << 28, read by the periodic
+    sampling entries only).  ``means`` are the wrapped centres.  A row can be longer than N, so cap = N is not safe:
+    the counting pass runs at every N unless ``cap`` is given or a capture is running (slab ``min(4N,
+    MAX_NEIGHBORS)`` then)."""
+
+    def __init__(self, means, conics, q_max, cap=None, periodic=None):
         lib = _lib.load()
+        self.periodic = None if periodic is None else (float(periodic[0]), float(periodic[1]))
+        self.period = 0.0 if self.periodic is None else self.periodic[1]
         if means.dim() != 2 or means.shape[1] != 2:
             raise NotImplementedError("aggregate_neighbors is implemented for d = 2")
         if means.dtype not in _DTYPES:
@@ -69,20 +83,23 @@ class NeighborLists:
         self.row_lists = self.col_lists = None
 
         def run(flags, cap_, with_lists):
+            tail = (_ptr(self.workspace), nbytes, flags, _ptr(self.row_counts),
+                    _ptr(self.row_lists) if with_lists else ctypes.c_void_p(0), _ptr(self.col_counts),
+                    _ptr(self.col_lists) if with_lists else ctypes.c_void_p(0), _ptr(self.overflow), _stream(dev))
             with torch.cuda.device(dev):
-                rc = lib.pigs_aggregate_lists(dt, N, cap_, _ptr(self.means), _ptr(self.conics), float(q_max),
-                                              _ptr(self.workspace), nbytes, flags, _ptr(self.row_counts),
-                                              _ptr(self.row_lists) if with_lists else ctypes.c_void_p(0),
-                                              _ptr(self.col_counts),
-                                              _ptr(self.col_lists) if with_lists else ctypes.c_void_p(0),
-                                              _ptr(self.overflow), _stream(dev))
-            _lib.check(rc, "pigs_aggregate_lists")
+                if self.periodic is None:
+                    rc = lib.pigs_aggregate_lists(dt, N, cap_, _ptr(self.means), _ptr(self.conics), float(q_max), *tail)
+                else:
+                    rc = lib.pigs_aggregate_lists_periodic(dt, N, cap_, _ptr(self.means), _ptr(self.conics), float(q_max),
+                                                           self.periodic[0], self.periodic[1], *tail)
+            _lib.check(rc, "pigs_aggregate_lists_periodic" if self.periodic else "pigs_aggregate_lists")
 
         flags = 1                                                  # PIGS_AGGREGATE_BUILD_GRID
-        if cap is None and N <= BRUTE_MAX:
+        if cap is None and N <= BRUTE_MAX and self.periodic is None:
             cap = max(1, N)                                        # every pair is tested; a slab of N cannot overflow
         if cap is None and N > 0 and torch.cuda.is_current_stream_capturing():
-            cap = min(N, MAX_NEIGHBORS[means.dtype])               # nothing can be read back inside a capture
+            # nothing can be read back inside a capture (periodic: a j can come through several images)
+            cap = min(N if self.periodic is None else 4 * N, MAX_NEIGHBORS[means.dtype])
         if cap is None and N > 0:
             run(flags, 1, False)                                   # counting pass (full lengths)
             flags = 0
@@ -113,11 +130,14 @@ class _Aggregate(torch.autograd.Function):
         out = torch.empty((N, L), dtype=dt, device=f.device)
         lse = torch.empty(N, dtype=dt, device=f.device)
         acc = torch.empty((N, L + 2 * E), dtype=dt, device=f.device)
+        tail = (_ptr(nb.means), _ptr(nb.conics), _ptr(nb.row_counts), _ptr(nb.row_lists), _ptr(f), _ptr(tr), _ptr(q), _ptr(k),
+                _ptr(fr), _ptr(dist), _ptr(out), _ptr(lse), _ptr(acc), _stream(f.device))
         with torch.cuda.device(f.device):
-            rc = lib.pigs_aggregate_forward(_DTYPES[dt], N, nb.cap, L, K, F, _ptr(nb.means), _ptr(nb.conics),
-                                            _ptr(nb.row_counts), _ptr(nb.row_lists), _ptr(f), _ptr(tr), _ptr(q), _ptr(k),
-                                            _ptr(fr), _ptr(dist), _ptr(out), _ptr(lse), _ptr(acc), _stream(f.device))
-        _lib.check(rc, "pigs_aggregate_forward")
+            if nb.periodic is None:
+                rc = lib.pigs_aggregate_forward(_DTYPES[dt], N, nb.cap, L, K, F, *tail)
+            else:
+                rc = lib.pigs_aggregate_forward_periodic(_DTYPES[dt], N, nb.cap, L, K, F, nb.period, *tail)
+        _lib.check(rc, "pigs_aggregate_forward_periodic" if nb.periodic else "pigs_aggregate_forward")
         ctx.nb = nb
         ctx.save_for_backward(f, tr, q, k, fr, dist, lse, acc)
         ctx.dims = (N, L, K, F, E)
@@ -136,14 +156,15 @@ class _Aggregate(torch.autograd.Function):
         g_f, g_tr, g_q, g_k, g_fr, g_dist = (torch.empty_like(t) for t in (f, tr, q, k, fr, dist))
         nbytes = lib.pigs_aggregate_backward_scratch_bytes(_DTYPES[dt], N, L, F)
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=f.device)
+        tail = (_ptr(nb.means), _ptr(nb.conics), _ptr(nb.row_counts), _ptr(nb.row_lists), _ptr(nb.col_counts),
+                _ptr(nb.col_lists), _ptr(f), _ptr(tr), _ptr(q), _ptr(k), _ptr(fr), _ptr(dist), _ptr(lse), _ptr(acc), _ptr(gout),
+                _ptr(scratch), nbytes, _ptr(g_f), _ptr(g_tr), _ptr(g_q), _ptr(g_k), _ptr(g_fr), _ptr(g_dist), _stream(f.device))
         with torch.cuda.device(f.device):
-            rc = lib.pigs_aggregate_backward(_DTYPES[dt], N, nb.cap, L, K, F, _ptr(nb.means), _ptr(nb.conics),
-                                             _ptr(nb.row_counts), _ptr(nb.row_lists), _ptr(nb.col_counts),
-                                             _ptr(nb.col_lists), _ptr(f), _ptr(tr), _ptr(q), _ptr(k), _ptr(fr), _ptr(dist),
-                                             _ptr(lse), _ptr(acc), _ptr(gout), _ptr(scratch), nbytes,
-                                             _ptr(g_f), _ptr(g_tr), _ptr(g_q), _ptr(g_k), _ptr(g_fr), _ptr(g_dist),
-                                             _stream(f.device))
-        _lib.check(rc, "pigs_aggregate_backward")
+            if nb.periodic is None:
+                rc = lib.pigs_aggregate_backward(_DTYPES[dt], N, nb.cap, L, K, F, *tail)
+            else:
+                rc = lib.pigs_aggregate_backward_periodic(_DTYPES[dt], N, nb.cap, L, K, F, nb.period, *tail)
+        _lib.check(rc, "pigs_aggregate_backward_periodic" if nb.periodic else "pigs_aggregate_backward")
         if N == 0:
             for g in (g_tr, g_fr, g_dist):
                 g.zero_()

@@ -102,11 +102,53 @@ __device__ __forceinline__ void for_row(const T* __restrict__ src, int n, Put&& 
     }
 }
 
-// q of centre `at` under Gaussian `of`: (mu_at - mu_of)^T C_of (mu_at - mu_of)
-template <typename T>
-__device__ __forceinline__ T q_of(const T* means, const T* conics, int64_t at, int64_t of, T* dx, T* dy) {
+// Periodic lists (pigs_aggregate_*_periodic): a list entry is j | k << 28, image k of Gaussian j in the block
+// order of pigs_periodic_images (periodic.hip image_shift; k = 0 is the unshifted one).
+constexpr int PER_SHIFT = 28;
+constexpr uint32_t PER_INDEX_MASK = (1u << PER_SHIFT) - 1u;
+// (kx, ky) of image k as in periodic.hip's image_shift, from two packed tables (2 bits per image, value + 1): no division
+constexpr uint32_t IMAGE_KX = 0x24891u, IMAGE_KY = 0x2A501u;
+constexpr bool image_tables_ok() {
+    for (int k = 0; k < 9; ++k) {
+        const int t = k == 0 ? 4 : (k <= 4 ? k - 1 : k);
+        if ((int)(IMAGE_KX >> 2 * k & 3u) != t % 3 || (int)(IMAGE_KY >> 2 * k & 3u) != t / 3) return false;
+    }
+    return true;
+}
+static_assert(image_tables_ok(), "IMAGE_KX / IMAGE_KY must repeat the block order of pigs_periodic_images");
+__device__ __forceinline__ void image_shift(int k, int& kx, int& ky) {
+    kx = (int)(IMAGE_KX >> 2 * k & 3u) - 1;
+    ky = (int)(IMAGE_KY >> 2 * k & 3u) - 1;
+}
+__device__ __forceinline__ int image_index(int kx, int ky) {                // its inverse
+    const int t = (ky + 1) * 3 + (kx + 1);
+    return t == 4 ? 0 : (t < 4 ? t + 1 : t);
+}
+template <bool PER>
+__device__ __forceinline__ void decode_entry(int32_t e, int64_t* j, int* k) {
+    if constexpr (PER) {
+        *j = (int64_t)((uint32_t)e & PER_INDEX_MASK);
+        *k = (int)((uint32_t)e >> PER_SHIFT);
+    } else {
+        *j = e;
+        *k = 0;
+    }
+}
+
+// q of centre `at` under Gaussian `of`: (mu_at - mu_of)^T C_of (mu_at - mu_of); PER: under image k of Gaussian `of`,
+// delta = (mu'_of - mu'_at) + s_k L -- the one place every kernel takes delta and q from (the shift is added to
+// the difference: for a pair across the seam the sum is small and the addition exact)
+template <typename T, bool PER = false>
+__device__ __forceinline__ T q_of(const T* means, const T* conics, int64_t at, int64_t of, T* dx, T* dy, int k = 0,
+                                  T period = T(0)) {
     *dx = means[2 * of] - means[2 * at];          // delta = mu_j - mu_i with i = at, j = of
     *dy = means[2 * of + 1] - means[2 * at + 1];
+    if constexpr (PER) {
+        int kx, ky;
+        image_shift(k, kx, ky);
+        *dx += (T)kx * period;
+        *dy += (T)ky * period;
+    }
     const T a = conics[3 * of], b = conics[3 * of + 1], c = conics[3 * of + 2];
     return a * *dx * *dx + T(2) * b * *dx * *dy + c * *dy * *dy;
 }
@@ -129,17 +171,47 @@ __global__ __launch_bounds__(256) void aggregate_cast_kernel(int64_t N, const T*
 // order ascending (deterministic); no grid, no workspace traffic.  At the model's N = 1 600 this is two
 // launches of ~13 us where the grid costs six.
 constexpr int64_t AGG_BRUTE_MAX = 2048;
-template <typename T, bool BY_COLUMN>
+// PER: with both centres in the box |delta| < L per axis and every half extent below L (the two preconditions of
+// pigs_aggregate_lists_periodic, include/pigs_amd.h; neither is checked), only the shifts k_x in {0, -sign dx},
+// k_y in {0, -sign dy} can reach: four tests a pair.  A lane's hits are a bit set over k; entries ascend in
+// (candidate, k).
+template <typename T, bool BY_COLUMN, bool PER>
 __global__ __launch_bounds__(256) void aggregate_lists_brute_kernel(int64_t N, int64_t cap, const T* __restrict__ means,
                                                                     const T* __restrict__ conics, T q_max,
                                                                     int32_t* __restrict__ counts, int32_t* __restrict__ lists,
-                                                                    int32_t* __restrict__ overflow) {
+                                                                    int32_t* __restrict__ overflow, T period) {
     const int lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= N) return;
     int64_t n = 0;
     for (int64_t o0 = 0; o0 < N; o0 += 64) {
         const int64_t o = o0 + lane;
+        if constexpr (PER) {
+            uint32_t hit = 0;
+            if (o < N) {
+                const int64_t at = BY_COLUMN ? o : r, of = BY_COLUMN ? r : o;
+                const int sx = means[2 * of] - means[2 * at] > T(0) ? -1 : 1;
+                const int sy = means[2 * of + 1] - means[2 * at + 1] > T(0) ? -1 : 1;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const int k = image_index(t & 1 ? sx : 0, t & 2 ? sy : 0);
+                    T dx, dy;
+                    if (q_of<T, true>(means, conics, at, of, &dx, &dy, k, period) <= q_max) hit |= 1u << k;
+                }
+            }
+            const int cnt = __builtin_popcount(hit);     // 0 .. 4: three ballots give the lanes' prefix sum
+            int64_t pos = n;
+#pragma unroll
+            for (int b = 0; b < 3; ++b) {
+                const uint64_t m = __ballot((cnt >> b & 1) != 0);
+                pos += (int64_t)__builtin_popcountll(m & ((1ull << lane) - 1ull)) << b;
+                n += (int64_t)__builtin_popcountll(m) << b;
+            }
+            if (lists)
+                for (uint32_t h = hit; h != 0u; h &= h - 1u, ++pos)
+                    if (pos < cap) lists[r * cap + pos] = (int32_t)((uint32_t)o | (uint32_t)__builtin_ctz(h) << PER_SHIFT);
+            continue;
+        }
         bool in = false;
         if (o < N) {
             T dx, dy;
@@ -159,11 +231,15 @@ __global__ __launch_bounds__(256) void aggregate_lists_brute_kernel(int64_t N, i
 
 // row r = { j : q_j(mu_r) <= q_max } (BY_COLUMN: column r = { i : q_r(mu_i) <= q_max }), a slab of `cap`
 // caller indices in grid order; `lists` == nullptr: count only (counts[] then holds the full lengths).
-template <typename T, bool BY_COLUMN>
+// PER: the grid holds the wrapped centres; a row walks it around mu'_r - s_k L, a column around its ellipse's box
+// shifted by s_k L, for each of the nine shifts (order: k, then grid order).  A column shift whose box misses the
+// periodic box is skipped (exact: every centre lies in it); a row shift is skipped when its point lies further from
+// the box than the largest half extent the grid's occupied levels admit (unbounded when the top level is occupied).
+template <typename T, bool BY_COLUMN, bool PER>
 __global__ __launch_bounds__(256) void aggregate_lists_kernel(PlanView pv, int64_t N, int64_t cap, const T* __restrict__ means,
                                                               const T* __restrict__ conics, T q_max, float q_grid,
                                                               int32_t* __restrict__ counts, int32_t* __restrict__ lists,
-                                                              int32_t* __restrict__ overflow) {
+                                                              int32_t* __restrict__ overflow, T lo, T period) {
     __shared__ TravLds lds_all[4];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -173,35 +249,65 @@ __global__ __launch_bounds__(256) void aggregate_lists_kernel(PlanView pv, int64
     const uint32_t level_mask = pv.params->level_mask;
     const uint32_t loff = pv.params->level_off[lane < PLAN_MAX_LEVELS ? lane : 0];
     const float mx = (float)means[2 * r], my = (float)means[2 * r + 1];
-    float bx0, by0, bx1, by1;
+    float hx = 0.f, hy = 0.f;
     if (BY_COLUMN) {       // the box of my q <= q_grid ellipse: the centres inside my ellipse lie in it
         const T a = conics[3 * r], b = conics[3 * r + 1], c = conics[3 * r + 2];
         const T k = (T)q_grid / (a * c - b * b);
-        float hx = (float)sqrt(k * c) * 1.001f, hy = (float)sqrt(k * a) * 1.001f;
+        hx = (float)sqrt(k * c) * 1.001f; hy = (float)sqrt(k * a) * 1.001f;
         if (!(hx < 3.0e38f)) hx = 3.0e38f;      // NaN / inf (degenerate conic): everybody is a candidate
         if (!(hy < 3.0e38f)) hy = 3.0e38f;
-        bx0 = mx - hx; bx1 = mx + hx; by0 = my - hy; by1 = my + hy;
-    } else {               // my centre (a float32 neighbourhood of it: the grid holds float32 roundings)
-        const float e = 4.0e-7f * fmaxf(fmaxf(fabsf(mx), fabsf(my)), 1.0e-30f);
-        bx0 = mx - e; bx1 = mx + e; by0 = my - e; by1 = my + e;
+    }
+    // PER: the periodic box with a float32 margin, and the reach of the widest Gaussian the grid can hold below its
+    // top level (level l holds R <= s0 2^l, R >= both half extents of the q <= q_grid ellipse)
+    const float blo = (float)lo, bhi = (float)(lo + period);
+    const float bm = 1.0e-6f * (fabsf(blo) + fabsf(bhi));
+    float reach = 3.0e38f;
+    if (PER && !BY_COLUMN) {
+        const int top = 31 - __builtin_clz(level_mask | 1u);
+        if (top < pv.L - 1) reach = gg.s0 * __builtin_amdgcn_ldexpf(1.f, top) * 1.01f;
     }
     int64_t n = 0;
-    traverse(pv, gg, level_mask, loff, bx0, by0, bx1, by1, lane, lds_all[wave], true,
-             [](int, uint32_t, uint32_t) {},
-             [&](const float4, const float4, uint64_t mask, uint32_t j) __attribute__((always_inline)) {
-        bool in = false;
-        int64_t o = 0;
-        if (mask >> lane & 1ull) {
-            o = (int64_t)pv.g2o[j];
-            T dx, dy;
-            const T q = BY_COLUMN ? q_of(means, conics, o, r, &dx, &dy) : q_of(means, conics, r, o, &dx, &dy);
-            in = q <= q_max;
+    // r, and with it every box and the cull below, is the same in all 64 lanes: a wave skips or walks a shift as a
+    // whole (the ballots inside traverse and the batch callback depend on that)
+    for (int k = 0; k < (PER ? 9 : 1); ++k) {
+        float cx = mx, cy = my;
+        if constexpr (PER) {
+            int kx, ky;
+            image_shift(k, kx, ky);
+            const float sxf = (float)kx * (float)period, syf = (float)ky * (float)period;
+            cx = BY_COLUMN ? mx + sxf : mx - sxf;
+            cy = BY_COLUMN ? my + syf : my - syf;
         }
-        const uint64_t m = __ballot(in);
-        const int64_t pos = n + __builtin_popcountll(m & ((1ull << lane) - 1ull));
-        if (in && lists && pos < cap) lists[r * cap + pos] = (int32_t)o;
-        n += __builtin_popcountll(m);
-    });
+        float bx0, by0, bx1, by1;
+        if (BY_COLUMN) {
+            bx0 = cx - hx; bx1 = cx + hx; by0 = cy - hy; by1 = cy + hy;
+        } else {           // my centre (a float32 neighbourhood of it: the grid holds float32 roundings)
+            const float e = 4.0e-7f * fmaxf(fmaxf(fabsf(cx), fabsf(cy)), 1.0e-30f);
+            bx0 = cx - e; bx1 = cx + e; by0 = cy - e; by1 = cy + e;
+        }
+        if constexpr (PER) {
+            const float rc = BY_COLUMN ? bm : reach + bm;
+            if (k != 0 && (bx1 < blo - rc || bx0 > bhi + rc || by1 < blo - rc || by0 > bhi + rc)) continue;
+        }
+        traverse(pv, gg, level_mask, loff, bx0, by0, bx1, by1, lane, lds_all[wave], true,
+                 [](int, uint32_t, uint32_t) {},
+                 [&](const float4, const float4, uint64_t mask, uint32_t j) __attribute__((always_inline)) {
+            bool in = false;
+            int64_t o = 0;
+            if (mask >> lane & 1ull) {
+                o = (int64_t)pv.g2o[j];
+                T dx, dy;
+                const T q = BY_COLUMN ? q_of<T, PER>(means, conics, o, r, &dx, &dy, k, period)
+                                      : q_of<T, PER>(means, conics, r, o, &dx, &dy, k, period);
+                in = q <= q_max;
+            }
+            const uint64_t m = __ballot(in);
+            const int64_t pos = n + __builtin_popcountll(m & ((1ull << lane) - 1ull));
+            if (in && lists && pos < cap)
+                lists[r * cap + pos] = PER ? (int32_t)((uint32_t)o | (uint32_t)k << PER_SHIFT) : (int32_t)o;
+            n += __builtin_popcountll(m);
+        });
+    }
     if (lane == 0) {
         counts[r] = (int32_t)(lists && n > cap ? cap : n);
         if (lists && n > cap) atomicOr(overflow, 1);
@@ -259,13 +365,13 @@ __device__ __forceinline__ WaveSlot wave_slot(int64_t N, int wpg) {
 
 // forward: out [N, L], lse [N] (log-sum-exp of the scaled scores), acc [N, L + 2E] = [fbar ; ebar]
 // LDS row of a pair: [features_j (L) ; sin f_k dx, cos f_k dx, sin f_k dy, cos f_k dy (4F)], stride odd
-template <typename T>
+template <typename T, bool PER>
 __global__ __launch_bounds__(256) void aggregate_forward_kernel(
     int64_t N, int L, int K, int F, int64_t cap, int wpg, const T* __restrict__ means, const T* __restrict__ conics,
     const int32_t* __restrict__ counts, const int32_t* __restrict__ lists, const T* __restrict__ features,
     const T* __restrict__ transform, const T* __restrict__ queries, const T* __restrict__ keys,
     const T* __restrict__ freq, const T* __restrict__ dist, T* __restrict__ out, T* __restrict__ lse,
-    T* __restrict__ acc_out) {
+    T* __restrict__ acc_out, T period) {
     extern __shared__ unsigned char smem_raw[];
     const WaveSlot ws = wave_slot(N, wpg);
     const int lane = ws.lane;
@@ -286,9 +392,11 @@ __global__ __launch_bounds__(256) void aggregate_forward_kernel(
     const bool dens0 = c0 >= L + C4, dens1 = c1 >= L + C4;
     for (int j0 = ws.g * 64; j0 < n; j0 += 64 * wpg) {
         const bool have = j0 + lane < n;
-        const int64_t j = have ? row[j0 + lane] : i;
+        int64_t j = i;
+        int kim = 0;
+        if (have) decode_entry<PER>(row[j0 + lane], &j, &kim);
         T dx, dy;
-        const T q = q_of(means, conics, i, j, &dx, &dy);
+        const T q = q_of<T, PER>(means, conics, i, j, &dx, &dy, kim, period);
         const T g = exp_<T>(T(-0.5) * q);
         T s = 0;
         for_row<T>(keys + j * K, K, [&](int k, T v) { s += qi[k] * v; });
@@ -388,13 +496,13 @@ __device__ __forceinline__ void pair_terms(int F, T dx, T dy, T g, T s, T dfeat,
 // (kept in the wave's LDS for the pairs; written out for the column pass by the Gaussian's first wave).
 // Then d queries_i [K] and the row's share of d frequencies [F].
 // LDS row of a pair: [keys_j (K) ; frequency terms (F)].
-template <typename T>
+template <typename T, bool PER>
 __global__ __launch_bounds__(256) void aggregate_backward_rows_kernel(
     int64_t N, int L, int K, int F, int64_t cap, int wpg, const T* __restrict__ means, const T* __restrict__ conics,
     const int32_t* __restrict__ counts, const int32_t* __restrict__ lists, const T* __restrict__ features,
     const T* __restrict__ transform, const T* __restrict__ queries, const T* __restrict__ keys, const T* __restrict__ freq,
     const T* __restrict__ dist, const T* __restrict__ lse, const T* __restrict__ acc_in, const T* __restrict__ gout,
-    T* __restrict__ dacc_out, T* __restrict__ D_out, T* __restrict__ g_queries, T* __restrict__ g_freq_rows) {
+    T* __restrict__ dacc_out, T* __restrict__ D_out, T* __restrict__ g_queries, T* __restrict__ g_freq_rows, T period) {
     extern __shared__ unsigned char smem_raw[];
     const WaveSlot ws = wave_slot(N, wpg);
     const int lane = ws.lane;
@@ -425,9 +533,11 @@ __global__ __launch_bounds__(256) void aggregate_backward_rows_kernel(
     const int WC = K + F;
     for (int j0 = ws.g * 64; j0 < n; j0 += 64 * wpg) {
         const bool have = j0 + lane < n;
-        const int64_t j = have ? row[j0 + lane] : i;
+        int64_t j = i;
+        int kim = 0;
+        if (have) decode_entry<PER>(row[j0 + lane], &j, &kim);
         T dx, dy;
-        const T q = q_of(means, conics, i, j, &dx, &dy);
+        const T q = q_of<T, PER>(means, conics, i, j, &dx, &dy, kim, period);
         const T g = exp_<T>(T(-0.5) * q);
         wave_lds_fence();
         T* xr = X + (size_t)lane * xs;
@@ -460,12 +570,12 @@ __global__ __launch_bounds__(256) void aggregate_backward_rows_kernel(
 
 // backward by columns: d features_j [L] and d keys_j [K], gathered over the rows i that hold j.
 // LDS row of a pair: [dfbar_i (L) ; queries_i (K)]
-template <typename T>
+template <typename T, bool PER>
 __global__ __launch_bounds__(256) void aggregate_backward_cols_kernel(
     int64_t N, int L, int K, int F, int64_t cap, int wpg, const T* __restrict__ means, const T* __restrict__ conics,
     const int32_t* __restrict__ counts, const int32_t* __restrict__ lists, const T* __restrict__ features,
     const T* __restrict__ queries, const T* __restrict__ keys, const T* __restrict__ freq, const T* __restrict__ lse,
-    const T* __restrict__ dacc, const T* __restrict__ D, T* __restrict__ g_features, T* __restrict__ g_keys) {
+    const T* __restrict__ dacc, const T* __restrict__ D, T* __restrict__ g_features, T* __restrict__ g_keys, T period) {
     extern __shared__ unsigned char smem_raw[];
     const WaveSlot ws = wave_slot(N, wpg);
     const int lane = ws.lane;
@@ -483,9 +593,11 @@ __global__ __launch_bounds__(256) void aggregate_backward_cols_kernel(
     const int WC = L + K;
     for (int s0 = ws.g * 64; s0 < n; s0 += 64 * wpg) {
         const bool have = s0 + lane < n;
-        const int64_t i = have ? col[s0 + lane] : j;
+        int64_t i = j;
+        int kim = 0;
+        if (have) decode_entry<PER>(col[s0 + lane], &i, &kim);
         T dx, dy;
-        const T q = q_of(means, conics, i, j, &dx, &dy);
+        const T q = q_of<T, PER>(means, conics, i, j, &dx, &dy, kim, period);
         const T g = exp_<T>(T(-0.5) * q);
         const T* di = dacc + i * W;
         wave_lds_fence();
@@ -583,17 +695,18 @@ size_t aggregate_workspace_bytes(int dtype, int64_t N) {
 // arithmetic rounds: a generous margin costs a few candidates, nothing else.
 static float grid_cutoff(int dtype, double q_max) { return (float)(q_max * (dtype == PIGS_F64 ? 1.05 : 1.02) + 1e-3); }
 
-template <typename T>
+template <typename T, bool PER>
 static int aggregate_lists_t(int dtype, int64_t N, int64_t cap, const void* means, const void* conics, double q_max,
                              void* workspace, size_t workspace_bytes, int flags, int32_t* row_counts, int32_t* row_lists,
-                             int32_t* col_counts, int32_t* col_lists, int32_t* overflow, hipStream_t stream) {
+                             int32_t* col_counts, int32_t* col_lists, int32_t* overflow, double lo, double period,
+                             hipStream_t stream) {
     const dim3 grid((unsigned)((N + 3) / 4)), block(256);
     if (N <= AGG_BRUTE_MAX) {
         clear_hip_error();
-        hipLaunchKernelGGL((aggregate_lists_brute_kernel<T, false>), grid, block, 0, stream, N, cap, (const T*)means,
-                           (const T*)conics, (T)q_max, row_counts, row_lists, overflow);
-        hipLaunchKernelGGL((aggregate_lists_brute_kernel<T, true>), grid, block, 0, stream, N, cap, (const T*)means,
-                           (const T*)conics, (T)q_max, col_counts, col_lists, overflow);
+        hipLaunchKernelGGL((aggregate_lists_brute_kernel<T, false, PER>), grid, block, 0, stream, N, cap, (const T*)means,
+                           (const T*)conics, (T)q_max, row_counts, row_lists, overflow, (T)period);
+        hipLaunchKernelGGL((aggregate_lists_brute_kernel<T, true, PER>), grid, block, 0, stream, N, cap, (const T*)means,
+                           (const T*)conics, (T)q_max, col_counts, col_lists, overflow, (T)period);
         return launch_status();
     }
     const size_t need = aggregate_workspace_bytes(dtype, N);
@@ -619,21 +732,24 @@ static int aggregate_lists_t(int dtype, int64_t N, int64_t cap, const void* mean
     }
     const PlanView pv = aggregate_grid_view(grid_ws, N, q_grid);
     clear_hip_error();
-    hipLaunchKernelGGL((aggregate_lists_kernel<T, false>), grid, block, 0, stream, pv, N, cap, (const T*)means, (const T*)conics,
-                       (T)q_max, q_grid, row_counts, row_lists, overflow);
-    hipLaunchKernelGGL((aggregate_lists_kernel<T, true>), grid, block, 0, stream, pv, N, cap, (const T*)means, (const T*)conics,
-                       (T)q_max, q_grid, col_counts, col_lists, overflow);
+    hipLaunchKernelGGL((aggregate_lists_kernel<T, false, PER>), grid, block, 0, stream, pv, N, cap, (const T*)means,
+                       (const T*)conics, (T)q_max, q_grid, row_counts, row_lists, overflow, (T)lo, (T)period);
+    hipLaunchKernelGGL((aggregate_lists_kernel<T, true, PER>), grid, block, 0, stream, pv, N, cap, (const T*)means,
+                       (const T*)conics, (T)q_max, q_grid, col_counts, col_lists, overflow, (T)lo, (T)period);
     return launch_status();
 }
 
+// period > 0: the periodic lists on the torus [lo, lo + period)^2 (means wrapped into it by the caller); 0: the plain ones
 int aggregate_lists(int dtype, int64_t N, int64_t cap, const void* means, const void* conics, double q_max, void* workspace,
                     size_t workspace_bytes, int flags, int32_t* row_counts, int32_t* row_lists, int32_t* col_counts,
-                    int32_t* col_lists, int32_t* overflow, hipStream_t stream) {
+                    int32_t* col_lists, int32_t* overflow, hipStream_t stream, double lo, double period) {
     if (N == 0) return PIGS_OK;
-    return dtype == PIGS_F32 ? aggregate_lists_t<float>(dtype, N, cap, means, conics, q_max, workspace, workspace_bytes, flags,
-                                                        row_counts, row_lists, col_counts, col_lists, overflow, stream)
-                             : aggregate_lists_t<double>(dtype, N, cap, means, conics, q_max, workspace, workspace_bytes, flags,
-                                                         row_counts, row_lists, col_counts, col_lists, overflow, stream);
+#define PIGS_AGG_LISTS(T, PER)                                                                                              \
+    aggregate_lists_t<T, PER>(dtype, N, cap, means, conics, q_max, workspace, workspace_bytes, flags, row_counts, row_lists, \
+                              col_counts, col_lists, overflow, lo, period, stream)
+    if (period > 0) return dtype == PIGS_F32 ? PIGS_AGG_LISTS(float, true) : PIGS_AGG_LISTS(double, true);
+    return dtype == PIGS_F32 ? PIGS_AGG_LISTS(float, false) : PIGS_AGG_LISTS(double, false);
+#undef PIGS_AGG_LISTS
 }
 
 // LDS of a sampling kernel: four wave regions of `region` values; beyond 64 KB the launch has to ask for it.
@@ -649,15 +765,15 @@ static size_t rows_region(int stride) { return (size_t)(64 * stride > PART ? 64 
 // (split every Gaussian's rounds over four waves); many Gaussians are a throughput problem (no idle waves)
 static int waves_per_gaussian(int64_t N) { return N <= 4096 ? 4 : N <= 8192 ? 2 : 1; }
 
-template <typename T>
+template <typename T, bool PER>
 static int aggregate_forward_t(const AggregateArgs& a, hipStream_t stream) {
-    const size_t lds = sampling_lds(aggregate_forward_kernel<T>, sizeof(T), rows_region((a.L + 4 * a.F) | 1));
+    const size_t lds = sampling_lds(aggregate_forward_kernel<T, PER>, sizeof(T), rows_region((a.L + 4 * a.F) | 1));
     const int wpg = waves_per_gaussian(a.N), gpw = 4 / wpg;
     clear_hip_error();
-    hipLaunchKernelGGL((aggregate_forward_kernel<T>), dim3((unsigned)((a.N + gpw - 1) / gpw)), dim3(256), lds, stream, a.N, a.L, a.K,
+    hipLaunchKernelGGL((aggregate_forward_kernel<T, PER>), dim3((unsigned)((a.N + gpw - 1) / gpw)), dim3(256), lds, stream, a.N, a.L, a.K,
                        a.F, a.cap, wpg, (const T*)a.means, (const T*)a.conics, a.row_counts, a.row_lists, (const T*)a.features,
                        (const T*)a.transform, (const T*)a.queries, (const T*)a.keys, (const T*)a.frequencies,
-                       (const T*)a.distance_transform, (T*)a.out, (T*)a.lse, (T*)a.acc);
+                       (const T*)a.distance_transform, (T*)a.out, (T*)a.lse, (T*)a.acc, (T)a.period);
     return launch_status();
 }
 
@@ -667,14 +783,14 @@ size_t aggregate_backward_scratch_bytes(int dtype, int64_t N, int L, int F) {
     return align_up(e * (size_t)N * (size_t)(W + 1 + F), 256);      // dacc [N][W], D [N], per-row d frequencies [N][F]
 }
 
-template <typename T>
+template <typename T, bool PER>
 static int aggregate_backward_t(const AggregateArgs& a, hipStream_t stream) {
     const int E = 4 * a.F + 1, W = a.L + 2 * E;
     T* dacc = (T*)a.scratch;
     T* D = dacc + (size_t)a.N * W;
     T* gfr = D + a.N;
-    const size_t lds_r = sampling_lds(aggregate_backward_rows_kernel<T>, sizeof(T), PART + rows_region((a.K + a.F) | 1));
-    const size_t lds_c = sampling_lds(aggregate_backward_cols_kernel<T>, sizeof(T), rows_region((a.L + a.K) | 1));
+    const size_t lds_r = sampling_lds(aggregate_backward_rows_kernel<T, PER>, sizeof(T), PART + rows_region((a.K + a.F) | 1));
+    const size_t lds_c = sampling_lds(aggregate_backward_cols_kernel<T, PER>, sizeof(T), rows_region((a.L + a.K) | 1));
     const int wpg = waves_per_gaussian(a.N), gpw = 4 / wpg;
     const dim3 grid((unsigned)((a.N + gpw - 1) / gpw)), block(256);
     // the sums over N: one split per ~2048 Gaussians (a single split is a plain, deterministic sum)
@@ -686,15 +802,15 @@ static int aggregate_backward_t(const AggregateArgs& a, hipStream_t stream) {
         hipLaunchKernelGGL((aggregate_zero_kernel<T>), dim3((unsigned)((mx + 255) / 256)), dim3(256), 0, stream, (T*)a.g_transform,
                            (int64_t)a.L * a.L, (T*)a.g_distance_transform, (int64_t)a.L * 2 * E, (T*)a.g_frequencies, (int64_t)a.F);
     }
-    hipLaunchKernelGGL((aggregate_backward_rows_kernel<T>), grid, block, lds_r, stream, a.N, a.L, a.K, a.F,
+    hipLaunchKernelGGL((aggregate_backward_rows_kernel<T, PER>), grid, block, lds_r, stream, a.N, a.L, a.K, a.F,
                        a.cap, wpg, (const T*)a.means, (const T*)a.conics, a.row_counts, a.row_lists, (const T*)a.features,
                        (const T*)a.transform, (const T*)a.queries, (const T*)a.keys, (const T*)a.frequencies,
                        (const T*)a.distance_transform, (const T*)a.lse, (const T*)a.acc, (const T*)a.gout, dacc, D,
-                       (T*)a.g_queries, gfr);
-    hipLaunchKernelGGL((aggregate_backward_cols_kernel<T>), grid, block, lds_c, stream, a.N, a.L, a.K, a.F,
+                       (T*)a.g_queries, gfr, (T)a.period);
+    hipLaunchKernelGGL((aggregate_backward_cols_kernel<T, PER>), grid, block, lds_c, stream, a.N, a.L, a.K, a.F,
                        a.cap, wpg, (const T*)a.means, (const T*)a.conics, a.col_counts, a.col_lists, (const T*)a.features,
                        (const T*)a.queries, (const T*)a.keys, (const T*)a.frequencies, (const T*)a.lse, (const T*)dacc,
-                       (const T*)D, (T*)a.g_features, (T*)a.g_keys);
+                       (const T*)D, (T*)a.g_features, (T*)a.g_keys, (T)a.period);
     hipLaunchKernelGGL((aggregate_outer_kernel<T>), dim3((unsigned)((W + a.F) * splits)), dim3(256), 0, stream, a.N, a.L, a.F, splits,
                        (const T*)a.gout, (const T*)a.acc, (const T*)gfr, (T*)a.g_transform, (T*)a.g_distance_transform,
                        (T*)a.g_frequencies);
@@ -703,12 +819,14 @@ static int aggregate_backward_t(const AggregateArgs& a, hipStream_t stream) {
 
 int aggregate_forward(const AggregateArgs& a, hipStream_t stream) {
     if (a.N == 0) return PIGS_OK;
-    return a.dtype == PIGS_F32 ? aggregate_forward_t<float>(a, stream) : aggregate_forward_t<double>(a, stream);
+    if (a.period > 0) return a.dtype == PIGS_F32 ? aggregate_forward_t<float, true>(a, stream) : aggregate_forward_t<double, true>(a, stream);
+    return a.dtype == PIGS_F32 ? aggregate_forward_t<float, false>(a, stream) : aggregate_forward_t<double, false>(a, stream);
 }
 
 int aggregate_backward(const AggregateArgs& a, hipStream_t stream) {
     if (a.N == 0) return PIGS_OK;
-    return a.dtype == PIGS_F32 ? aggregate_backward_t<float>(a, stream) : aggregate_backward_t<double>(a, stream);
+    if (a.period > 0) return a.dtype == PIGS_F32 ? aggregate_backward_t<float, true>(a, stream) : aggregate_backward_t<double, true>(a, stream);
+    return a.dtype == PIGS_F32 ? aggregate_backward_t<float, false>(a, stream) : aggregate_backward_t<double, false>(a, stream);
 }
 
 }  // namespace pigs

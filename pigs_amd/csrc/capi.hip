@@ -218,32 +218,78 @@ size_t pigs_aggregate_workspace_bytes(int dtype, int64_t N) {
     return aggregate_workspace_bytes(dtype, N);
 }
 
-int pigs_aggregate_lists(int dtype, int64_t N, int64_t cap, const void* means, const void* conics, double q_max,
-                         void* workspace, size_t workspace_bytes, int flags, int32_t* row_counts, int32_t* row_lists,
-                         int32_t* col_counts, int32_t* col_lists, int32_t* overflow, void* stream) {
+// the periodic entry points: argument checks before any HIP call (a list entry is j | k << 28)
+static int periodic_box_ok(int dtype, int64_t N, double lo, double period) {
+    if (dtype != PIGS_F32 && dtype != PIGS_F64) return PIGS_ERR_UNSUPPORTED;
+    if (!std::isfinite(lo) || !std::isfinite(period) || !(period > 0) || !std::isfinite(lo + period)) return PIGS_ERR_INVALID;
+    if (N >= (1LL << 28)) return PIGS_ERR_UNSUPPORTED;
+    return PIGS_OK;
+}
+
+static int aggregate_lists_checked(int dtype, int64_t N, int64_t cap, const void* means, const void* conics, double q_max,
+                                   double lo, double period, void* workspace, size_t workspace_bytes, int flags,
+                                   int32_t* row_counts, int32_t* row_lists, int32_t* col_counts, int32_t* col_lists,
+                                   int32_t* overflow, void* stream) {
     if (dtype != PIGS_F32 && dtype != PIGS_F64) return PIGS_ERR_UNSUPPORTED;
     if (N < 0 || cap < 1 || !(q_max > 0)) return PIGS_ERR_INVALID;
     if ((row_lists == nullptr) != (col_lists == nullptr)) return PIGS_ERR_INVALID;
     if (N > 0 && (!means || !conics || !row_counts || !col_counts || (row_lists && !overflow))) return PIGS_ERR_INVALID;
     return aggregate_lists(dtype, N, cap, means, conics, q_max, workspace, workspace_bytes, flags, row_counts, row_lists,
-                           col_counts, col_lists, overflow, (hipStream_t)stream);
+                           col_counts, col_lists, overflow, (hipStream_t)stream, lo, period);
 }
 
-int pigs_aggregate_forward(int dtype, int64_t N, int64_t cap, int L, int K, int F, const void* means, const void* conics,
-                           const int32_t* row_counts, const int32_t* row_lists, const void* features,
-                           const void* transform, const void* queries, const void* keys, const void* frequencies,
-                           const void* distance_transform, void* out, void* lse, void* acc, void* stream) {
+int pigs_aggregate_lists(int dtype, int64_t N, int64_t cap, const void* means, const void* conics, double q_max,
+                         void* workspace, size_t workspace_bytes, int flags, int32_t* row_counts, int32_t* row_lists,
+                         int32_t* col_counts, int32_t* col_lists, int32_t* overflow, void* stream) {
+    return aggregate_lists_checked(dtype, N, cap, means, conics, q_max, 0.0, 0.0, workspace, workspace_bytes, flags, row_counts,
+                                   row_lists, col_counts, col_lists, overflow, stream);
+}
+
+int pigs_aggregate_lists_periodic(int dtype, int64_t N, int64_t cap, const void* means, const void* conics, double q_max,
+                                  double lo, double period, void* workspace, size_t workspace_bytes, int flags,
+                                  int32_t* row_counts, int32_t* row_lists, int32_t* col_counts, int32_t* col_lists,
+                                  int32_t* overflow, void* stream) {
+    const int rc = periodic_box_ok(dtype, N, lo, period);
+    if (rc != PIGS_OK) return rc;
+    return aggregate_lists_checked(dtype, N, cap, means, conics, q_max, lo, period, workspace, workspace_bytes, flags, row_counts,
+                                   row_lists, col_counts, col_lists, overflow, stream);
+}
+
+static int aggregate_forward_checked(int dtype, int64_t N, int64_t cap, int L, int K, int F, double period, const void* means,
+                                     const void* conics, const int32_t* row_counts, const int32_t* row_lists,
+                                     const void* features, const void* transform, const void* queries, const void* keys,
+                                     const void* frequencies, const void* distance_transform, void* out, void* lse, void* acc,
+                                     void* stream) {
     const int rc = aggregate_sizes_ok(dtype, N, cap, L, K, F);
     if (rc != PIGS_OK) return rc;
     if (N > 0 && (!means || !conics || !row_counts || !row_lists || !features || !transform || !queries || !keys ||
                   (F > 0 && !frequencies) || !distance_transform || !out || !lse || !acc))
         return PIGS_ERR_INVALID;
     AggregateArgs a{};
-    a.dtype = dtype; a.N = N; a.cap = cap; a.L = L; a.K = K; a.F = F;
+    a.dtype = dtype; a.N = N; a.cap = cap; a.L = L; a.K = K; a.F = F; a.period = period;
     a.means = means; a.conics = conics; a.row_counts = row_counts; a.row_lists = row_lists;
     a.features = features; a.transform = transform; a.queries = queries; a.keys = keys; a.frequencies = frequencies;
     a.distance_transform = distance_transform; a.out = out; a.lse = lse; a.acc = acc;
     return aggregate_forward(a, (hipStream_t)stream);
+}
+
+int pigs_aggregate_forward(int dtype, int64_t N, int64_t cap, int L, int K, int F, const void* means, const void* conics,
+                           const int32_t* row_counts, const int32_t* row_lists, const void* features,
+                           const void* transform, const void* queries, const void* keys, const void* frequencies,
+                           const void* distance_transform, void* out, void* lse, void* acc, void* stream) {
+    return aggregate_forward_checked(dtype, N, cap, L, K, F, 0.0, means, conics, row_counts, row_lists, features, transform,
+                                     queries, keys, frequencies, distance_transform, out, lse, acc, stream);
+}
+
+int pigs_aggregate_forward_periodic(int dtype, int64_t N, int64_t cap, int L, int K, int F, double period, const void* means,
+                                    const void* conics, const int32_t* row_counts, const int32_t* row_lists,
+                                    const void* features, const void* transform, const void* queries, const void* keys,
+                                    const void* frequencies, const void* distance_transform, void* out, void* lse, void* acc,
+                                    void* stream) {
+    const int rc = periodic_box_ok(dtype, N, 0.0, period);
+    if (rc != PIGS_OK) return rc;
+    return aggregate_forward_checked(dtype, N, cap, L, K, F, period, means, conics, row_counts, row_lists, features, transform,
+                                     queries, keys, frequencies, distance_transform, out, lse, acc, stream);
 }
 
 size_t pigs_aggregate_backward_scratch_bytes(int dtype, int64_t N, int L, int F) {
@@ -251,7 +297,7 @@ size_t pigs_aggregate_backward_scratch_bytes(int dtype, int64_t N, int L, int F)
     return aggregate_backward_scratch_bytes(dtype, N, L, F);
 }
 
-int pigs_aggregate_backward(int dtype, int64_t N, int64_t cap, int L, int K, int F, const void* means,
+static int aggregate_backward_checked(int dtype, int64_t N, int64_t cap, int L, int K, int F, double period, const void* means,
                             const void* conics, const int32_t* row_counts, const int32_t* row_lists,
                             const int32_t* col_counts, const int32_t* col_lists, const void* features,
                             const void* transform, const void* queries, const void* keys, const void* frequencies,
@@ -266,7 +312,7 @@ int pigs_aggregate_backward(int dtype, int64_t N, int64_t cap, int L, int K, int
         return PIGS_ERR_INVALID;
     if (N > 0 && scratch_bytes < aggregate_backward_scratch_bytes(dtype, N, L, F)) return PIGS_ERR_WORKSPACE;
     AggregateArgs a{};
-    a.dtype = dtype; a.N = N; a.cap = cap; a.L = L; a.K = K; a.F = F;
+    a.dtype = dtype; a.N = N; a.cap = cap; a.L = L; a.K = K; a.F = F; a.period = period;
     a.means = means; a.conics = conics; a.row_counts = row_counts; a.row_lists = row_lists;
     a.col_counts = col_counts; a.col_lists = col_lists;
     a.features = features; a.transform = transform; a.queries = queries; a.keys = keys; a.frequencies = frequencies;
@@ -275,6 +321,35 @@ int pigs_aggregate_backward(int dtype, int64_t N, int64_t cap, int L, int K, int
     a.g_features = g_features; a.g_transform = g_transform; a.g_queries = g_queries; a.g_keys = g_keys;
     a.g_frequencies = g_frequencies; a.g_distance_transform = g_distance_transform;
     return aggregate_backward(a, (hipStream_t)stream);
+}
+
+int pigs_aggregate_backward(int dtype, int64_t N, int64_t cap, int L, int K, int F, const void* means,
+                            const void* conics, const int32_t* row_counts, const int32_t* row_lists,
+                            const int32_t* col_counts, const int32_t* col_lists, const void* features,
+                            const void* transform, const void* queries, const void* keys, const void* frequencies,
+                            const void* distance_transform, const void* lse, const void* acc, const void* gout,
+                            void* scratch, size_t scratch_bytes, void* g_features, void* g_transform, void* g_queries,
+                            void* g_keys, void* g_frequencies, void* g_distance_transform, void* stream) {
+    return aggregate_backward_checked(dtype, N, cap, L, K, F, 0.0, means, conics, row_counts, row_lists, col_counts, col_lists,
+                                      features, transform, queries, keys, frequencies, distance_transform, lse, acc, gout, scratch,
+                                      scratch_bytes, g_features, g_transform, g_queries, g_keys, g_frequencies,
+                                      g_distance_transform, stream);
+}
+
+int pigs_aggregate_backward_periodic(int dtype, int64_t N, int64_t cap, int L, int K, int F, double period, const void* means,
+                                     const void* conics, const int32_t* row_counts, const int32_t* row_lists,
+                                     const int32_t* col_counts, const int32_t* col_lists, const void* features,
+                                     const void* transform, const void* queries, const void* keys, const void* frequencies,
+                                     const void* distance_transform, const void* lse, const void* acc, const void* gout,
+                                     void* scratch, size_t scratch_bytes, void* g_features, void* g_transform,
+                                     void* g_queries, void* g_keys, void* g_frequencies, void* g_distance_transform,
+                                     void* stream) {
+    const int rc = periodic_box_ok(dtype, N, 0.0, period);
+    if (rc != PIGS_OK) return rc;
+    return aggregate_backward_checked(dtype, N, cap, L, K, F, period, means, conics, row_counts, row_lists, col_counts, col_lists,
+                                      features, transform, queries, keys, frequencies, distance_transform, lse, acc, gout, scratch,
+                                      scratch_bytes, g_features, g_transform, g_queries, g_keys, g_frequencies,
+                                      g_distance_transform, stream);
 }
 
 }  // extern "C"

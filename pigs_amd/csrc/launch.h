@@ -34,6 +34,7 @@ struct AggregateArgs {
     int dtype;
     int64_t N, cap;
     int L, K, F;
+    double period;                                 // > 0: periodic lists (entries j | k << 28), means wrapped; 0: plain
     const void *means, *conics;
     const int32_t *row_counts, *row_lists, *col_counts, *col_lists;
     const void *features, *transform, *queries, *keys, *frequencies, *distance_transform;
@@ -46,7 +47,7 @@ size_t aggregate_backward_scratch_bytes(int dtype, int64_t N, int L, int F);
 size_t aggregate_workspace_bytes(int dtype, int64_t N);
 int aggregate_lists(int dtype, int64_t N, int64_t cap, const void* means, const void* conics, double q_max, void* workspace,
                     size_t workspace_bytes, int flags, int32_t* row_counts, int32_t* row_lists, int32_t* col_counts,
-                    int32_t* col_lists, int32_t* overflow, hipStream_t stream);
+                    int32_t* col_lists, int32_t* overflow, hipStream_t stream, double lo = 0.0, double period = 0.0);
 int aggregate_forward(const AggregateArgs& a, hipStream_t stream);
 int aggregate_backward(const AggregateArgs& a, hipStream_t stream);
 

@@ -527,7 +527,12 @@ struct NeighborLists {
     at::Tensor means, conics, workspace, row_counts, col_counts, row_lists, col_lists, overflow;
     int64_t N = 0, cap = 1;
 
-    NeighborLists(const at::Tensor& means_in, const at::Tensor& conics_in, double q_max, int64_t cap_in) {
+    bool periodic = false;       // lists of the torus [lo, lo + period)^2 (entries j | k << 28); means = the wrapped centres
+    double lo = 0, period = 0;
+
+    NeighborLists(const at::Tensor& means_in, const at::Tensor& conics_in, double q_max, int64_t cap_in,
+                  const std::optional<std::pair<double, double>>& box = std::nullopt) {
+        if (box) { periodic = true; lo = box->first; period = box->second - box->first; }
         if (means_in.dim() != 2 || means_in.size(1) != 2) raise_py(PyExc_NotImplementedError, "aggregate_neighbors is implemented for d = 2");
         at::AutoGradMode no_grad(false);
         means = means_in.detach().contiguous();
@@ -544,16 +549,26 @@ struct NeighborLists {
         c10::DeviceGuard guard(means.device());
         const hipStream_t stream = current_stream(means);
         auto run = [&](int flags, int64_t cap_, bool with_lists) {
-            check(pigs_aggregate_lists(dt, N, cap_, ptr(means), ptr(conics), q_max, workspace.data_ptr(), nbytes, flags,
-                                       (int32_t*)ptr(row_counts), with_lists ? (int32_t*)ptr(row_lists) : nullptr,
-                                       (int32_t*)ptr(col_counts), with_lists ? (int32_t*)ptr(col_lists) : nullptr,
-                                       (int32_t*)ptr(overflow), stream),
-                  "pigs_aggregate_lists");
+            int32_t* rl = with_lists ? (int32_t*)ptr(row_lists) : nullptr;
+            int32_t* cl = with_lists ? (int32_t*)ptr(col_lists) : nullptr;
+            if (periodic)
+                check(pigs_aggregate_lists_periodic(dt, N, cap_, ptr(means), ptr(conics), q_max, lo, period, workspace.data_ptr(),
+                                                    nbytes, flags, (int32_t*)ptr(row_counts), rl, (int32_t*)ptr(col_counts), cl,
+                                                    (int32_t*)ptr(overflow), stream),
+                      "pigs_aggregate_lists_periodic");
+            else
+                check(pigs_aggregate_lists(dt, N, cap_, ptr(means), ptr(conics), q_max, workspace.data_ptr(), nbytes, flags,
+                                           (int32_t*)ptr(row_counts), rl, (int32_t*)ptr(col_counts), cl, (int32_t*)ptr(overflow),
+                                           stream),
+                      "pigs_aggregate_lists");
         };
         int flags = PIGS_AGGREGATE_BUILD_GRID;
         int64_t c = cap_in;
-        if (c <= 0 && N <= AGG_BRUTE_MAX) c = N > 0 ? N : 1;
-        if (c <= 0 && capturing(stream)) c = std::min<int64_t>(N, means.scalar_type() == at::kDouble ? 4096 : 8192);
+        // periodic: a j can come through several images, a row can be longer than N -- always the counting pass
+        if (c <= 0 && N <= AGG_BRUTE_MAX && !periodic) c = N > 0 ? N : 1;
+        if (c <= 0 && N > 0 && capturing(stream))
+            c = std::min<int64_t>(periodic ? 4 * N : N, means.scalar_type() == at::kDouble ? 4096 : 8192);
+        if (c <= 0 && N == 0) c = 1;
         if (c <= 0) {        // counting pass; the longest list is read back once (the one synchronisation)
             run(flags, 1, false);
             flags = 0;
@@ -598,12 +613,21 @@ struct AggregateBackward : public torch::autograd::Node {
             const size_t nbytes = pigs_aggregate_backward_scratch_bytes(dt, N, L, F);
             at::Tensor scratch = at::empty({(int64_t)nbytes}, f.options().dtype(at::kByte));
             c10::DeviceGuard guard(f.device());
-            check(pigs_aggregate_backward(dt, N, nb->cap, L, K, F, ptr(nb->means), ptr(nb->conics), (const int32_t*)ptr(nb->row_counts),
-                                          (const int32_t*)ptr(nb->row_lists), (const int32_t*)ptr(nb->col_counts),
-                                          (const int32_t*)ptr(nb->col_lists), ptr(f), ptr(tr), ptr(q), ptr(k), ptr(fr), ptr(dist),
-                                          ptr(lse), ptr(acc), ptr(gout), scratch.data_ptr(), nbytes, ptr(g_f), ptr(g_tr), ptr(g_q),
-                                          ptr(g_k), ptr(g_fr), ptr(g_dist), current_stream(f)),
-                  "pigs_aggregate_backward");
+            if (nb->periodic)
+                check(pigs_aggregate_backward_periodic(dt, N, nb->cap, L, K, F, nb->period, ptr(nb->means), ptr(nb->conics),
+                                                       (const int32_t*)ptr(nb->row_counts), (const int32_t*)ptr(nb->row_lists),
+                                                       (const int32_t*)ptr(nb->col_counts), (const int32_t*)ptr(nb->col_lists), ptr(f),
+                                                       ptr(tr), ptr(q), ptr(k), ptr(fr), ptr(dist), ptr(lse), ptr(acc), ptr(gout),
+                                                       scratch.data_ptr(), nbytes, ptr(g_f), ptr(g_tr), ptr(g_q), ptr(g_k), ptr(g_fr),
+                                                       ptr(g_dist), current_stream(f)),
+                      "pigs_aggregate_backward_periodic");
+            else
+                check(pigs_aggregate_backward(dt, N, nb->cap, L, K, F, ptr(nb->means), ptr(nb->conics), (const int32_t*)ptr(nb->row_counts),
+                                              (const int32_t*)ptr(nb->row_lists), (const int32_t*)ptr(nb->col_counts),
+                                              (const int32_t*)ptr(nb->col_lists), ptr(f), ptr(tr), ptr(q), ptr(k), ptr(fr), ptr(dist),
+                                              ptr(lse), ptr(acc), ptr(gout), scratch.data_ptr(), nbytes, ptr(g_f), ptr(g_tr), ptr(g_q),
+                                              ptr(g_k), ptr(g_fr), ptr(g_dist), current_stream(f)),
+                      "pigs_aggregate_backward");
         } else {
             g_tr.zero_(); g_fr.zero_(); g_dist.zero_();
         }
@@ -646,10 +670,17 @@ at::Tensor aggregate_apply(const std::shared_ptr<NeighborLists>& nb, const at::T
     at::Tensor out = at::empty({N, L}, opt), lse = at::empty({N}, opt), acc = at::empty({N, L + 2 * E}, opt);
     if (N > 0) {
         c10::DeviceGuard guard(c[0].device());
-        check(pigs_aggregate_forward(dtype_code(c[0]), N, nb->cap, (int)L, (int)K, (int)F, ptr(nb->means), ptr(nb->conics),
-                                     (const int32_t*)ptr(nb->row_counts), (const int32_t*)ptr(nb->row_lists), ptr(c[0]), ptr(c[1]),
-                                     ptr(c[2]), ptr(c[3]), ptr(c[4]), ptr(c[5]), ptr(out), ptr(lse), ptr(acc), current_stream(c[0])),
-              "pigs_aggregate_forward");
+        if (nb->periodic)
+            check(pigs_aggregate_forward_periodic(dtype_code(c[0]), N, nb->cap, (int)L, (int)K, (int)F, nb->period, ptr(nb->means),
+                                                  ptr(nb->conics), (const int32_t*)ptr(nb->row_counts),
+                                                  (const int32_t*)ptr(nb->row_lists), ptr(c[0]), ptr(c[1]), ptr(c[2]), ptr(c[3]),
+                                                  ptr(c[4]), ptr(c[5]), ptr(out), ptr(lse), ptr(acc), current_stream(c[0])),
+                  "pigs_aggregate_forward_periodic");
+        else
+            check(pigs_aggregate_forward(dtype_code(c[0]), N, nb->cap, (int)L, (int)K, (int)F, ptr(nb->means), ptr(nb->conics),
+                                         (const int32_t*)ptr(nb->row_counts), (const int32_t*)ptr(nb->row_lists), ptr(c[0]), ptr(c[1]),
+                                         ptr(c[2]), ptr(c[3]), ptr(c[4]), ptr(c[5]), ptr(out), ptr(lse), ptr(acc), current_stream(c[0])),
+                  "pigs_aggregate_forward");
     }
     if (out.scalar_type() != features.scalar_type()) out = out.to(features.scalar_type());
     bool need = false;
@@ -686,6 +717,8 @@ struct Core {
                                       // not to modify the samples tensor between replays (GraphedStep(static_samples=True))
     // periodic box (lo, hi), or none; set by the Python wrapper after construction, like defer_lists
     std::optional<std::pair<double, double>> periodic;
+    bool periodic_aggregate = false;  // preprocess_aggregate builds the lists of the torus (set like `periodic`)
+    std::optional<std::pair<double, double>> bound_box;      // the box the bound images were made with
     bool bound = false;
     at::Tensor means, values, conics, samples, samples_source;
     at::Tensor caller_means, caller_conics;      // the caller's N Gaussians (periodic: the bound arrays are their images)
@@ -755,6 +788,7 @@ struct Core {
         conics = conics_in.contiguous();
         caller_means = means;
         caller_conics = conics;
+        bound_box = periodic;
         if (periodic) {
             bound = false;      // a preprocess that raises leaves nothing bound
             if (d != 2) raise_py(PyExc_NotImplementedError, "periodic=(lo, hi) is implemented for d = 2");
@@ -911,8 +945,15 @@ struct Core {
     void preprocess_aggregate(int64_t cap) {
         require_inputs();
         if (means.size(1) != 2) raise_py(PyExc_NotImplementedError, "aggregate_neighbors is implemented for d = 2");
-        // the caller's N Gaussians, not the periodic images: the neighbour lists are not periodic
-        neighbors = std::make_shared<NeighborLists>(caller_means, caller_conics, (double)q_max, cap);
+        if (periodic_aggregate) {
+            if (!bound_box) raise_py(PyExc_RuntimeError, "periodic_aggregate=True: preprocess() must have run with periodic=(lo, hi)");
+            // block 0 of the bound images: the wrapped centres and their conics
+            const int64_t N = caller_means.size(0);
+            neighbors = std::make_shared<NeighborLists>(means.narrow(0, 0, N), conics.narrow(0, 0, N), (double)q_max, cap, bound_box);
+        } else {
+            // the caller's N Gaussians, not the periodic images
+            neighbors = std::make_shared<NeighborLists>(caller_means, caller_conics, (double)q_max, cap);
+        }
         if (debug) neighbors->check_overflow();
     }
 
@@ -1031,6 +1072,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def_readonly("plan3", &Core::plan3)
         .def_readwrite("defer_lists", &Core::defer_lists)
         .def_readwrite("periodic", &Core::periodic)
+        .def_readwrite("periodic_aggregate", &Core::periodic_aggregate)
         .def_readwrite("static_samples", &Core::static_samples)
         .def_property_readonly("sample_plans", [](const Core& c) { return c.sample_plans; })
         .def_property_readonly("pool_size", [](const Core& c) { return c.pool->size(); })

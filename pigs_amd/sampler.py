@@ -613,7 +613,16 @@ class GaussianSampler:
     Sigma_ii) < L with q_cut = max(q_max, q_max_backward, q_max_order3) -- debug mode (``flag``) checks this and
     raises ``ValueError``.  d = 2 only (d = 1 raises ``NotImplementedError``); dense and binned alike, the ``auto``
     rule counting the 9N images.  ``preprocess_aggregate`` / ``aggregate_neighbors`` keep working on the caller's N
-    Gaussians with the non-periodic neighbour definition: periodic neighbour lists are not implemented.
+    Gaussians with the non-periodic neighbour definition unless ``periodic_aggregate`` is set.
+
+    ``periodic_aggregate`` (extension, keyword only; default False; settable like ``periodic``; True without
+    ``periodic`` raises ``ValueError``): ``preprocess_aggregate`` builds the neighbour lists of the torus from the
+    wrapped centres (block 0 of the bound images) and ``aggregate_neighbors`` runs on them: the neighbours of i are
+    the pairs (j, image k) whose shifted ellipse reaches the wrapped centre of i, each with its own offset
+    mu'_j + s_k L - mu'_i, density and softmax entry -- the non-periodic definition on the 9N images, rows of the
+    originals; the result is invariant under a translation of all means round the torus.  A Gaussian can be met
+    through several images, so a list can be longer than N: the list size always comes from the counting pass (one
+    read-back) unless ``aggregate_cap`` is given or a capture is running (slab min(4N, 8192 / 4096 in float64)).
 
     ``host`` (extension, keyword only): ``"native"`` (default; environment override PIGS_AMD_HOST) keeps
     the sampler's state and its autograd node in the C++ torch extension ``pigs_amd/_pigs_host.so``
@@ -637,7 +646,7 @@ class GaussianSampler:
 
     def __init__(self, flag=False, *, fuse="auto", backend="auto", q_max=36.0, q_max_order3=None,
                  q_max_backward=None, reuse_samples=True, unpinned_aggregate=False, aggregate_cap=None, host=None,
-                 defer_lists=False, periodic=None):
+                 defer_lists=False, periodic=None, periodic_aggregate=False):
         if fuse not in ("auto", "all", "none"):
             raise ValueError("fuse must be 'auto', 'all' or 'none'")
         if backend not in ("auto", "dense", "binned"):
@@ -662,7 +671,11 @@ class GaussianSampler:
         self.reuse_samples = 4 if reuse_samples is True else max(0, int(reuse_samples))
         self.defer_lists = bool(defer_lists)
         self._periodic = _periodic_box(periodic)
+        self._periodic_aggregate = bool(periodic_aggregate)
+        if self._periodic_aggregate and self._periodic is None:
+            raise ValueError("periodic_aggregate=True needs periodic=(lo, hi)")
         self._st_caller = None
+        self._st_box = None
         self._static_samples = False
         self.unpinned_aggregate = bool(unpinned_aggregate)
         self.aggregate_cap = None if aggregate_cap is None else int(aggregate_cap)
@@ -682,6 +695,21 @@ class GaussianSampler:
                                                          self.reuse_samples)
             self._core.defer_lists = self.defer_lists
             self._core.periodic = self._periodic
+            self._core.periodic_aggregate = self._periodic_aggregate
+
+    @property
+    def periodic_aggregate(self):
+        """Settable: whether ``preprocess_aggregate`` builds the neighbour lists of the torus (class docstring); takes
+        effect at the next ``preprocess_aggregate``, on both hosts."""
+        return self._periodic_aggregate
+
+    @periodic_aggregate.setter
+    def periodic_aggregate(self, value):
+        if value and self._periodic is None:
+            raise ValueError("periodic_aggregate=True needs periodic=(lo, hi)")
+        self._periodic_aggregate = bool(value)
+        if self._core is not None:
+            self._core.periodic_aggregate = self._periodic_aggregate
 
     @property
     def periodic(self):
@@ -691,7 +719,10 @@ class GaussianSampler:
 
     @periodic.setter
     def periodic(self, value):
-        self._periodic = _periodic_box(value)
+        box = _periodic_box(value)
+        if box is None and self._periodic_aggregate:
+            raise ValueError("periodic_aggregate=True needs periodic=(lo, hi): clear periodic_aggregate first")
+        self._periodic = box
         if self._core is not None:
             self._core.periodic = self._periodic
 
@@ -793,6 +824,7 @@ class GaussianSampler:
                           "of means, values and conics only); use the derivative outputs instead", stacklevel=2)
         means, values, conics = means.contiguous(), values.contiguous(), conics.contiguous()
         self._st_caller = (means, conics)
+        self._st_box = self.periodic             # the box the bound images were made with
         if self.periodic is not None:
             self._st_inputs = None          # a preprocess that raises leaves nothing bound
             if d != 2:
@@ -1004,7 +1036,15 @@ class GaussianSampler:
         means, conics = self._st_caller          # the caller's N Gaussians, not the periodic images
         if means.shape[1] != 2:
             raise NotImplementedError("aggregate_neighbors is implemented for d = 2")
-        self._neighbors = aggregate.NeighborLists(means, conics, self.q_max, cap=self.aggregate_cap)
+        box = None
+        if self._periodic_aggregate:
+            if self._st_box is None:
+                raise RuntimeError("periodic_aggregate=True: preprocess() must have run with periodic=(lo, hi)")
+            # block 0 of the bound images: the wrapped centres and their conics
+            N = means.shape[0]
+            means, conics = self._st_inputs[0][:N], self._st_inputs[2][:N]
+            box = (self._st_box[0], self._st_box[1] - self._st_box[0])
+        self._neighbors = aggregate.NeighborLists(means, conics, self.q_max, cap=self.aggregate_cap, periodic=box)
         if self.debug:
             self._neighbors.check()
 
