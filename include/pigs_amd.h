@@ -216,6 +216,41 @@ int pigs_residual_backward(int dtype, int d, int c, int64_t N, int64_t M,
                            const double coeffs[4], const void* gout, void* g_means, void* g_conics, void* g_values,
                            void* plan_ws, size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes, void* stream);
 
+/*
+ * General residual in ONE launch (additive to ABI 10): per-point coefficients and an advection term,
+ *     w_i(m)   = sum_c' advect_by[i][c'] u_c'(x_m)
+ *     r[m][ch] = a0_m u_ch + sum_i a1_{m,i} d_i u_ch + aL_m lap u_ch + adv_m sum_i w_i(m) d_i u_ch - target[m][ch]
+ * -- the reference's time-blended losses (model_pn.py:794-805, IntegrationRule.TRAPEZOID; the random time weight
+ * per point of test_no_mlp.py:122-144) and the Burgers term u u_x.  Each of a0, a1, aL, adv is the HOST double of
+ * `terms` where its field pointer is NULL, else a DEVICE field in the call's dtype, contiguous: a0_pt [M],
+ * a1_pt [M][d], aL_pt [M], adv_pt [M] (per point, shared by the channels).  advect_by is d x c host constants
+ * (rows i < d, columns c' < c are read).  target [M][c] or NULL; out [M][c].
+ * aux [M][1+d][c] or NULL: the forward also writes u (row 0) and d_i u (rows 1..d) of every point there; the
+ * backward reads them to form the gradients that arrive at u and grad u through the advection term.  The backward
+ * therefore needs the aux of THE SAME forward (same inputs, same plan) whenever advection is active (adv != 0 or
+ * adv_pt), and the coefficient fields must stay unmodified between the forward and its backward.  The backward
+ * returns the gradients wrt means, conics, values (overwritten); d r / d target = -1 is the caller's; there are no
+ * gradients wrt the coefficient fields.  plan_ws == NULL: dense (d in {1,2}, c <= 4, f32 / f64); else through a built
+ * plan (d = 2, f32, c <= 2; backward with the plan's wide cut-off; on a PIGS_BUILD_FORWARD_ONLY plan the backward
+ * writes NaN gradients, as pigs_residual_backward does).
+ */
+typedef struct PigsResidualTerms {
+    double a0, a1[2], aL, adv;                   /* used where the field pointer is NULL */
+    double advect_by[2][4];                      /* B[i][c'] */
+    const void *a0_pt, *a1_pt, *aL_pt, *adv_pt;  /* device fields or NULL */
+} PigsResidualTerms;
+int pigs_residual_terms_forward(int dtype, int d, int c, int64_t N, int64_t M,
+                                const void* means, const void* conics, const void* values, const void* samples,
+                                const PigsResidualTerms* terms, const void* target, void* out, void* aux,
+                                void* plan_ws, size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes,
+                                void* stream);
+int pigs_residual_terms_backward(int dtype, int d, int c, int64_t N, int64_t M,
+                                 const void* means, const void* conics, const void* values, const void* samples,
+                                 const PigsResidualTerms* terms, const void* gout, const void* aux,
+                                 void* g_means, void* g_conics, void* g_values,
+                                 void* plan_ws, size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes,
+                                 void* stream);
+
 /* Byte offset, inside a samples / plan workspace, of a uint32 DIAGNOSTIC that a build leaves at 0 and
  * sets to non-zero when a workgroup of its in-kernel scan did not receive a predecessor's total within
  * the bounded wait and summed that predecessor's counters itself.  The result is valid either way

@@ -21,6 +21,17 @@ _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _i64 = ctypes.c_int64
 
+
+
+class PigsResidualTerms(ctypes.Structure):
+    """struct PigsResidualTerms of include/pigs_amd.h (the general residual's coefficients)"""
+    _fields_ = [("a0", ctypes.c_double), ("a1", ctypes.c_double * 2), ("aL", ctypes.c_double), ("adv", ctypes.c_double),
+                ("advect_by", (ctypes.c_double * 4) * 2),
+                ("a0_pt", _vp), ("a1_pt", _vp), ("aL_pt", _vp), ("adv_pt", _vp)]
+
+
+_terms_p = ctypes.POINTER(PigsResidualTerms)
+
 # name -> (restype, argtypes); must list every symbol include/pigs_amd.h declares
 SIGNATURES = {
     "pigs_abi_version": (_i, []),
@@ -49,6 +60,11 @@ SIGNATURES = {
                               + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
     "pigs_residual_backward": (_i, [_i, _i, _i, _i64, _i64] + [_vp] * 4 + [ctypes.POINTER(ctypes.c_double), _vp] + [_vp] * 3
                                + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
+    # the general residual (additive to ABI 10): terms, target, out, aux / terms, gout, aux, gradients
+    "pigs_residual_terms_forward": (_i, [_i, _i, _i, _i64, _i64] + [_vp] * 4 + [_terms_p, _vp, _vp, _vp]
+                                    + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
+    "pigs_residual_terms_backward": (_i, [_i, _i, _i, _i64, _i64] + [_vp] * 4 + [_terms_p, _vp, _vp] + [_vp] * 3
+                                     + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
     "pigs_periodic_images": (_i, [_i, _i, _i64, ctypes.c_double, ctypes.c_double, ctypes.c_double] + [_vp] * 6
                              + [_vp, _vp]),
     "pigs_periodic_images_backward": (_i, [_i, _i, _i64] + [_vp] * 6 + [_vp]),

@@ -182,6 +182,57 @@ int pigs_residual_backward(int dtype, int d, int c, int64_t N, int64_t M, const 
     return dense_dispatch(true, a, (hipStream_t)stream);
 }
 
+// ---- general residual (pair_math.h ORDG): per-point coefficients and an advection term
+static bool terms_advect(const PigsResidualTerms* t) { return t->adv != 0.0 || t->adv_pt != nullptr; }
+
+int pigs_residual_terms_forward(int dtype, int d, int c, int64_t N, int64_t M, const void* means, const void* conics,
+                                const void* values, const void* samples, const PigsResidualTerms* terms, const void* target,
+                                void* out, void* aux, void* plan_ws, size_t plan_ws_bytes, const void* samples_ws,
+                                size_t samples_ws_bytes, void* stream) {
+    if (!terms || (M > 0 && !out)) return PIGS_ERR_INVALID;
+    if (plan_ws) {
+        if (dtype != PIGS_F32 || d != 2) return PIGS_ERR_UNSUPPORTED;
+        void* outs[4] = {out, nullptr, nullptr, nullptr};
+        return plan_forward(plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, N, M, c, 0.f, 64, outs, (hipStream_t)stream,
+                            nullptr, target, terms, aux);
+    }
+    int rc = check_common(dtype, d, c, 1, N, M, means, conics, values, samples);
+    if (rc != PIGS_OK) return rc;
+    SampleArgs a{};
+    a.dtype = dtype; a.d = d; a.c = c; a.orders_mask = 64; a.N = N; a.M = M;
+    a.means = means; a.conics = conics; a.values = values; a.samples = samples;
+    a.out[0] = out;
+    a.target = target;
+    a.terms = terms;
+    a.aux = aux;
+    return dense_dispatch(false, a, (hipStream_t)stream);
+}
+
+int pigs_residual_terms_backward(int dtype, int d, int c, int64_t N, int64_t M, const void* means, const void* conics,
+                                 const void* values, const void* samples, const PigsResidualTerms* terms, const void* gout,
+                                 const void* aux, void* g_means, void* g_conics, void* g_values, void* plan_ws,
+                                 size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes, void* stream) {
+    if (!terms || (M > 0 && !gout) || (N > 0 && (!g_means || !g_conics || !g_values))) return PIGS_ERR_INVALID;
+    if (terms_advect(terms) && !aux) return PIGS_ERR_INVALID;
+    if (!terms_advect(terms)) aux = nullptr;      // nothing of it is needed
+    if (plan_ws) {
+        if (dtype != PIGS_F32 || d != 2) return PIGS_ERR_UNSUPPORTED;
+        const void* gs[4] = {gout, nullptr, nullptr, nullptr};
+        return plan_backward(plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, N, M, c, 0.f, 64, gs, g_means, g_conics,
+                             g_values, (hipStream_t)stream, nullptr, terms, aux);
+    }
+    int rc = check_common(dtype, d, c, 1, N, M, means, conics, values, samples);
+    if (rc != PIGS_OK) return rc;
+    SampleArgs a{};
+    a.dtype = dtype; a.d = d; a.c = c; a.orders_mask = 64; a.N = N; a.M = M;
+    a.means = means; a.conics = conics; a.values = values; a.samples = samples;
+    a.gout[0] = gout;
+    a.g_means = g_means; a.g_conics = g_conics; a.g_values = g_values;
+    a.terms = terms;
+    a.aux = const_cast<void*>(aux);
+    return dense_dispatch(true, a, (hipStream_t)stream);
+}
+
 // ---- periodic domain (ABI 10): the 3 x 3 images of every Gaussian and the fold of their gradients (periodic.hip)
 int pigs_periodic_images(int dtype, int c, int64_t N, double lo, double period, double q_cut, const void* means,
                          const void* conics, const void* values, void* img_means, void* img_conics, void* img_values,

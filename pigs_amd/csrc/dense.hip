@@ -22,7 +22,7 @@ template <typename T, int D, int C, int MASK, int NW>
 __global__ __launch_bounds__(NW * 64) void dense_forward_kernel(
     int64_t N, int64_t M, const T* __restrict__ means, const T* __restrict__ conics,
     const T* __restrict__ values, const T* __restrict__ samples, T* __restrict__ o0, T* __restrict__ o1,
-    T* __restrict__ o2, T* __restrict__ o3, Resid<T> rz) {
+    T* __restrict__ o2, T* __restrict__ o3, RzOf<T, MASK> rz) {
     using L = FwdLayout<D, C, MASK>;
     constexpr int NF = Sym<D>::NF;
     __shared__ T red[(NW > 1 ? NW - 1 : 1) * L::N * 64];
@@ -90,12 +90,44 @@ __global__ __launch_bounds__(NW * 64) void dense_backward_kernel(
     int64_t N, int64_t M, const T* __restrict__ means, const T* __restrict__ conics,
     const T* __restrict__ values, const T* __restrict__ samples, const T* __restrict__ G0,
     const T* __restrict__ G1, const T* __restrict__ G2, const T* __restrict__ G3, T* __restrict__ g_means,
-    T* __restrict__ g_conics, T* __restrict__ g_values, Resid<T> rz) {
+    T* __restrict__ g_conics, T* __restrict__ g_values, RzOf<T, MASK> rz) {
     using L = BwdLayout<D, C>;
-    constexpr int EM = MASK == ORDR ? ORDR_AS : MASK;      // a residual's backward = orders 0, 1, trace
+    constexpr int EM = bwd_mask_of(MASK);      // a residual's backward = orders 0, 1, trace
     auto load = [&](Gsym<T, D, C, EM>& G, int64_t m) {
         if constexpr (MASK == ORDR) G.load_residual(m, G0, rz);
+        else if constexpr (MASK == ORDG) G.load_terms(m, G0, rz);
         else G.load(m, G0, G1, G2, G3);
+    };
+    // the general residual: the two points' wave-uniform values (coefficients, gr, aux) are fetched field by field,
+    // so that every field's pair of loads leaves together, and only then composed
+    auto load2 = [&](Gsym<T, D, C, EM>& Ga, Gsym<T, D, C, EM>& Gb, int64_t m) {
+        if constexpr (MASK == ORDG) {
+            TermsAt<T, D> ka, kb;
+            T gra[C], grb[C], axa[(1 + D) * C], axb[(1 + D) * C];
+#pragma unroll
+            for (int ch = 0; ch < C; ++ch) { gra[ch] = G0[m * C + ch]; grb[ch] = G0[(m + 1) * C + ch]; }
+            ka.a0 = kb.a0 = rz.a0; ka.aL = kb.aL = rz.aL; ka.adv = kb.adv = rz.adv;
+#pragma unroll
+            for (int i = 0; i < D; ++i) ka.a1[i] = kb.a1[i] = rz.a1[i];
+            if (rz.a0_pt) { ka.a0 = rz.a0_pt[m]; kb.a0 = rz.a0_pt[m + 1]; }
+            if (rz.a1_pt) {
+#pragma unroll
+                for (int i = 0; i < D; ++i) { ka.a1[i] = rz.a1_pt[m * D + i]; kb.a1[i] = rz.a1_pt[(m + 1) * D + i]; }
+            }
+            if (rz.aL_pt) { ka.aL = rz.aL_pt[m]; kb.aL = rz.aL_pt[m + 1]; }
+            if (rz.adv_pt) { ka.adv = rz.adv_pt[m]; kb.adv = rz.adv_pt[m + 1]; }
+#pragma unroll
+            for (int q = 0; q < (1 + D) * C; ++q) axa[q] = axb[q] = T(0);
+            if (rz.aux) {
+#pragma unroll
+                for (int q = 0; q < (1 + D) * C; ++q) {
+                    axa[q] = rz.aux[m * (1 + D) * C + q];
+                    axb[q] = rz.aux[(m + 1) * (1 + D) * C + q];
+                }
+            }
+            Ga.form_terms(gra, ka, rz.aux != nullptr, axa, axa + C, rz);
+            Gb.form_terms(grb, kb, rz.aux != nullptr, axb, axb + C, rz);
+        }
     };
     constexpr int NF = Sym<D>::NF;
     __shared__ T red[(NW > 1 ? NW - 1 : 1) * L::N * 64];
@@ -130,8 +162,12 @@ __global__ __launch_bounds__(NW * 64) void dense_backward_kernel(
 #pragma unroll
         for (int i = 0; i < D; ++i) { s0[i] = samples[m * D + i]; s1[i] = samples[(m + 1) * D + i]; }
         Gsym<T, D, C, EM> Ga, Gb;
-        load(Ga, m);
-        load(Gb, m + 1);
+        if constexpr (MASK == ORDG) {
+            load2(Ga, Gb, m);
+        } else {
+            load(Ga, m);
+            load(Gb, m + 1);
+        }
         bwd_accumulate<T, D, C, EM, true>(acc, s0, mu, con, v, Ga);
         bwd_accumulate<T, D, C, EM, true>(acc, s1, mu, con, v, Gb);
     }
@@ -194,7 +230,7 @@ template <typename T, int D, int C, int MASK>
 __global__ __launch_bounds__(64 * ROWS_WAVES) void dense_forward_rows_kernel(
     int64_t N, int64_t M, const T* __restrict__ means, const T* __restrict__ conics, const T* __restrict__ values,
     const T* __restrict__ samples, T* __restrict__ o0, T* __restrict__ o1, T* __restrict__ o2, T* __restrict__ o3,
-    Resid<T> rz) {
+    RzOf<T, MASK> rz) {
     using L = FwdLayout<D, C, MASK>;
     constexpr int NF = Sym<D>::NF;
     constexpr int SLICES = 4 * ROWS_WAVES;
@@ -265,11 +301,11 @@ template <typename T, int D, int C, int MASK>
 __global__ __launch_bounds__(256) void dense_backward_staged_kernel(
     int64_t N, int64_t M, const T* __restrict__ means, const T* __restrict__ conics, const T* __restrict__ values,
     const T* __restrict__ samples, const T* __restrict__ G0, const T* __restrict__ G1, const T* __restrict__ G2,
-    const T* __restrict__ G3, T* __restrict__ g_means, T* __restrict__ g_conics, T* __restrict__ g_values, Resid<T> rz,
+    const T* __restrict__ G3, T* __restrict__ g_means, T* __restrict__ g_conics, T* __restrict__ g_values, RzOf<T, MASK> rz,
     int slice) {      // points per slice: 64, or 32 where 64 would leave most of the chip without a workgroup
     using L = BwdLayout<D, C>;
     constexpr int NF = Sym<D>::NF;
-    constexpr int EM = MASK == ORDR ? ORDR_AS : MASK;
+    constexpr int EM = bwd_mask_of(MASK);
     struct Pt {
         T s[D];
         Gsym<T, D, C, EM> G;
@@ -293,6 +329,7 @@ __global__ __launch_bounds__(256) void dense_backward_staged_kernel(
 #pragma unroll
         for (int k = 0; k < D; ++k) p.s[k] = samples[m * D + k];
         if constexpr (MASK == ORDR) p.G.load_residual(m, G0, rz);
+        else if constexpr (MASK == ORDG) p.G.load_terms(m, G0, rz);
         else p.G.load(m, G0, G1, G2, G3);
         pts[threadIdx.x] = p;
     }
@@ -326,6 +363,16 @@ __global__ __launch_bounds__(256) void zero_grads_kernel(uint32_t* __restrict__ 
 // Host-side launchers
 // ------------------------------------------------------------------------------------------
 
+// the coefficient block of a launch compiled for MASK (aux: the forward's output, the backward's input)
+template <typename T, int MASK>
+static RzOf<T, MASK> rz_of(const SampleArgs& a, bool backward) {
+    if constexpr (MASK == ORDG) {
+        return make_terms<T>(*a.terms, backward ? nullptr : a.target, a.aux);
+    } else {
+        return Resid<T>{(T)a.resid[0], {(T)a.resid[1], (T)a.resid[2]}, (T)a.resid[3], backward ? nullptr : (const T*)a.target};
+    }
+}
+
 template <typename T, int D, int C, int MASK>
 static int launch_dense_forward(const SampleArgs& a, hipStream_t stream) {
     const int64_t blocks = (a.M + 63) / 64;
@@ -335,7 +382,7 @@ static int launch_dense_forward(const SampleArgs& a, hipStream_t stream) {
     const T* means = (const T*)a.means; const T* conics = (const T*)a.conics;
     const T* values = (const T*)a.values; const T* samples = (const T*)a.samples;
     T* o0 = (T*)a.out[0]; T* o1 = (T*)a.out[1]; T* o2 = (T*)a.out[2]; T* o3 = (T*)a.out[3];
-    const Resid<T> rz{(T)a.resid[0], {(T)a.resid[1], (T)a.resid[2]}, (T)a.resid[3], (const T*)a.target};
+    const RzOf<T, MASK> rz = rz_of<T, MASK>(a, false);
     constexpr int NACC = FwdLayout<D, C, MASK>::N;
     // few point blocks: spread the Gaussian loop over 16 waves per workgroup
     // (a 1 024-thread workgroup leaves 128 VGPRs per wave: the wide accumulator sets -- several channels, third
@@ -394,7 +441,7 @@ static int launch_dense_backward(const SampleArgs& a, hipStream_t stream) {
         hipLaunchKernelGGL((dense_backward_staged_kernel<T, D, C, MASK>), dim3((unsigned)gx, (unsigned)((a.M + slice - 1) / slice)),
                            dim3(256), 0, stream, a.N, a.M, (const T*)a.means, (const T*)a.conics, (const T*)a.values,
                            (const T*)a.samples, (const T*)a.gout[0], (const T*)a.gout[1], (const T*)a.gout[2], (const T*)a.gout[3],
-                           gm, gc, gv, Resid<T>{(T)a.resid[0], {(T)a.resid[1], (T)a.resid[2]}, (T)a.resid[3], nullptr}, slice);
+                           gm, gc, gv, rz_of<T, MASK>(a, true), slice);
         return launch_status();
     }
     // split the point range over gridDim.y so that ~2048 workgroups exist; each wave should
@@ -408,8 +455,7 @@ static int launch_dense_backward(const SampleArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL((dense_backward_kernel<T, D, C, MASK, 4>), dim3((unsigned)gblocks, (unsigned)ysplit), dim3(256),
                        0, stream, a.N, a.M, (const T*)a.means, (const T*)a.conics, (const T*)a.values,
                        (const T*)a.samples, (const T*)a.gout[0], (const T*)a.gout[1], (const T*)a.gout[2],
-                       (const T*)a.gout[3], gm, gc, gv,
-                       Resid<T>{(T)a.resid[0], {(T)a.resid[1], (T)a.resid[2]}, (T)a.resid[3], nullptr});
+                       (const T*)a.gout[3], gm, gc, gv, rz_of<T, MASK>(a, true));
     return launch_status();
 }
 
@@ -424,7 +470,7 @@ static int dispatch_mask(bool backward, const SampleArgs& a, hipStream_t stream)
                         : launch_dense_forward<T, D, C, MK>(a, stream);
     switch (mask) {
         PIGS_CASE(1) PIGS_CASE(2) PIGS_CASE(4) PIGS_CASE(8) PIGS_CASE(7) PIGS_CASE(15) PIGS_CASE(16) PIGS_CASE(19)
-        PIGS_CASE(32)
+        PIGS_CASE(32) PIGS_CASE(64)
         default: break;
     }
 #undef PIGS_CASE

@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace pigs {
 
 constexpr int ORD0 = 1, ORD1 = 2, ORD2 = 4, ORD3 = 8;
@@ -31,6 +33,52 @@ constexpr int ORDR_AS = ORD0 | ORD1 | ORD2T;      // the order mask whose backwa
 template <typename T> struct Resid {
     T a0, a1[2], aL;
     const T* target;      // [M][c] or null
+};
+
+// THE GENERAL RESIDUAL (mask == ORDG, alone): per-point coefficients and an advection term,
+//   w_i(m)   = sum_c' B[i][c'] u_c'(x_m)
+//   r[m][ch] = a0_m u_ch + sum_i a1_{m,i} d_i u_ch + aL_m lap u_ch + adv_m sum_i w_i(m) d_i u_ch - target[m][ch]
+// -- the reference's time-blended losses (model_pn.py:794-805, IntegrationRule.TRAPEZOID; test_no_mlp.py:122-144,
+// time_samples) and its Burgers term u u_x.  The product of two sums over the Gaussians is no sum over pairs, so the
+// accumulators are those of orders 0, 1 and the trace (ORDR_AS) and the residual is composed once per point, where
+// the finished sums are stored (fwd_store).  Its backward is the ORDR_AS backward with
+//   g0[c'] = a0 gr_c' + adv sum_i B[i][c'] sum_ch gr_ch d_i u_ch,  g1[i][ch] = (a1_i + adv w_i) gr_ch,  trace = aL gr
+// formed from gr, the coefficients and the forward's aux[m][1+d][c] = (u, d_i u)  (Gsym::load_terms).
+constexpr int ORDG = 64;
+constexpr int bwd_mask_of(int MASK) { return (MASK == ORDR || MASK == ORDG) ? ORDR_AS : MASK; }
+
+template <typename T> struct Terms {
+    T a0, a1[2], aL, adv;                           // used where the field pointer is null
+    T B[2][4];                                      // advect_by[i][c']
+    const T *a0_pt, *a1_pt, *aL_pt, *adv_pt;        // per-point fields [M], [M][d], [M], [M] or null
+    const T* target;                                // [M][c] or null
+    T* aux;                                         // [M][1+d][c]: written by the forward, read by the backward; or null
+};
+// host side: the block from the C ABI's PigsResidualTerms (include/pigs_amd.h) in the launch's type
+template <typename T, typename ABI>
+inline Terms<T> make_terms(const ABI& t, const void* target, const void* aux) {
+    Terms<T> z{};
+    z.a0 = (T)t.a0; z.a1[0] = (T)t.a1[0]; z.a1[1] = (T)t.a1[1]; z.aL = (T)t.aL; z.adv = (T)t.adv;
+    for (int i = 0; i < 2; ++i)
+        for (int k = 0; k < 4; ++k) z.B[i][k] = (T)t.advect_by[i][k];
+    z.a0_pt = (const T*)t.a0_pt; z.a1_pt = (const T*)t.a1_pt; z.aL_pt = (const T*)t.aL_pt; z.adv_pt = (const T*)t.adv_pt;
+    z.target = (const T*)target;
+    z.aux = (T*)const_cast<void*>(aux);
+    return z;
+}
+// the coefficient block a kernel compiled for MASK receives
+template <typename T, int MASK> using RzOf = std::conditional_t<MASK == ORDG, Terms<T>, Resid<T>>;
+
+// the coefficients of the general residual at one point
+template <typename T, int D> struct TermsAt {
+    T a0, a1[D], aL, adv;
+    __device__ __forceinline__ void load(const Terms<T>& tz, int64_t m) {
+        a0 = tz.a0_pt ? tz.a0_pt[m] : tz.a0;
+#pragma unroll
+        for (int i = 0; i < D; ++i) a1[i] = tz.a1_pt ? tz.a1_pt[m * D + i] : tz.a1[i];
+        aL = tz.aL_pt ? tz.aL_pt[m] : tz.aL;
+        adv = tz.adv_pt ? tz.adv_pt[m] : tz.adv;
+    }
 };
 
 template <int D> struct Sym {
@@ -55,7 +103,8 @@ template <typename T> __device__ __forceinline__ T fma_(T a, T b, T c) { return 
 template <> __device__ __forceinline__ float fma_<float>(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 
 // Layout of the flat forward accumulator array for a compile-time order mask.
-template <int D, int C, int MASK> struct FwdLayout {
+template <int D, int C, int MASK_> struct FwdLayout {
+    static constexpr int MASK = MASK_ == ORDG ? ORDR_AS : MASK_;      // the general residual accumulates u, grad u, trace
     static constexpr int O0 = 0;
     static constexpr int O1 = O0 + ((MASK & ORD0) ? C : 0);
     static constexpr int O2 = O1 + ((MASK & ORD1) ? D * C : 0);
@@ -85,7 +134,11 @@ template <typename T, int D> struct Pair {
 // The order-1 accumulator holds +sum(p w); the sign is applied on store.
 template <typename T, int D, int C, int MASK>
 __device__ __forceinline__ void fwd_accumulate(T* acc, const T* s, const T* mu, const T* con, const T* v,
-                                               const Resid<T>* rz = nullptr) {
+                                               const RzOf<T, MASK>* rz = nullptr) {
+    if constexpr (MASK == ORDG) {
+        fwd_accumulate<T, D, C, ORDR_AS>(acc, s, mu, con, v);
+        return;
+    }
     using L = FwdLayout<D, C, MASK>;
     Pair<T, D> pr;
     pr.eval(s, mu, con);
@@ -179,8 +232,38 @@ __device__ __forceinline__ void store_out(T* p, T v) {
 }
 template <typename T, int D, int C, int MASK, bool STREAM = false>
 __device__ __forceinline__ void fwd_store(const T* acc, int64_t m, T* __restrict__ o0, T* __restrict__ o1,
-                                          T* __restrict__ o2, T* __restrict__ o3, const Resid<T>* rz = nullptr) {
+                                          T* __restrict__ o2, T* __restrict__ o3, const RzOf<T, MASK>* rz = nullptr) {
     using L = FwdLayout<D, C, MASK>;
+    if constexpr (MASK == ORDG) {
+        // the composing store: the point's coefficients and target meet its finished sums
+        TermsAt<T, D> k;
+        k.load(*rz, m);
+        T coef[D];      // a1_i + adv w_i
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            T w = T(0);
+#pragma unroll
+            for (int cc = 0; cc < C; ++cc) w = fma_<T>(rz->B[i][cc], acc[L::O0 + cc], w);
+            coef[i] = fma_<T>(k.adv, w, k.a1[i]);
+        }
+#pragma unroll
+        for (int ch = 0; ch < C; ++ch) {
+            T r = fma_<T>(k.aL, acc[L::O2 + ch], k.a0 * acc[L::O0 + ch]);
+#pragma unroll
+            for (int i = 0; i < D; ++i) r = fma_<T>(-coef[i], acc[L::O1 + i * C + ch], r);      // the accumulator holds -d_i u
+            store_out<STREAM>(&o0[m * C + ch], rz->target ? r - rz->target[m * C + ch] : r);
+        }
+        if (rz->aux) {
+            T* ax = rz->aux + m * (1 + D) * C;
+#pragma unroll
+            for (int ch = 0; ch < C; ++ch) store_out<STREAM>(&ax[ch], acc[L::O0 + ch]);
+#pragma unroll
+            for (int i = 0; i < D; ++i)
+#pragma unroll
+                for (int ch = 0; ch < C; ++ch) store_out<STREAM>(&ax[(1 + i) * C + ch], -acc[L::O1 + i * C + ch]);
+        }
+        return;
+    }
     if constexpr (MASK == ORDR) {
 #pragma unroll
         for (int ch = 0; ch < C; ++ch)
@@ -352,6 +435,50 @@ template <typename T, int D, int C, int MASK> struct Gsym {
 #pragma unroll
             for (int k = 0; k < Sym<D>::NF; ++k) g2[k][ch] = (k == 0 || k == Sym<D>::NF - 1) ? rz.aL * gr : T(0);
         }
+    }
+    // the incoming gradient gr [M][c] of a general residual (MASK = ORDR_AS), its coefficients k at the point and the
+    // forward's aux (u, d_i u; read when `advects`)
+    __device__ __forceinline__ void form_terms(const T* gr, const TermsAt<T, D>& k, bool advects, const T* u, const T* du,
+                                               const Terms<T>& tz) {
+        static_assert(MASK == ORDR_AS, "a residual's backward runs on orders 0, 1 and the trace");
+        T coef[D];      // a1_i + adv w_i
+#pragma unroll
+        for (int i = 0; i < D; ++i) coef[i] = k.a1[i];
+#pragma unroll
+        for (int ch = 0; ch < C; ++ch) g0[ch] = k.a0 * gr[ch];
+        if (advects) {
+#pragma unroll
+            for (int i = 0; i < D; ++i) {
+                T w = T(0), dot = T(0);      // w_i and sum_ch gr_ch d_i u_ch
+#pragma unroll
+                for (int ch = 0; ch < C; ++ch) {
+                    w = fma_<T>(tz.B[i][ch], u[ch], w);
+                    dot = fma_<T>(gr[ch], du[i * C + ch], dot);
+                }
+                coef[i] = fma_<T>(k.adv, w, coef[i]);
+                dot *= k.adv;
+#pragma unroll
+                for (int ch = 0; ch < C; ++ch) g0[ch] = fma_<T>(tz.B[i][ch], dot, g0[ch]);
+            }
+        }
+#pragma unroll
+        for (int ch = 0; ch < C; ++ch) {
+#pragma unroll
+            for (int i = 0; i < D; ++i) g1[i][ch] = coef[i] * gr[ch];
+#pragma unroll
+            for (int kk = 0; kk < Sym<D>::NF; ++kk) g2[kk][ch] = (kk == 0 || kk == Sym<D>::NF - 1) ? k.aL * gr[ch] : T(0);
+        }
+    }
+    // the same with everything read at point m (lane = point)
+    __device__ __forceinline__ void load_terms(int64_t m, const T* __restrict__ GR, const Terms<T>& tz) {
+        TermsAt<T, D> k;
+        k.load(tz, m);
+        T gr[C], ax[(1 + D) * C];
+#pragma unroll
+        for (int ch = 0; ch < C; ++ch) gr[ch] = GR[m * C + ch];
+#pragma unroll
+        for (int q = 0; q < (1 + D) * C; ++q) ax[q] = tz.aux ? tz.aux[m * (1 + D) * C + q] : T(0);
+        form_terms(gr, k, tz.aux != nullptr, ax, ax + C, tz);
     }
 };
 

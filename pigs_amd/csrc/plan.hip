@@ -1936,7 +1936,7 @@ __device__ __forceinline__ Rec rec_of(const LdsRec<C>& x) {
 // the LDS block, never used).
 template <int C, int MASK>
 __device__ __forceinline__ void evaluate_rows(float* acc, const float* s, const FwdLds& lds, int rows, int lane,
-                                              const Resid<float>& rz) {
+                                              const RzOf<float, MASK>& rz) {
     static_assert(PIGS_FWD_UNROLL == 2, "two rows per register set");
     uint32_t q = lds_addr(lds.rec) + (uint32_t)(lane >> 4) * FwdLds::GSTRIDE;
     LdsRec<C> ra[2], rb[2];
@@ -1970,7 +1970,7 @@ __device__ __forceinline__ void evaluate_rows(float* acc, const float* s, const 
 template <int C, int MASK>
 constexpr int fwd_waves() {
     constexpr int n = FwdLayout<2, C, MASK>::N;
-    return n > 12 ? 4 : n > 10 ? 5 : (C == 1 && (MASK == 7 || MASK == 19 || MASK == 1 || MASK == ORDR)) ? PIGS_FWD_WAVES : 6;
+    return n > 12 ? 4 : n > 10 ? 5 : (C == 1 && (MASK == 7 || MASK == 19 || MASK == 1 || MASK == ORDR || MASK == ORDG)) ? PIGS_FWD_WAVES : 6;
 }
 constexpr bool fwd_can_stage(int C, int MASK) { return C == 1 && (MASK == 7 || MASK == 19); }
 // staged outputs (PlanView::stage): one record per point at its original index instead of the three stores
@@ -1989,7 +1989,7 @@ __device__ __forceinline__ void stage_store(const PlanView& pv, const float* acc
 template <int C, int MASK>
 __device__ __forceinline__ void forward_points_quad(const PlanView& pv, const SamplesView& sv, uint32_t tile, uint32_t quad, int lane,
                                                     float q_f, float* __restrict__ o0, float* __restrict__ o1,
-                                                    float* __restrict__ o2, float* __restrict__ o3, const Resid<float>& rz) {
+                                                    float* __restrict__ o2, float* __restrict__ o3, const RzOf<float, MASK>& rz) {
     using L = FwdLayout<2, C, MASK>;
     const int row = lane >> 4, i = lane & 15;
     const uint32_t m = tile * TILE_POINTS + quad * 4u + (uint32_t)row;
@@ -2021,7 +2021,7 @@ __device__ __forceinline__ void forward_points_quad(const PlanView& pv, const Sa
 template <int C, int MASK>
 __device__ __forceinline__ void forward_tile(const PlanView& pv, const SamplesView& sv, uint32_t tile, int lane, FwdLds& lds,
                                              float* __restrict__ o0, float* __restrict__ o1, float* __restrict__ o2,
-                                             float* __restrict__ o3, const Resid<float>& rz) {
+                                             float* __restrict__ o3, const RzOf<float, MASK>& rz) {
     using L = FwdLayout<2, C, MASK>;
     constexpr int U = PIGS_FWD_UNROLL;
     constexpr bool CAN_STAGE = fwd_can_stage(C, MASK);
@@ -2183,7 +2183,7 @@ __device__ __forceinline__ void forward_tile(const PlanView& pv, const SamplesVi
 template <int C, int MASK>
 __global__ __launch_bounds__(64 * PIGS_FWD_WG_WAVES, (fwd_waves<C, MASK>())) void tile_forward_kernel(
     PlanView pv, SamplesView sv, float* __restrict__ o0, float* __restrict__ o1, float* __restrict__ o2,
-    float* __restrict__ o3, Resid<float> rz) {
+    float* __restrict__ o3, RzOf<float, MASK> rz) {
     constexpr uint32_t FW = PIGS_FWD_WG_WAVES;
     __shared__ FwdLds lds_all[FW];
     const int lane = threadIdx.x & 63;
@@ -2233,7 +2233,7 @@ __global__ __launch_bounds__(64 * PIGS_FWD_WG_WAVES, (fwd_waves<C, MASK>())) voi
 // ------------------------------------------------------------------------------------------
 template <int C, int MASK>
 __global__ __launch_bounds__(256) void plan_lists_forward_kernel(ListArgs a, float* __restrict__ o0, float* __restrict__ o1,
-                                                                 float* __restrict__ o2, float* __restrict__ o3, Resid<float> rz) {
+                                                                 float* __restrict__ o2, float* __restrict__ o3, RzOf<float, MASK> rz) {
     __shared__ ListsLds<LISTS_TPW> lds_all[4];
     static_assert(sizeof(FwdLds) <= sizeof(ListsLds<LISTS_TPW>), "the forward's queues live in the list build's LDS");
     const int lane = threadIdx.x & 63;
@@ -2442,14 +2442,17 @@ constexpr int bwd_waves() {
     // c = 2: the sums table has 8 floats per row (NV = 7), 47.7 KB of LDS per workgroup -> 3 workgroups per
     // CU whatever the registers allow, so every c = 2 variant asks for 3 waves (168 VGPRs: no spills in
     // the widest gradient sets either); c = 1 with order 3 the same for its registers
+    // (the general residual, c = 1: one wave less than its siblings 7 / 19 / ORDR, which fit 6 waves' 80 VGPRs only with
+    // two registers in scratch memory; at 5 waves it has none)
+    if (MASK == ORDG && C == 1) return PIGS_BWD_WAVES - 1;
     return (C == 2 || MASK == 15) ? 3 : (MASK == 7 || MASK == 19 || MASK == ORDR || MASK == 1 || MASK == 2) ? PIGS_BWD_WAVES : 4;
 }
 // this lane's point of a tile and the gradients that arrive at it (lanes behind the last point: zero)
 template <int C, int MASK>
 __device__ __forceinline__ void load_tile_point(const SamplesView& sv, uint32_t tile, int lane, const float* __restrict__ G0p,
                                                 const float* __restrict__ G1p, const float* __restrict__ G2p,
-                                                const float* __restrict__ G3p, const Resid<float>& rz, SPoint& sp, bool& valid,
-                                                Gsym<float, 2, C, (MASK == ORDR ? ORDR_AS : MASK)>& G,
+                                                const float* __restrict__ G3p, const RzOf<float, MASK>& rz, SPoint& sp, bool& valid,
+                                                Gsym<float, 2, C, bwd_mask_of(MASK)>& G,
                                                 const float4* __restrict__ stage = nullptr) {
     const uint32_t m = tile * TILE_POINTS + (uint32_t)lane;
     valid = m < sv.M;
@@ -2468,6 +2471,7 @@ __device__ __forceinline__ void load_tile_point(const SamplesView& sv, uint32_t 
             G.load((int64_t)sp.m, G0p, G1p, G2p, G3p);
         }
     } else if constexpr (MASK == ORDR) G.load_residual((int64_t)sp.m, G0p, rz);
+    else if constexpr (MASK == ORDG) G.load_terms((int64_t)sp.m, G0p, rz);
     else G.load((int64_t)sp.m, G0p, G1p, G2p, G3p);
     if (!valid) {
 #pragma unroll
@@ -2533,8 +2537,8 @@ template <int C, int MASK>
 __device__ __forceinline__ void backward_tile(const PlanView& pv, const SamplesView& sv, uint32_t tile,
                                               TileLdsBwd<BwdLayout<2, C>::N>& lds, int lane, const float* __restrict__ G0p,
                                               const float* __restrict__ G1p, const float* __restrict__ G2p,
-                                              const float* __restrict__ G3p, const Resid<float>& rz) {
-    constexpr int EM = MASK == ORDR ? ORDR_AS : MASK;      // a residual's backward = orders 0, 1, trace
+                                              const float* __restrict__ G3p, const RzOf<float, MASK>& rz) {
+    constexpr int EM = bwd_mask_of(MASK);      // a residual's backward = orders 0, 1, trace
     using BL = BwdLayout<2, C>;
     constexpr int NV = BL::N;
     constexpr int S = TileLdsBwd<NV>::S;
@@ -2603,8 +2607,8 @@ template <int C, int MASK>
 __device__ __forceinline__ void backward_points_helper(const PlanView& pv, const SamplesView& sv, uint32_t hw, uint32_t nhw, int lane,
                                                        const float* __restrict__ G0p, const float* __restrict__ G1p,
                                                        const float* __restrict__ G2p, const float* __restrict__ G3p,
-                                                       const Resid<float>& rz) {
-    constexpr int EM = MASK == ORDR ? ORDR_AS : MASK;
+                                                       const RzOf<float, MASK>& rz) {
+    constexpr int EM = bwd_mask_of(MASK);
     constexpr int NV = BwdLayout<2, C>::N;
     constexpr bool WIDE = (EM & (ORD2 | ORD3 | ORD2T)) != 0;
     const uint32_t n = pv.params->n_points;
@@ -2618,6 +2622,7 @@ __device__ __forceinline__ void backward_points_helper(const PlanView& pv, const
         const float s[2] = {sp.x, sp.y};
         Gsym<float, 2, C, EM> G;
         if constexpr (MASK == ORDR) G.load_residual((int64_t)sp.m, G0p, rz);
+        else if constexpr (MASK == ORDG) G.load_terms((int64_t)sp.m, G0p, rz);
         else G.load((int64_t)sp.m, G0p, G1p, G2p, G3p);
         // The walk in step over the whole wave (round 4): every lane meets its own (point, Gaussian) pair, and a pair's
         // NV sums leave as ONE atomic request -- lane = (pair, value), eight pairs per instruction, each a pair's 32-byte
@@ -2654,7 +2659,7 @@ __device__ __forceinline__ void backward_points_helper(const PlanView& pv, const
 template <int C, int MASK>
 __global__ __launch_bounds__(256, (bwd_waves<C, MASK>())) void tile_backward_kernel(
     PlanView pv, SamplesView sv, const float* __restrict__ G0p, const float* __restrict__ G1p,
-    const float* __restrict__ G2p, const float* __restrict__ G3p, Resid<float> rz) {
+    const float* __restrict__ G2p, const float* __restrict__ G3p, RzOf<float, MASK> rz) {
     __shared__ TileLdsBwd<BwdLayout<2, C>::N> lds_all[4];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -2683,8 +2688,8 @@ __global__ __launch_bounds__(256, (bwd_waves<C, MASK>())) void tile_backward_ker
 template <int C, int MASK>
 __global__ __launch_bounds__(256, (bwd_waves<C, MASK>())) void block_backward_kernel(
     PlanView pv, SamplesView sv, const float* __restrict__ G0p, const float* __restrict__ G1p,
-    const float* __restrict__ G2p, const float* __restrict__ G3p, Resid<float> rz) {
-    constexpr int EM = MASK == ORDR ? ORDR_AS : MASK;
+    const float* __restrict__ G2p, const float* __restrict__ G3p, RzOf<float, MASK> rz) {
+    constexpr int EM = bwd_mask_of(MASK);
     using BL = BwdLayout<2, C>;
     constexpr int NV = BL::N;
     constexpr int S = TileLdsBwd<NV>::S;
@@ -3466,7 +3471,7 @@ template <int C> static bool fused_first_compiled(int mask) { return C == 1 ? (m
 
 template <int C>
 static int plan_forward_c(const PlanView& pv_in, const SamplesView& sv, int mask, float* const* out, hipStream_t stream,
-                          const Resid<float>& rz, const ListArgs* first = nullptr) {
+                          const Resid<float>& rz, const ListArgs* first = nullptr, const Terms<float>* tz = nullptr) {
     // + the helper workgroups of the TILE_MODE_POINTS tiles (they leave at once when the plan queued none)
     const dim3 grid((sv.ntiles + PIGS_FWD_WG_WAVES - 1) / PIGS_FWD_WG_WAVES + POINT_HELPER_BLOCKS * 4 / PIGS_FWD_WG_WAVES),
         block(64 * PIGS_FWD_WG_WAVES);
@@ -3503,7 +3508,10 @@ static int plan_forward_c(const PlanView& pv_in, const SamplesView& sv, int mask
         hipLaunchKernelGGL((tile_forward_kernel<C, MK>), grid, block, 0, stream, pv, sv, out[0], out[1], out[2], \
                            out[3], rz);                                                                        \
         break;
-    if (!done) switch (mask) {
+    if (mask == ORDG) {      // the general residual: its own coefficient block (never fused with the list launch)
+        if (!tz) return PIGS_ERR_INVALID;
+        hipLaunchKernelGGL((tile_forward_kernel<C, ORDG>), grid, block, 0, stream, pv, sv, out[0], out[1], out[2], out[3], *tz);
+    } else if (!done) switch (mask) {
         PIGS_CASE(1) PIGS_CASE(2) PIGS_CASE(4) PIGS_CASE(8) PIGS_CASE(7) PIGS_CASE(15) PIGS_CASE(16) PIGS_CASE(19) PIGS_CASE(32)
         default: return PIGS_ERR_UNSUPPORTED;
     }
@@ -3518,7 +3526,7 @@ static int plan_forward_c(const PlanView& pv_in, const SamplesView& sv, int mask
 
 template <int C>
 static int plan_backward_c(const PlanView& pv_in, const SamplesView& sv, int mask, const float* const* g, float* gm,
-                           float* gc, float* gv, hipStream_t stream, const Resid<float>& rz) {
+                           float* gc, float* gv, hipStream_t stream, const Resid<float>& rz, const Terms<float>* tz = nullptr) {
     const dim3 grid((sv.ntiles + 3) / 4 + POINT_HELPER_BLOCKS), block(256);
     // points that arrive in no order fetch their incoming gradients from the staging records (PlanView::stage)
     PlanView pv = pv_in;
@@ -3542,13 +3550,24 @@ static int plan_backward_c(const PlanView& pv_in, const SamplesView& sv, int mas
         hipLaunchKernelGGL((tile_backward_kernel<C, MK>), grid, block, 0, stream, pv, sv, g[0], g[1], g[2], g[3], rz); \
         break;
 #endif
-    switch (mask) {
+    if (mask == ORDG) {
+        if (!tz) return PIGS_ERR_INVALID;
+#if PIGS_BWD_BLOCK
+        hipLaunchKernelGGL((block_backward_kernel<C, ORDG>), bgrid, block, 0, stream, pv, sv, g[0], g[1], g[2], g[3], *tz);
+#else
+        hipLaunchKernelGGL((tile_backward_kernel<C, ORDG>), grid, block, 0, stream, pv, sv, g[0], g[1], g[2], g[3], *tz);
+#endif
+    } else switch (mask) {
         PIGS_CASE(1) PIGS_CASE(2) PIGS_CASE(4) PIGS_CASE(8) PIGS_CASE(7) PIGS_CASE(15) PIGS_CASE(16) PIGS_CASE(19) PIGS_CASE(32)
         default: return PIGS_ERR_UNSUPPORTED;
     }
 #undef PIGS_CASE
     hipLaunchKernelGGL((plan_unpermute_kernel<C>), dim3((pv.N + 255) / 256), dim3(256), 0, stream, pv, gm, gc, gv);
     return launch_status();
+}
+
+static Terms<float> terms_of(const PigsResidualTerms* t, const void* target, const void* aux) {
+    return t ? make_terms<float>(*t, target, aux) : Terms<float>{};
 }
 
 static Resid<float> resid_of(const double* r, const void* target) {
@@ -3559,7 +3578,8 @@ static Resid<float> resid_of(const double* r, const void* target) {
 }
 
 int plan_forward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, int64_t N, int64_t M, int c,
-                 float q_max, int mask, void* const* out, hipStream_t stream, const double* resid, const void* target) {
+                 float q_max, int mask, void* const* out, hipStream_t stream, const double* resid, const void* target,
+                 const PigsResidualTerms* terms, void* aux) {
     if (!plan_supported(N, M, c)) return PIGS_ERR_UNSUPPORTED;
     const PlanLayout p = make_plan_layout(N, M, c);
     const SamplesLayout s = make_samples_layout(M);
@@ -3574,15 +3594,17 @@ int plan_forward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, i
     ListArgs la{};
     const bool first = defer_take(ws, d);
     if (first) la = make_list_args(p, s, ws, sws, d.q_f, d.q_wide);
-    const int rc = c == 1 ? plan_forward_c<1>(pv, sv, cm, o, stream, resid_of(resid, target), first ? &la : nullptr)
-                          : plan_forward_c<2>(pv, sv, cm, o, stream, resid_of(resid, target), first ? &la : nullptr);
+    const Terms<float> tz = terms_of(terms, target, aux);
+    const Terms<float>* tp = terms ? &tz : nullptr;
+    const int rc = c == 1 ? plan_forward_c<1>(pv, sv, cm, o, stream, resid_of(resid, target), first ? &la : nullptr, tp)
+                          : plan_forward_c<2>(pv, sv, cm, o, stream, resid_of(resid, target), first ? &la : nullptr, tp);
     if (first && rc == PIGS_OK) plan_note_points(p, ws, stream);
     return rc;
 }
 
 int plan_backward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, int64_t N, int64_t M, int c,
                   float q_max, int mask, const void* const* gout, void* g_means, void* g_conics, void* g_values,
-                  hipStream_t stream, const double* resid) {
+                  hipStream_t stream, const double* resid, const PigsResidualTerms* terms, const void* aux) {
     if (!plan_supported(N, M, c)) return PIGS_ERR_UNSUPPORTED;
     const PlanLayout p = make_plan_layout(N, M, c);
     const SamplesLayout s = make_samples_layout(M);
@@ -3602,9 +3624,11 @@ int plan_backward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, 
     const float* g[4];
     for (int k = 0; k < 4; ++k) g[k] = mask_uses_slot(mask, k) ? (const float*)gout[k] : nullptr;
     const int cm = covering_mask_of(mask);
+    const Terms<float> tz = terms_of(terms, nullptr, aux);
+    const Terms<float>* tp = terms ? &tz : nullptr;
     switch (c) {
-        case 1: return plan_backward_c<1>(pv, sv, cm, g, (float*)g_means, (float*)g_conics, (float*)g_values, stream, resid_of(resid, nullptr));
-        case 2: return plan_backward_c<2>(pv, sv, cm, g, (float*)g_means, (float*)g_conics, (float*)g_values, stream, resid_of(resid, nullptr));
+        case 1: return plan_backward_c<1>(pv, sv, cm, g, (float*)g_means, (float*)g_conics, (float*)g_values, stream, resid_of(resid, nullptr), tp);
+        case 2: return plan_backward_c<2>(pv, sv, cm, g, (float*)g_means, (float*)g_conics, (float*)g_values, stream, resid_of(resid, nullptr), tp);
     }
     return PIGS_ERR_UNSUPPORTED;
 }

@@ -518,6 +518,111 @@ at::Tensor residual_apply(const at::Tensor& means, const at::Tensor& values, con
 }
 
 // ---------------------------------------------------------------------------------------------
+// residual() with per-point coefficients and an advection term (pigs_residual_terms_*): one launch each way; the node
+// owns inputs, plan, coefficient fields and aux (u, grad u of the forward: what the advection term's backward reads).
+// ---------------------------------------------------------------------------------------------
+struct TermsHost {
+    at::Tensor fields[4];                  // a0 [M], a1 [M, d], aL [M], adv [M]: detached, contiguous, or undefined
+    double consts[5] = {0, 0, 0, 0, 0};    // a0, a1x, a1y, aL, adv where the field is undefined
+    double by[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool advects() const { return fields[3].defined() || consts[4] != 0.0; }
+    PigsResidualTerms abi() const {
+        PigsResidualTerms t{};
+        t.a0 = consts[0]; t.a1[0] = consts[1]; t.a1[1] = consts[2]; t.aL = consts[3]; t.adv = consts[4];
+        for (int i = 0; i < 2; ++i)
+            for (int k = 0; k < 4; ++k) t.advect_by[i][k] = by[4 * i + k];
+        t.a0_pt = ptr(fields[0]); t.a1_pt = ptr(fields[1]); t.aL_pt = ptr(fields[2]); t.adv_pt = ptr(fields[3]);
+        return t;
+    }
+};
+
+struct ResidualTermsBackward : public torch::autograd::Node {
+    at::Tensor means, values, conics, samples, aux;
+    uint32_t versions[4] = {0, 0, 0, 0};
+    TermsHost terms;
+    bool debug = false, has_target = false;
+    at::ScalarType target_dtype = at::kFloat;
+    std::shared_ptr<Plan> plan;
+
+    std::string name() const override { return "PigsResidualTermsBackward"; }
+    void release_variables() override {}
+
+    torch::autograd::variable_list apply(torch::autograd::variable_list&& grads) override {
+        if (means._version() != versions[0] || values._version() != versions[1] || conics._version() != versions[2] ||
+            samples._version() != versions[3])
+            throw std::runtime_error(
+                "one of the tensors handed to GaussianSampler.preprocess() has been modified in place before the "
+                "backward of a residual() output that was computed from it");
+        torch::autograd::variable_list res(has_target ? 4 : 3);
+        if (grads.empty() || !grads[0].defined()) return res;
+        at::AutoGradMode no_grad(false);
+        if (grads[0].requires_grad()) throw std::runtime_error("GaussianSampler.residual() is differentiable once");
+        if (debug && plan && plan->forward_only) throw std::logic_error("a residual() node holds a forward-only plan");
+        const at::Tensor gout = grads[0].contiguous();
+        const int64_t N = means.size(0), d = means.size(1), c = values.size(1), M = samples.size(0);
+        auto gv3 = gradient_views(means, values, conics);
+        at::Tensor g_means = gv3[0], g_values = gv3[1], g_conics = gv3[2];
+        if (N > 0 && M > 0) {
+            c10::DeviceGuard guard(means.device());
+            const hipStream_t stream = current_stream(means);
+            const PlanPtrs pp = plan_ptrs(plan.get(), stream);
+            const PigsResidualTerms t = terms.abi();
+            check(pigs_residual_terms_backward(dtype_code(means), (int)d, (int)c, N, M, ptr(means), ptr(conics), ptr(values),
+                                               ptr(samples), &t, ptr(gout), ptr(aux), ptr(g_means), ptr(g_conics), ptr(g_values),
+                                               pp.pw, pp.pb, pp.sw, pp.sb, stream),
+                  "pigs_residual_terms_backward");
+        } else {
+            g_means.zero_(); g_values.zero_(); g_conics.zero_();
+        }
+        if (debug) device_sync(means);
+        res[0] = g_means; res[1] = g_values; res[2] = g_conics;
+        if (has_target && task_should_compute_output(3)) res[3] = gout.neg().to(target_dtype);
+        return res;
+    }
+};
+
+at::Tensor residual_terms_apply(const at::Tensor& means, const at::Tensor& values, const at::Tensor& conics,
+                                const at::Tensor& samples, const TermsHost& terms, const c10::optional<at::Tensor>& target,
+                                bool debug, const std::shared_ptr<Plan>& plan) {
+    const int64_t N = means.size(0), d = means.size(1), c = values.size(1), M = samples.size(0);
+    at::Tensor tgt;
+    if (target.has_value()) {
+        at::AutoGradMode no_grad(false);
+        tgt = target->detach().to(means.scalar_type()).contiguous();
+    }
+    const bool tgrad = target.has_value() && target->requires_grad();
+    const bool differentiable =
+        at::GradMode::is_enabled() && (means.requires_grad() || values.requires_grad() || conics.requires_grad() || tgrad);
+    at::Tensor out = at::empty({M, c}, means.options());
+    at::Tensor aux;      // only when advection is active and a backward can follow
+    if (terms.advects() && differentiable && M > 0) aux = at::empty({M, 1 + d, c}, means.options());
+    if (M > 0) {
+        c10::DeviceGuard guard(means.device());
+        const hipStream_t stream = current_stream(means);
+        const PlanPtrs pp = plan_ptrs(plan.get(), stream);
+        const PigsResidualTerms t = terms.abi();
+        check(pigs_residual_terms_forward(dtype_code(means), (int)d, (int)c, N, M, ptr(means), ptr(conics), ptr(values),
+                                          ptr(samples), &t, ptr(tgt), ptr(out), ptr(aux), pp.pw, pp.pb, pp.sw, pp.sb, stream),
+              "pigs_residual_terms_forward");
+    }
+    if (debug) device_sync(means);
+    if (differentiable) {
+        std::shared_ptr<ResidualTermsBackward> node(new ResidualTermsBackward(), torch::autograd::deleteNode);
+        if (target.has_value()) node->set_next_edges(torch::autograd::collect_next_edges(means, values, conics, *target));
+        else node->set_next_edges(torch::autograd::collect_next_edges(means, values, conics));
+        node->means = means; node->values = values; node->conics = conics; node->samples = samples; node->aux = aux;
+        node->versions[0] = means._version(); node->versions[1] = values._version();
+        node->versions[2] = conics._version(); node->versions[3] = samples._version();
+        node->terms = terms;
+        node->debug = debug; node->plan = plan;
+        node->has_target = target.has_value();
+        if (target.has_value()) node->target_dtype = target->scalar_type();
+        torch::autograd::create_gradient_edge(out, node);
+    }
+    return out;
+}
+
+// ---------------------------------------------------------------------------------------------
 // preprocess_aggregate / aggregate_neighbors (model_pn.py:257-264; parity unpinned: this repository's own
 // definition, pigs_amd/csrc/aggregate.hip).  Same structure as pigs_amd/aggregate.py.
 // ---------------------------------------------------------------------------------------------
@@ -942,6 +1047,19 @@ struct Core {
         return residual_apply(means, values, conics, samples, coeffs, target, debug, plan_for(0, target));
     }
 
+    // fields: a0, a1, aL, adv as validated, detached, contiguous tensors (or None); consts: a0, a1x, a1y, aL, adv;
+    // advect_by: [2][4] row-major (the Python wrapper validates and converts)
+    at::Tensor residual_terms(const std::array<c10::optional<at::Tensor>, 4>& fields, const std::array<double, 5>& consts,
+                              const std::array<double, 8>& advect_by, const c10::optional<at::Tensor>& target) {
+        require_inputs();
+        TermsHost t;
+        for (int k = 0; k < 4; ++k)
+            if (fields[k].has_value()) t.fields[k] = *fields[k];
+        for (int k = 0; k < 5; ++k) t.consts[k] = consts[k];
+        for (int k = 0; k < 8; ++k) t.by[k] = advect_by[k];
+        return residual_terms_apply(means, values, conics, samples, t, target, debug, plan_for(0, target));
+    }
+
     void preprocess_aggregate(int64_t cap) {
         require_inputs();
         if (means.size(1) != 2) raise_py(PyExc_NotImplementedError, "aggregate_neighbors is implemented for d = 2");
@@ -1065,6 +1183,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("sample", &Core::sample)
         .def("inputs", &Core::inputs)
         .def("residual", &Core::residual, py::arg("coeffs"), py::arg("target") = c10::optional<at::Tensor>())
+        .def("residual_terms", &Core::residual_terms, py::arg("fields"), py::arg("consts"), py::arg("advect_by"),
+             py::arg("target") = c10::optional<at::Tensor>())
         .def("preprocess_aggregate", &Core::preprocess_aggregate, py::arg("cap") = -1)
         .def("aggregate_neighbors", &Core::aggregate_neighbors)
         .def_readonly("neighbors", &Core::neighbors)

@@ -453,6 +453,108 @@ class _ResidualFunction(torch.autograd.Function):
         return g_means, g_values, g_conics, None, g_target, None, None, None
 
 
+class ResidualTerms:
+    """The coefficients of a general residual() call: floats or detached device fields (a0, aL, adv: [M]; a1: d floats
+    or [M, d]) and the d x c constants ``advect_by``.  ``advects``: the advection term is active."""
+
+    def __init__(self, a0, a1, aL, adv, advect_by):
+        self.a0, self.a1, self.aL, self.adv, self.advect_by = a0, a1, aL, adv, advect_by
+        self.advects = isinstance(adv, torch.Tensor) or adv != 0.0
+
+    def struct(self):
+        t = _lib.PigsResidualTerms()
+        for name, v in (("a0", self.a0), ("aL", self.aL), ("adv", self.adv)):
+            if isinstance(v, torch.Tensor):
+                setattr(t, name + "_pt", v.data_ptr())
+            else:
+                setattr(t, name, v)
+        if isinstance(self.a1, torch.Tensor):
+            t.a1_pt = self.a1.data_ptr()
+        else:
+            for i, v in enumerate(self.a1):
+                t.a1[i] = v
+        for i, row in enumerate(self.advect_by):
+            for k, v in enumerate(row):
+                t.advect_by[i][k] = v
+        return t
+
+
+def _residual_terms_call(backward, means, values, conics, samples, terms, plan, target=None, gout=None, aux=None):
+    """pigs_residual_terms_forward / _backward on contiguous device tensors (through the plan when given)."""
+    lib = _lib.load()
+    N, d = means.shape
+    c = values.shape[1]
+    M = samples.shape[0]
+    tz = terms.struct()
+    if backward and plan is not None and M > 0 and getattr(plan, "forward_only", False):
+        plan = plan.full_for_backward(means, values, conics, samples)
+    pw = (_ptr(plan.workspace), plan.workspace.numel(), _ptr(plan.samples.workspace), plan.samples.workspace.numel()) \
+        if plan is not None else (ctypes.c_void_p(0), 0, ctypes.c_void_p(0), 0)
+    with _on_device(means.device):
+        stream = _stream(means.device)
+        if plan is not None and hasattr(plan, "note_stream"):
+            plan.note_stream(stream.value)
+        if not backward:
+            out = torch.empty((M, c), dtype=means.dtype, device=means.device)
+            if M > 0:
+                rc = lib.pigs_residual_terms_forward(_DTYPES[means.dtype], d, c, N, M, _ptr(means), _ptr(conics), _ptr(values),
+                                                     _ptr(samples), ctypes.byref(tz), _ptr(target), _ptr(out), _ptr(aux), *pw,
+                                                     stream)
+                _lib.check(rc, "pigs_residual_terms_forward")
+            return out
+        g_means, g_values, g_conics = _gradient_views(means, values, conics)
+        if N > 0:
+            if M > 0:
+                rc = lib.pigs_residual_terms_backward(_DTYPES[means.dtype], d, c, N, M, _ptr(means), _ptr(conics), _ptr(values),
+                                                      _ptr(samples), ctypes.byref(tz), _ptr(gout), _ptr(aux), _ptr(g_means),
+                                                      _ptr(g_conics), _ptr(g_values), *pw, stream)
+                _lib.check(rc, "pigs_residual_terms_backward")
+            else:
+                for g in (g_means, g_values, g_conics):
+                    g.zero_()
+        return g_means, g_values, g_conics
+
+
+class _ResidualTermsFunction(torch.autograd.Function):
+    """The general residual (per-point coefficients, advection term) in one launch; its backward is one launch too.
+    The node owns its inputs, plan, coefficient fields and ``aux`` (u and grad u of the forward, which the backward
+    of the advection term reads) like :class:`_ResidualFunction`."""
+
+    @staticmethod
+    def forward(ctx, means, values, conics, samples, target, terms, debug, plan, want_aux):
+        tgt = None if target is None else target.detach().to(means.dtype).contiguous()
+        M, d, c = samples.shape[0], means.shape[1], values.shape[1]
+        aux = torch.empty((M, 1 + d, c), dtype=means.dtype, device=means.device) if want_aux and M > 0 else None
+        out = _residual_terms_call(False, means, values, conics, samples, terms, plan, target=tgt, aux=aux)
+        if debug:
+            torch.cuda.synchronize(means.device)
+        ctx.inputs = (means, values, conics, samples)
+        ctx.versions = (means._version, values._version, conics._version, samples._version)
+        ctx.terms, ctx.aux, ctx.debug, ctx.plan = terms, aux, debug, plan
+        ctx.target_dtype = None if target is None else target.dtype
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        means, values, conics, samples = ctx.inputs
+        if (means._version, values._version, conics._version, samples._version) != ctx.versions:
+            raise RuntimeError("one of the tensors handed to GaussianSampler.preprocess() has been modified in place "
+                               "before the backward of a residual() output that was computed from it")
+        if ctx.terms.advects and ctx.aux is None and samples.shape[0] > 0:
+            raise RuntimeError("this residual() output was computed without the record its backward needs "
+                               "(no input required grad when it ran)")
+        gout = gout.contiguous()
+        if ctx.debug:
+            assert ctx.plan is None or not ctx.plan.forward_only, "a residual() node holds a forward-only plan"
+        g_means, g_values, g_conics = _residual_terms_call(True, means, values, conics, samples, ctx.terms, ctx.plan,
+                                                           gout=gout, aux=ctx.aux)
+        if ctx.debug:
+            torch.cuda.synchronize(means.device)
+        g_target = None if ctx.target_dtype is None or not ctx.needs_input_grad[4] else (-gout).to(ctx.target_dtype)
+        return g_means, g_values, g_conics, None, g_target, None, None, None, None
+
+
 class _SampleFunction(torch.autograd.Function):
     """One fused launch producing the outputs of every order in ``mask``; its backward is one
     fused launch over the outputs that received a gradient.
@@ -969,7 +1071,30 @@ class GaussianSampler:
             self._cache[TRACE] = self._cache[2].diagonal(dim1=1, dim2=2).sum(-1)
         return tuple(self._cache[o] for o in orders)
 
-    def residual(self, a0=0.0, a1=None, lap=0.0, target=None):
+    def _residual_field(self, name, v, cols):
+        """A coefficient of residual(): a float (or ``cols`` floats) stays a host constant, a tensor becomes a detached
+        contiguous device field [M] / [M, cols] in the means' dtype."""
+        means, _, _, samples = self._require_inputs()
+        M = samples.shape[0]
+        if isinstance(v, torch.Tensor):
+            if v.requires_grad:
+                raise ValueError(f"{name}: the coefficients of residual() are constants; detach() the tensor "
+                                 "(there are no gradients with respect to coefficient fields)")
+            if v.device != means.device:
+                raise RuntimeError(f"{name} must be a tensor on the sampler's device (no CPU fallback)")
+            ok = tuple(v.shape) in ((M, cols),) + (((M,),) if cols == 1 else ())
+            if not ok:
+                raise ValueError(f"{name} must have shape [{M}, {cols}]" + (f" or [{M}]" if cols == 1 else "")
+                                 + f", got {tuple(v.shape)}")
+            return v.detach().to(means.dtype).reshape(M, cols).contiguous()
+        if cols == 1 and not hasattr(v, "__len__"):
+            return float(v)
+        v = tuple(float(x) for x in (v if hasattr(v, "__len__") else (v,)))
+        if len(v) != cols:
+            raise ValueError(f"{name} must hold d = {cols} coefficients")
+        return v
+
+    def residual(self, a0=0.0, a1=None, lap=0.0, target=None, *, advect=None, advect_by=None):
         """Extension of the reference API: the linear residual
         ``r = a0 u + a1 . grad u + lap (u_xx + u_yy) - target`` as [M, c] in ONE launch (4 bytes per point and
         channel instead of the 28 of u, grad u and the Hessian), differentiable wrt means, values, conics (one
@@ -977,19 +1102,63 @@ class GaussianSampler:
         (or [M] for c = 1) or None.  The reference's diffusion loss (model_pn.py:612-617, 834-849;
         test_no_mlp.py:127-144: ``(u - u_prev) / dt - D lap u``) is
         ``sampler.residual(a0=1 / dt, lap=-D, target=u_prev / dt).pow(2).mean()``.  Binned plans evaluate the
-        backward with the wide cut-off ``q_max_backward``."""
+        backward with the wide cut-off ``q_max_backward``.
+
+        THE GENERAL FORM (per-point coefficients and an advection term; still one launch each way):
+        ``r = a0 u + a1 . grad u + lap (u_xx + u_yy) + advect (w . grad) u - target`` with
+        ``w_i = sum_c' advect_by[i][c'] u_c'``.  ``a0``, ``lap``, ``advect`` also accept a tensor of M elements
+        ([M] or [M, 1]) and ``a1`` a tensor [M, d]: fields per point, shared by the channels -- the reference's blend
+        of two time levels with a random weight per point (model_pn.py:794-805, test_no_mlp.py:122-144).
+        ``advect_by``: d x c floats; default the identity when c == d, i.e. (u . grad) u, the Burgers term.  The
+        coefficients are constants (a tensor that requires grad raises ValueError); they are cast to the means' dtype
+        and detached, and a field must not be modified in place between the call and its backward.  A call with
+        floats only and ``advect=None`` is the linear residual above, on its own kernel.  INTEGRATION.md has the
+        Burgers and trapezoid-diffusion recipes; DESIGN.md 12 the measured times against the same loss composed from
+        ``sample((0, 1, "lap"))``: a training step is 19-25 % shorter, the forward alone (``no_grad``) is SLOWER
+        (1.30x - 1.35x) when the coefficient fields are rebuilt in torch every step."""
         means, values, conics, samples = self._require_inputs()
         d, c, M = means.shape[1], values.shape[1], samples.shape[0]
-        a1 = (0.0,) * d if a1 is None else tuple(float(x) for x in (a1 if hasattr(a1, "__len__") else (a1,)))
-        if len(a1) != d:
-            raise ValueError(f"a1 must hold d = {d} coefficients")
-        coeffs = (float(a0), a1[0], a1[1] if d == 2 else 0.0, float(lap))
+        general = advect is not None or advect_by is not None or any(isinstance(v, torch.Tensor) for v in (a0, a1, lap))
+        if general:
+            f0 = self._residual_field("a0", a0, 1)
+            f1 = self._residual_field("a1", (0.0,) * d if a1 is None else a1, d)
+            fL = self._residual_field("lap", lap, 1)
+            fA = self._residual_field("advect", 0.0 if advect is None else advect, 1)
+            if advect_by is None:
+                if advect is not None and c != d:
+                    raise ValueError(f"advect with c = {c} channels in d = {d} dimensions needs advect_by (d x c floats): "
+                                     "the default, the field advecting itself, exists for c == d only")
+                B = tuple(tuple(1.0 if i == k else 0.0 for k in range(c)) for i in range(d))
+            else:
+                B = tuple(tuple(float(x) for x in row) for row in advect_by)
+                if len(B) != d or any(len(row) != c for row in B):
+                    raise ValueError(f"advect_by must be d x c = {d} x {c} floats")
+            terms = ResidualTerms(f0, f1, fL, fA, B)
+        if not general:
+            a1 = (0.0,) * d if a1 is None else tuple(float(x) for x in (a1 if hasattr(a1, "__len__") else (a1,)))
+            if len(a1) != d:
+                raise ValueError(f"a1 must hold d = {d} coefficients")
+            coeffs = (float(a0), a1[0], a1[1] if d == 2 else 0.0, float(lap))
         if target is not None:
             if not isinstance(target, torch.Tensor) or not target.is_cuda:
                 raise RuntimeError("target must be a tensor on the GPU (no CPU fallback)")
             if target.numel() != M * c:
                 raise ValueError(f"target must hold M*c = {M * c} elements, got {tuple(target.shape)}")
             target = target.reshape(M, c)
+        if general:
+            if self._core is not None:
+                consts = [0.0 if isinstance(f0, torch.Tensor) else f0, 0.0, 0.0, 0.0 if isinstance(fL, torch.Tensor) else fL,
+                          0.0 if isinstance(fA, torch.Tensor) else fA]
+                if not isinstance(f1, torch.Tensor):
+                    consts[1:1 + d] = f1
+                flat = [0.0] * 8                  # advect_by as [2][4]
+                for i, row in enumerate(B):
+                    flat[4 * i:4 * i + c] = row
+                return self._core.residual_terms([v if isinstance(v, torch.Tensor) else None for v in (f0, f1, fL, fA)],
+                                                 consts, flat, target)
+            want_aux = terms.advects and self._needs_backward(target)
+            return _ResidualTermsFunction.apply(means, values, conics, samples, target, terms, self.debug,
+                                                self._plan_for(0, target), want_aux)
         if self._core is not None:
             return self._core.residual(coeffs, target)
         return _ResidualFunction.apply(means, values, conics, samples, target, coeffs, self.debug, self._plan_for(0, target))
