@@ -373,6 +373,7 @@ static RzOf<T, MASK> rz_of(const SampleArgs& a, bool backward) {
     }
 }
 
+// tests/test_dense_matrix.py mirrors the selection of the two launchers below: a threshold changed here is changed there
 template <typename T, int D, int C, int MASK>
 static int launch_dense_forward(const SampleArgs& a, hipStream_t stream) {
     const int64_t blocks = (a.M + 63) / 64;

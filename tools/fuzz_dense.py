@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Campaign: the dense HIP path (float32 and float64) against the fp64 C oracle on the adversarial
-cases of tests/test_fuzz_gpu.py, shrunk so that the oracle stays fast (argv: n_seeds)."""
+cases of tests/test_fuzz_gpu.py, shrunk so that the oracle stays fast (argv: n_seeds).  The launch variants
+(which kernel a size takes, for every dtype, d, c and order mask) are pinned by tests/test_dense_matrix_gpu.py; this
+tool keeps the adversarial geometry at one small size."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
