@@ -251,6 +251,29 @@ int pigs_residual_terms_backward(int dtype, int d, int c, int64_t N, int64_t M,
                                  void* plan_ws, size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes,
                                  void* stream);
 
+/*
+ * The vorticity terms of a two-channel field u = (u_x, u_y) in two dimensions in ONE launch (additive to ABI 10;
+ * d = 2 and c = 2 are implied): one packed row per point,
+ *     out[m][0..6] = (u_x, u_y, div u, w, w_x, w_y, lap w),   w = d_x u_y - d_y u_x,
+ * -- the seven numbers the reference's Navier-Stokes problem keeps of orders 0..3 of its field: Model.forward
+ * (model_pn.py:650-659) and Model.sample / compute_loss (model_pn.py:770-781, 801-805, 817-849), with
+ * div = ux[:,0,0] + ux[:,1,1] (:848), w = ux[:,0,1] - ux[:,1,0] (:779), wx = uxx[...,0,1] - uxx[...,1,0] (:655, :780)
+ * and lap w = wxx[:,0,0] + wxx[:,1,1] of wxx = uxxx[...,0,1] - uxxx[...,1,0] (:656, :781, :630).  Each is a sum over
+ * the pairs: 7 accumulators and 28 B per point (float32) instead of the 30 and 120 B of orders 0..3.
+ * means [N][2], conics [N][3], values [N][2], samples [M][2]; out and gout [M][7], contiguous.  The backward is the
+ * backward of orders 0..3 with the incoming gradients formed from gout; it overwrites g_means [N][2], g_conics [N][3],
+ * g_values [N][2].  plan_ws == NULL: dense (f32 / f64, the launch variants of every other mask); else through a built
+ * plan (f32; the caller builds it with the cut-off it wants for third derivatives; backward with the plan's wide
+ * cut-off; on a PIGS_BUILD_FORWARD_ONLY plan the backward writes NaN gradients, as pigs_residual_backward does).
+ */
+int pigs_vorticity_forward(int dtype, int64_t N, int64_t M,
+                           const void* means, const void* conics, const void* values, const void* samples, void* out,
+                           void* plan_ws, size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes, void* stream);
+int pigs_vorticity_backward(int dtype, int64_t N, int64_t M,
+                            const void* means, const void* conics, const void* values, const void* samples, const void* gout,
+                            void* g_means, void* g_conics, void* g_values,
+                            void* plan_ws, size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes, void* stream);
+
 /* Byte offset, inside a samples / plan workspace, of a uint32 DIAGNOSTIC that a build leaves at 0 and
  * sets to non-zero when a workgroup of its in-kernel scan did not receive a predecessor's total within
  * the bounded wait and summed that predecessor's counters itself.  The result is valid either way

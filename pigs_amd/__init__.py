@@ -2,6 +2,7 @@
 
 Public surface:
     GaussianSampler         drop-in for ``diff_gaussian_sampling.GaussianSampler``
+    VORTICITY_COLUMNS       the column names of ``GaussianSampler.vorticity_terms()``
     covariances             fused ``build_covariances`` / ``build_full_covariances`` (gaussians.py:163-193)
     build()                 compile the HIP library (hipcc, gfx950) and the native host extension in-tree
 """
@@ -13,4 +14,7 @@ def __getattr__(name):
     if name == "GaussianSampler":
         from .sampler import GaussianSampler
         return GaussianSampler
+    if name == "VORTICITY_COLUMNS":
+        from .sampler import VORTICITY_COLUMNS
+        return VORTICITY_COLUMNS
     raise AttributeError(name)

@@ -65,6 +65,10 @@ SIGNATURES = {
                                     + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
     "pigs_residual_terms_backward": (_i, [_i, _i, _i, _i64, _i64] + [_vp] * 4 + [_terms_p, _vp, _vp] + [_vp] * 3
                                      + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
+    # the vorticity terms (additive to ABI 10; d = 2, c = 2 implied): out [M][7] / gout [M][7], gradients
+    "pigs_vorticity_forward": (_i, [_i, _i64, _i64] + [_vp] * 4 + [_vp] + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
+    "pigs_vorticity_backward": (_i, [_i, _i64, _i64] + [_vp] * 4 + [_vp] + [_vp] * 3
+                                + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
     "pigs_periodic_images": (_i, [_i, _i, _i64, ctypes.c_double, ctypes.c_double, ctypes.c_double] + [_vp] * 6
                              + [_vp, _vp]),
     "pigs_periodic_images_backward": (_i, [_i, _i, _i64] + [_vp] * 6 + [_vp]),

@@ -233,6 +233,49 @@ int pigs_residual_terms_backward(int dtype, int d, int c, int64_t N, int64_t M, 
     return dense_dispatch(true, a, (hipStream_t)stream);
 }
 
+// ---- vorticity terms (pair_math.h ORDV): (u_x, u_y, div, w, w_x, w_y, lap w) of a two-channel field, d = 2
+static SampleArgs vorticity_args(int dtype, int64_t N, int64_t M, const void* means, const void* conics, const void* values,
+                                 const void* samples) {
+    SampleArgs a{};
+    a.dtype = dtype; a.d = 2; a.c = 2; a.orders_mask = 128; a.N = N; a.M = M;
+    a.means = means; a.conics = conics; a.values = values; a.samples = samples;
+    return a;
+}
+
+int pigs_vorticity_forward(int dtype, int64_t N, int64_t M, const void* means, const void* conics, const void* values,
+                           const void* samples, void* out, void* plan_ws, size_t plan_ws_bytes, const void* samples_ws,
+                           size_t samples_ws_bytes, void* stream) {
+    if (M > 0 && !out) return PIGS_ERR_INVALID;
+    if (plan_ws) {
+        if (dtype != PIGS_F32) return PIGS_ERR_UNSUPPORTED;
+        void* outs[4] = {out, nullptr, nullptr, nullptr};
+        return plan_forward(plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, N, M, 2, 0.f, 128, outs, (hipStream_t)stream);
+    }
+    int rc = check_common(dtype, 2, 2, 1, N, M, means, conics, values, samples);
+    if (rc != PIGS_OK) return rc;
+    SampleArgs a = vorticity_args(dtype, N, M, means, conics, values, samples);
+    a.out[0] = out;
+    return dense_dispatch(false, a, (hipStream_t)stream);
+}
+
+int pigs_vorticity_backward(int dtype, int64_t N, int64_t M, const void* means, const void* conics, const void* values,
+                            const void* samples, const void* gout, void* g_means, void* g_conics, void* g_values,
+                            void* plan_ws, size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes, void* stream) {
+    if ((M > 0 && !gout) || (N > 0 && (!g_means || !g_conics || !g_values))) return PIGS_ERR_INVALID;
+    if (plan_ws) {
+        if (dtype != PIGS_F32) return PIGS_ERR_UNSUPPORTED;
+        const void* gs[4] = {gout, nullptr, nullptr, nullptr};
+        return plan_backward(plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, N, M, 2, 0.f, 128, gs, g_means, g_conics,
+                             g_values, (hipStream_t)stream);
+    }
+    int rc = check_common(dtype, 2, 2, 1, N, M, means, conics, values, samples);
+    if (rc != PIGS_OK) return rc;
+    SampleArgs a = vorticity_args(dtype, N, M, means, conics, values, samples);
+    a.gout[0] = gout;
+    a.g_means = g_means; a.g_conics = g_conics; a.g_values = g_values;
+    return dense_dispatch(true, a, (hipStream_t)stream);
+}
+
 // ---- periodic domain (ABI 10): the 3 x 3 images of every Gaussian and the fold of their gradients (periodic.hip)
 int pigs_periodic_images(int dtype, int c, int64_t N, double lo, double period, double q_cut, const void* means,
                          const void* conics, const void* values, void* img_means, void* img_conics, void* img_values,

@@ -96,6 +96,7 @@ __global__ __launch_bounds__(NW * 64) void dense_backward_kernel(
     auto load = [&](Gsym<T, D, C, EM>& G, int64_t m) {
         if constexpr (MASK == ORDR) G.load_residual(m, G0, rz);
         else if constexpr (MASK == ORDG) G.load_terms(m, G0, rz);
+        else if constexpr (MASK == ORDV) G.load_vorticity(m, G0);
         else G.load(m, G0, G1, G2, G3);
     };
     // the general residual: the two points' wave-uniform values (coefficients, gr, aux) are fetched field by field,
@@ -330,6 +331,7 @@ __global__ __launch_bounds__(256) void dense_backward_staged_kernel(
         for (int k = 0; k < D; ++k) p.s[k] = samples[m * D + k];
         if constexpr (MASK == ORDR) p.G.load_residual(m, G0, rz);
         else if constexpr (MASK == ORDG) p.G.load_terms(m, G0, rz);
+        else if constexpr (MASK == ORDV) p.G.load_vorticity(m, G0);
         else p.G.load(m, G0, G1, G2, G3);
         pts[threadIdx.x] = p;
     }
@@ -473,6 +475,13 @@ static int dispatch_mask(bool backward, const SampleArgs& a, hipStream_t stream)
         PIGS_CASE(1) PIGS_CASE(2) PIGS_CASE(4) PIGS_CASE(8) PIGS_CASE(7) PIGS_CASE(15) PIGS_CASE(16) PIGS_CASE(19)
         PIGS_CASE(32) PIGS_CASE(64)
         default: break;
+    }
+    // the vorticity terms (ORDV): a two-channel field in two dimensions, the only instantiations compiled
+    if constexpr (D == 2 && C == 2) {
+        switch (mask) {
+            PIGS_CASE(128)
+            default: break;
+        }
     }
 #undef PIGS_CASE
     return PIGS_ERR_UNSUPPORTED;

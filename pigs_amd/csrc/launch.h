@@ -81,13 +81,14 @@ size_t plan_error_offset();
 // Order masks: bit k < 4 = derivative order k (pointer slot k); bit 4 (16) = the TRACE of the order-2
 // output (the Laplacian), which takes pointer slot 2 in place of the full Hessian, [M][c].
 // 32 = the linear residual (pair_math.h ORDR), alone, in slot 0 -- reachable through pigs_residual_* only;
-// 64 = the general residual (ORDG), likewise -- through pigs_residual_terms_* only.
+// 64 = the general residual (ORDG), likewise -- through pigs_residual_terms_* only;
+// 128 = the vorticity terms (ORDV; d = 2, c = 2), one packed row [M][7] in slot 0 -- through pigs_vorticity_* only.
 inline bool mask_valid(int m) { return m > 0 && m < 32 && !((m & 4) && (m & 16)); }
-inline bool mask_uses_slot(int m, int k) { return (m == 32 || m == 64) ? k == 0 : (m >> k & 1) || (k == 2 && (m & 16)); }
+inline bool mask_uses_slot(int m, int k) { return (m == 32 || m == 64 || m == 128) ? k == 0 : (m >> k & 1) || (k == 2 && (m & 16)); }
 // Smallest compiled mask covering the request (compiled: single orders, 0..2, 0..3, the trace alone
 // and orders 0, 1 + trace); 0 = no compiled kernel (trace together with order 3).
 inline int covering_mask_of(int mask) {
-    if (mask == 32 || mask == 64) return mask;
+    if (mask == 32 || mask == 64 || mask == 128) return mask;
     if (mask & 16) return mask == 16 ? 16 : (mask & ~19) == 0 ? 19 : 0;
     if (mask == 1 || mask == 2 || mask == 4 || mask == 8) return mask;
     if ((mask & ~7) == 0) return 7;

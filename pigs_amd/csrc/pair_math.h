@@ -45,7 +45,18 @@ template <typename T> struct Resid {
 //   g0[c'] = a0 gr_c' + adv sum_i B[i][c'] sum_ch gr_ch d_i u_ch,  g1[i][ch] = (a1_i + adv w_i) gr_ch,  trace = aL gr
 // formed from gr, the coefficients and the forward's aux[m][1+d][c] = (u, d_i u)  (Gsym::load_terms).
 constexpr int ORDG = 64;
-constexpr int bwd_mask_of(int MASK) { return (MASK == ORDR || MASK == ORDG) ? ORDR_AS : MASK; }
+// THE VORTICITY TERMS of a two-channel field u = (u_x, u_y) in two dimensions (mask == ORDV, alone; D == 2, C == 2):
+// the seven numbers per point the reference's Navier-Stokes loss keeps of orders 0..3 (model_pn.py:650-659, 770-781,
+// 848: div = ux[:,0,0] + ux[:,1,1], w = ux[:,0,1] - ux[:,1,0], wx = uxx[...,0,1] - uxx[...,1,0],
+// lap w = trace of uxxx[...,0,1] - uxxx[...,1,0]) as one packed row
+//   out[m][0..6] = (u_x, u_y, div u, w, w_x, w_y, lap w)
+// Every one of them is a sum over the pairs, so the accumulators ARE the outputs: 7 slots instead of the 30 of
+// orders 0..3 and 28 B per point instead of 120.  Its backward is the backward of orders 0..3 with the four
+// incoming gradients formed on the fly from gout[m][0..6] (Gsym::load_vorticity).
+constexpr int ORDV = 128;
+constexpr int ORDV_AS = ORD0 | ORD1 | ORD2 | ORD3;
+constexpr int NVORT = 7;
+constexpr int bwd_mask_of(int MASK) { return (MASK == ORDR || MASK == ORDG) ? ORDR_AS : MASK == ORDV ? ORDV_AS : MASK; }
 
 template <typename T> struct Terms {
     T a0, a1[2], aL, adv;                           // used where the field pointer is null
@@ -109,7 +120,7 @@ template <int D, int C, int MASK_> struct FwdLayout {
     static constexpr int O1 = O0 + ((MASK & ORD0) ? C : 0);
     static constexpr int O2 = O1 + ((MASK & ORD1) ? D * C : 0);
     static constexpr int O3 = O2 + ((MASK & ORD2) ? Sym<D>::NF * C : (MASK & ORD2T) ? C : 0);
-    static constexpr int N = O3 + ((MASK & ORD3) ? Sym<D>::N3 * C : 0) + ((MASK & ORDR) ? C : 0);
+    static constexpr int N = O3 + ((MASK & ORD3) ? Sym<D>::N3 * C : 0) + ((MASK & ORDR) ? C : 0) + (MASK == ORDV ? NVORT : 0);
 };
 
 // Pair geometry: x, p, g (and nothing else) for one (point, Gaussian).
@@ -154,6 +165,26 @@ __device__ __forceinline__ void fwd_accumulate(T* acc, const T* s, const T* mu, 
         const T Fg = F * pr.g;
 #pragma unroll
         for (int ch = 0; ch < C; ++ch) acc[ch] = fma_<T>(v[ch], Fg, acc[ch]);
+        return;
+    }
+    if constexpr (MASK == ORDV) {
+        static_assert(D == 2 && C == 2, "the vorticity terms are those of a two-channel field in two dimensions");
+        // the guard of ORD3 below: an underflowed g must not meet an overflowing cubic (L_k)
+        const bool live = pr.g > T(0);
+        const T px = live ? pr.p[0] : T(0), py = live ? pr.p[1] : T(0);
+        const T txx = fma_<T>(px, px, -con[0]), txy = fma_<T>(px, py, -con[1]), tyy = fma_<T>(py, py, -con[2]);
+        // L_k = sum_i t3_iik = 2 (C p)_k - (|p|^2 - tr C) p_k     (t3_ijk = C_ij p_k + C_ik p_j + C_jk p_i - p_i p_j p_k)
+        const T ttr = txx + tyy;
+        const T Lx = fma_<T>(T(2), fma_<T>(con[0], px, con[1] * py), -ttr * px);
+        const T Ly = fma_<T>(T(2), fma_<T>(con[1], px, con[2] * py), -ttr * py);
+        const T wx = v[0] * pr.g, wy = v[1] * pr.g;      // d_i u_ch = -p_i w_ch, d_i d_j u_ch = t_ij w_ch
+        acc[0] += wx;
+        acc[1] += wy;
+        acc[2] = fma_<T>(-px, wx, fma_<T>(-py, wy, acc[2]));      // d_x u_x + d_y u_y
+        acc[3] = fma_<T>(py, wx, fma_<T>(-px, wy, acc[3]));       // d_x u_y - d_y u_x
+        acc[4] = fma_<T>(txx, wy, fma_<T>(-txy, wx, acc[4]));     // d_x w
+        acc[5] = fma_<T>(txy, wy, fma_<T>(-tyy, wx, acc[5]));     // d_y w
+        acc[6] = fma_<T>(Lx, wy, fma_<T>(-Ly, wx, acc[6]));       // lap w
         return;
     }
     if constexpr ((MASK & ORD3) != 0) {
@@ -270,6 +301,17 @@ __device__ __forceinline__ void fwd_store(const T* acc, int64_t m, T* __restrict
             store_out<STREAM>(&o0[m * C + ch], rz->target ? acc[ch] - rz->target[m * C + ch] : acc[ch]);
         return;
     }
+    if constexpr (MASK == ORDV) {
+        // one packed row of seven adjacent words (word-aligned only): the compiler joins them into a four-word and a
+        // three-word store (checked in the ISA: global_store_dwordx4 + global_store_dwordx3, `nt` under STREAM)
+        // (the empty asm: a caller with a streamed and a plain branch would otherwise see the two branches' identical
+        // unconditional stores hoisted into one, which loses the hint)
+        T* row = o0 + m * NVORT;
+        if constexpr (STREAM) asm volatile("" ::: "memory");
+#pragma unroll
+        for (int k = 0; k < NVORT; ++k) store_out<STREAM>(&row[k], acc[k]);
+        return;
+    }
     if constexpr ((MASK & ORD0) != 0) {
         if (o0) {
 #pragma unroll
@@ -325,6 +367,11 @@ __device__ __forceinline__ void fwd_load(T* acc, int64_t m, const T* __restrict_
     using L = FwdLayout<D, C, MASK>;
 #pragma unroll
     for (int k = 0; k < L::N; ++k) acc[k] = T(0);
+    if constexpr (MASK == ORDV) {      // the accumulators are the outputs
+#pragma unroll
+        for (int k = 0; k < NVORT; ++k) acc[k] = o0[m * NVORT + k];
+        return;
+    }
     if constexpr ((MASK & ORD0) != 0) {
         if (o0) {
 #pragma unroll
@@ -435,6 +482,27 @@ template <typename T, int D, int C, int MASK> struct Gsym {
 #pragma unroll
             for (int k = 0; k < Sym<D>::NF; ++k) g2[k][ch] = (k == 0 || k == Sym<D>::NF - 1) ? rz.aL * gr : T(0);
         }
+    }
+    // the incoming gradient gv [M][7] of the vorticity terms (MASK = ORDV_AS, D = 2, C = 2) as the gradients that arrive
+    // at orders 0..3, in this struct's symmetric components (g2[i + j], g3[i + j + k]: each the SUM over the index
+    // orders that share it):
+    //   div = o1[0][0] + o1[1][1],  w = o1[0][1] - o1[1][0],  w_i = o2[i][0][1] - o2[i][1][0],
+    //   lap w = sum_i o3[i][i][0][1] - o3[i][i][1][0]                                (last index: the channel)
+    __device__ __forceinline__ void load_vorticity(int64_t m, const T* __restrict__ GV) {
+        static_assert(MASK == ORDV_AS && D == 2 && C == 2, "the vorticity terms' backward runs on orders 0..3 of d = 2, c = 2");
+        T gv[NVORT];
+#pragma unroll
+        for (int k = 0; k < NVORT; ++k) gv[k] = GV[m * NVORT + k];
+        g0[0] = gv[0];          g0[1] = gv[1];
+        g1[0][0] = gv[2];       g1[0][1] = gv[3];
+        g1[1][0] = -gv[3];      g1[1][1] = gv[2];
+        g2[0][0] = T(0);        g2[0][1] = gv[4];      // xx
+        g2[1][0] = -gv[4];      g2[1][1] = gv[5];      // xy (+ yx)
+        g2[2][0] = -gv[5];      g2[2][1] = T(0);       // yy
+        g3[0][0] = T(0);        g3[0][1] = gv[6];      // xxx
+        g3[1][0] = -gv[6];      g3[1][1] = T(0);       // xxy: (0,0,1) of channel x
+        g3[2][0] = T(0);        g3[2][1] = gv[6];      // xyy: (1,1,0) of channel y
+        g3[3][0] = -gv[6];      g3[3][1] = T(0);       // yyy
     }
     // the incoming gradient gr [M][c] of a general residual (MASK = ORDR_AS), its coefficients k at the point and the
     // forward's aux (u, d_i u; read when `advects`)

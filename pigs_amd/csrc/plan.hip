@@ -2472,6 +2472,7 @@ __device__ __forceinline__ void load_tile_point(const SamplesView& sv, uint32_t 
         }
     } else if constexpr (MASK == ORDR) G.load_residual((int64_t)sp.m, G0p, rz);
     else if constexpr (MASK == ORDG) G.load_terms((int64_t)sp.m, G0p, rz);
+    else if constexpr (MASK == ORDV) G.load_vorticity((int64_t)sp.m, G0p);
     else G.load((int64_t)sp.m, G0p, G1p, G2p, G3p);
     if (!valid) {
 #pragma unroll
@@ -2623,6 +2624,7 @@ __device__ __forceinline__ void backward_points_helper(const PlanView& pv, const
         Gsym<float, 2, C, EM> G;
         if constexpr (MASK == ORDR) G.load_residual((int64_t)sp.m, G0p, rz);
         else if constexpr (MASK == ORDG) G.load_terms((int64_t)sp.m, G0p, rz);
+        else if constexpr (MASK == ORDV) G.load_vorticity((int64_t)sp.m, G0p);
         else G.load((int64_t)sp.m, G0p, G1p, G2p, G3p);
         // The walk in step over the whole wave (round 4): every lane meets its own (point, Gaussian) pair, and a pair's
         // NV sums leave as ONE atomic request -- lane = (pair, value), eight pairs per instruction, each a pair's 32-byte
@@ -3511,6 +3513,12 @@ static int plan_forward_c(const PlanView& pv_in, const SamplesView& sv, int mask
     if (mask == ORDG) {      // the general residual: its own coefficient block (never fused with the list launch)
         if (!tz) return PIGS_ERR_INVALID;
         hipLaunchKernelGGL((tile_forward_kernel<C, ORDG>), grid, block, 0, stream, pv, sv, out[0], out[1], out[2], out[3], *tz);
+    } else if (mask == ORDV) {      // the vorticity terms: two channels only (never fused with the list launch)
+        if constexpr (C == 2) {
+            hipLaunchKernelGGL((tile_forward_kernel<C, ORDV>), grid, block, 0, stream, pv, sv, out[0], out[1], out[2], out[3], rz);
+        } else {
+            return PIGS_ERR_UNSUPPORTED;
+        }
     } else if (!done) switch (mask) {
         PIGS_CASE(1) PIGS_CASE(2) PIGS_CASE(4) PIGS_CASE(8) PIGS_CASE(7) PIGS_CASE(15) PIGS_CASE(16) PIGS_CASE(19) PIGS_CASE(32)
         default: return PIGS_ERR_UNSUPPORTED;
@@ -3557,6 +3565,16 @@ static int plan_backward_c(const PlanView& pv_in, const SamplesView& sv, int mas
 #else
         hipLaunchKernelGGL((tile_backward_kernel<C, ORDG>), grid, block, 0, stream, pv, sv, g[0], g[1], g[2], g[3], *tz);
 #endif
+    } else if (mask == ORDV) {
+        if constexpr (C == 2) {
+#if PIGS_BWD_BLOCK
+            hipLaunchKernelGGL((block_backward_kernel<C, ORDV>), bgrid, block, 0, stream, pv, sv, g[0], g[1], g[2], g[3], rz);
+#else
+            hipLaunchKernelGGL((tile_backward_kernel<C, ORDV>), grid, block, 0, stream, pv, sv, g[0], g[1], g[2], g[3], rz);
+#endif
+        } else {
+            return PIGS_ERR_UNSUPPORTED;
+        }
     } else switch (mask) {
         PIGS_CASE(1) PIGS_CASE(2) PIGS_CASE(4) PIGS_CASE(8) PIGS_CASE(7) PIGS_CASE(15) PIGS_CASE(16) PIGS_CASE(19) PIGS_CASE(32)
         default: return PIGS_ERR_UNSUPPORTED;

@@ -623,6 +623,77 @@ at::Tensor residual_terms_apply(const at::Tensor& means, const at::Tensor& value
 }
 
 // ---------------------------------------------------------------------------------------------
+// vorticity_terms(): (u_x, u_y, div, w, w_x, w_y, lap w) as [M, 7] in one launch (pigs_vorticity_*); the node owns its
+// inputs and plan like ResidualBackward.
+// ---------------------------------------------------------------------------------------------
+constexpr int64_t VORTICITY_COLUMNS = 7;
+
+struct VorticityBackward : public torch::autograd::Node {
+    at::Tensor means, values, conics, samples;
+    uint32_t versions[4] = {0, 0, 0, 0};
+    bool debug = false;
+    std::shared_ptr<Plan> plan;
+
+    std::string name() const override { return "PigsVorticityBackward"; }
+    void release_variables() override {}
+
+    torch::autograd::variable_list apply(torch::autograd::variable_list&& grads) override {
+        if (means._version() != versions[0] || values._version() != versions[1] || conics._version() != versions[2] ||
+            samples._version() != versions[3])
+            throw std::runtime_error(
+                "one of the tensors handed to GaussianSampler.preprocess() has been modified in place before the "
+                "backward of a vorticity_terms() output that was computed from it");
+        torch::autograd::variable_list res(3);
+        if (grads.empty() || !grads[0].defined()) return res;
+        at::AutoGradMode no_grad(false);
+        if (grads[0].requires_grad()) throw std::runtime_error("GaussianSampler.vorticity_terms() is differentiable once");
+        if (debug && plan && plan->forward_only) throw std::logic_error("a vorticity_terms() node holds a forward-only plan");
+        const at::Tensor gout = grads[0].contiguous();
+        const int64_t N = means.size(0), M = samples.size(0);
+        auto gv3 = gradient_views(means, values, conics);
+        at::Tensor g_means = gv3[0], g_values = gv3[1], g_conics = gv3[2];
+        if (N > 0 && M > 0) {
+            c10::DeviceGuard guard(means.device());
+            const hipStream_t stream = current_stream(means);
+            const PlanPtrs pp = plan_ptrs(plan.get(), stream);
+            check(pigs_vorticity_backward(dtype_code(means), N, M, ptr(means), ptr(conics), ptr(values), ptr(samples), ptr(gout),
+                                          ptr(g_means), ptr(g_conics), ptr(g_values), pp.pw, pp.pb, pp.sw, pp.sb, stream),
+                  "pigs_vorticity_backward");
+        } else {
+            g_means.zero_(); g_values.zero_(); g_conics.zero_();
+        }
+        if (debug) device_sync(means);
+        res[0] = g_means; res[1] = g_values; res[2] = g_conics;
+        return res;
+    }
+};
+
+at::Tensor vorticity_apply(const at::Tensor& means, const at::Tensor& values, const at::Tensor& conics, const at::Tensor& samples,
+                           bool debug, const std::shared_ptr<Plan>& plan) {
+    const int64_t N = means.size(0), M = samples.size(0);
+    at::Tensor out = at::empty({M, VORTICITY_COLUMNS}, means.options());
+    if (M > 0) {
+        c10::DeviceGuard guard(means.device());
+        const hipStream_t stream = current_stream(means);
+        const PlanPtrs pp = plan_ptrs(plan.get(), stream);
+        check(pigs_vorticity_forward(dtype_code(means), N, M, ptr(means), ptr(conics), ptr(values), ptr(samples), ptr(out), pp.pw,
+                                     pp.pb, pp.sw, pp.sb, stream),
+              "pigs_vorticity_forward");
+    }
+    if (debug) device_sync(means);
+    if (at::GradMode::is_enabled() && (means.requires_grad() || values.requires_grad() || conics.requires_grad())) {
+        std::shared_ptr<VorticityBackward> node(new VorticityBackward(), torch::autograd::deleteNode);
+        node->set_next_edges(torch::autograd::collect_next_edges(means, values, conics));
+        node->means = means; node->values = values; node->conics = conics; node->samples = samples;
+        node->versions[0] = means._version(); node->versions[1] = values._version();
+        node->versions[2] = conics._version(); node->versions[3] = samples._version();
+        node->debug = debug; node->plan = plan;
+        torch::autograd::create_gradient_edge(out, node);
+    }
+    return out;
+}
+
+// ---------------------------------------------------------------------------------------------
 // preprocess_aggregate / aggregate_neighbors (model_pn.py:257-264; parity unpinned: this repository's own
 // definition, pigs_amd/csrc/aggregate.hip).  Same structure as pigs_amd/aggregate.py.
 // ---------------------------------------------------------------------------------------------
@@ -831,6 +902,7 @@ struct Core {
     std::vector<std::shared_ptr<SamplePlan>> sample_plans;      // most recently used first
     std::shared_ptr<PlanPool> pool = std::make_shared<PlanPool>();
     Outs cache;
+    at::Tensor vorticity;             // the cached vorticity_terms() of the bound inputs
     std::shared_ptr<NeighborLists> neighbors;
     static bool warned_samples_grad;
 
@@ -903,6 +975,7 @@ struct Core {
         samples_source = samples_in;
         bound = true;
         for (auto& t : cache) t = at::Tensor();
+        vorticity = at::Tensor();
         plan.reset();
         plan3.reset();
         neighbors.reset();
@@ -1060,6 +1133,18 @@ struct Core {
         return residual_terms_apply(means, values, conics, samples, t, target, debug, plan_for(0, target));
     }
 
+    // (u_x, u_y, div, w, w_x, w_y, lap w) [M, 7]; on the order-3 plan where there is one
+    at::Tensor vorticity_terms() {
+        require_inputs();
+        if (means.size(1) != 2 || values.size(1) != 2)
+            raise_py(PyExc_NotImplementedError, "vorticity_terms() needs a two-channel field in two dimensions, got d = " +
+                                                    std::to_string(means.size(1)) + ", c = " + std::to_string(values.size(1)));
+        // (a result computed where no backward could follow is not handed to a later differentiable call)
+        if (!vorticity.defined() || (needs_backward() && !vorticity.requires_grad()))
+            vorticity = vorticity_apply(means, values, conics, samples, debug, plan_for(8));
+        return vorticity;
+    }
+
     void preprocess_aggregate(int64_t cap) {
         require_inputs();
         if (means.size(1) != 2) raise_py(PyExc_NotImplementedError, "aggregate_neighbors is implemented for d = 2");
@@ -1185,6 +1270,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("residual", &Core::residual, py::arg("coeffs"), py::arg("target") = c10::optional<at::Tensor>())
         .def("residual_terms", &Core::residual_terms, py::arg("fields"), py::arg("consts"), py::arg("advect_by"),
              py::arg("target") = c10::optional<at::Tensor>())
+        .def("vorticity_terms", &Core::vorticity_terms)
         .def("preprocess_aggregate", &Core::preprocess_aggregate, py::arg("cap") = -1)
         .def("aggregate_neighbors", &Core::aggregate_neighbors)
         .def_readonly("neighbors", &Core::neighbors)

@@ -34,6 +34,9 @@ _DTYPES = {torch.float32: _lib.PIGS_F32, torch.float64: _lib.PIGS_F64}
 
 
 TRACE = 4       # order index of the Hessian's trace (mask bit 16); it travels in pointer slot 2
+# the columns of GaussianSampler.vorticity_terms(): the field, its divergence, the vorticity w = d_x u_y - d_y u_x,
+# its gradient and its Laplacian
+VORTICITY_COLUMNS = ("u_x", "u_y", "div", "w", "w_x", "w_y", "lap_w")
 
 
 def _out_shape(order, M, d, c):
@@ -555,6 +558,69 @@ class _ResidualTermsFunction(torch.autograd.Function):
         return g_means, g_values, g_conics, None, g_target, None, None, None, None
 
 
+def _vorticity_call(backward, means, values, conics, samples, plan, gout=None):
+    """pigs_vorticity_forward / _backward on contiguous device tensors (through the plan when given)."""
+    lib = _lib.load()
+    N, M = means.shape[0], samples.shape[0]
+    ncol = len(VORTICITY_COLUMNS)
+    if backward and plan is not None and M > 0 and getattr(plan, "forward_only", False):
+        plan = plan.full_for_backward(means, values, conics, samples)
+    pw = (_ptr(plan.workspace), plan.workspace.numel(), _ptr(plan.samples.workspace), plan.samples.workspace.numel()) \
+        if plan is not None else (ctypes.c_void_p(0), 0, ctypes.c_void_p(0), 0)
+    with _on_device(means.device):
+        stream = _stream(means.device)
+        if plan is not None and hasattr(plan, "note_stream"):
+            plan.note_stream(stream.value)
+        if not backward:
+            out = torch.empty((M, ncol), dtype=means.dtype, device=means.device)
+            if M > 0:
+                rc = lib.pigs_vorticity_forward(_DTYPES[means.dtype], N, M, _ptr(means), _ptr(conics), _ptr(values),
+                                                _ptr(samples), _ptr(out), *pw, stream)
+                _lib.check(rc, "pigs_vorticity_forward")
+            return out
+        g_means, g_values, g_conics = _gradient_views(means, values, conics)
+        if N > 0:
+            if M > 0:
+                rc = lib.pigs_vorticity_backward(_DTYPES[means.dtype], N, M, _ptr(means), _ptr(conics), _ptr(values),
+                                                 _ptr(samples), _ptr(gout), _ptr(g_means), _ptr(g_conics), _ptr(g_values),
+                                                 *pw, stream)
+                _lib.check(rc, "pigs_vorticity_backward")
+            else:
+                for g in (g_means, g_values, g_conics):
+                    g.zero_()
+        return g_means, g_values, g_conics
+
+
+class _VorticityFunction(torch.autograd.Function):
+    """(u_x, u_y, div, w, w_x, w_y, lap w) as [M, 7] in one launch; its backward is one launch too.  The node owns
+    its inputs and plan like :class:`_ResidualFunction`."""
+
+    @staticmethod
+    def forward(ctx, means, values, conics, samples, debug, plan):
+        out = _vorticity_call(False, means, values, conics, samples, plan)
+        if debug:
+            torch.cuda.synchronize(means.device)
+        ctx.inputs = (means, values, conics, samples)
+        ctx.versions = (means._version, values._version, conics._version, samples._version)
+        ctx.debug, ctx.plan = debug, plan
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        means, values, conics, samples = ctx.inputs
+        if (means._version, values._version, conics._version, samples._version) != ctx.versions:
+            raise RuntimeError("one of the tensors handed to GaussianSampler.preprocess() has been modified in place "
+                               "before the backward of a vorticity_terms() output that was computed from it")
+        gout = gout.contiguous()
+        if ctx.debug:
+            assert ctx.plan is None or not ctx.plan.forward_only, "a vorticity_terms() node holds a forward-only plan"
+        g_means, g_values, g_conics = _vorticity_call(True, means, values, conics, samples, ctx.plan, gout=gout)
+        if ctx.debug:
+            torch.cuda.synchronize(means.device)
+        return g_means, g_values, g_conics, None, None, None
+
+
 class _SampleFunction(torch.autograd.Function):
     """One fused launch producing the outputs of every order in ``mask``; its backward is one
     fused launch over the outputs that received a gradient.
@@ -789,6 +855,7 @@ class GaussianSampler:
         self._plan_pool = _PlanPool()
         self._samples_source = None
         self._cache = {}
+        self._vorticity = None           # the cached vorticity_terms() of the bound inputs
         _lib.load()  # fail at construction, not at first use, if the HIP library is missing
         self._core = None
         if host == "native":
@@ -935,6 +1002,7 @@ class GaussianSampler:
         self._st_inputs = (means, values, conics, samples.detach().contiguous())
         self._samples_source = samples
         self._cache = {}
+        self._vorticity = None
         self._st_plan = None
         self._st_plan3 = None
         self._neighbors = None
@@ -1162,6 +1230,31 @@ class GaussianSampler:
         if self._core is not None:
             return self._core.residual(coeffs, target)
         return _ResidualFunction.apply(means, values, conics, samples, target, coeffs, self.debug, self._plan_for(0, target))
+
+    def vorticity_terms(self):
+        """Extension of the reference API: the seven numbers per point that the reference's Navier-Stokes problem keeps
+        of orders 0..3 of its two-channel field (model_pn.py:650-659, 770-781, 848), as ONE tensor [M, 7] with the
+        columns ``pigs_amd.VORTICITY_COLUMNS`` = ``(u_x, u_y, div, w, w_x, w_y, lap_w)``: the field, its divergence
+        ``d_x u_x + d_y u_y``, the vorticity ``w = d_x u_y - d_y u_x``, its gradient and its Laplacian.  One launch with
+        7 accumulators and 28 bytes per point, where ``sample((0, 1, 2, 3))`` carries 30 and stores 120 and a dozen
+        slicing kernels follow; differentiable wrt means, values and conics in one launch.  d = 2 and c = 2 only
+        (anything else raises ``NotImplementedError``).  Binned plans run it on the order-3 plan (``q_max_order3``),
+        the backward with the wide cut-off.  The result is cached until the next ``preprocess`` (a result computed
+        where no backward could follow -- ``no_grad`` -- is not handed to a later differentiable call: that call
+        launches again).
+
+        Take the columns with ``u_x, u_y, div, w, w_x, w_y, lap_w = t.unbind(1)``: the backward of ``unbind`` is one
+        ``stack``, where seven slices ``t[:, k]`` would each scatter into a zeroed [M, 7] of their own.
+        INTEGRATION.md has the Navier-Stokes recipe; DESIGN.md 13 the measured times."""
+        means, values, conics, samples = self._require_inputs()
+        d, c = means.shape[1], values.shape[1]
+        if d != 2 or c != 2:
+            raise NotImplementedError(f"vorticity_terms() needs a two-channel field in two dimensions, got d = {d}, c = {c}")
+        if self._core is not None:
+            return self._core.vorticity_terms()
+        if self._vorticity is None or (self._needs_backward() and not self._vorticity.requires_grad):
+            self._vorticity = _VorticityFunction.apply(means, values, conics, samples, self.debug, self._plan_for(8))
+        return self._vorticity
 
     def sample_gaussians(self):
         """u [M, c]"""
