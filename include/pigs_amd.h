@@ -197,7 +197,7 @@ int pigs_plan_backward(void* workspace, size_t workspace_bytes, const void* samp
                        void* g_means, void* g_conics, void* g_values, void* stream);
 
 /*
- * Linear residual of the sampled field in ONE launch (extension): the diffusion / wave
+ * Linear residual of the sampled field in ONE launch (extension): the diffusion
  * residuals of the reference's losses (model_pn.py:612-617, 834-849; test_no_mlp.py:127-144) are
  *     r[m][c] = a0 u + a1x du/dx + a1y du/dy + aL (u_xx + u_yy) - target[m][c]
  * with constant coefficients `coeffs` = {a0, a1x, a1y, aL} (HOST doubles) and an optional `target`
@@ -250,6 +250,40 @@ int pigs_residual_terms_backward(int dtype, int d, int c, int64_t N, int64_t M,
                                  void* g_means, void* g_conics, void* g_values,
                                  void* plan_ws, size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes,
                                  void* stream);
+
+/*
+ * Coupled residual in ONE launch (additive to ABI 10): the channels mixed by two constant c x c matrices under a
+ * per-point weight,
+ *     r[m][ch] = a0_m u_ch + aL_m lap u_ch
+ *              + cw_m sum_c' ( couple0[ch][c'] u_c' + couple_lap[ch][c'] lap u_c' ) - target[m][ch]
+ * -- the reference's wave system (test_no_mlp.py:127-139: res0 = u_t[0] - ub[1], res1 = u_t[1] - (10 lap ub[0] - 0.1 ub[1])
+ * with ub blended by a random weight per point; model_pn.py:623-627, 843-845), which no coefficient shared by the
+ * channels expresses.  Each of a0, aL, cw is the HOST double of `coupling` where its field pointer is NULL, else a
+ * DEVICE field [M] in the call's dtype, contiguous.  couple0 and couple_lap are host constants, row = output channel,
+ * column = input channel (rows and columns < c are read).  target [M][c] or NULL; out [M][c].  Only u and the
+ * trace are accumulated (2 c sums per point).  The backward takes gout [M][c] and returns the gradients wrt means,
+ * conics, values (overwritten); it is linear in the field, so it needs nothing of the forward, but the coefficient
+ * fields must stay unmodified between the forward and its backward; d r / d target = -1 is the caller's; there are no
+ * gradients wrt the coefficients.  c = 1 is PIGS_ERR_UNSUPPORTED (nothing to couple).  plan_ws == NULL: dense
+ * (d in {1,2}, c in {2,3,4}, f32 / f64); else through a built plan (d = 2, f32, c = 2; backward with the plan's wide
+ * cut-off; on a PIGS_BUILD_FORWARD_ONLY plan the backward writes NaN gradients, as pigs_residual_backward does).
+ */
+typedef struct PigsResidualCoupling {
+    double a0, aL, cw;                      /* used where the field pointer is NULL */
+    double couple0[4][4], couple_lap[4][4]; /* [ch][c'] */
+    const void *a0_pt, *aL_pt, *cw_pt;      /* device fields [M] or NULL */
+} PigsResidualCoupling;
+int pigs_residual_coupled_forward(int dtype, int d, int c, int64_t N, int64_t M,
+                                  const void* means, const void* conics, const void* values, const void* samples,
+                                  const PigsResidualCoupling* coupling, const void* target, void* out,
+                                  void* plan_ws, size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes,
+                                  void* stream);
+int pigs_residual_coupled_backward(int dtype, int d, int c, int64_t N, int64_t M,
+                                   const void* means, const void* conics, const void* values, const void* samples,
+                                   const PigsResidualCoupling* coupling, const void* gout,
+                                   void* g_means, void* g_conics, void* g_values,
+                                   void* plan_ws, size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes,
+                                   void* stream);
 
 /*
  * The vorticity terms of a two-channel field u = (u_x, u_y) in two dimensions in ONE launch (additive to ABI 10;

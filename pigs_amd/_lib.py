@@ -32,6 +32,16 @@ class PigsResidualTerms(ctypes.Structure):
 
 _terms_p = ctypes.POINTER(PigsResidualTerms)
 
+
+class PigsResidualCoupling(ctypes.Structure):
+    """struct PigsResidualCoupling of include/pigs_amd.h (the coupled residual's coefficients and matrices)"""
+    _fields_ = [("a0", ctypes.c_double), ("aL", ctypes.c_double), ("cw", ctypes.c_double),
+                ("couple0", (ctypes.c_double * 4) * 4), ("couple_lap", (ctypes.c_double * 4) * 4),
+                ("a0_pt", _vp), ("aL_pt", _vp), ("cw_pt", _vp)]
+
+
+_coupling_p = ctypes.POINTER(PigsResidualCoupling)
+
 # name -> (restype, argtypes); must list every symbol include/pigs_amd.h declares
 SIGNATURES = {
     "pigs_abi_version": (_i, []),
@@ -69,6 +79,11 @@ SIGNATURES = {
     "pigs_vorticity_forward": (_i, [_i, _i64, _i64] + [_vp] * 4 + [_vp] + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
     "pigs_vorticity_backward": (_i, [_i, _i64, _i64] + [_vp] * 4 + [_vp] + [_vp] * 3
                                 + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
+    # the coupled residual (additive to ABI 10): coupling, target, out / coupling, gout, gradients
+    "pigs_residual_coupled_forward": (_i, [_i, _i, _i, _i64, _i64] + [_vp] * 4 + [_coupling_p, _vp, _vp]
+                                      + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
+    "pigs_residual_coupled_backward": (_i, [_i, _i, _i, _i64, _i64] + [_vp] * 4 + [_coupling_p, _vp] + [_vp] * 3
+                                       + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
     "pigs_periodic_images": (_i, [_i, _i, _i64, ctypes.c_double, ctypes.c_double, ctypes.c_double] + [_vp] * 6
                              + [_vp, _vp]),
     "pigs_periodic_images_backward": (_i, [_i, _i, _i64] + [_vp] * 6 + [_vp]),

@@ -233,6 +233,56 @@ int pigs_residual_terms_backward(int dtype, int d, int c, int64_t N, int64_t M, 
     return dense_dispatch(true, a, (hipStream_t)stream);
 }
 
+// ---- coupled residual (pair_math.h ORDC): the channels mixed by two constant matrices under a per-point weight
+static SampleArgs coupled_args(int dtype, int d, int c, int64_t N, int64_t M, const void* means, const void* conics,
+                               const void* values, const void* samples, const PigsResidualCoupling* coupling) {
+    SampleArgs a{};
+    a.dtype = dtype; a.d = d; a.c = c; a.orders_mask = 256; a.N = N; a.M = M;
+    a.means = means; a.conics = conics; a.values = values; a.samples = samples;
+    a.coupling = coupling;
+    return a;
+}
+
+int pigs_residual_coupled_forward(int dtype, int d, int c, int64_t N, int64_t M, const void* means, const void* conics,
+                                  const void* values, const void* samples, const PigsResidualCoupling* coupling,
+                                  const void* target, void* out, void* plan_ws, size_t plan_ws_bytes, const void* samples_ws,
+                                  size_t samples_ws_bytes, void* stream) {
+    if (!coupling || (M > 0 && !out)) return PIGS_ERR_INVALID;
+    if (c == 1) return PIGS_ERR_UNSUPPORTED;      // nothing to couple: pigs_residual_* / pigs_residual_terms_*
+    if (plan_ws) {
+        if (dtype != PIGS_F32 || d != 2 || c != 2) return PIGS_ERR_UNSUPPORTED;
+        void* outs[4] = {out, nullptr, nullptr, nullptr};
+        return plan_forward(plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, N, M, c, 0.f, 256, outs, (hipStream_t)stream,
+                            nullptr, target, nullptr, nullptr, coupling);
+    }
+    int rc = check_common(dtype, d, c, 1, N, M, means, conics, values, samples);
+    if (rc != PIGS_OK) return rc;
+    SampleArgs a = coupled_args(dtype, d, c, N, M, means, conics, values, samples, coupling);
+    a.out[0] = out;
+    a.target = target;
+    return dense_dispatch(false, a, (hipStream_t)stream);
+}
+
+int pigs_residual_coupled_backward(int dtype, int d, int c, int64_t N, int64_t M, const void* means, const void* conics,
+                                   const void* values, const void* samples, const PigsResidualCoupling* coupling,
+                                   const void* gout, void* g_means, void* g_conics, void* g_values, void* plan_ws,
+                                   size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes, void* stream) {
+    if (!coupling || (M > 0 && !gout) || (N > 0 && (!g_means || !g_conics || !g_values))) return PIGS_ERR_INVALID;
+    if (c == 1) return PIGS_ERR_UNSUPPORTED;
+    if (plan_ws) {
+        if (dtype != PIGS_F32 || d != 2 || c != 2) return PIGS_ERR_UNSUPPORTED;
+        const void* gs[4] = {gout, nullptr, nullptr, nullptr};
+        return plan_backward(plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, N, M, c, 0.f, 256, gs, g_means, g_conics,
+                             g_values, (hipStream_t)stream, nullptr, nullptr, nullptr, coupling);
+    }
+    int rc = check_common(dtype, d, c, 1, N, M, means, conics, values, samples);
+    if (rc != PIGS_OK) return rc;
+    SampleArgs a = coupled_args(dtype, d, c, N, M, means, conics, values, samples, coupling);
+    a.gout[0] = gout;
+    a.g_means = g_means; a.g_conics = g_conics; a.g_values = g_values;
+    return dense_dispatch(true, a, (hipStream_t)stream);
+}
+
 // ---- vorticity terms (pair_math.h ORDV): (u_x, u_y, div, w, w_x, w_y, lap w) of a two-channel field, d = 2
 static SampleArgs vorticity_args(int dtype, int64_t N, int64_t M, const void* means, const void* conics, const void* values,
                                  const void* samples) {

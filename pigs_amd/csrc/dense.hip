@@ -97,6 +97,7 @@ __global__ __launch_bounds__(NW * 64) void dense_backward_kernel(
         if constexpr (MASK == ORDR) G.load_residual(m, G0, rz);
         else if constexpr (MASK == ORDG) G.load_terms(m, G0, rz);
         else if constexpr (MASK == ORDV) G.load_vorticity(m, G0);
+        else if constexpr (MASK == ORDC) G.load_coupled(m, G0, rz);
         else G.load(m, G0, G1, G2, G3);
     };
     // the general residual: the two points' wave-uniform values (coefficients, gr, aux) are fetched field by field,
@@ -332,6 +333,7 @@ __global__ __launch_bounds__(256) void dense_backward_staged_kernel(
         if constexpr (MASK == ORDR) p.G.load_residual(m, G0, rz);
         else if constexpr (MASK == ORDG) p.G.load_terms(m, G0, rz);
         else if constexpr (MASK == ORDV) p.G.load_vorticity(m, G0);
+        else if constexpr (MASK == ORDC) p.G.load_coupled(m, G0, rz);
         else p.G.load(m, G0, G1, G2, G3);
         pts[threadIdx.x] = p;
     }
@@ -370,6 +372,8 @@ template <typename T, int MASK>
 static RzOf<T, MASK> rz_of(const SampleArgs& a, bool backward) {
     if constexpr (MASK == ORDG) {
         return make_terms<T>(*a.terms, backward ? nullptr : a.target, a.aux);
+    } else if constexpr (MASK == ORDC) {
+        return make_coupled<T>(*a.coupling, backward ? nullptr : a.target);
     } else {
         return Resid<T>{(T)a.resid[0], {(T)a.resid[1], (T)a.resid[2]}, (T)a.resid[3], backward ? nullptr : (const T*)a.target};
     }
@@ -480,6 +484,13 @@ static int dispatch_mask(bool backward, const SampleArgs& a, hipStream_t stream)
     if constexpr (D == 2 && C == 2) {
         switch (mask) {
             PIGS_CASE(128)
+            default: break;
+        }
+    }
+    // the coupled residual (ORDC) mixes channels: compiled for two and more
+    if constexpr (C >= 2) {
+        switch (mask) {
+            PIGS_CASE(256)
             default: break;
         }
     }

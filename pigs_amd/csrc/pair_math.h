@@ -23,8 +23,8 @@ constexpr int ORD0 = 1, ORD1 = 2, ORD2 = 4, ORD3 = 8;
 constexpr int ORD2T = 16;
 // A LINEAR RESIDUAL of the sampled field as the only output (mask == ORDR, alone):
 //   r[m][c] = a0 u + a1 . grad u + aL (u_xx + u_yy) - target[m][c]
-// -- the diffusion / wave residuals of the reference's losses (model_pn.py:612-617, 834-849;
-// test_no_mlp.py:127-144: u_t - D lap u with u_t = (u - u_prev) / dt) in one launch and 4 B per point and
+// -- the diffusion residual of the reference's losses (model_pn.py:612-617, 834-849;
+// test_no_mlp.py:127-144: u_t - D lap u with u_t = (u - u_prev) / dt; the wave system mixes its channels: ORDC) in one launch and 4 B per point and
 // channel instead of u, grad u and the Hessian (28 B).  Its backward is the backward of orders 0, 1 and
 // the trace with the incoming gradients a0 gr, a1 gr, aL gr formed on the fly.
 constexpr int ORDR = 32;
@@ -56,7 +56,19 @@ constexpr int ORDG = 64;
 constexpr int ORDV = 128;
 constexpr int ORDV_AS = ORD0 | ORD1 | ORD2 | ORD3;
 constexpr int NVORT = 7;
-constexpr int bwd_mask_of(int MASK) { return (MASK == ORDR || MASK == ORDG) ? ORDR_AS : MASK == ORDV ? ORDV_AS : MASK; }
+// THE COUPLED RESIDUAL (mask == ORDC, alone): the channels mixed by two constant c x c matrices under a per-point weight,
+//   r[m][ch] = a0_m u_ch + aL_m lap u_ch + cw_m sum_c' (Q0[ch][c'] u_c' + QL[ch][c'] lap u_c') - target[m][ch]
+// -- the reference's wave system (test_no_mlp.py:127-139, model_pn.py:623-627, 843-845: res0 = u_t[0] - ub[1],
+// res1 = u_t[1] - (10 lap ub[0] - 0.1 ub[1]) with ub blended per point).  Nothing of grad u is read, so the accumulators
+// are those of order 0 and the trace alone (ORDC_AS: 2 c of them, against the 2 c + d c of ORDG) and the residual is
+// composed once per point in fwd_store.  Its backward is the ORDC_AS backward with
+//   g0[c'] = a0 gr_c' + cw sum_ch Q0[ch][c'] gr_ch,  trace[c'] = aL gr_c' + cw sum_ch QL[ch][c'] gr_ch
+// (Gsym::load_coupled): linear in the field, so no record of the forward is needed.
+constexpr int ORDC = 256;
+constexpr int ORDC_AS = ORD0 | ORD2T;
+constexpr int bwd_mask_of(int MASK) {
+    return (MASK == ORDR || MASK == ORDG) ? ORDR_AS : MASK == ORDV ? ORDV_AS : MASK == ORDC ? ORDC_AS : MASK;
+}
 
 template <typename T> struct Terms {
     T a0, a1[2], aL, adv;                           // used where the field pointer is null
@@ -77,8 +89,26 @@ inline Terms<T> make_terms(const ABI& t, const void* target, const void* aux) {
     z.aux = (T*)const_cast<void*>(aux);
     return z;
 }
+template <typename T> struct Coupled {
+    T a0, aL, cw;                                   // used where the field pointer is null
+    T Q0[4][4], QL[4][4];                           // couple0[ch][c'], couple_lap[ch][c']
+    const T *a0_pt, *aL_pt, *cw_pt;                 // per-point fields [M] or null
+    const T* target;                                // [M][c] or null
+};
+// host side: the block from the C ABI's PigsResidualCoupling (include/pigs_amd.h) in the launch's type
+template <typename T, typename ABI>
+inline Coupled<T> make_coupled(const ABI& t, const void* target) {
+    Coupled<T> z{};
+    z.a0 = (T)t.a0; z.aL = (T)t.aL; z.cw = (T)t.cw;
+    for (int i = 0; i < 4; ++i)
+        for (int k = 0; k < 4; ++k) { z.Q0[i][k] = (T)t.couple0[i][k]; z.QL[i][k] = (T)t.couple_lap[i][k]; }
+    z.a0_pt = (const T*)t.a0_pt; z.aL_pt = (const T*)t.aL_pt; z.cw_pt = (const T*)t.cw_pt;
+    z.target = (const T*)target;
+    return z;
+}
 // the coefficient block a kernel compiled for MASK receives
-template <typename T, int MASK> using RzOf = std::conditional_t<MASK == ORDG, Terms<T>, Resid<T>>;
+template <typename T, int MASK>
+using RzOf = std::conditional_t<MASK == ORDG, Terms<T>, std::conditional_t<MASK == ORDC, Coupled<T>, Resid<T>>>;
 
 // the coefficients of the general residual at one point
 template <typename T, int D> struct TermsAt {
@@ -115,7 +145,8 @@ template <> __device__ __forceinline__ float fma_<float>(float a, float b, float
 
 // Layout of the flat forward accumulator array for a compile-time order mask.
 template <int D, int C, int MASK_> struct FwdLayout {
-    static constexpr int MASK = MASK_ == ORDG ? ORDR_AS : MASK_;      // the general residual accumulates u, grad u, trace
+    // the general residual accumulates u, grad u, trace; the coupled one u and the trace
+    static constexpr int MASK = MASK_ == ORDG ? ORDR_AS : MASK_ == ORDC ? ORDC_AS : MASK_;
     static constexpr int O0 = 0;
     static constexpr int O1 = O0 + ((MASK & ORD0) ? C : 0);
     static constexpr int O2 = O1 + ((MASK & ORD1) ? D * C : 0);
@@ -148,6 +179,10 @@ __device__ __forceinline__ void fwd_accumulate(T* acc, const T* s, const T* mu, 
                                                const RzOf<T, MASK>* rz = nullptr) {
     if constexpr (MASK == ORDG) {
         fwd_accumulate<T, D, C, ORDR_AS>(acc, s, mu, con, v);
+        return;
+    }
+    if constexpr (MASK == ORDC) {
+        fwd_accumulate<T, D, C, ORDC_AS>(acc, s, mu, con, v);
         return;
     }
     using L = FwdLayout<D, C, MASK>;
@@ -292,6 +327,21 @@ __device__ __forceinline__ void fwd_store(const T* acc, int64_t m, T* __restrict
             for (int i = 0; i < D; ++i)
 #pragma unroll
                 for (int ch = 0; ch < C; ++ch) store_out<STREAM>(&ax[(1 + i) * C + ch], -acc[L::O1 + i * C + ch]);
+        }
+        return;
+    }
+    if constexpr (MASK == ORDC) {
+        // the composing store: the point's three coefficients, the two matrices (kernel arguments) and the target
+        const T a0 = rz->a0_pt ? rz->a0_pt[m] : rz->a0, aL = rz->aL_pt ? rz->aL_pt[m] : rz->aL;
+        const T cw = rz->cw_pt ? rz->cw_pt[m] : rz->cw;
+#pragma unroll
+        for (int ch = 0; ch < C; ++ch) {
+            T mix = T(0);
+#pragma unroll
+            for (int cc = 0; cc < C; ++cc)
+                mix = fma_<T>(rz->Q0[ch][cc], acc[L::O0 + cc], fma_<T>(rz->QL[ch][cc], acc[L::O2 + cc], mix));
+            const T r = fma_<T>(cw, mix, fma_<T>(aL, acc[L::O2 + ch], a0 * acc[L::O0 + ch]));
+            store_out<STREAM>(&o0[m * C + ch], rz->target ? r - rz->target[m * C + ch] : r);
         }
         return;
     }
@@ -482,6 +532,31 @@ template <typename T, int D, int C, int MASK> struct Gsym {
 #pragma unroll
             for (int k = 0; k < Sym<D>::NF; ++k) g2[k][ch] = (k == 0 || k == Sym<D>::NF - 1) ? rz.aL * gr : T(0);
         }
+    }
+    // the incoming gradient gr [M][c] of a coupled residual (MASK = ORDC_AS) with the point's coefficients a0, aL, cw:
+    //   g0[c'] = a0 gr_c' + cw sum_ch Q0[ch][c'] gr_ch,  trace[c'] = aL gr_c' + cw sum_ch QL[ch][c'] gr_ch
+    __device__ __forceinline__ void form_coupled(const T* gr, T a0, T aL, T cw, const Coupled<T>& cz) {
+        static_assert(MASK == ORDC_AS, "a coupled residual's backward runs on order 0 and the trace");
+#pragma unroll
+        for (int cc = 0; cc < C; ++cc) {
+            T m0 = T(0), mL = T(0);
+#pragma unroll
+            for (int ch = 0; ch < C; ++ch) {
+                m0 = fma_<T>(cz.Q0[ch][cc], gr[ch], m0);
+                mL = fma_<T>(cz.QL[ch][cc], gr[ch], mL);
+            }
+            g0[cc] = fma_<T>(cw, m0, a0 * gr[cc]);
+            const T tr = fma_<T>(cw, mL, aL * gr[cc]);
+#pragma unroll
+            for (int k = 0; k < Sym<D>::NF; ++k) g2[k][cc] = (k == 0 || k == Sym<D>::NF - 1) ? tr : T(0);
+        }
+    }
+    // the same with everything read at point m
+    __device__ __forceinline__ void load_coupled(int64_t m, const T* __restrict__ GR, const Coupled<T>& cz) {
+        T gr[C];
+#pragma unroll
+        for (int ch = 0; ch < C; ++ch) gr[ch] = GR[m * C + ch];
+        form_coupled(gr, cz.a0_pt ? cz.a0_pt[m] : cz.a0, cz.aL_pt ? cz.aL_pt[m] : cz.aL, cz.cw_pt ? cz.cw_pt[m] : cz.cw, cz);
     }
     // the incoming gradient gv [M][7] of the vorticity terms (MASK = ORDV_AS, D = 2, C = 2) as the gradients that arrive
     // at orders 0..3, in this struct's symmetric components (g2[i + j], g3[i + j + k]: each the SUM over the index

@@ -1970,6 +1970,8 @@ __device__ __forceinline__ void evaluate_rows(float* acc, const float* s, const 
 template <int C, int MASK>
 constexpr int fwd_waves() {
     constexpr int n = FwdLayout<2, C, MASK>::N;
+    // the coupled residual (c = 2, 4 accumulators): 65 VGPRs -- 7 waves; held to 8 waves' 64 it puts two registers in scratch
+    if (MASK == ORDC) return 7;
     return n > 12 ? 4 : n > 10 ? 5 : (C == 1 && (MASK == 7 || MASK == 19 || MASK == 1 || MASK == ORDR || MASK == ORDG)) ? PIGS_FWD_WAVES : 6;
 }
 constexpr bool fwd_can_stage(int C, int MASK) { return C == 1 && (MASK == 7 || MASK == 19); }
@@ -2473,6 +2475,7 @@ __device__ __forceinline__ void load_tile_point(const SamplesView& sv, uint32_t 
     } else if constexpr (MASK == ORDR) G.load_residual((int64_t)sp.m, G0p, rz);
     else if constexpr (MASK == ORDG) G.load_terms((int64_t)sp.m, G0p, rz);
     else if constexpr (MASK == ORDV) G.load_vorticity((int64_t)sp.m, G0p);
+    else if constexpr (MASK == ORDC) G.load_coupled((int64_t)sp.m, G0p, rz);
     else G.load((int64_t)sp.m, G0p, G1p, G2p, G3p);
     if (!valid) {
 #pragma unroll
@@ -2625,6 +2628,7 @@ __device__ __forceinline__ void backward_points_helper(const PlanView& pv, const
         if constexpr (MASK == ORDR) G.load_residual((int64_t)sp.m, G0p, rz);
         else if constexpr (MASK == ORDG) G.load_terms((int64_t)sp.m, G0p, rz);
         else if constexpr (MASK == ORDV) G.load_vorticity((int64_t)sp.m, G0p);
+        else if constexpr (MASK == ORDC) G.load_coupled((int64_t)sp.m, G0p, rz);
         else G.load((int64_t)sp.m, G0p, G1p, G2p, G3p);
         // The walk in step over the whole wave (round 4): every lane meets its own (point, Gaussian) pair, and a pair's
         // NV sums leave as ONE atomic request -- lane = (pair, value), eight pairs per instruction, each a pair's 32-byte
@@ -3473,7 +3477,8 @@ template <int C> static bool fused_first_compiled(int mask) { return C == 1 ? (m
 
 template <int C>
 static int plan_forward_c(const PlanView& pv_in, const SamplesView& sv, int mask, float* const* out, hipStream_t stream,
-                          const Resid<float>& rz, const ListArgs* first = nullptr, const Terms<float>* tz = nullptr) {
+                          const Resid<float>& rz, const ListArgs* first = nullptr, const Terms<float>* tz = nullptr,
+                          const Coupled<float>* cz = nullptr) {
     // + the helper workgroups of the TILE_MODE_POINTS tiles (they leave at once when the plan queued none)
     const dim3 grid((sv.ntiles + PIGS_FWD_WG_WAVES - 1) / PIGS_FWD_WG_WAVES + POINT_HELPER_BLOCKS * 4 / PIGS_FWD_WG_WAVES),
         block(64 * PIGS_FWD_WG_WAVES);
@@ -3513,6 +3518,13 @@ static int plan_forward_c(const PlanView& pv_in, const SamplesView& sv, int mask
     if (mask == ORDG) {      // the general residual: its own coefficient block (never fused with the list launch)
         if (!tz) return PIGS_ERR_INVALID;
         hipLaunchKernelGGL((tile_forward_kernel<C, ORDG>), grid, block, 0, stream, pv, sv, out[0], out[1], out[2], out[3], *tz);
+    } else if (mask == ORDC) {      // the coupled residual: two channels, its own coefficient block (never fused either)
+        if (!cz) return PIGS_ERR_INVALID;
+        if constexpr (C == 2) {
+            hipLaunchKernelGGL((tile_forward_kernel<C, ORDC>), grid, block, 0, stream, pv, sv, out[0], out[1], out[2], out[3], *cz);
+        } else {
+            return PIGS_ERR_UNSUPPORTED;
+        }
     } else if (mask == ORDV) {      // the vorticity terms: two channels only (never fused with the list launch)
         if constexpr (C == 2) {
             hipLaunchKernelGGL((tile_forward_kernel<C, ORDV>), grid, block, 0, stream, pv, sv, out[0], out[1], out[2], out[3], rz);
@@ -3534,7 +3546,8 @@ static int plan_forward_c(const PlanView& pv_in, const SamplesView& sv, int mask
 
 template <int C>
 static int plan_backward_c(const PlanView& pv_in, const SamplesView& sv, int mask, const float* const* g, float* gm,
-                           float* gc, float* gv, hipStream_t stream, const Resid<float>& rz, const Terms<float>* tz = nullptr) {
+                           float* gc, float* gv, hipStream_t stream, const Resid<float>& rz, const Terms<float>* tz = nullptr,
+                           const Coupled<float>* cz = nullptr) {
     const dim3 grid((sv.ntiles + 3) / 4 + POINT_HELPER_BLOCKS), block(256);
     // points that arrive in no order fetch their incoming gradients from the staging records (PlanView::stage)
     PlanView pv = pv_in;
@@ -3565,6 +3578,17 @@ static int plan_backward_c(const PlanView& pv_in, const SamplesView& sv, int mas
 #else
         hipLaunchKernelGGL((tile_backward_kernel<C, ORDG>), grid, block, 0, stream, pv, sv, g[0], g[1], g[2], g[3], *tz);
 #endif
+    } else if (mask == ORDC) {
+        if (!cz) return PIGS_ERR_INVALID;
+        if constexpr (C == 2) {
+#if PIGS_BWD_BLOCK
+            hipLaunchKernelGGL((block_backward_kernel<C, ORDC>), bgrid, block, 0, stream, pv, sv, g[0], g[1], g[2], g[3], *cz);
+#else
+            hipLaunchKernelGGL((tile_backward_kernel<C, ORDC>), grid, block, 0, stream, pv, sv, g[0], g[1], g[2], g[3], *cz);
+#endif
+        } else {
+            return PIGS_ERR_UNSUPPORTED;
+        }
     } else if (mask == ORDV) {
         if constexpr (C == 2) {
 #if PIGS_BWD_BLOCK
@@ -3597,7 +3621,7 @@ static Resid<float> resid_of(const double* r, const void* target) {
 
 int plan_forward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, int64_t N, int64_t M, int c,
                  float q_max, int mask, void* const* out, hipStream_t stream, const double* resid, const void* target,
-                 const PigsResidualTerms* terms, void* aux) {
+                 const PigsResidualTerms* terms, void* aux, const PigsResidualCoupling* coupling) {
     if (!plan_supported(N, M, c)) return PIGS_ERR_UNSUPPORTED;
     const PlanLayout p = make_plan_layout(N, M, c);
     const SamplesLayout s = make_samples_layout(M);
@@ -3614,15 +3638,18 @@ int plan_forward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, i
     if (first) la = make_list_args(p, s, ws, sws, d.q_f, d.q_wide);
     const Terms<float> tz = terms_of(terms, target, aux);
     const Terms<float>* tp = terms ? &tz : nullptr;
-    const int rc = c == 1 ? plan_forward_c<1>(pv, sv, cm, o, stream, resid_of(resid, target), first ? &la : nullptr, tp)
-                          : plan_forward_c<2>(pv, sv, cm, o, stream, resid_of(resid, target), first ? &la : nullptr, tp);
+    const Coupled<float> cz = coupling ? make_coupled<float>(*coupling, target) : Coupled<float>{};
+    const Coupled<float>* cp = coupling ? &cz : nullptr;
+    const int rc = c == 1 ? plan_forward_c<1>(pv, sv, cm, o, stream, resid_of(resid, target), first ? &la : nullptr, tp, cp)
+                          : plan_forward_c<2>(pv, sv, cm, o, stream, resid_of(resid, target), first ? &la : nullptr, tp, cp);
     if (first && rc == PIGS_OK) plan_note_points(p, ws, stream);
     return rc;
 }
 
 int plan_backward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, int64_t N, int64_t M, int c,
                   float q_max, int mask, const void* const* gout, void* g_means, void* g_conics, void* g_values,
-                  hipStream_t stream, const double* resid, const PigsResidualTerms* terms, const void* aux) {
+                  hipStream_t stream, const double* resid, const PigsResidualTerms* terms, const void* aux,
+                  const PigsResidualCoupling* coupling) {
     if (!plan_supported(N, M, c)) return PIGS_ERR_UNSUPPORTED;
     const PlanLayout p = make_plan_layout(N, M, c);
     const SamplesLayout s = make_samples_layout(M);
@@ -3644,9 +3671,11 @@ int plan_backward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, 
     const int cm = covering_mask_of(mask);
     const Terms<float> tz = terms_of(terms, nullptr, aux);
     const Terms<float>* tp = terms ? &tz : nullptr;
+    const Coupled<float> cz = coupling ? make_coupled<float>(*coupling, nullptr) : Coupled<float>{};
+    const Coupled<float>* cp = coupling ? &cz : nullptr;
     switch (c) {
-        case 1: return plan_backward_c<1>(pv, sv, cm, g, (float*)g_means, (float*)g_conics, (float*)g_values, stream, resid_of(resid, nullptr), tp);
-        case 2: return plan_backward_c<2>(pv, sv, cm, g, (float*)g_means, (float*)g_conics, (float*)g_values, stream, resid_of(resid, nullptr), tp);
+        case 1: return plan_backward_c<1>(pv, sv, cm, g, (float*)g_means, (float*)g_conics, (float*)g_values, stream, resid_of(resid, nullptr), tp, cp);
+        case 2: return plan_backward_c<2>(pv, sv, cm, g, (float*)g_means, (float*)g_conics, (float*)g_values, stream, resid_of(resid, nullptr), tp, cp);
     }
     return PIGS_ERR_UNSUPPORTED;
 }

@@ -623,6 +623,108 @@ at::Tensor residual_terms_apply(const at::Tensor& means, const at::Tensor& value
 }
 
 // ---------------------------------------------------------------------------------------------
+// residual() with coupled channels (pigs_residual_coupled_*): one launch each way; the node owns inputs, plan and
+// coefficient fields.  The residual is linear in the field: nothing of the forward is kept for the backward.
+// ---------------------------------------------------------------------------------------------
+struct CouplingHost {
+    at::Tensor fields[3];                  // a0, aL, cw [M]: detached, contiguous, or undefined
+    double consts[3] = {0, 0, 1};          // a0, aL, cw where the field is undefined
+    double q0[16] = {}, qL[16] = {};       // couple0, couple_lap as [4][4]
+    PigsResidualCoupling abi() const {
+        PigsResidualCoupling t{};
+        t.a0 = consts[0]; t.aL = consts[1]; t.cw = consts[2];
+        for (int i = 0; i < 4; ++i)
+            for (int k = 0; k < 4; ++k) { t.couple0[i][k] = q0[4 * i + k]; t.couple_lap[i][k] = qL[4 * i + k]; }
+        t.a0_pt = ptr(fields[0]); t.aL_pt = ptr(fields[1]); t.cw_pt = ptr(fields[2]);
+        return t;
+    }
+};
+
+struct ResidualCoupledBackward : public torch::autograd::Node {
+    at::Tensor means, values, conics, samples;
+    uint32_t versions[4] = {0, 0, 0, 0};
+    CouplingHost coupling;
+    bool debug = false, has_target = false;
+    at::ScalarType target_dtype = at::kFloat;
+    std::shared_ptr<Plan> plan;
+
+    std::string name() const override { return "PigsResidualCoupledBackward"; }
+    void release_variables() override {}
+
+    torch::autograd::variable_list apply(torch::autograd::variable_list&& grads) override {
+        if (means._version() != versions[0] || values._version() != versions[1] || conics._version() != versions[2] ||
+            samples._version() != versions[3])
+            throw std::runtime_error(
+                "one of the tensors handed to GaussianSampler.preprocess() has been modified in place before the "
+                "backward of a residual() output that was computed from it");
+        torch::autograd::variable_list res(has_target ? 4 : 3);
+        if (grads.empty() || !grads[0].defined()) return res;
+        at::AutoGradMode no_grad(false);
+        if (grads[0].requires_grad()) throw std::runtime_error("GaussianSampler.residual() is differentiable once");
+        if (debug && plan && plan->forward_only) throw std::logic_error("a residual() node holds a forward-only plan");
+        const at::Tensor gout = grads[0].contiguous();
+        const int64_t N = means.size(0), d = means.size(1), c = values.size(1), M = samples.size(0);
+        auto gv3 = gradient_views(means, values, conics);
+        at::Tensor g_means = gv3[0], g_values = gv3[1], g_conics = gv3[2];
+        if (N > 0 && M > 0) {
+            c10::DeviceGuard guard(means.device());
+            const hipStream_t stream = current_stream(means);
+            const PlanPtrs pp = plan_ptrs(plan.get(), stream);
+            const PigsResidualCoupling t = coupling.abi();
+            check(pigs_residual_coupled_backward(dtype_code(means), (int)d, (int)c, N, M, ptr(means), ptr(conics), ptr(values),
+                                                 ptr(samples), &t, ptr(gout), ptr(g_means), ptr(g_conics), ptr(g_values),
+                                                 pp.pw, pp.pb, pp.sw, pp.sb, stream),
+                  "pigs_residual_coupled_backward");
+        } else {
+            g_means.zero_(); g_values.zero_(); g_conics.zero_();
+        }
+        if (debug) device_sync(means);
+        res[0] = g_means; res[1] = g_values; res[2] = g_conics;
+        if (has_target && task_should_compute_output(3)) res[3] = gout.neg().to(target_dtype);
+        return res;
+    }
+};
+
+at::Tensor residual_coupled_apply(const at::Tensor& means, const at::Tensor& values, const at::Tensor& conics,
+                                  const at::Tensor& samples, const CouplingHost& coupling,
+                                  const c10::optional<at::Tensor>& target, bool debug, const std::shared_ptr<Plan>& plan) {
+    const int64_t N = means.size(0), d = means.size(1), c = values.size(1), M = samples.size(0);
+    at::Tensor tgt;
+    if (target.has_value()) {
+        at::AutoGradMode no_grad(false);
+        tgt = target->detach().to(means.scalar_type()).contiguous();
+    }
+    const bool tgrad = target.has_value() && target->requires_grad();
+    const bool differentiable =
+        at::GradMode::is_enabled() && (means.requires_grad() || values.requires_grad() || conics.requires_grad() || tgrad);
+    at::Tensor out = at::empty({M, c}, means.options());
+    if (M > 0) {
+        c10::DeviceGuard guard(means.device());
+        const hipStream_t stream = current_stream(means);
+        const PlanPtrs pp = plan_ptrs(plan.get(), stream);
+        const PigsResidualCoupling t = coupling.abi();
+        check(pigs_residual_coupled_forward(dtype_code(means), (int)d, (int)c, N, M, ptr(means), ptr(conics), ptr(values),
+                                            ptr(samples), &t, ptr(tgt), ptr(out), pp.pw, pp.pb, pp.sw, pp.sb, stream),
+              "pigs_residual_coupled_forward");
+    }
+    if (debug) device_sync(means);
+    if (differentiable) {
+        std::shared_ptr<ResidualCoupledBackward> node(new ResidualCoupledBackward(), torch::autograd::deleteNode);
+        if (target.has_value()) node->set_next_edges(torch::autograd::collect_next_edges(means, values, conics, *target));
+        else node->set_next_edges(torch::autograd::collect_next_edges(means, values, conics));
+        node->means = means; node->values = values; node->conics = conics; node->samples = samples;
+        node->versions[0] = means._version(); node->versions[1] = values._version();
+        node->versions[2] = conics._version(); node->versions[3] = samples._version();
+        node->coupling = coupling;
+        node->debug = debug; node->plan = plan;
+        node->has_target = target.has_value();
+        if (target.has_value()) node->target_dtype = target->scalar_type();
+        torch::autograd::create_gradient_edge(out, node);
+    }
+    return out;
+}
+
+// ---------------------------------------------------------------------------------------------
 // vorticity_terms(): (u_x, u_y, div, w, w_x, w_y, lap w) as [M, 7] in one launch (pigs_vorticity_*); the node owns its
 // inputs and plan like ResidualBackward.
 // ---------------------------------------------------------------------------------------------
@@ -1133,6 +1235,21 @@ struct Core {
         return residual_terms_apply(means, values, conics, samples, t, target, debug, plan_for(0, target));
     }
 
+    // fields: a0, aL, cw as validated, detached, contiguous tensors (or None); consts: the same three where no field;
+    // couple0 / couple_lap: [4][4] row-major, [ch][c'] (the Python wrapper validates and converts)
+    at::Tensor residual_coupled(const std::array<c10::optional<at::Tensor>, 3>& fields, const std::array<double, 3>& consts,
+                                const std::array<double, 16>& couple0, const std::array<double, 16>& couple_lap,
+                                const c10::optional<at::Tensor>& target) {
+        require_inputs();
+        CouplingHost t;
+        for (int k = 0; k < 3; ++k) {
+            if (fields[k].has_value()) t.fields[k] = *fields[k];
+            t.consts[k] = consts[k];
+        }
+        for (int k = 0; k < 16; ++k) { t.q0[k] = couple0[k]; t.qL[k] = couple_lap[k]; }
+        return residual_coupled_apply(means, values, conics, samples, t, target, debug, plan_for(0, target));
+    }
+
     // (u_x, u_y, div, w, w_x, w_y, lap w) [M, 7]; on the order-3 plan where there is one
     at::Tensor vorticity_terms() {
         require_inputs();
@@ -1270,6 +1387,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("residual", &Core::residual, py::arg("coeffs"), py::arg("target") = c10::optional<at::Tensor>())
         .def("residual_terms", &Core::residual_terms, py::arg("fields"), py::arg("consts"), py::arg("advect_by"),
              py::arg("target") = c10::optional<at::Tensor>())
+        .def("residual_coupled", &Core::residual_coupled, py::arg("fields"), py::arg("consts"), py::arg("couple0"),
+             py::arg("couple_lap"), py::arg("target") = c10::optional<at::Tensor>())
         .def("vorticity_terms", &Core::vorticity_terms)
         .def("preprocess_aggregate", &Core::preprocess_aggregate, py::arg("cap") = -1)
         .def("aggregate_neighbors", &Core::aggregate_neighbors)

@@ -558,6 +558,98 @@ class _ResidualTermsFunction(torch.autograd.Function):
         return g_means, g_values, g_conics, None, g_target, None, None, None, None
 
 
+class ResidualCoupling:
+    """The coefficients of a coupled residual() call: a0, aL, cw as floats or detached device fields [M], and the two
+    c x c constant matrices (row = output channel, column = input channel)."""
+
+    def __init__(self, a0, aL, cw, couple0, couple_lap):
+        self.a0, self.aL, self.cw, self.couple0, self.couple_lap = a0, aL, cw, couple0, couple_lap
+
+    def struct(self):
+        t = _lib.PigsResidualCoupling()
+        for name, v in (("a0", self.a0), ("aL", self.aL), ("cw", self.cw)):
+            if isinstance(v, torch.Tensor):
+                setattr(t, name + "_pt", v.data_ptr())
+            else:
+                setattr(t, name, v)
+        for dst, src in ((t.couple0, self.couple0), (t.couple_lap, self.couple_lap)):
+            for i, row in enumerate(src):
+                for k, v in enumerate(row):
+                    dst[i][k] = v
+        return t
+
+
+def _residual_coupled_call(backward, means, values, conics, samples, coupling, plan, target=None, gout=None):
+    """pigs_residual_coupled_forward / _backward on contiguous device tensors (through the plan when given)."""
+    lib = _lib.load()
+    N, d = means.shape
+    c = values.shape[1]
+    M = samples.shape[0]
+    cz = coupling.struct()
+    if backward and plan is not None and M > 0 and getattr(plan, "forward_only", False):
+        plan = plan.full_for_backward(means, values, conics, samples)
+    pw = (_ptr(plan.workspace), plan.workspace.numel(), _ptr(plan.samples.workspace), plan.samples.workspace.numel()) \
+        if plan is not None else (ctypes.c_void_p(0), 0, ctypes.c_void_p(0), 0)
+    with _on_device(means.device):
+        stream = _stream(means.device)
+        if plan is not None and hasattr(plan, "note_stream"):
+            plan.note_stream(stream.value)
+        if not backward:
+            out = torch.empty((M, c), dtype=means.dtype, device=means.device)
+            if M > 0:
+                rc = lib.pigs_residual_coupled_forward(_DTYPES[means.dtype], d, c, N, M, _ptr(means), _ptr(conics),
+                                                       _ptr(values), _ptr(samples), ctypes.byref(cz), _ptr(target), _ptr(out),
+                                                       *pw, stream)
+                _lib.check(rc, "pigs_residual_coupled_forward")
+            return out
+        g_means, g_values, g_conics = _gradient_views(means, values, conics)
+        if N > 0:
+            if M > 0:
+                rc = lib.pigs_residual_coupled_backward(_DTYPES[means.dtype], d, c, N, M, _ptr(means), _ptr(conics),
+                                                        _ptr(values), _ptr(samples), ctypes.byref(cz), _ptr(gout),
+                                                        _ptr(g_means), _ptr(g_conics), _ptr(g_values), *pw, stream)
+                _lib.check(rc, "pigs_residual_coupled_backward")
+            else:
+                for g in (g_means, g_values, g_conics):
+                    g.zero_()
+        return g_means, g_values, g_conics
+
+
+class _ResidualCoupledFunction(torch.autograd.Function):
+    """The coupled residual (two constant matrices mix the channels under a per-point weight) in one launch; its
+    backward is one launch too.  The node owns its inputs, plan and coefficient fields like
+    :class:`_ResidualTermsFunction`; the residual is linear in the field, so no record of the forward is kept."""
+
+    @staticmethod
+    def forward(ctx, means, values, conics, samples, target, coupling, debug, plan):
+        tgt = None if target is None else target.detach().to(means.dtype).contiguous()
+        out = _residual_coupled_call(False, means, values, conics, samples, coupling, plan, target=tgt)
+        if debug:
+            torch.cuda.synchronize(means.device)
+        ctx.inputs = (means, values, conics, samples)
+        ctx.versions = (means._version, values._version, conics._version, samples._version)
+        ctx.coupling, ctx.debug, ctx.plan = coupling, debug, plan
+        ctx.target_dtype = None if target is None else target.dtype
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        means, values, conics, samples = ctx.inputs
+        if (means._version, values._version, conics._version, samples._version) != ctx.versions:
+            raise RuntimeError("one of the tensors handed to GaussianSampler.preprocess() has been modified in place "
+                               "before the backward of a residual() output that was computed from it")
+        gout = gout.contiguous()
+        if ctx.debug:
+            assert ctx.plan is None or not ctx.plan.forward_only, "a residual() node holds a forward-only plan"
+        g_means, g_values, g_conics = _residual_coupled_call(True, means, values, conics, samples, ctx.coupling, ctx.plan,
+                                                             gout=gout)
+        if ctx.debug:
+            torch.cuda.synchronize(means.device)
+        g_target = None if ctx.target_dtype is None or not ctx.needs_input_grad[4] else (-gout).to(ctx.target_dtype)
+        return g_means, g_values, g_conics, None, g_target, None, None, None
+
+
 def _vorticity_call(backward, means, values, conics, samples, plan, gout=None):
     """pigs_vorticity_forward / _backward on contiguous device tensors (through the plan when given)."""
     lib = _lib.load()
@@ -1162,7 +1254,57 @@ class GaussianSampler:
             raise ValueError(f"{name} must hold d = {cols} coefficients")
         return v
 
-    def residual(self, a0=0.0, a1=None, lap=0.0, target=None, *, advect=None, advect_by=None):
+    def _coupling_matrix(self, name, q, c):
+        """couple0 / couple_lap of residual(): c x c constants as a tuple of tuples (None: the zero matrix)."""
+        if q is None:
+            return tuple((0.0,) * c for _ in range(c))
+        if isinstance(q, torch.Tensor) and q.requires_grad:
+            raise ValueError(f"{name}: the coupling matrices of residual() are constants; detach() the tensor")
+        try:
+            q = tuple(tuple(float(x) for x in row) for row in q)
+        except TypeError:
+            raise ValueError(f"{name} must be c x c = {c} x {c} floats") from None
+        if len(q) != c or any(len(row) != c for row in q):
+            raise ValueError(f"{name} must be c x c = {c} x {c} floats")
+        return q
+
+    def _residual_coupled(self, a0, a1, lap, target, advect, advect_by, couple0, couple_lap, couple_weight):
+        """The coupled form of residual(): every refusal, then one launch."""
+        means, values, conics, samples = self._require_inputs()
+        d, c, M = means.shape[1], values.shape[1], samples.shape[0]
+        if couple0 is None and couple_lap is None:
+            raise ValueError("couple_weight weighs couple0 / couple_lap: give at least one of the two matrices")
+        if c == 1:
+            raise ValueError("a one-channel field has nothing to couple: use a0 / lap")
+        Q0 = self._coupling_matrix("couple0", couple0, c)
+        QL = self._coupling_matrix("couple_lap", couple_lap, c)
+        a1_zero = a1 is None or (not isinstance(a1, torch.Tensor)
+                                 and all(float(x) == 0.0 for x in (a1 if hasattr(a1, "__len__") else (a1,))))
+        if not a1_zero or advect is not None or advect_by is not None:
+            raise NotImplementedError("a coupled residual() with a first-derivative (a1) or advection term is not built: "
+                                      "compose it from sample((0, 1, \"lap\"))")
+        f0 = self._residual_field("a0", a0, 1)
+        fL = self._residual_field("lap", lap, 1)
+        fW = self._residual_field("couple_weight", 1.0 if couple_weight is None else couple_weight, 1)
+        if target is not None:
+            if not isinstance(target, torch.Tensor) or not target.is_cuda:
+                raise RuntimeError("target must be a tensor on the GPU (no CPU fallback)")
+            if target.numel() != M * c:
+                raise ValueError(f"target must hold M*c = {M * c} elements, got {tuple(target.shape)}")
+            target = target.reshape(M, c)
+        if self._core is not None:
+            flat0, flatL = [0.0] * 16, [0.0] * 16          # the matrices as [4][4]
+            for i in range(c):
+                flat0[4 * i:4 * i + c] = Q0[i]
+                flatL[4 * i:4 * i + c] = QL[i]
+            fields = [v if isinstance(v, torch.Tensor) else None for v in (f0, fL, fW)]
+            consts = [0.0 if isinstance(v, torch.Tensor) else v for v in (f0, fL, fW)]
+            return self._core.residual_coupled(fields, consts, flat0, flatL, target)
+        return _ResidualCoupledFunction.apply(means, values, conics, samples, target, ResidualCoupling(f0, fL, fW, Q0, QL),
+                                              self.debug, self._plan_for(0, target))
+
+    def residual(self, a0=0.0, a1=None, lap=0.0, target=None, *, advect=None, advect_by=None,
+                 couple0=None, couple_lap=None, couple_weight=None):
         """Extension of the reference API: the linear residual
         ``r = a0 u + a1 . grad u + lap (u_xx + u_yy) - target`` as [M, c] in ONE launch (4 bytes per point and
         channel instead of the 28 of u, grad u and the Hessian), differentiable wrt means, values, conics (one
@@ -1183,7 +1325,27 @@ class GaussianSampler:
         floats only and ``advect=None`` is the linear residual above, on its own kernel.  INTEGRATION.md has the
         Burgers and trapezoid-diffusion recipes; DESIGN.md 12 the measured times against the same loss composed from
         ``sample((0, 1, "lap"))``: a training step is 19-25 % shorter, the forward alone (``no_grad``) is SLOWER
-        (1.30x - 1.35x) when the coefficient fields are rebuilt in torch every step."""
+        (1.30x - 1.35x) when the coefficient fields are rebuilt in torch every step.
+
+        THE COUPLED FORM (the channels mixed by constants; one launch each way; c >= 2):
+        ``r = a0 u + lap (u_xx + u_yy) + couple_weight * (u @ couple0.T + lap_u @ couple_lap.T) - target``.
+        ``couple0``, ``couple_lap``: c x c floats (nested sequences or arrays; row = output channel, column = input
+        channel; a missing one is zero; constants -- a tensor that requires grad raises ValueError).  ``couple_weight``:
+        a float (default 1.0) or a field of M elements, treated like ``a0`` and ``lap``, which keep their meaning.  Only
+        u and the Laplacian are accumulated (2 c sums per point).  ``a1``, ``advect`` and ``advect_by`` cannot be
+        combined with it (NotImplementedError: compose from ``sample()``).  The reference's wave system
+        (test_no_mlp.py:127-139: ``res0 = u_t[0] - ub[1]``, ``res1 = u_t[1] - (10 lap ub[0] - 0.1 ub[1])``, ``ub`` blended
+        by a random weight ``tau`` per point) is two launches::
+
+            Q0, QL = np.array(((0, -1), (0, 0.1))), np.array(((0, 0), (-10, 0)))
+            with torch.no_grad():      # the previous step's Gaussians bound to `prev`
+                T = prev.residual(a0=1 / dt, couple_weight=tau, couple0=-Q0, couple_lap=-QL)
+            r = cur.residual(a0=1 / dt, couple_weight=1 - tau, couple0=Q0, couple_lap=QL, target=T)
+            loss = r[:, 0].pow(2).mean() + 0.01 * r[:, 1].pow(2).mean()
+
+        INTEGRATION.md 1 has the recipe in full; DESIGN.md 14 the kernel and the measured times."""
+        if couple0 is not None or couple_lap is not None or couple_weight is not None:
+            return self._residual_coupled(a0, a1, lap, target, advect, advect_by, couple0, couple_lap, couple_weight)
         means, values, conics, samples = self._require_inputs()
         d, c, M = means.shape[1], values.shape[1], samples.shape[0]
         general = advect is not None or advect_by is not None or any(isinstance(v, torch.Tensor) for v in (a0, a1, lap))
