@@ -403,11 +403,14 @@ int pigs_periodic_images_backward(int dtype, int c, int64_t N,
  *   needs no counting pass); beyond, through the sampler's multi-level Gaussian grid in `workspace`
  *   (pigs_aggregate_workspace_bytes(dtype, N) bytes, 256-byte aligned; 0 = unsupported N): `flags` & PIGS_AGGREGATE_BUILD_GRID (re)builds the grid from
  *   `means` / `conics` first (4 launches; float64 inputs are binned through float32 copies with a
- *   widened cut-off -- the grid only nominates candidates, every pair is tested in the caller's dtype;
- *   this presumes ellipses far larger than the float32 spacing of the coordinates), without it the
- *   workspace must hold the grid of the same Gaussians.  With row_lists == col_lists == NULL only the
- *   counts are written (the FULL list lengths: the caller sizes `cap` from their maximum, then calls
- *   again with the lists).  *overflow (int32, zeroed by the caller) is set when a list did not fit
+ *   widened cut-off -- the grid only nominates candidates, every pair is tested in the caller's dtype),
+ *   without it the workspace must hold the grid of the same Gaussians.
+ *   PRECONDITION of the float64 grid build, not checked: the cut-off is widened by 5 %, which covers a displacement
+ *   of sqrt(q) by 0.148 at q_max = 36; the float32 copies move a difference of centres by up to 2 sqrt(2) 2^-24
+ *   max|mu|, so every Gaussian's smallest standard deviation along any axis must stay above that / 0.148
+ *   ~ 1.14e-6 max|mu| (8e-4 for centres near (300, -700)).  A narrower Gaussian can lose neighbours.
+ *   With row_lists == col_lists == NULL only the counts are written (the FULL list lengths: the caller sizes
+ *   `cap` from their maximum, then calls again with the lists).  *overflow (int32, zeroed by the caller) is set when a list did not fit
  *   `cap` (it is then truncated).  List order is the grid's (not ascending; may differ between builds).
  * pigs_aggregate_forward: out [N][L], and for the backward lse [N] (log-sum-exp of the scaled scores)
  *   and acc [N][L + 2E] = (sum_j a_ij features_j ; sum_j a_ij [e_ij ; g_ij e_ij]).
@@ -418,9 +421,25 @@ int pigs_periodic_images_backward(int dtype, int c, int64_t N,
  *   frequency gradient between the launches.  The per-Gaussian gradients are gathers (no atomics); the
  *   three sums over the Gaussians are plain sums up to N = 2048 and atomic sums of 2048-Gaussian
  *   partials beyond.
+ * Sizes: L + 2E <= 128, L + K <= 128, K + F <= 128 (two components per lane), and the three sampling kernels' dynamic
+ *   LDS -- sizeof(T) * 4 * region values, region = max(64 ((L + 4F) | 1), 136) in the forward, the same with
+ *   (L + K) | 1 in the backward by columns, 136 + the same with (K + F) | 1 in the backward by rows -- must fit a
+ *   CU's PIGS_AGGREGATE_LDS_MAX bytes.  Every float32 shape of the first rule does (at most 134 272 B); in float64
+ *   the strides are limited to 79 in the forward and the backward by columns (e.g. L + K <= 79) and to 77 in the
+ *   backward by rows (K + F <= 77).  pigs_aggregate_lds_bytes(dtype, L, K, F) is the largest of
+ *   the three (0: a size out of range).  pigs_aggregate_forward applies all of this, the backward's kernels
+ *   included -- a forward that could never be differentiated is refused -- and so does pigs_aggregate_backward:
+ *   PIGS_ERR_UNSUPPORTED before any HIP call.  (pigs_aggregate_lds_bytes is additive to ABI 10.)
+ * pigs_aggregate_grid_info: introspection for tests (never needed to use the lists; additive to ABI 10).  After a grid
+ *   build (N > 2048) info[0] = byte offset inside `workspace` of a uint32 whose bit l is set when level l of the grid
+ *   holds a Gaussian, info[1] = the grid's levels (the top one, a single cell, is level info[1] - 1).
+ *   PIGS_ERR_UNSUPPORTED where pigs_aggregate_lists builds no grid.
  */
 #define PIGS_AGGREGATE_BUILD_GRID 1
+#define PIGS_AGGREGATE_LDS_MAX 163840
 size_t pigs_aggregate_workspace_bytes(int dtype, int64_t N);
+size_t pigs_aggregate_lds_bytes(int dtype, int L, int K, int F);
+int pigs_aggregate_grid_info(int dtype, int64_t N, int64_t info[2]);
 int pigs_aggregate_lists(int dtype, int64_t N, int64_t cap, const void* means, const void* conics, double q_max,
                          void* workspace, size_t workspace_bytes, int flags,
                          int32_t* row_counts, int32_t* row_lists, int32_t* col_counts, int32_t* col_lists,

@@ -88,6 +88,8 @@ SIGNATURES = {
                              + [_vp, _vp]),
     "pigs_periodic_images_backward": (_i, [_i, _i, _i64] + [_vp] * 6 + [_vp]),
     "pigs_aggregate_workspace_bytes": (ctypes.c_size_t, [_i, _i64]),
+    "pigs_aggregate_lds_bytes": (ctypes.c_size_t, [_i, _i, _i, _i]),      # additive to ABI 10
+    "pigs_aggregate_grid_info": (_i, [_i, _i64, ctypes.POINTER(_i64)]),     # additive to ABI 10
     "pigs_aggregate_lists": (_i, [_i, _i64, _i64, _vp, _vp, ctypes.c_double, _vp, ctypes.c_size_t, _i] + [_vp] * 5 + [_vp]),
     "pigs_aggregate_forward": (_i, [_i, _i64, _i64, _i, _i, _i] + [_vp] * 4 + [_vp] * 6 + [_vp] * 3 + [_vp]),
     "pigs_aggregate_backward_scratch_bytes": (ctypes.c_size_t, [_i, _i64, _i, _i]),

@@ -34,6 +34,7 @@ from . import _lib
 
 _DTYPES = {torch.float32: _lib.PIGS_F32, torch.float64: _lib.PIGS_F64}
 BRUTE_MAX = 2048     # pigs_amd/csrc/aggregate.hip AGG_BRUTE_MAX: up to here every pair is tested, cap = N
+LDS_MAX = 163840     # PIGS_AGGREGATE_LDS_MAX of include/pigs_amd.h: the LDS of a CU
 MAX_NEIGHBORS = {torch.float32: 8192, torch.float64: 4096}      # slab size when the counting pass cannot be read back (capture)
 
 
@@ -188,4 +189,9 @@ def aggregate(nb, features, transform, queries, keys, frequencies, distance_tran
             raise RuntimeError(f"{name} is on {t.device}: aggregate_neighbors runs on the GPU only (no CPU fallback)")
     if L + 2 * E > 128:
         raise NotImplementedError(f"L + 2E = {L + 2 * E} > 128 is not supported")
+    dt = nb.means.dtype
+    lds = _lib.load().pigs_aggregate_lds_bytes(_DTYPES[dt], L, K, F)
+    if lds > LDS_MAX:      # the backward's kernels included: a forward that cannot be differentiated is refused
+        raise NotImplementedError(f"{str(dt).replace('torch.', '')} with L = {L}, K = {K}, F = {F} needs {lds} bytes of LDS "
+                                  f"in one of the forward's or the backward's kernels; the limit is {LDS_MAX}")
     return _Aggregate.apply(nb, features, transform, queries, keys, frequencies, distance_transform)

@@ -691,6 +691,13 @@ size_t aggregate_workspace_bytes(int dtype, int64_t N) {
     return g == 0 ? 0 : cast_bytes(dtype, N) + g;
 }
 
+int aggregate_grid_info(int dtype, int64_t N, int64_t* info) {
+    if (N <= AGG_BRUTE_MAX || aggregate_workspace_bytes(dtype, N) == 0) return PIGS_ERR_UNSUPPORTED;     // no grid
+    aggregate_grid_levels(N, info);
+    info[0] += (int64_t)cast_bytes(dtype, N);
+    return PIGS_OK;
+}
+
 // The grid's cut-off only nominates candidates; it must cover q <= q_max however the float32 grid
 // arithmetic rounds: a generous margin costs a few candidates, nothing else.
 static float grid_cutoff(int dtype, double q_max) { return (float)(q_max * (dtype == PIGS_F64 ? 1.05 : 1.02) + 1e-3); }
@@ -753,21 +760,38 @@ int aggregate_lists(int dtype, int64_t N, int64_t cap, const void* means, const 
 }
 
 // LDS of a sampling kernel: four wave regions of `region` values; beyond 64 KB the launch has to ask for it.
+// *rc keeps the first refusal (the C API admits no shape beyond AGG_LDS_MAX, so this is a runtime that grants less).
 template <typename Kernel>
-static size_t sampling_lds(Kernel kernel, size_t elem, size_t region) {
+static size_t sampling_lds(Kernel kernel, size_t elem, size_t region, int* rc) {
     const size_t bytes = elem * 4 * region;
-    if (bytes > 64 * 1024)
-        (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (bytes > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess && *rc == PIGS_OK) {
+            (void)hipGetLastError();
+            g_last_hip_error = e;
+            *rc = PIGS_ERR_LAUNCH;
+        }
+    }
     return bytes;
 }
 static size_t rows_region(int stride) { return (size_t)(64 * stride > PART ? 64 * stride : PART); }
+static size_t forward_region(int L, int F) { return rows_region((L + 4 * F) | 1); }
+static size_t backward_rows_region(int K, int F) { return PART + rows_region((K + F) | 1); }
+static size_t backward_cols_region(int L, int K) { return rows_region((L + K) | 1); }
+// the most dynamic LDS any of the three sampling kernels asks for at these sizes (a CU has AGG_LDS_MAX = 160 KB)
+size_t aggregate_lds_bytes(int dtype, int L, int K, int F) {
+    const size_t a = forward_region(L, F), b = backward_rows_region(K, F), c = backward_cols_region(L, K);
+    return (dtype == PIGS_F64 ? 8 : 4) * 4 * (a > b ? (a > c ? a : c) : (b > c ? b : c));
+}
 // waves per Gaussian: a launch of few Gaussians is one generation of waves bound by a wave's serial life
 // (split every Gaussian's rounds over four waves); many Gaussians are a throughput problem (no idle waves)
 static int waves_per_gaussian(int64_t N) { return N <= 4096 ? 4 : N <= 8192 ? 2 : 1; }
 
 template <typename T, bool PER>
 static int aggregate_forward_t(const AggregateArgs& a, hipStream_t stream) {
-    const size_t lds = sampling_lds(aggregate_forward_kernel<T, PER>, sizeof(T), rows_region((a.L + 4 * a.F) | 1));
+    int rc = PIGS_OK;
+    const size_t lds = sampling_lds(aggregate_forward_kernel<T, PER>, sizeof(T), forward_region(a.L, a.F), &rc);
+    if (rc != PIGS_OK) return rc;
     const int wpg = waves_per_gaussian(a.N), gpw = 4 / wpg;
     clear_hip_error();
     hipLaunchKernelGGL((aggregate_forward_kernel<T, PER>), dim3((unsigned)((a.N + gpw - 1) / gpw)), dim3(256), lds, stream, a.N, a.L, a.K,
@@ -789,8 +813,10 @@ static int aggregate_backward_t(const AggregateArgs& a, hipStream_t stream) {
     T* dacc = (T*)a.scratch;
     T* D = dacc + (size_t)a.N * W;
     T* gfr = D + a.N;
-    const size_t lds_r = sampling_lds(aggregate_backward_rows_kernel<T, PER>, sizeof(T), PART + rows_region((a.K + a.F) | 1));
-    const size_t lds_c = sampling_lds(aggregate_backward_cols_kernel<T, PER>, sizeof(T), rows_region((a.L + a.K) | 1));
+    int rc = PIGS_OK;
+    const size_t lds_r = sampling_lds(aggregate_backward_rows_kernel<T, PER>, sizeof(T), backward_rows_region(a.K, a.F), &rc);
+    const size_t lds_c = sampling_lds(aggregate_backward_cols_kernel<T, PER>, sizeof(T), backward_cols_region(a.L, a.K), &rc);
+    if (rc != PIGS_OK) return rc;
     const int wpg = waves_per_gaussian(a.N), gpw = 4 / wpg;
     const dim3 grid((unsigned)((a.N + gpw - 1) / gpw)), block(256);
     // the sums over N: one split per ~2048 Gaussians (a single split is a plain, deterministic sum)

@@ -354,7 +354,20 @@ static int aggregate_sizes_ok(int dtype, int64_t N, int64_t cap, int L, int K, i
     if (dtype != PIGS_F32 && dtype != PIGS_F64) return PIGS_ERR_UNSUPPORTED;
     if (N < 0 || cap < 1 || L < 1 || K < 1 || F < 0) return PIGS_ERR_INVALID;
     if (L + 2 * (4 * F + 1) > 128 || L + K > 128 || K + F > 128 || N > 0x7fffffffLL) return PIGS_ERR_UNSUPPORTED;   // two components per lane
+    // the forward, too, refuses a shape whose backward could not run: all three kernels' LDS must fit a CU
+    if (aggregate_lds_bytes(dtype, L, K, F) > AGG_LDS_MAX) return PIGS_ERR_UNSUPPORTED;
     return PIGS_OK;
+}
+
+size_t pigs_aggregate_lds_bytes(int dtype, int L, int K, int F) {
+    if ((dtype != PIGS_F32 && dtype != PIGS_F64) || L < 1 || K < 1 || F < 0 || L > 128 || K > 128 || F > 128) return 0;
+    return aggregate_lds_bytes(dtype, L, K, F);
+}
+
+int pigs_aggregate_grid_info(int dtype, int64_t N, int64_t info[2]) {
+    if (dtype != PIGS_F32 && dtype != PIGS_F64) return PIGS_ERR_UNSUPPORTED;
+    if (N < 0 || !info) return PIGS_ERR_INVALID;
+    return aggregate_grid_info(dtype, N, info);
 }
 
 size_t pigs_aggregate_workspace_bytes(int dtype, int64_t N) {

@@ -48,6 +48,8 @@ struct AggregateArgs {
 };
 size_t aggregate_backward_scratch_bytes(int dtype, int64_t N, int L, int F);
 size_t aggregate_workspace_bytes(int dtype, int64_t N);
+constexpr size_t AGG_LDS_MAX = 160 * 1024;       // LDS of a gfx950 CU: what one workgroup can ask for
+size_t aggregate_lds_bytes(int dtype, int L, int K, int F);
 int aggregate_lists(int dtype, int64_t N, int64_t cap, const void* means, const void* conics, double q_max, void* workspace,
                     size_t workspace_bytes, int flags, int32_t* row_counts, int32_t* row_lists, int32_t* col_counts,
                     int32_t* col_lists, int32_t* overflow, hipStream_t stream, double lo = 0.0, double period = 0.0);
@@ -73,6 +75,8 @@ int plan_backward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, 
 int plan_layout_info(int64_t N, int64_t M, int c, int64_t* info);
 // the Gaussian grid alone (aggregate.hip): plan.hip
 size_t aggregate_grid_bytes(int64_t N);
+void aggregate_grid_levels(int64_t N, int64_t* info);
+int aggregate_grid_info(int dtype, int64_t N, int64_t* info);
 int aggregate_grid_build(void* ws, size_t ws_bytes, int64_t N, float q_grid, const float* means, const float* conics,
                          hipStream_t stream);
 size_t samples_error_offset();

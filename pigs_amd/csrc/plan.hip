@@ -3455,6 +3455,13 @@ int aggregate_grid_build(void* ws, size_t ws_bytes, int64_t N, float q_grid, con
                      means, means, stream, false);
 }
 
+// info[0] = byte offset of PlanParams::level_mask inside the grid workspace, info[1] = levels of the grid
+void aggregate_grid_levels(int64_t N, int64_t* info) {
+    const PlanLayout p = make_plan_layout(N, N, 1);
+    info[0] = (int64_t)(align_up(make_samples_layout(N).total_bytes, 256) + p.off_params + offsetof(PlanParams, level_mask));
+    info[1] = p.L;
+}
+
 PlanView aggregate_grid_view(void* ws, int64_t N, float q_grid) {
     const size_t sb = align_up(make_samples_layout(N).total_bytes, 256);
     return make_view(make_plan_layout(N, N, 1), (char*)ws + sb, q_grid);

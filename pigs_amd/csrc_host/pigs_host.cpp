@@ -939,6 +939,12 @@ at::Tensor aggregate_apply(const std::shared_ptr<NeighborLists>& nb, const at::T
                                              ": aggregate_neighbors runs on the GPU only (no CPU fallback)");
     if (L + 2 * E > 128) raise_py(PyExc_NotImplementedError, "L + 2E = " + std::to_string(L + 2 * E) + " > 128 is not supported");
     const auto dt = nb->means.scalar_type();
+    const size_t lds = pigs_aggregate_lds_bytes(dt == at::kDouble ? PIGS_F64 : PIGS_F32, (int)L, (int)K, (int)F);
+    if (lds > PIGS_AGGREGATE_LDS_MAX)      // the backward's kernels included: a forward that cannot be differentiated is refused
+        raise_py(PyExc_NotImplementedError, std::string(dt == at::kDouble ? "float64" : "float32") + " with L = " + std::to_string(L) +
+                                                ", K = " + std::to_string(K) + ", F = " + std::to_string(F) + " needs " +
+                                                std::to_string(lds) + " bytes of LDS in one of the forward's or the backward's kernels; "
+                                                "the limit is " + std::to_string(PIGS_AGGREGATE_LDS_MAX));
     at::Tensor c[6];
     {
         at::AutoGradMode no_grad(false);
