@@ -31,6 +31,9 @@
  *     the PDE residuals consume (model_pn.py:614-617) -- written to / read from the out2 / gout2
  *     slot in place of the full Hessian; bits 2 and 4 exclude each other (PIGS_ERR_INVALID), the
  *     trace together with order 3 has no fused kernel (PIGS_ERR_UNSUPPORTED: two calls).
+ *     The composed outputs have entry points of their own and no mask bit a caller may pass (PIGS_ERR_INVALID):
+ *     the library's masks 32, 64, 128, 256 and 512 stand for pigs_residual_*, pigs_residual_terms_*,
+ *     pigs_vorticity_*, pigs_residual_coupled_* and pigs_vorticity_residual_*.
  *   - supported: d in {1,2}, c in {1..4}, dtype f32/f64 (binned plan: d=2, f32).
  *   - return value: PIGS_OK or an error code; pigs_status_string() names it.
  */
@@ -307,6 +310,40 @@ int pigs_vorticity_backward(int dtype, int64_t N, int64_t M,
                             const void* means, const void* conics, const void* values, const void* samples, const void* gout,
                             void* g_means, void* g_conics, void* g_values,
                             void* plan_ws, size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes, void* stream);
+
+/*
+ * The Navier-Stokes residual in the vorticity formulation in ONE launch (additive to ABI 10; d = 2 and c = 2 are
+ * implied).  With `now` = the seven vorticity terms of the Gaussians at point m (the row of pigs_vorticity_forward),
+ * prev[m][0..6] the same seven of the previous time level (device, contiguous [M][7]; NULL reads as zeros) and
+ * tau = params->tau, or tau_pt[m] where tau_pt is not NULL (a DEVICE field [M] in the call's dtype):
+ *     X_b       = tau X_now + (1 - tau) X_prev            for X in u_x, u_y, div, w_x, w_y, lap_w
+ *     out[m][0] = div_b
+ *     out[m][1] = time_term (w_now - w_prev) - dt (nu lap_w_b - (u_x_b w_x_b + u_y_b w_y_b))
+ * -- compute_loss of the reference's model for Problem.NAVIER_STOKES (model_pn.py:794-818, 629-631, 830, 848-849):
+ * tau per point is IntegrationRule.TRAPEZOID, tau = 1 BACKWARD, tau = 0 FORWARD; time_term = 0, dt = -1 and no prev
+ * give column 1 = nu lap_w - u . grad w, the sample_pde of Model.forward (:655-659).  out and gout are [M][2].
+ * aux [M][4] or NULL: the forward also writes (u_x_b, u_y_b, w_x_b, w_y_b) there; the backward reads gout, tau and the
+ * aux of THE SAME forward (not prev) and needs it whenever M > 0; tau_pt must stay unmodified in between.  The backward
+ * overwrites g_means [N][2], g_conics [N][3], g_values [N][2]; there are no gradients wrt prev, tau or the samples.
+ * plan_ws == NULL: dense (f32 / f64); else through a built plan (f32; built with the cut-off wanted for third
+ * derivatives; backward with the plan's wide cut-off; on a PIGS_BUILD_FORWARD_ONLY plan the backward writes NaN
+ * gradients, as pigs_residual_backward does).
+ */
+typedef struct PigsVorticityResidual {
+    double nu, dt, time_term, tau;          /* tau: used where tau_pt is NULL */
+    const void* tau_pt;                     /* device field [M] or NULL */
+} PigsVorticityResidual;
+int pigs_vorticity_residual_forward(int dtype, int64_t N, int64_t M,
+                                    const void* means, const void* conics, const void* values, const void* samples,
+                                    const PigsVorticityResidual* params, const void* prev, void* out, void* aux,
+                                    void* plan_ws, size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes,
+                                    void* stream);
+int pigs_vorticity_residual_backward(int dtype, int64_t N, int64_t M,
+                                     const void* means, const void* conics, const void* values, const void* samples,
+                                     const PigsVorticityResidual* params, const void* gout, const void* aux,
+                                     void* g_means, void* g_conics, void* g_values,
+                                     void* plan_ws, size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes,
+                                     void* stream);
 
 /* Byte offset, inside a samples / plan workspace, of a uint32 DIAGNOSTIC that a build leaves at 0 and
  * sets to non-zero when a workgroup of its in-kernel scan did not receive a predecessor's total within

@@ -3,6 +3,7 @@
 Public surface:
     GaussianSampler         drop-in for ``diff_gaussian_sampling.GaussianSampler``
     VORTICITY_COLUMNS       the column names of ``GaussianSampler.vorticity_terms()``
+    VORTICITY_RESIDUAL_COLUMNS  the column names of ``GaussianSampler.vorticity_residual()``
     covariances             fused ``build_covariances`` / ``build_full_covariances`` (gaussians.py:163-193)
     build()                 compile the HIP library (hipcc, gfx950) and the native host extension in-tree
 """
@@ -17,4 +18,7 @@ def __getattr__(name):
     if name == "VORTICITY_COLUMNS":
         from .sampler import VORTICITY_COLUMNS
         return VORTICITY_COLUMNS
+    if name == "VORTICITY_RESIDUAL_COLUMNS":
+        from .sampler import VORTICITY_RESIDUAL_COLUMNS
+        return VORTICITY_RESIDUAL_COLUMNS
     raise AttributeError(name)

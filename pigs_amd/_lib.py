@@ -42,6 +42,15 @@ class PigsResidualCoupling(ctypes.Structure):
 
 _coupling_p = ctypes.POINTER(PigsResidualCoupling)
 
+
+class PigsVorticityResidual(ctypes.Structure):
+    """struct PigsVorticityResidual of include/pigs_amd.h (the vorticity residual's coefficients and tau field)"""
+    _fields_ = [("nu", ctypes.c_double), ("dt", ctypes.c_double), ("time_term", ctypes.c_double), ("tau", ctypes.c_double),
+                ("tau_pt", _vp)]
+
+
+_vorticity_residual_p = ctypes.POINTER(PigsVorticityResidual)
+
 # name -> (restype, argtypes); must list every symbol include/pigs_amd.h declares
 SIGNATURES = {
     "pigs_abi_version": (_i, []),
@@ -79,6 +88,11 @@ SIGNATURES = {
     "pigs_vorticity_forward": (_i, [_i, _i64, _i64] + [_vp] * 4 + [_vp] + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
     "pigs_vorticity_backward": (_i, [_i, _i64, _i64] + [_vp] * 4 + [_vp] + [_vp] * 3
                                 + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
+    # the vorticity residual (additive to ABI 10): params, prev, out, aux / params, gout, aux, gradients
+    "pigs_vorticity_residual_forward": (_i, [_i, _i64, _i64] + [_vp] * 4 + [_vorticity_residual_p, _vp, _vp, _vp]
+                                        + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
+    "pigs_vorticity_residual_backward": (_i, [_i, _i64, _i64] + [_vp] * 4 + [_vorticity_residual_p, _vp, _vp] + [_vp] * 3
+                                         + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
     # the coupled residual (additive to ABI 10): coupling, target, out / coupling, gout, gradients
     "pigs_residual_coupled_forward": (_i, [_i, _i, _i, _i64, _i64] + [_vp] * 4 + [_coupling_p, _vp, _vp]
                                       + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),

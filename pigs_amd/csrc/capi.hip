@@ -326,6 +326,51 @@ int pigs_vorticity_backward(int dtype, int64_t N, int64_t M, const void* means, 
     return dense_dispatch(true, a, (hipStream_t)stream);
 }
 
+// ---- vorticity residual (pair_math.h ORDN): (div_b, the time-blended vorticity equation's residual), d = 2, c = 2
+int pigs_vorticity_residual_forward(int dtype, int64_t N, int64_t M, const void* means, const void* conics, const void* values,
+                                    const void* samples, const PigsVorticityResidual* params, const void* prev, void* out,
+                                    void* aux, void* plan_ws, size_t plan_ws_bytes, const void* samples_ws,
+                                    size_t samples_ws_bytes, void* stream) {
+    if (!params || (M > 0 && !out)) return PIGS_ERR_INVALID;
+    if (plan_ws) {
+        if (dtype != PIGS_F32) return PIGS_ERR_UNSUPPORTED;
+        void* outs[4] = {out, nullptr, nullptr, nullptr};
+        return plan_forward(plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, N, M, 2, 0.f, 512, outs, (hipStream_t)stream,
+                            nullptr, prev, nullptr, aux, nullptr, params);
+    }
+    int rc = check_common(dtype, 2, 2, 1, N, M, means, conics, values, samples);
+    if (rc != PIGS_OK) return rc;
+    SampleArgs a = vorticity_args(dtype, N, M, means, conics, values, samples);
+    a.orders_mask = 512;
+    a.out[0] = out;
+    a.vort = params;
+    a.target = prev;
+    a.aux = aux;
+    return dense_dispatch(false, a, (hipStream_t)stream);
+}
+
+int pigs_vorticity_residual_backward(int dtype, int64_t N, int64_t M, const void* means, const void* conics, const void* values,
+                                     const void* samples, const PigsVorticityResidual* params, const void* gout, const void* aux,
+                                     void* g_means, void* g_conics, void* g_values, void* plan_ws, size_t plan_ws_bytes,
+                                     const void* samples_ws, size_t samples_ws_bytes, void* stream) {
+    if (!params || (M > 0 && (!gout || !aux)) || (N > 0 && (!g_means || !g_conics || !g_values))) return PIGS_ERR_INVALID;
+    if (plan_ws) {
+        if (dtype != PIGS_F32) return PIGS_ERR_UNSUPPORTED;
+        const void* gs[4] = {gout, nullptr, nullptr, nullptr};
+        return plan_backward(plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, N, M, 2, 0.f, 512, gs, g_means, g_conics,
+                             g_values, (hipStream_t)stream, nullptr, nullptr, aux, nullptr, params);
+    }
+    int rc = check_common(dtype, 2, 2, 1, N, M, means, conics, values, samples);
+    if (rc != PIGS_OK) return rc;
+    SampleArgs a = vorticity_args(dtype, N, M, means, conics, values, samples);
+    a.orders_mask = 512;
+    a.gout[0] = gout;
+    a.g_means = g_means; a.g_conics = g_conics; a.g_values = g_values;
+    a.vort = params;
+    a.aux = const_cast<void*>(aux);
+    return dense_dispatch(true, a, (hipStream_t)stream);
+}
+
 // ---- periodic domain (ABI 10): the 3 x 3 images of every Gaussian and the fold of their gradients (periodic.hip)
 int pigs_periodic_images(int dtype, int c, int64_t N, double lo, double period, double q_cut, const void* means,
                          const void* conics, const void* values, void* img_means, void* img_conics, void* img_values,

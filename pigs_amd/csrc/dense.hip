@@ -98,6 +98,7 @@ __global__ __launch_bounds__(NW * 64) void dense_backward_kernel(
         else if constexpr (MASK == ORDG) G.load_terms(m, G0, rz);
         else if constexpr (MASK == ORDV) G.load_vorticity(m, G0);
         else if constexpr (MASK == ORDC) G.load_coupled(m, G0, rz);
+        else if constexpr (MASK == ORDN) G.load_vorticity_residual(m, G0, rz);
         else G.load(m, G0, G1, G2, G3);
     };
     // the general residual: the two points' wave-uniform values (coefficients, gr, aux) are fetched field by field,
@@ -334,6 +335,7 @@ __global__ __launch_bounds__(256) void dense_backward_staged_kernel(
         else if constexpr (MASK == ORDG) p.G.load_terms(m, G0, rz);
         else if constexpr (MASK == ORDV) p.G.load_vorticity(m, G0);
         else if constexpr (MASK == ORDC) p.G.load_coupled(m, G0, rz);
+        else if constexpr (MASK == ORDN) p.G.load_vorticity_residual(m, G0, rz);
         else p.G.load(m, G0, G1, G2, G3);
         pts[threadIdx.x] = p;
     }
@@ -374,6 +376,8 @@ static RzOf<T, MASK> rz_of(const SampleArgs& a, bool backward) {
         return make_terms<T>(*a.terms, backward ? nullptr : a.target, a.aux);
     } else if constexpr (MASK == ORDC) {
         return make_coupled<T>(*a.coupling, backward ? nullptr : a.target);
+    } else if constexpr (MASK == ORDN) {
+        return make_vort_resid<T>(*a.vort, backward ? nullptr : a.target, a.aux);
     } else {
         return Resid<T>{(T)a.resid[0], {(T)a.resid[1], (T)a.resid[2]}, (T)a.resid[3], backward ? nullptr : (const T*)a.target};
     }
@@ -480,10 +484,10 @@ static int dispatch_mask(bool backward, const SampleArgs& a, hipStream_t stream)
         PIGS_CASE(32) PIGS_CASE(64)
         default: break;
     }
-    // the vorticity terms (ORDV): a two-channel field in two dimensions, the only instantiations compiled
+    // the vorticity terms (ORDV) and residual (ORDN): a two-channel field in two dimensions, the only instantiations compiled
     if constexpr (D == 2 && C == 2) {
         switch (mask) {
-            PIGS_CASE(128)
+            PIGS_CASE(128) PIGS_CASE(512)
             default: break;
         }
     }

@@ -19,6 +19,8 @@ struct SampleArgs {
     const PigsResidualTerms* terms;      // orders_mask == 64 (general residual): coefficients, fields, advect_by
     void* aux;                           //   and aux [M][1+d][c] (the forward writes it, the backward reads it; or null)
     const PigsResidualCoupling* coupling;      // orders_mask == 256 (coupled residual): coefficients, fields, the two matrices
+    const PigsVorticityResidual* vort;         // orders_mask == 512 (vorticity residual): coefficients, tau field; `target` = prev
+                                               //   [M][7] or null, `aux` = [M][4] (the forward writes it, the backward reads it)
 };
 
 int dense_dispatch(bool backward, const SampleArgs& a, hipStream_t stream);
@@ -67,11 +69,12 @@ int plan_build(void* ws, size_t ws_bytes, void* sws, size_t sws_bytes, int flags
 int plan_forward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, int64_t N, int64_t M, int c,
                  float q_max, int mask, void* const* out, hipStream_t stream, const double* resid = nullptr,
                  const void* target = nullptr, const PigsResidualTerms* terms = nullptr, void* aux = nullptr,
-                 const PigsResidualCoupling* coupling = nullptr);
+                 const PigsResidualCoupling* coupling = nullptr, const PigsVorticityResidual* vort = nullptr);
 int plan_backward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, int64_t N, int64_t M, int c,
                   float q_max, int mask, const void* const* gout, void* g_means, void* g_conics, void* g_values,
                   hipStream_t stream, const double* resid = nullptr, const PigsResidualTerms* terms = nullptr,
-                  const void* aux = nullptr, const PigsResidualCoupling* coupling = nullptr);
+                  const void* aux = nullptr, const PigsResidualCoupling* coupling = nullptr,
+                  const PigsVorticityResidual* vort = nullptr);
 int plan_layout_info(int64_t N, int64_t M, int c, int64_t* info);
 // the Gaussian grid alone (aggregate.hip): plan.hip
 size_t aggregate_grid_bytes(int64_t N);
@@ -89,13 +92,14 @@ size_t plan_error_offset();
 // 32 = the linear residual (pair_math.h ORDR), alone, in slot 0 -- reachable through pigs_residual_* only;
 // 64 = the general residual (ORDG), likewise -- through pigs_residual_terms_* only;
 // 128 = the vorticity terms (ORDV; d = 2, c = 2), one packed row [M][7] in slot 0 -- through pigs_vorticity_* only;
-// 256 = the coupled residual (ORDC; c >= 2), [M][c] in slot 0 -- through pigs_residual_coupled_* only.
+// 256 = the coupled residual (ORDC; c >= 2), [M][c] in slot 0 -- through pigs_residual_coupled_* only;
+// 512 = the vorticity residual (ORDN; d = 2, c = 2), [M][2] in slot 0 -- through pigs_vorticity_residual_* only.
 inline bool mask_valid(int m) { return m > 0 && m < 32 && !((m & 4) && (m & 16)); }
-inline bool mask_uses_slot(int m, int k) { return (m == 32 || m == 64 || m == 128 || m == 256) ? k == 0 : (m >> k & 1) || (k == 2 && (m & 16)); }
+inline bool mask_uses_slot(int m, int k) { return (m == 32 || m == 64 || m == 128 || m == 256 || m == 512) ? k == 0 : (m >> k & 1) || (k == 2 && (m & 16)); }
 // Smallest compiled mask covering the request (compiled: single orders, 0..2, 0..3, the trace alone
 // and orders 0, 1 + trace); 0 = no compiled kernel (trace together with order 3).
 inline int covering_mask_of(int mask) {
-    if (mask == 32 || mask == 64 || mask == 128 || mask == 256) return mask;
+    if (mask == 32 || mask == 64 || mask == 128 || mask == 256 || mask == 512) return mask;
     if (mask & 16) return mask == 16 ? 16 : (mask & ~19) == 0 ? 19 : 0;
     if (mask == 1 || mask == 2 || mask == 4 || mask == 8) return mask;
     if ((mask & ~7) == 0) return 7;

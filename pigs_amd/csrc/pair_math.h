@@ -66,8 +66,20 @@ constexpr int NVORT = 7;
 // (Gsym::load_coupled): linear in the field, so no record of the forward is needed.
 constexpr int ORDC = 256;
 constexpr int ORDC_AS = ORD0 | ORD2T;
+// THE VORTICITY RESIDUAL (mask == ORDN, alone; D == 2, C == 2): the Navier-Stokes residual in the vorticity formulation,
+// composed from the seven sums of ORDV, a per-point time weight tau and the previous time level's seven prev[m][0..6]
+// (null: zeros), with X_b = tau X + (1 - tau) X_prev for X in u_x, u_y, div, w_x, w_y, lap w:
+//   out[m][0] = div_b
+//   out[m][1] = time_term (w - w_prev) - dt (nu lap w_b - (u_x_b w_x_b + u_y_b w_y_b))
+// -- compute_loss of the reference's model for Problem.NAVIER_STOKES under its three integration rules
+// (model_pn.py:794-818, 629-631, 830, 848-849: tau per point = TRAPEZOID, 1 = BACKWARD, 0 = FORWARD).  The advection
+// u . grad w is a product of two sums, so the accumulators are those of ORDV and the two numbers are composed once per
+// point in fwd_store, which also leaves aux[m][0..3] = (u_x_b, u_y_b, w_x_b, w_y_b).  Its backward is the ORDV_AS
+// backward with the seven incoming gradients formed from gout[m][0..1], the coefficients and that record
+// (Gsym::load_vorticity_residual); prev is not read there.
+constexpr int ORDN = 512;
 constexpr int bwd_mask_of(int MASK) {
-    return (MASK == ORDR || MASK == ORDG) ? ORDR_AS : MASK == ORDV ? ORDV_AS : MASK == ORDC ? ORDC_AS : MASK;
+    return (MASK == ORDR || MASK == ORDG) ? ORDR_AS : (MASK == ORDV || MASK == ORDN) ? ORDV_AS : MASK == ORDC ? ORDC_AS : MASK;
 }
 
 template <typename T> struct Terms {
@@ -106,9 +118,26 @@ inline Coupled<T> make_coupled(const ABI& t, const void* target) {
     z.target = (const T*)target;
     return z;
 }
+template <typename T> struct VortResid {
+    T nu, dt, time_term, tau;                       // tau: used where tau_pt is null
+    const T* tau_pt;                                // [M] or null
+    const T* prev;                                  // [M][7], the previous time level's vorticity terms; or null (zeros)
+    T* aux;                                         // [M][4]: written by the forward, read by the backward; or null
+};
+// host side: the block from the C ABI's PigsVorticityResidual (include/pigs_amd.h) in the launch's type
+template <typename T, typename ABI>
+inline VortResid<T> make_vort_resid(const ABI& t, const void* prev, const void* aux) {
+    VortResid<T> z{};
+    z.nu = (T)t.nu; z.dt = (T)t.dt; z.time_term = (T)t.time_term; z.tau = (T)t.tau;
+    z.tau_pt = (const T*)t.tau_pt;
+    z.prev = (const T*)prev;
+    z.aux = (T*)const_cast<void*>(aux);
+    return z;
+}
 // the coefficient block a kernel compiled for MASK receives
 template <typename T, int MASK>
-using RzOf = std::conditional_t<MASK == ORDG, Terms<T>, std::conditional_t<MASK == ORDC, Coupled<T>, Resid<T>>>;
+using RzOf = std::conditional_t<MASK == ORDG, Terms<T>, std::conditional_t<MASK == ORDC, Coupled<T>,
+             std::conditional_t<MASK == ORDN, VortResid<T>, Resid<T>>>>;
 
 // the coefficients of the general residual at one point
 template <typename T, int D> struct TermsAt {
@@ -151,7 +180,7 @@ template <int D, int C, int MASK_> struct FwdLayout {
     static constexpr int O1 = O0 + ((MASK & ORD0) ? C : 0);
     static constexpr int O2 = O1 + ((MASK & ORD1) ? D * C : 0);
     static constexpr int O3 = O2 + ((MASK & ORD2) ? Sym<D>::NF * C : (MASK & ORD2T) ? C : 0);
-    static constexpr int N = O3 + ((MASK & ORD3) ? Sym<D>::N3 * C : 0) + ((MASK & ORDR) ? C : 0) + (MASK == ORDV ? NVORT : 0);
+    static constexpr int N = O3 + ((MASK & ORD3) ? Sym<D>::N3 * C : 0) + ((MASK & ORDR) ? C : 0) + ((MASK == ORDV || MASK == ORDN) ? NVORT : 0);
 };
 
 // Pair geometry: x, p, g (and nothing else) for one (point, Gaussian).
@@ -183,6 +212,10 @@ __device__ __forceinline__ void fwd_accumulate(T* acc, const T* s, const T* mu, 
     }
     if constexpr (MASK == ORDC) {
         fwd_accumulate<T, D, C, ORDC_AS>(acc, s, mu, con, v);
+        return;
+    }
+    if constexpr (MASK == ORDN) {      // the seven sums of the vorticity terms, their `live` guard included
+        fwd_accumulate<T, D, C, ORDV>(acc, s, mu, con, v);
         return;
     }
     using L = FwdLayout<D, C, MASK>;
@@ -342,6 +375,31 @@ __device__ __forceinline__ void fwd_store(const T* acc, int64_t m, T* __restrict
                 mix = fma_<T>(rz->Q0[ch][cc], acc[L::O0 + cc], fma_<T>(rz->QL[ch][cc], acc[L::O2 + cc], mix));
             const T r = fma_<T>(cw, mix, fma_<T>(aL, acc[L::O2 + ch], a0 * acc[L::O0 + ch]));
             store_out<STREAM>(&o0[m * C + ch], rz->target ? r - rz->target[m * C + ch] : r);
+        }
+        return;
+    }
+    if constexpr (MASK == ORDN) {
+        // the composing store: the point's tau and its row of the previous level meet the seven finished sums
+        static_assert(D == 2 && C == 2, "the vorticity residual is that of a two-channel field in two dimensions");
+        const T tau = rz->tau_pt ? rz->tau_pt[m] : rz->tau;
+        T pv[NVORT];
+#pragma unroll
+        for (int k = 0; k < NVORT; ++k) pv[k] = rz->prev ? rz->prev[m * NVORT + k] : T(0);
+        const T om = T(1) - tau;
+        T b[NVORT];      // the blend; b[3] (w) is not one: the time term takes the difference of the levels
+#pragma unroll
+        for (int k = 0; k < NVORT; ++k) b[k] = fma_<T>(tau, acc[k], om * pv[k]);
+        const T adv = fma_<T>(b[0], b[4], b[1] * b[5]);      // u_b . grad w_b
+        const T r = fma_<T>(rz->time_term, acc[3] - pv[3], -rz->dt * fma_<T>(rz->nu, b[6], -adv));
+        if constexpr (STREAM) asm volatile("" ::: "memory");      // as for ORDV below: keeps the hint
+        store_out<STREAM>(&o0[m * 2], b[2]);
+        store_out<STREAM>(&o0[m * 2 + 1], r);
+        if (rz->aux) {
+            T* ax = rz->aux + m * 4;
+            store_out<STREAM>(&ax[0], b[0]);
+            store_out<STREAM>(&ax[1], b[1]);
+            store_out<STREAM>(&ax[2], b[4]);
+            store_out<STREAM>(&ax[3], b[5]);
         }
         return;
     }
@@ -568,6 +626,11 @@ template <typename T, int D, int C, int MASK> struct Gsym {
         T gv[NVORT];
 #pragma unroll
         for (int k = 0; k < NVORT; ++k) gv[k] = GV[m * NVORT + k];
+        form_vorticity(gv);
+    }
+    // the same from the seven numbers in registers
+    __device__ __forceinline__ void form_vorticity(const T* gv) {
+        static_assert(MASK == ORDV_AS && D == 2 && C == 2, "the vorticity terms' backward runs on orders 0..3 of d = 2, c = 2");
         g0[0] = gv[0];          g0[1] = gv[1];
         g1[0][0] = gv[2];       g1[0][1] = gv[3];
         g1[1][0] = -gv[3];      g1[1][1] = gv[2];
@@ -578,6 +641,24 @@ template <typename T, int D, int C, int MASK> struct Gsym {
         g3[1][0] = -gv[6];      g3[1][1] = T(0);       // xxy: (0,0,1) of channel x
         g3[2][0] = T(0);        g3[2][1] = gv[6];      // xyy: (1,1,0) of channel y
         g3[3][0] = -gv[6];      g3[3][1] = T(0);       // yyy
+    }
+    // the incoming gradient gout [M][2] = (g_d, g_r) of a vorticity residual (MASK = ORDV_AS), its coefficients and the
+    // forward's aux[m][0..3] = (u_x_b, u_y_b, w_x_b, w_y_b), as the gradient that arrives at the seven vorticity terms:
+    //   d r / d (u_x, u_y) = dt tau (w_x_b, w_y_b),  d div_b / d div = tau,  d r / d w = time_term,
+    //   d r / d (w_x, w_y) = dt tau (u_x_b, u_y_b),  d r / d lap w = -dt nu tau
+    __device__ __forceinline__ void load_vorticity_residual(int64_t m, const T* __restrict__ GR, const VortResid<T>& vz) {
+        const T gd = GR[m * 2], gr = GR[m * 2 + 1];
+        const T tau = vz.tau_pt ? vz.tau_pt[m] : vz.tau;
+        T ax[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) ax[q] = vz.aux ? vz.aux[m * 4 + q] : T(0);
+        const T k = gr * vz.dt * tau;
+        T gv[NVORT];
+        gv[0] = k * ax[2];      gv[1] = k * ax[3];
+        gv[2] = gd * tau;       gv[3] = gr * vz.time_term;
+        gv[4] = k * ax[0];      gv[5] = k * ax[1];
+        gv[6] = -k * vz.nu;
+        form_vorticity(gv);
     }
     // the incoming gradient gr [M][c] of a general residual (MASK = ORDR_AS), its coefficients k at the point and the
     // forward's aux (u, d_i u; read when `advects`)

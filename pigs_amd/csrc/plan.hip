@@ -2476,6 +2476,7 @@ __device__ __forceinline__ void load_tile_point(const SamplesView& sv, uint32_t 
     else if constexpr (MASK == ORDG) G.load_terms((int64_t)sp.m, G0p, rz);
     else if constexpr (MASK == ORDV) G.load_vorticity((int64_t)sp.m, G0p);
     else if constexpr (MASK == ORDC) G.load_coupled((int64_t)sp.m, G0p, rz);
+    else if constexpr (MASK == ORDN) G.load_vorticity_residual((int64_t)sp.m, G0p, rz);
     else G.load((int64_t)sp.m, G0p, G1p, G2p, G3p);
     if (!valid) {
 #pragma unroll
@@ -2629,6 +2630,7 @@ __device__ __forceinline__ void backward_points_helper(const PlanView& pv, const
         else if constexpr (MASK == ORDG) G.load_terms((int64_t)sp.m, G0p, rz);
         else if constexpr (MASK == ORDV) G.load_vorticity((int64_t)sp.m, G0p);
         else if constexpr (MASK == ORDC) G.load_coupled((int64_t)sp.m, G0p, rz);
+        else if constexpr (MASK == ORDN) G.load_vorticity_residual((int64_t)sp.m, G0p, rz);
         else G.load((int64_t)sp.m, G0p, G1p, G2p, G3p);
         // The walk in step over the whole wave (round 4): every lane meets its own (point, Gaussian) pair, and a pair's
         // NV sums leave as ONE atomic request -- lane = (pair, value), eight pairs per instruction, each a pair's 32-byte
@@ -3485,7 +3487,7 @@ template <int C> static bool fused_first_compiled(int mask) { return C == 1 ? (m
 template <int C>
 static int plan_forward_c(const PlanView& pv_in, const SamplesView& sv, int mask, float* const* out, hipStream_t stream,
                           const Resid<float>& rz, const ListArgs* first = nullptr, const Terms<float>* tz = nullptr,
-                          const Coupled<float>* cz = nullptr) {
+                          const Coupled<float>* cz = nullptr, const VortResid<float>* vz = nullptr) {
     // + the helper workgroups of the TILE_MODE_POINTS tiles (they leave at once when the plan queued none)
     const dim3 grid((sv.ntiles + PIGS_FWD_WG_WAVES - 1) / PIGS_FWD_WG_WAVES + POINT_HELPER_BLOCKS * 4 / PIGS_FWD_WG_WAVES),
         block(64 * PIGS_FWD_WG_WAVES);
@@ -3538,6 +3540,13 @@ static int plan_forward_c(const PlanView& pv_in, const SamplesView& sv, int mask
         } else {
             return PIGS_ERR_UNSUPPORTED;
         }
+    } else if (mask == ORDN) {      // the vorticity residual: two channels only, its own coefficient block (never fused either)
+        if (!vz) return PIGS_ERR_INVALID;
+        if constexpr (C == 2) {
+            hipLaunchKernelGGL((tile_forward_kernel<C, ORDN>), grid, block, 0, stream, pv, sv, out[0], out[1], out[2], out[3], *vz);
+        } else {
+            return PIGS_ERR_UNSUPPORTED;
+        }
     } else if (!done) switch (mask) {
         PIGS_CASE(1) PIGS_CASE(2) PIGS_CASE(4) PIGS_CASE(8) PIGS_CASE(7) PIGS_CASE(15) PIGS_CASE(16) PIGS_CASE(19) PIGS_CASE(32)
         default: return PIGS_ERR_UNSUPPORTED;
@@ -3554,7 +3563,7 @@ static int plan_forward_c(const PlanView& pv_in, const SamplesView& sv, int mask
 template <int C>
 static int plan_backward_c(const PlanView& pv_in, const SamplesView& sv, int mask, const float* const* g, float* gm,
                            float* gc, float* gv, hipStream_t stream, const Resid<float>& rz, const Terms<float>* tz = nullptr,
-                           const Coupled<float>* cz = nullptr) {
+                           const Coupled<float>* cz = nullptr, const VortResid<float>* vz = nullptr) {
     const dim3 grid((sv.ntiles + 3) / 4 + POINT_HELPER_BLOCKS), block(256);
     // points that arrive in no order fetch their incoming gradients from the staging records (PlanView::stage)
     PlanView pv = pv_in;
@@ -3606,6 +3615,17 @@ static int plan_backward_c(const PlanView& pv_in, const SamplesView& sv, int mas
         } else {
             return PIGS_ERR_UNSUPPORTED;
         }
+    } else if (mask == ORDN) {
+        if (!vz) return PIGS_ERR_INVALID;
+        if constexpr (C == 2) {
+#if PIGS_BWD_BLOCK
+            hipLaunchKernelGGL((block_backward_kernel<C, ORDN>), bgrid, block, 0, stream, pv, sv, g[0], g[1], g[2], g[3], *vz);
+#else
+            hipLaunchKernelGGL((tile_backward_kernel<C, ORDN>), grid, block, 0, stream, pv, sv, g[0], g[1], g[2], g[3], *vz);
+#endif
+        } else {
+            return PIGS_ERR_UNSUPPORTED;
+        }
     } else switch (mask) {
         PIGS_CASE(1) PIGS_CASE(2) PIGS_CASE(4) PIGS_CASE(8) PIGS_CASE(7) PIGS_CASE(15) PIGS_CASE(16) PIGS_CASE(19) PIGS_CASE(32)
         default: return PIGS_ERR_UNSUPPORTED;
@@ -3628,7 +3648,8 @@ static Resid<float> resid_of(const double* r, const void* target) {
 
 int plan_forward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, int64_t N, int64_t M, int c,
                  float q_max, int mask, void* const* out, hipStream_t stream, const double* resid, const void* target,
-                 const PigsResidualTerms* terms, void* aux, const PigsResidualCoupling* coupling) {
+                 const PigsResidualTerms* terms, void* aux, const PigsResidualCoupling* coupling,
+                 const PigsVorticityResidual* vort) {
     if (!plan_supported(N, M, c)) return PIGS_ERR_UNSUPPORTED;
     const PlanLayout p = make_plan_layout(N, M, c);
     const SamplesLayout s = make_samples_layout(M);
@@ -3647,8 +3668,11 @@ int plan_forward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, i
     const Terms<float>* tp = terms ? &tz : nullptr;
     const Coupled<float> cz = coupling ? make_coupled<float>(*coupling, target) : Coupled<float>{};
     const Coupled<float>* cp = coupling ? &cz : nullptr;
-    const int rc = c == 1 ? plan_forward_c<1>(pv, sv, cm, o, stream, resid_of(resid, target), first ? &la : nullptr, tp, cp)
-                          : plan_forward_c<2>(pv, sv, cm, o, stream, resid_of(resid, target), first ? &la : nullptr, tp, cp);
+    // the vorticity residual: `target` is the previous level's rows [M][7]
+    const VortResid<float> vz = vort ? make_vort_resid<float>(*vort, target, aux) : VortResid<float>{};
+    const VortResid<float>* vp = vort ? &vz : nullptr;
+    const int rc = c == 1 ? plan_forward_c<1>(pv, sv, cm, o, stream, resid_of(resid, target), first ? &la : nullptr, tp, cp, vp)
+                          : plan_forward_c<2>(pv, sv, cm, o, stream, resid_of(resid, target), first ? &la : nullptr, tp, cp, vp);
     if (first && rc == PIGS_OK) plan_note_points(p, ws, stream);
     return rc;
 }
@@ -3656,7 +3680,7 @@ int plan_forward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, i
 int plan_backward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, int64_t N, int64_t M, int c,
                   float q_max, int mask, const void* const* gout, void* g_means, void* g_conics, void* g_values,
                   hipStream_t stream, const double* resid, const PigsResidualTerms* terms, const void* aux,
-                  const PigsResidualCoupling* coupling) {
+                  const PigsResidualCoupling* coupling, const PigsVorticityResidual* vort) {
     if (!plan_supported(N, M, c)) return PIGS_ERR_UNSUPPORTED;
     const PlanLayout p = make_plan_layout(N, M, c);
     const SamplesLayout s = make_samples_layout(M);
@@ -3680,9 +3704,11 @@ int plan_backward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, 
     const Terms<float>* tp = terms ? &tz : nullptr;
     const Coupled<float> cz = coupling ? make_coupled<float>(*coupling, nullptr) : Coupled<float>{};
     const Coupled<float>* cp = coupling ? &cz : nullptr;
+    const VortResid<float> vz = vort ? make_vort_resid<float>(*vort, nullptr, aux) : VortResid<float>{};
+    const VortResid<float>* vp = vort ? &vz : nullptr;
     switch (c) {
-        case 1: return plan_backward_c<1>(pv, sv, cm, g, (float*)g_means, (float*)g_conics, (float*)g_values, stream, resid_of(resid, nullptr), tp, cp);
-        case 2: return plan_backward_c<2>(pv, sv, cm, g, (float*)g_means, (float*)g_conics, (float*)g_values, stream, resid_of(resid, nullptr), tp, cp);
+        case 1: return plan_backward_c<1>(pv, sv, cm, g, (float*)g_means, (float*)g_conics, (float*)g_values, stream, resid_of(resid, nullptr), tp, cp, vp);
+        case 2: return plan_backward_c<2>(pv, sv, cm, g, (float*)g_means, (float*)g_conics, (float*)g_values, stream, resid_of(resid, nullptr), tp, cp, vp);
     }
     return PIGS_ERR_UNSUPPORTED;
 }

@@ -796,6 +796,100 @@ at::Tensor vorticity_apply(const at::Tensor& means, const at::Tensor& values, co
 }
 
 // ---------------------------------------------------------------------------------------------
+// vorticity_residual(): (div_b, r) of the Navier-Stokes residual as [M, 2] in one launch (pigs_vorticity_residual_*); the
+// node owns inputs, plan, tau, prev and aux (the blended u and grad w of the forward: what the backward reads).
+// ---------------------------------------------------------------------------------------------
+struct VorticityResidualHost {
+    double nu = 0, dt = 0, time_term = 1, tau = 1;      // tau where the field is undefined
+    at::Tensor tau_field;                               // [M, 1]: detached, contiguous, or undefined
+    PigsVorticityResidual abi() const {
+        PigsVorticityResidual t{};
+        t.nu = nu; t.dt = dt; t.time_term = time_term; t.tau = tau;
+        t.tau_pt = ptr(tau_field);
+        return t;
+    }
+};
+
+struct VorticityResidualBackward : public torch::autograd::Node {
+    at::Tensor means, values, conics, samples, prev, aux;
+    uint32_t versions[4] = {0, 0, 0, 0};
+    VorticityResidualHost params;
+    bool debug = false;
+    std::shared_ptr<Plan> plan;
+
+    std::string name() const override { return "PigsVorticityResidualBackward"; }
+    void release_variables() override {}
+
+    torch::autograd::variable_list apply(torch::autograd::variable_list&& grads) override {
+        if (means._version() != versions[0] || values._version() != versions[1] || conics._version() != versions[2] ||
+            samples._version() != versions[3])
+            throw std::runtime_error(
+                "one of the tensors handed to GaussianSampler.preprocess() has been modified in place before the "
+                "backward of a vorticity_residual() output that was computed from it");
+        torch::autograd::variable_list res(3);
+        if (grads.empty() || !grads[0].defined()) return res;
+        at::AutoGradMode no_grad(false);
+        if (grads[0].requires_grad()) throw std::runtime_error("GaussianSampler.vorticity_residual() is differentiable once");
+        if (debug && plan && plan->forward_only) throw std::logic_error("a vorticity_residual() node holds a forward-only plan");
+        const at::Tensor gout = grads[0].contiguous();
+        const int64_t N = means.size(0), M = samples.size(0);
+        if (!aux.defined() && M > 0)
+            throw std::runtime_error("this vorticity_residual() output was computed without the record its backward needs "
+                                     "(no input required grad when it ran)");
+        auto gv3 = gradient_views(means, values, conics);
+        at::Tensor g_means = gv3[0], g_values = gv3[1], g_conics = gv3[2];
+        if (N > 0 && M > 0) {
+            c10::DeviceGuard guard(means.device());
+            const hipStream_t stream = current_stream(means);
+            const PlanPtrs pp = plan_ptrs(plan.get(), stream);
+            const PigsVorticityResidual t = params.abi();
+            check(pigs_vorticity_residual_backward(dtype_code(means), N, M, ptr(means), ptr(conics), ptr(values), ptr(samples), &t,
+                                                   ptr(gout), ptr(aux), ptr(g_means), ptr(g_conics), ptr(g_values), pp.pw, pp.pb,
+                                                   pp.sw, pp.sb, stream),
+                  "pigs_vorticity_residual_backward");
+        } else {
+            g_means.zero_(); g_values.zero_(); g_conics.zero_();
+        }
+        if (debug) device_sync(means);
+        res[0] = g_means; res[1] = g_values; res[2] = g_conics;
+        return res;
+    }
+};
+
+at::Tensor vorticity_residual_apply(const at::Tensor& means, const at::Tensor& values, const at::Tensor& conics,
+                                    const at::Tensor& samples, const VorticityResidualHost& params, const at::Tensor& prev,
+                                    bool debug, const std::shared_ptr<Plan>& plan) {
+    const int64_t N = means.size(0), M = samples.size(0);
+    const bool differentiable =
+        at::GradMode::is_enabled() && (means.requires_grad() || values.requires_grad() || conics.requires_grad());
+    at::Tensor out = at::empty({M, 2}, means.options());
+    at::Tensor aux;      // only when a backward can follow
+    if (differentiable && M > 0) aux = at::empty({M, 4}, means.options());
+    if (M > 0) {
+        c10::DeviceGuard guard(means.device());
+        const hipStream_t stream = current_stream(means);
+        const PlanPtrs pp = plan_ptrs(plan.get(), stream);
+        const PigsVorticityResidual t = params.abi();
+        check(pigs_vorticity_residual_forward(dtype_code(means), N, M, ptr(means), ptr(conics), ptr(values), ptr(samples), &t,
+                                              ptr(prev), ptr(out), ptr(aux), pp.pw, pp.pb, pp.sw, pp.sb, stream),
+              "pigs_vorticity_residual_forward");
+    }
+    if (debug) device_sync(means);
+    if (differentiable) {
+        std::shared_ptr<VorticityResidualBackward> node(new VorticityResidualBackward(), torch::autograd::deleteNode);
+        node->set_next_edges(torch::autograd::collect_next_edges(means, values, conics));
+        node->means = means; node->values = values; node->conics = conics; node->samples = samples;
+        node->prev = prev; node->aux = aux;
+        node->versions[0] = means._version(); node->versions[1] = values._version();
+        node->versions[2] = conics._version(); node->versions[3] = samples._version();
+        node->params = params;
+        node->debug = debug; node->plan = plan;
+        torch::autograd::create_gradient_edge(out, node);
+    }
+    return out;
+}
+
+// ---------------------------------------------------------------------------------------------
 // preprocess_aggregate / aggregate_neighbors (model_pn.py:257-264; parity unpinned: this repository's own
 // definition, pigs_amd/csrc/aggregate.hip).  Same structure as pigs_amd/aggregate.py.
 // ---------------------------------------------------------------------------------------------
@@ -1268,6 +1362,18 @@ struct Core {
         return vorticity;
     }
 
+    // tau_field, prev: validated, detached, contiguous tensors in the means' dtype (or None; the Python wrapper does it);
+    // never cached: the arguments vary from call to call
+    at::Tensor vorticity_residual(double nu, double dt, double time_term, double tau, const c10::optional<at::Tensor>& tau_field,
+                                  const c10::optional<at::Tensor>& prev) {
+        require_inputs();
+        VorticityResidualHost t;
+        t.nu = nu; t.dt = dt; t.time_term = time_term; t.tau = tau;
+        if (tau_field.has_value()) t.tau_field = *tau_field;
+        return vorticity_residual_apply(means, values, conics, samples, t, prev.has_value() ? *prev : at::Tensor(), debug,
+                                        plan_for(8));
+    }
+
     void preprocess_aggregate(int64_t cap) {
         require_inputs();
         if (means.size(1) != 2) raise_py(PyExc_NotImplementedError, "aggregate_neighbors is implemented for d = 2");
@@ -1396,6 +1502,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("residual_coupled", &Core::residual_coupled, py::arg("fields"), py::arg("consts"), py::arg("couple0"),
              py::arg("couple_lap"), py::arg("target") = c10::optional<at::Tensor>())
         .def("vorticity_terms", &Core::vorticity_terms)
+        .def("vorticity_residual", &Core::vorticity_residual, py::arg("nu"), py::arg("dt"), py::arg("time_term"), py::arg("tau"),
+             py::arg("tau_field") = c10::optional<at::Tensor>(), py::arg("prev") = c10::optional<at::Tensor>())
         .def("preprocess_aggregate", &Core::preprocess_aggregate, py::arg("cap") = -1)
         .def("aggregate_neighbors", &Core::aggregate_neighbors)
         .def_readonly("neighbors", &Core::neighbors)

@@ -37,6 +37,8 @@ TRACE = 4       # order index of the Hessian's trace (mask bit 16); it travels i
 # the columns of GaussianSampler.vorticity_terms(): the field, its divergence, the vorticity w = d_x u_y - d_y u_x,
 # its gradient and its Laplacian
 VORTICITY_COLUMNS = ("u_x", "u_y", "div", "w", "w_x", "w_y", "lap_w")
+# the columns of GaussianSampler.vorticity_residual(): the blended divergence and the vorticity equation's residual
+VORTICITY_RESIDUAL_COLUMNS = ("div", "r")
 
 
 def _out_shape(order, M, d, c):
@@ -711,6 +713,94 @@ class _VorticityFunction(torch.autograd.Function):
         if ctx.debug:
             torch.cuda.synchronize(means.device)
         return g_means, g_values, g_conics, None, None, None
+
+
+class VorticityResidual:
+    """The coefficients of a vorticity_residual() call: three floats and ``tau``, a float or a detached device field
+    [M, 1]."""
+
+    def __init__(self, nu, dt, time_term, tau):
+        self.nu, self.dt, self.time_term, self.tau = nu, dt, time_term, tau
+
+    def struct(self):
+        t = _lib.PigsVorticityResidual()
+        t.nu, t.dt, t.time_term = self.nu, self.dt, self.time_term
+        if isinstance(self.tau, torch.Tensor):
+            t.tau_pt = self.tau.data_ptr()
+        else:
+            t.tau = self.tau
+        return t
+
+
+def _vorticity_residual_call(backward, means, values, conics, samples, params, plan, prev=None, gout=None, aux=None):
+    """pigs_vorticity_residual_forward / _backward on contiguous device tensors (through the plan when given)."""
+    lib = _lib.load()
+    N, M = means.shape[0], samples.shape[0]
+    vz = params.struct()
+    if backward and plan is not None and M > 0 and getattr(plan, "forward_only", False):
+        plan = plan.full_for_backward(means, values, conics, samples)
+    pw = (_ptr(plan.workspace), plan.workspace.numel(), _ptr(plan.samples.workspace), plan.samples.workspace.numel()) \
+        if plan is not None else (ctypes.c_void_p(0), 0, ctypes.c_void_p(0), 0)
+    with _on_device(means.device):
+        stream = _stream(means.device)
+        if plan is not None and hasattr(plan, "note_stream"):
+            plan.note_stream(stream.value)
+        if not backward:
+            out = torch.empty((M, len(VORTICITY_RESIDUAL_COLUMNS)), dtype=means.dtype, device=means.device)
+            if M > 0:
+                rc = lib.pigs_vorticity_residual_forward(_DTYPES[means.dtype], N, M, _ptr(means), _ptr(conics), _ptr(values),
+                                                         _ptr(samples), ctypes.byref(vz), _ptr(prev), _ptr(out), _ptr(aux),
+                                                         *pw, stream)
+                _lib.check(rc, "pigs_vorticity_residual_forward")
+            return out
+        g_means, g_values, g_conics = _gradient_views(means, values, conics)
+        if N > 0:
+            if M > 0:
+                rc = lib.pigs_vorticity_residual_backward(_DTYPES[means.dtype], N, M, _ptr(means), _ptr(conics), _ptr(values),
+                                                          _ptr(samples), ctypes.byref(vz), _ptr(gout), _ptr(aux),
+                                                          _ptr(g_means), _ptr(g_conics), _ptr(g_values), *pw, stream)
+                _lib.check(rc, "pigs_vorticity_residual_backward")
+            else:
+                for g in (g_means, g_values, g_conics):
+                    g.zero_()
+        return g_means, g_values, g_conics
+
+
+class _VorticityResidualFunction(torch.autograd.Function):
+    """(div_b, r) of the Navier-Stokes residual as [M, 2] in one launch; its backward is one launch too.  The node owns
+    its inputs, plan, ``tau``, ``prev`` and ``aux`` (the blended u and grad w of the forward, which the backward of the
+    advection term reads) like :class:`_ResidualTermsFunction`."""
+
+    @staticmethod
+    def forward(ctx, means, values, conics, samples, params, prev, debug, plan, want_aux):
+        M = samples.shape[0]
+        aux = torch.empty((M, 4), dtype=means.dtype, device=means.device) if want_aux and M > 0 else None
+        out = _vorticity_residual_call(False, means, values, conics, samples, params, plan, prev=prev, aux=aux)
+        if debug:
+            torch.cuda.synchronize(means.device)
+        ctx.inputs = (means, values, conics, samples)
+        ctx.versions = (means._version, values._version, conics._version, samples._version)
+        ctx.params, ctx.prev, ctx.aux, ctx.debug, ctx.plan = params, prev, aux, debug, plan
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        means, values, conics, samples = ctx.inputs
+        if (means._version, values._version, conics._version, samples._version) != ctx.versions:
+            raise RuntimeError("one of the tensors handed to GaussianSampler.preprocess() has been modified in place "
+                               "before the backward of a vorticity_residual() output that was computed from it")
+        if ctx.aux is None and samples.shape[0] > 0:
+            raise RuntimeError("this vorticity_residual() output was computed without the record its backward needs "
+                               "(no input required grad when it ran)")
+        gout = gout.contiguous()
+        if ctx.debug:
+            assert ctx.plan is None or not ctx.plan.forward_only, "a vorticity_residual() node holds a forward-only plan"
+        g_means, g_values, g_conics = _vorticity_residual_call(True, means, values, conics, samples, ctx.params, ctx.plan,
+                                                               gout=gout, aux=ctx.aux)
+        if ctx.debug:
+            torch.cuda.synchronize(means.device)
+        return g_means, g_values, g_conics, None, None, None, None, None, None
 
 
 class _SampleFunction(torch.autograd.Function):
@@ -1417,6 +1507,50 @@ class GaussianSampler:
         if self._vorticity is None or (self._needs_backward() and not self._vorticity.requires_grad):
             self._vorticity = _VorticityFunction.apply(means, values, conics, samples, self.debug, self._plan_for(8))
         return self._vorticity
+
+    def vorticity_residual(self, nu, dt, prev=None, tau=1.0, *, time_term=1.0):
+        """Extension of the reference API: the Navier-Stokes residual of the reference's flagship problem (a periodic
+        box in the vorticity formulation, ``compute_loss`` for ``Problem.NAVIER_STOKES``: model_pn.py:794-818, 629-631,
+        830, 848-849) as ONE tensor [M, 2] with the columns ``pigs_amd.VORTICITY_RESIDUAL_COLUMNS`` = ``(div, r)``, in one
+        launch forward and one backward.  With ``now`` the seven ``vorticity_terms()`` of the bound Gaussians, ``prev``
+        [M, 7] the same seven of the previous time level (``None`` reads as zeros) and ``tau`` a float or a field of M
+        elements ([M] or [M, 1])::
+
+            X_b  = tau * X_now + (1 - tau) * X_prev          # X in u_x, u_y, div, w_x, w_y, lap_w
+            div  = div_b
+            r    = time_term * (w_now - w_prev) - dt * (nu * lap_w_b - (u_x_b * w_x_b + u_y_b * w_y_b))
+
+        ``tau`` per point is the reference's ``TRAPEZOID`` rule, ``tau=1`` ``BACKWARD``, ``tau=0`` ``FORWARD``; the loss
+        is ``out.pow(2).mean(0).sum()``.  ``time_term=0, dt=-1`` without ``prev`` gives ``r = nu lap_w - u . grad w``, the
+        ``sample_pde`` of ``Model.forward`` (:655-659).  ``nu``, ``dt``, ``time_term``: floats.  ``tau`` as a tensor is
+        treated like the coefficient fields of ``residual()`` (detached, cast to the means' dtype; ``requires_grad``
+        raises ValueError).  ``prev`` is a constant on the device.  Differentiable wrt means, values and conics; d = 2
+        and c = 2 only.  Binned plans run it on the order-3 plan (``q_max_order3``), the backward with the wide cut-off.
+        The result is not cached: its arguments vary from call to call.  INTEGRATION.md 3 has the recipe (two calls
+        and one line of loss); DESIGN.md 15 the kernels (the step's time against the same loss composed from
+        ``vorticity_terms()`` has not been measured yet: ``tools/bench_vorticity.py`` times the two side by side)."""
+        means, values, conics, samples = self._require_inputs()
+        d, c, M = means.shape[1], values.shape[1], samples.shape[0]
+        if d != 2 or c != 2:
+            raise NotImplementedError(f"vorticity_residual() needs a two-channel field in two dimensions, got d = {d}, c = {c}")
+        f_tau = self._residual_field("tau", tau, 1)
+        if prev is not None:
+            if not isinstance(prev, torch.Tensor) or prev.device != means.device:
+                raise RuntimeError("prev must be a tensor on the sampler's device (no CPU fallback)")
+            if prev.requires_grad:
+                raise ValueError("prev: the previous time level of vorticity_residual() is a constant; detach() the tensor. "
+                                 "When the previous level must receive a gradient, compose the residual from "
+                                 "vorticity_terms() of both levels instead")
+            if tuple(prev.shape) != (M, len(VORTICITY_COLUMNS)):
+                raise ValueError(f"prev must have shape [{M}, {len(VORTICITY_COLUMNS)}] (the vorticity_terms() of the "
+                                 f"previous time level), got {tuple(prev.shape)}")
+            prev = prev.detach().to(means.dtype).contiguous()
+        nu, dt, time_term = float(nu), float(dt), float(time_term)
+        if self._core is not None:
+            field = f_tau if isinstance(f_tau, torch.Tensor) else None
+            return self._core.vorticity_residual(nu, dt, time_term, 0.0 if field is not None else f_tau, field, prev)
+        return _VorticityResidualFunction.apply(means, values, conics, samples, VorticityResidual(nu, dt, time_term, f_tau),
+                                                prev, self.debug, self._plan_for(8), self._needs_backward())
 
     def sample_gaussians(self):
         """u [M, c]"""

@@ -4,7 +4,9 @@ IntegrationRule.TRAPEZOID: mean(div^2) + mean((w_t - dt (nu lap w - u . grad w))
 a random weight per point, the previous level frozen) and its gradients
 
   (a) "fused"     through GaussianSampler.vorticity_terms(): one forward launch writing [M, 7], one backward launch;
-  (b) "composed"  the same loss from sample((0, 1, 2, 3)) and the reference's slicing lines with their autograd,
+  (b) "composed"  the same loss from sample((0, 1, 2, 3)) and the reference's slicing lines with their autograd;
+  (c) "residual"  through GaussianSampler.vorticity_residual(): one forward launch writing [M, 2] (and the [M, 4] record
+                  of the blend when a backward follows), one backward launch, and ``out.pow(2).mean(0).sum()``,
 
 on the same build, alternating in one process, timed with HIP events (warm-ups first), medians and spreads.  Sizes:
 
@@ -15,7 +17,7 @@ on the same build, alternating in one process, timed with HIP events (warm-ups f
 Three measures per size: "fwd" is preprocess + loss under no_grad; "step" is preprocess + loss + gradients wrt means,
 values, conics; "issue" is the host's wall-clock time to issue one step (no synchronisation inside; the queue is drained
 before each).  Prints one JSON line per (size, measure).  ``--bytes`` prints the bytes each path moves per point between
-the sampler's kernels and the loss (no GPU needed) and exits.  DESIGN.md 13 holds the recorded numbers.
+the sampler's kernels and the loss (no GPU needed) and exits.  DESIGN.md 13 and 15 hold the recorded numbers.
 """
 import argparse
 import json
@@ -35,7 +37,10 @@ def point_bytes(elem=4):
     """Bytes per sample point that cross kernel boundaries, sampler side only (d = 2, c = 2, float32): what the forward
     writes and what the backward reads (the loss chain's own temporaries are not counted)."""
     full = (2 + 4 + 8 + 16) * elem
-    return {"fused_fwd": 7 * elem, "fused_bwd": 7 * elem, "composed_fwd": full, "composed_bwd": full}
+    # the residual: 8 B written forward (the record of the blend, 16 B more, only when a backward follows); the backward
+    # reads the 8 B gradient and that 16 B record
+    return {"fused_fwd": 7 * elem, "fused_bwd": 7 * elem, "composed_fwd": full, "composed_bwd": full,
+            "residual_fwd": 2 * elem, "residual_bwd": 2 * elem + 4 * elem}
 
 
 def ref_case(n, M, seed=1):
@@ -93,6 +98,9 @@ def make_steps(gs, pts, backend, periodic, host):
         rhs = DT * (NU * (wxx[:, 0, 0] + wxx[:, 1, 1]) - (u[:, 0] * wx[:, 0] + u[:, 1] * wx[:, 1]))
         return torch.mean((ux[:, 0, 0] + ux[:, 1, 1]) ** 2) + torch.mean((wt - rhs) ** 2)
 
+    def loss_residual():
+        return s.vorticity_residual(NU, DT, prev, tau).pow(2).mean(0).sum()
+
     def variant(loss_fn):
         def fwd():
             with torch.no_grad():
@@ -105,7 +113,7 @@ def make_steps(gs, pts, backend, periodic, host):
             return (loss,) + torch.autograd.grad(loss, leaves)
         return fwd, step
 
-    return s, {"fused": variant(loss_fused), "composed": variant(loss_composed)}
+    return s, {"fused": variant(loss_fused), "composed": variant(loss_composed), "residual": variant(loss_residual)}
 
 
 def time_once(f):
@@ -138,20 +146,22 @@ def run(label, make_case, warmup, iters, host):
     s, variants = make_steps(gs, pts, backend, periodic, host)
     # the two paths compute the same thing (at the size that is timed)
     outs = {k: [x.detach().clone() for x in v[1]()] for k, v in variants.items()}
-    agree = max(float((a - b).abs().max() / b.abs().max()) for a, b in zip(outs["fused"], outs["composed"]))
+    agree = max(float((a - b).abs().max() / b.abs().max()) for k in ("fused", "residual")
+                for a, b in zip(outs[k], outs["composed"]))
     for name, pick, timer in (("fwd", 0, time_once), ("step", 1, time_once), ("issue", 1, issue_once)):
         times = {k: [] for k in variants}
         for _ in range(warmup):
             for v in variants.values():
                 v[pick]()
         torch.cuda.synchronize()
-        for _ in range(iters):       # alternating: both see the same drift of the machine
+        for _ in range(iters):       # alternating: all see the same drift of the machine
             for k, v in variants.items():
                 times[k].append(timer(v[pick]))
         res = {k: stats(x) for k, x in times.items()}
         print(json.dumps({"case": label, "what": name, "N": gs["means"].shape[0], "M": pts.shape[0], "host": host,
                           "backend": "binned" if s._plan is not None else "dense", "periodic": periodic is not None,
                           **res, "fused_over_composed": round(res["fused"]["median_us"] / res["composed"]["median_us"], 3),
+                          "residual_over_fused": round(res["residual"]["median_us"] / res["fused"]["median_us"], 3),
                           "loss_and_gradients_agree_to": float(f"{agree:.3g}")}), flush=True)
     del s, variants
     torch.cuda.empty_cache()
