@@ -121,8 +121,10 @@ int pigs_plan_forward(void* workspace, size_t workspace_bytes, const void* sampl
     void* outs[4] = {out0, out1, out2, out3};
     for (int k = 0; k < 4; ++k)
         if (mask_uses_slot(orders_mask, k) && !outs[k]) return PIGS_ERR_INVALID;
-    return plan_forward(workspace, workspace_bytes, samples_ws, samples_ws_bytes, N, M, c, q_max, orders_mask, outs,
-                        (hipStream_t)stream);
+    SampleArgs a{};
+    a.dtype = PIGS_F32; a.d = 2; a.c = c; a.orders_mask = orders_mask; a.N = N; a.M = M;
+    for (int k = 0; k < 4; ++k) a.out[k] = outs[k];
+    return plan_forward(workspace, workspace_bytes, samples_ws, samples_ws_bytes, q_max, a, (hipStream_t)stream);
 }
 
 int pigs_plan_backward(void* workspace, size_t workspace_bytes, const void* samples_ws, size_t samples_ws_bytes,
@@ -134,30 +136,51 @@ int pigs_plan_backward(void* workspace, size_t workspace_bytes, const void* samp
     for (int k = 0; k < 4; ++k)
         if (mask_uses_slot(orders_mask, k) && !gs[k]) return PIGS_ERR_INVALID;
     if (!g_means || !g_conics || !g_values) return PIGS_ERR_INVALID;
-    return plan_backward(workspace, workspace_bytes, samples_ws, samples_ws_bytes, N, M, c, q_max, orders_mask, gs,
-                         g_means, g_conics, g_values, (hipStream_t)stream);
+    SampleArgs a{};
+    a.dtype = PIGS_F32; a.d = 2; a.c = c; a.orders_mask = orders_mask; a.N = N; a.M = M;
+    for (int k = 0; k < 4; ++k) a.gout[k] = gs[k];
+    a.g_means = g_means; a.g_conics = g_conics; a.g_values = g_values;
+    return plan_backward(workspace, workspace_bytes, samples_ws, samples_ws_bytes, q_max, a, (hipStream_t)stream);
 }
 
-// ---- linear residual (pair_math.h ORDR): dense when plan_ws is null, else through the plan
+// ---- the fused outputs (launch.h MASK_*): dense when plan_ws is null, else through the plan.  An entry point does its
+// own null checks, fills a SampleArgs and leaves the rest to fused_launch.
+static SampleArgs fused_args(int mask, int dtype, int d, int c, int64_t N, int64_t M, const void* means, const void* conics,
+                             const void* values, const void* samples) {
+    SampleArgs a{};
+    a.dtype = dtype; a.d = d; a.c = c; a.orders_mask = mask; a.N = N; a.M = M;
+    a.means = means; a.conics = conics; a.values = values; a.samples = samples;
+    return a;
+}
+
+static void fused_gradients(SampleArgs& a, const void* gout, void* g_means, void* g_conics, void* g_values) {
+    a.gout[0] = gout;
+    a.g_means = g_means; a.g_conics = g_conics; a.g_values = g_values;
+}
+
+static int fused_launch(bool backward, const SampleArgs& a, void* plan_ws, size_t plan_ws_bytes, const void* samples_ws,
+                        size_t samples_ws_bytes, void* stream) {
+    if (plan_ws) {
+        // the binned kernels: float32 in two dimensions; the coupled residual for two channels only
+        if (a.dtype != PIGS_F32 || a.d != 2 || (a.orders_mask == MASK_COUPLED && a.c != 2)) return PIGS_ERR_UNSUPPORTED;
+        return backward ? plan_backward(plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, 0.f, a, (hipStream_t)stream)
+                        : plan_forward(plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, 0.f, a, (hipStream_t)stream);
+    }
+    const int rc = check_common(a.dtype, a.d, a.c, 1, a.N, a.M, a.means, a.conics, a.values, a.samples);
+    if (rc != PIGS_OK) return rc;
+    return dense_dispatch(backward, a, (hipStream_t)stream);
+}
+
+// linear residual (pair_math.h ORDR)
 int pigs_residual_forward(int dtype, int d, int c, int64_t N, int64_t M, const void* means, const void* conics,
                           const void* values, const void* samples, const double* coeffs, const void* target, void* out,
                           void* plan_ws, size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes, void* stream) {
     if (!coeffs || (M > 0 && !out)) return PIGS_ERR_INVALID;
-    if (plan_ws) {
-        if (dtype != PIGS_F32 || d != 2) return PIGS_ERR_UNSUPPORTED;
-        void* outs[4] = {out, nullptr, nullptr, nullptr};
-        return plan_forward(plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, N, M, c, 0.f, 32, outs, (hipStream_t)stream,
-                            coeffs, target);
-    }
-    int rc = check_common(dtype, d, c, 1, N, M, means, conics, values, samples);
-    if (rc != PIGS_OK) return rc;
-    SampleArgs a{};
-    a.dtype = dtype; a.d = d; a.c = c; a.orders_mask = 32; a.N = N; a.M = M;
-    a.means = means; a.conics = conics; a.values = values; a.samples = samples;
-    a.out[0] = out;
+    SampleArgs a = fused_args(MASK_RESIDUAL, dtype, d, c, N, M, means, conics, values, samples);
     for (int k = 0; k < 4; ++k) a.resid[k] = coeffs[k];
     a.target = target;
-    return dense_dispatch(false, a, (hipStream_t)stream);
+    a.out[0] = out;
+    return fused_launch(false, a, plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, stream);
 }
 
 int pigs_residual_backward(int dtype, int d, int c, int64_t N, int64_t M, const void* means, const void* conics,
@@ -165,24 +188,13 @@ int pigs_residual_backward(int dtype, int d, int c, int64_t N, int64_t M, const 
                            void* g_conics, void* g_values, void* plan_ws, size_t plan_ws_bytes, const void* samples_ws,
                            size_t samples_ws_bytes, void* stream) {
     if (!coeffs || (M > 0 && !gout) || (N > 0 && (!g_means || !g_conics || !g_values))) return PIGS_ERR_INVALID;
-    if (plan_ws) {
-        if (dtype != PIGS_F32 || d != 2) return PIGS_ERR_UNSUPPORTED;
-        const void* gs[4] = {gout, nullptr, nullptr, nullptr};
-        return plan_backward(plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, N, M, c, 0.f, 32, gs, g_means, g_conics,
-                             g_values, (hipStream_t)stream, coeffs);
-    }
-    int rc = check_common(dtype, d, c, 1, N, M, means, conics, values, samples);
-    if (rc != PIGS_OK) return rc;
-    SampleArgs a{};
-    a.dtype = dtype; a.d = d; a.c = c; a.orders_mask = 32; a.N = N; a.M = M;
-    a.means = means; a.conics = conics; a.values = values; a.samples = samples;
-    a.gout[0] = gout;
-    a.g_means = g_means; a.g_conics = g_conics; a.g_values = g_values;
+    SampleArgs a = fused_args(MASK_RESIDUAL, dtype, d, c, N, M, means, conics, values, samples);
     for (int k = 0; k < 4; ++k) a.resid[k] = coeffs[k];
-    return dense_dispatch(true, a, (hipStream_t)stream);
+    fused_gradients(a, gout, g_means, g_conics, g_values);
+    return fused_launch(true, a, plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, stream);
 }
 
-// ---- general residual (pair_math.h ORDG): per-point coefficients and an advection term
+// general residual (pair_math.h ORDG): per-point coefficients and an advection term
 static bool terms_advect(const PigsResidualTerms* t) { return t->adv != 0.0 || t->adv_pt != nullptr; }
 
 int pigs_residual_terms_forward(int dtype, int d, int c, int64_t N, int64_t M, const void* means, const void* conics,
@@ -190,22 +202,12 @@ int pigs_residual_terms_forward(int dtype, int d, int c, int64_t N, int64_t M, c
                                 void* out, void* aux, void* plan_ws, size_t plan_ws_bytes, const void* samples_ws,
                                 size_t samples_ws_bytes, void* stream) {
     if (!terms || (M > 0 && !out)) return PIGS_ERR_INVALID;
-    if (plan_ws) {
-        if (dtype != PIGS_F32 || d != 2) return PIGS_ERR_UNSUPPORTED;
-        void* outs[4] = {out, nullptr, nullptr, nullptr};
-        return plan_forward(plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, N, M, c, 0.f, 64, outs, (hipStream_t)stream,
-                            nullptr, target, terms, aux);
-    }
-    int rc = check_common(dtype, d, c, 1, N, M, means, conics, values, samples);
-    if (rc != PIGS_OK) return rc;
-    SampleArgs a{};
-    a.dtype = dtype; a.d = d; a.c = c; a.orders_mask = 64; a.N = N; a.M = M;
-    a.means = means; a.conics = conics; a.values = values; a.samples = samples;
-    a.out[0] = out;
-    a.target = target;
+    SampleArgs a = fused_args(MASK_TERMS, dtype, d, c, N, M, means, conics, values, samples);
     a.terms = terms;
+    a.target = target;
+    a.out[0] = out;
     a.aux = aux;
-    return dense_dispatch(false, a, (hipStream_t)stream);
+    return fused_launch(false, a, plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, stream);
 }
 
 int pigs_residual_terms_backward(int dtype, int d, int c, int64_t N, int64_t M, const void* means, const void* conics,
@@ -214,53 +216,25 @@ int pigs_residual_terms_backward(int dtype, int d, int c, int64_t N, int64_t M, 
                                  size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes, void* stream) {
     if (!terms || (M > 0 && !gout) || (N > 0 && (!g_means || !g_conics || !g_values))) return PIGS_ERR_INVALID;
     if (terms_advect(terms) && !aux) return PIGS_ERR_INVALID;
-    if (!terms_advect(terms)) aux = nullptr;      // nothing of it is needed
-    if (plan_ws) {
-        if (dtype != PIGS_F32 || d != 2) return PIGS_ERR_UNSUPPORTED;
-        const void* gs[4] = {gout, nullptr, nullptr, nullptr};
-        return plan_backward(plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, N, M, c, 0.f, 64, gs, g_means, g_conics,
-                             g_values, (hipStream_t)stream, nullptr, terms, aux);
-    }
-    int rc = check_common(dtype, d, c, 1, N, M, means, conics, values, samples);
-    if (rc != PIGS_OK) return rc;
-    SampleArgs a{};
-    a.dtype = dtype; a.d = d; a.c = c; a.orders_mask = 64; a.N = N; a.M = M;
-    a.means = means; a.conics = conics; a.values = values; a.samples = samples;
-    a.gout[0] = gout;
-    a.g_means = g_means; a.g_conics = g_conics; a.g_values = g_values;
+    SampleArgs a = fused_args(MASK_TERMS, dtype, d, c, N, M, means, conics, values, samples);
     a.terms = terms;
-    a.aux = const_cast<void*>(aux);
-    return dense_dispatch(true, a, (hipStream_t)stream);
+    a.aux = terms_advect(terms) ? const_cast<void*>(aux) : nullptr;      // without advection nothing of it is needed
+    fused_gradients(a, gout, g_means, g_conics, g_values);
+    return fused_launch(true, a, plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, stream);
 }
 
-// ---- coupled residual (pair_math.h ORDC): the channels mixed by two constant matrices under a per-point weight
-static SampleArgs coupled_args(int dtype, int d, int c, int64_t N, int64_t M, const void* means, const void* conics,
-                               const void* values, const void* samples, const PigsResidualCoupling* coupling) {
-    SampleArgs a{};
-    a.dtype = dtype; a.d = d; a.c = c; a.orders_mask = 256; a.N = N; a.M = M;
-    a.means = means; a.conics = conics; a.values = values; a.samples = samples;
-    a.coupling = coupling;
-    return a;
-}
-
+// coupled residual (pair_math.h ORDC): the channels mixed by two constant matrices under a per-point weight
 int pigs_residual_coupled_forward(int dtype, int d, int c, int64_t N, int64_t M, const void* means, const void* conics,
                                   const void* values, const void* samples, const PigsResidualCoupling* coupling,
                                   const void* target, void* out, void* plan_ws, size_t plan_ws_bytes, const void* samples_ws,
                                   size_t samples_ws_bytes, void* stream) {
     if (!coupling || (M > 0 && !out)) return PIGS_ERR_INVALID;
     if (c == 1) return PIGS_ERR_UNSUPPORTED;      // nothing to couple: pigs_residual_* / pigs_residual_terms_*
-    if (plan_ws) {
-        if (dtype != PIGS_F32 || d != 2 || c != 2) return PIGS_ERR_UNSUPPORTED;
-        void* outs[4] = {out, nullptr, nullptr, nullptr};
-        return plan_forward(plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, N, M, c, 0.f, 256, outs, (hipStream_t)stream,
-                            nullptr, target, nullptr, nullptr, coupling);
-    }
-    int rc = check_common(dtype, d, c, 1, N, M, means, conics, values, samples);
-    if (rc != PIGS_OK) return rc;
-    SampleArgs a = coupled_args(dtype, d, c, N, M, means, conics, values, samples, coupling);
-    a.out[0] = out;
+    SampleArgs a = fused_args(MASK_COUPLED, dtype, d, c, N, M, means, conics, values, samples);
+    a.coupling = coupling;
     a.target = target;
-    return dense_dispatch(false, a, (hipStream_t)stream);
+    a.out[0] = out;
+    return fused_launch(false, a, plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, stream);
 }
 
 int pigs_residual_coupled_backward(int dtype, int d, int c, int64_t N, int64_t M, const void* means, const void* conics,
@@ -269,84 +243,43 @@ int pigs_residual_coupled_backward(int dtype, int d, int c, int64_t N, int64_t M
                                    size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes, void* stream) {
     if (!coupling || (M > 0 && !gout) || (N > 0 && (!g_means || !g_conics || !g_values))) return PIGS_ERR_INVALID;
     if (c == 1) return PIGS_ERR_UNSUPPORTED;
-    if (plan_ws) {
-        if (dtype != PIGS_F32 || d != 2 || c != 2) return PIGS_ERR_UNSUPPORTED;
-        const void* gs[4] = {gout, nullptr, nullptr, nullptr};
-        return plan_backward(plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, N, M, c, 0.f, 256, gs, g_means, g_conics,
-                             g_values, (hipStream_t)stream, nullptr, nullptr, nullptr, coupling);
-    }
-    int rc = check_common(dtype, d, c, 1, N, M, means, conics, values, samples);
-    if (rc != PIGS_OK) return rc;
-    SampleArgs a = coupled_args(dtype, d, c, N, M, means, conics, values, samples, coupling);
-    a.gout[0] = gout;
-    a.g_means = g_means; a.g_conics = g_conics; a.g_values = g_values;
-    return dense_dispatch(true, a, (hipStream_t)stream);
+    SampleArgs a = fused_args(MASK_COUPLED, dtype, d, c, N, M, means, conics, values, samples);
+    a.coupling = coupling;
+    fused_gradients(a, gout, g_means, g_conics, g_values);
+    return fused_launch(true, a, plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, stream);
 }
 
-// ---- vorticity terms (pair_math.h ORDV): (u_x, u_y, div, w, w_x, w_y, lap w) of a two-channel field, d = 2
-static SampleArgs vorticity_args(int dtype, int64_t N, int64_t M, const void* means, const void* conics, const void* values,
-                                 const void* samples) {
-    SampleArgs a{};
-    a.dtype = dtype; a.d = 2; a.c = 2; a.orders_mask = 128; a.N = N; a.M = M;
-    a.means = means; a.conics = conics; a.values = values; a.samples = samples;
-    return a;
-}
-
+// vorticity terms (pair_math.h ORDV): (u_x, u_y, div, w, w_x, w_y, lap w) of a two-channel field, d = 2
 int pigs_vorticity_forward(int dtype, int64_t N, int64_t M, const void* means, const void* conics, const void* values,
                            const void* samples, void* out, void* plan_ws, size_t plan_ws_bytes, const void* samples_ws,
                            size_t samples_ws_bytes, void* stream) {
     if (M > 0 && !out) return PIGS_ERR_INVALID;
-    if (plan_ws) {
-        if (dtype != PIGS_F32) return PIGS_ERR_UNSUPPORTED;
-        void* outs[4] = {out, nullptr, nullptr, nullptr};
-        return plan_forward(plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, N, M, 2, 0.f, 128, outs, (hipStream_t)stream);
-    }
-    int rc = check_common(dtype, 2, 2, 1, N, M, means, conics, values, samples);
-    if (rc != PIGS_OK) return rc;
-    SampleArgs a = vorticity_args(dtype, N, M, means, conics, values, samples);
+    SampleArgs a = fused_args(MASK_VORTICITY, dtype, 2, 2, N, M, means, conics, values, samples);
     a.out[0] = out;
-    return dense_dispatch(false, a, (hipStream_t)stream);
+    return fused_launch(false, a, plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, stream);
 }
 
 int pigs_vorticity_backward(int dtype, int64_t N, int64_t M, const void* means, const void* conics, const void* values,
                             const void* samples, const void* gout, void* g_means, void* g_conics, void* g_values,
                             void* plan_ws, size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes, void* stream) {
     if ((M > 0 && !gout) || (N > 0 && (!g_means || !g_conics || !g_values))) return PIGS_ERR_INVALID;
-    if (plan_ws) {
-        if (dtype != PIGS_F32) return PIGS_ERR_UNSUPPORTED;
-        const void* gs[4] = {gout, nullptr, nullptr, nullptr};
-        return plan_backward(plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, N, M, 2, 0.f, 128, gs, g_means, g_conics,
-                             g_values, (hipStream_t)stream);
-    }
-    int rc = check_common(dtype, 2, 2, 1, N, M, means, conics, values, samples);
-    if (rc != PIGS_OK) return rc;
-    SampleArgs a = vorticity_args(dtype, N, M, means, conics, values, samples);
-    a.gout[0] = gout;
-    a.g_means = g_means; a.g_conics = g_conics; a.g_values = g_values;
-    return dense_dispatch(true, a, (hipStream_t)stream);
+    SampleArgs a = fused_args(MASK_VORTICITY, dtype, 2, 2, N, M, means, conics, values, samples);
+    fused_gradients(a, gout, g_means, g_conics, g_values);
+    return fused_launch(true, a, plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, stream);
 }
 
-// ---- vorticity residual (pair_math.h ORDN): (div_b, the time-blended vorticity equation's residual), d = 2, c = 2
+// vorticity residual (pair_math.h ORDN): (div_b, the time-blended vorticity equation's residual), d = 2, c = 2
 int pigs_vorticity_residual_forward(int dtype, int64_t N, int64_t M, const void* means, const void* conics, const void* values,
                                     const void* samples, const PigsVorticityResidual* params, const void* prev, void* out,
                                     void* aux, void* plan_ws, size_t plan_ws_bytes, const void* samples_ws,
                                     size_t samples_ws_bytes, void* stream) {
     if (!params || (M > 0 && !out)) return PIGS_ERR_INVALID;
-    if (plan_ws) {
-        if (dtype != PIGS_F32) return PIGS_ERR_UNSUPPORTED;
-        void* outs[4] = {out, nullptr, nullptr, nullptr};
-        return plan_forward(plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, N, M, 2, 0.f, 512, outs, (hipStream_t)stream,
-                            nullptr, prev, nullptr, aux, nullptr, params);
-    }
-    int rc = check_common(dtype, 2, 2, 1, N, M, means, conics, values, samples);
-    if (rc != PIGS_OK) return rc;
-    SampleArgs a = vorticity_args(dtype, N, M, means, conics, values, samples);
-    a.orders_mask = 512;
-    a.out[0] = out;
+    SampleArgs a = fused_args(MASK_VORT_RESIDUAL, dtype, 2, 2, N, M, means, conics, values, samples);
     a.vort = params;
     a.target = prev;
+    a.out[0] = out;
     a.aux = aux;
-    return dense_dispatch(false, a, (hipStream_t)stream);
+    return fused_launch(false, a, plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, stream);
 }
 
 int pigs_vorticity_residual_backward(int dtype, int64_t N, int64_t M, const void* means, const void* conics, const void* values,
@@ -354,21 +287,11 @@ int pigs_vorticity_residual_backward(int dtype, int64_t N, int64_t M, const void
                                      void* g_means, void* g_conics, void* g_values, void* plan_ws, size_t plan_ws_bytes,
                                      const void* samples_ws, size_t samples_ws_bytes, void* stream) {
     if (!params || (M > 0 && (!gout || !aux)) || (N > 0 && (!g_means || !g_conics || !g_values))) return PIGS_ERR_INVALID;
-    if (plan_ws) {
-        if (dtype != PIGS_F32) return PIGS_ERR_UNSUPPORTED;
-        const void* gs[4] = {gout, nullptr, nullptr, nullptr};
-        return plan_backward(plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, N, M, 2, 0.f, 512, gs, g_means, g_conics,
-                             g_values, (hipStream_t)stream, nullptr, nullptr, aux, nullptr, params);
-    }
-    int rc = check_common(dtype, 2, 2, 1, N, M, means, conics, values, samples);
-    if (rc != PIGS_OK) return rc;
-    SampleArgs a = vorticity_args(dtype, N, M, means, conics, values, samples);
-    a.orders_mask = 512;
-    a.gout[0] = gout;
-    a.g_means = g_means; a.g_conics = g_conics; a.g_values = g_values;
+    SampleArgs a = fused_args(MASK_VORT_RESIDUAL, dtype, 2, 2, N, M, means, conics, values, samples);
     a.vort = params;
     a.aux = const_cast<void*>(aux);
-    return dense_dispatch(true, a, (hipStream_t)stream);
+    fused_gradients(a, gout, g_means, g_conics, g_values);
+    return fused_launch(true, a, plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, stream);
 }
 
 // ---- periodic domain (ABI 10): the 3 x 3 images of every Gaussian and the fold of their gradients (periodic.hip)

@@ -18,6 +18,10 @@
 
 namespace pigs {
 
+static_assert(MASK_RESIDUAL == ORDR && MASK_TERMS == ORDG && MASK_VORTICITY == ORDV && MASK_COUPLED == ORDC &&
+                  MASK_VORT_RESIDUAL == ORDN,
+              "launch.h and pair_math.h name the same fused-output masks");
+
 template <typename T, int D, int C, int MASK, int NW>
 __global__ __launch_bounds__(NW * 64) void dense_forward_kernel(
     int64_t N, int64_t M, const T* __restrict__ means, const T* __restrict__ conics,
@@ -368,20 +372,6 @@ __global__ __launch_bounds__(256) void zero_grads_kernel(uint32_t* __restrict__ 
 // ------------------------------------------------------------------------------------------
 // Host-side launchers
 // ------------------------------------------------------------------------------------------
-
-// the coefficient block of a launch compiled for MASK (aux: the forward's output, the backward's input)
-template <typename T, int MASK>
-static RzOf<T, MASK> rz_of(const SampleArgs& a, bool backward) {
-    if constexpr (MASK == ORDG) {
-        return make_terms<T>(*a.terms, backward ? nullptr : a.target, a.aux);
-    } else if constexpr (MASK == ORDC) {
-        return make_coupled<T>(*a.coupling, backward ? nullptr : a.target);
-    } else if constexpr (MASK == ORDN) {
-        return make_vort_resid<T>(*a.vort, backward ? nullptr : a.target, a.aux);
-    } else {
-        return Resid<T>{(T)a.resid[0], {(T)a.resid[1], (T)a.resid[2]}, (T)a.resid[3], backward ? nullptr : (const T*)a.target};
-    }
-}
 
 // tests/test_dense_matrix.py mirrors the selection of the two launchers below: a threshold changed here is changed there
 template <typename T, int D, int C, int MASK>

@@ -14,13 +14,14 @@ struct SampleArgs {
     void* out[4];          // forward outputs (orders 0..3)
     const void* gout[4];   // backward: incoming gradients
     void *g_means, *g_conics, *g_values;
-    double resid[4];       // orders_mask == 32 (linear residual): a0, a1x, a1y, aL
+    // the fused outputs (MASK_* below), the only way their coefficient blocks reach a launcher:
+    double resid[4];       // MASK_RESIDUAL: a0, a1x, a1y, aL
     const void* target;    //   and its target [M][c] (or null)
-    const PigsResidualTerms* terms;      // orders_mask == 64 (general residual): coefficients, fields, advect_by
+    const PigsResidualTerms* terms;      // MASK_TERMS: coefficients, fields, advect_by
     void* aux;                           //   and aux [M][1+d][c] (the forward writes it, the backward reads it; or null)
-    const PigsResidualCoupling* coupling;      // orders_mask == 256 (coupled residual): coefficients, fields, the two matrices
-    const PigsVorticityResidual* vort;         // orders_mask == 512 (vorticity residual): coefficients, tau field; `target` = prev
-                                               //   [M][7] or null, `aux` = [M][4] (the forward writes it, the backward reads it)
+    const PigsResidualCoupling* coupling;      // MASK_COUPLED: coefficients, fields, the two matrices
+    const PigsVorticityResidual* vort;         // MASK_VORT_RESIDUAL: coefficients, tau field; `target` = prev [M][7] or null,
+                                               //   `aux` = [M][4] (the forward writes it, the backward reads it)
 };
 
 int dense_dispatch(bool backward, const SampleArgs& a, hipStream_t stream);
@@ -66,15 +67,11 @@ int samples_order_hint(int64_t M);
 int plan_build(void* ws, size_t ws_bytes, void* sws, size_t sws_bytes, int flags, int64_t N, int64_t M, int c,
                float q_max, float q_max_backward, const void* means, const void* conics, const void* values, const void* samples,
                hipStream_t stream);
-int plan_forward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, int64_t N, int64_t M, int c,
-                 float q_max, int mask, void* const* out, hipStream_t stream, const double* resid = nullptr,
-                 const void* target = nullptr, const PigsResidualTerms* terms = nullptr, void* aux = nullptr,
-                 const PigsResidualCoupling* coupling = nullptr, const PigsVorticityResidual* vort = nullptr);
-int plan_backward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, int64_t N, int64_t M, int c,
-                  float q_max, int mask, const void* const* gout, void* g_means, void* g_conics, void* g_values,
-                  hipStream_t stream, const double* resid = nullptr, const PigsResidualTerms* terms = nullptr,
-                  const void* aux = nullptr, const PigsResidualCoupling* coupling = nullptr,
-                  const PigsVorticityResidual* vort = nullptr);
+// the fused outputs' coefficient blocks travel in `a` (also N, M, c, orders_mask, out / gout and the gradients)
+int plan_forward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, float q_max, const SampleArgs& a,
+                 hipStream_t stream);
+int plan_backward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, float q_max, const SampleArgs& a,
+                  hipStream_t stream);
 int plan_layout_info(int64_t N, int64_t M, int c, int64_t* info);
 // the Gaussian grid alone (aggregate.hip): plan.hip
 size_t aggregate_grid_bytes(int64_t N);
@@ -89,17 +86,22 @@ size_t plan_error_offset();
 
 // Order masks: bit k < 4 = derivative order k (pointer slot k); bit 4 (16) = the TRACE of the order-2
 // output (the Laplacian), which takes pointer slot 2 in place of the full Hessian, [M][c].
-// 32 = the linear residual (pair_math.h ORDR), alone, in slot 0 -- reachable through pigs_residual_* only;
-// 64 = the general residual (ORDG), likewise -- through pigs_residual_terms_* only;
-// 128 = the vorticity terms (ORDV; d = 2, c = 2), one packed row [M][7] in slot 0 -- through pigs_vorticity_* only;
-// 256 = the coupled residual (ORDC; c >= 2), [M][c] in slot 0 -- through pigs_residual_coupled_* only;
-// 512 = the vorticity residual (ORDN; d = 2, c = 2), [M][2] in slot 0 -- through pigs_vorticity_residual_* only.
+// The fused outputs: one mask each, alone, the output in slot 0, reachable through their own entry points only.  The
+// kernels know them as ORDR, ORDG, ORDV, ORDC, ORDN (pair_math.h; dense.hip asserts that the two sets agree).
+constexpr int MASK_RESIDUAL = 32;             // the linear residual, [M][c] -- pigs_residual_*
+constexpr int MASK_TERMS = 64;                // the general residual, [M][c] -- pigs_residual_terms_*
+constexpr int MASK_VORTICITY = 128;           // the vorticity terms (d = 2, c = 2), [M][7] -- pigs_vorticity_*
+constexpr int MASK_COUPLED = 256;             // the coupled residual (c >= 2), [M][c] -- pigs_residual_coupled_*
+constexpr int MASK_VORT_RESIDUAL = 512;       // the vorticity residual (d = 2, c = 2), [M][2] -- pigs_vorticity_residual_*
+inline bool is_fused_output(int m) {
+    return m == MASK_RESIDUAL || m == MASK_TERMS || m == MASK_VORTICITY || m == MASK_COUPLED || m == MASK_VORT_RESIDUAL;
+}
 inline bool mask_valid(int m) { return m > 0 && m < 32 && !((m & 4) && (m & 16)); }
-inline bool mask_uses_slot(int m, int k) { return (m == 32 || m == 64 || m == 128 || m == 256 || m == 512) ? k == 0 : (m >> k & 1) || (k == 2 && (m & 16)); }
+inline bool mask_uses_slot(int m, int k) { return is_fused_output(m) ? k == 0 : (m >> k & 1) || (k == 2 && (m & 16)); }
 // Smallest compiled mask covering the request (compiled: single orders, 0..2, 0..3, the trace alone
 // and orders 0, 1 + trace); 0 = no compiled kernel (trace together with order 3).
 inline int covering_mask_of(int mask) {
-    if (mask == 32 || mask == 64 || mask == 128 || mask == 256 || mask == 512) return mask;
+    if (is_fused_output(mask)) return mask;
     if (mask & 16) return mask == 16 ? 16 : (mask & ~19) == 0 ? 19 : 0;
     if (mask == 1 || mask == 2 || mask == 4 || mask == 8) return mask;
     if ((mask & ~7) == 0) return 7;

@@ -138,6 +138,20 @@ inline VortResid<T> make_vort_resid(const ABI& t, const void* prev, const void* 
 template <typename T, int MASK>
 using RzOf = std::conditional_t<MASK == ORDG, Terms<T>, std::conditional_t<MASK == ORDC, Coupled<T>,
              std::conditional_t<MASK == ORDN, VortResid<T>, Resid<T>>>>;
+// host side: that block from a launcher's arguments (launch.h's SampleArgs; aux: the forward's output, the backward's
+// input; the target / previous level is read by the forward alone)
+template <typename T, int MASK, typename ARGS>
+inline RzOf<T, MASK> rz_of(const ARGS& a, bool backward) {
+    if constexpr (MASK == ORDG) {
+        return make_terms<T>(*a.terms, backward ? nullptr : a.target, a.aux);
+    } else if constexpr (MASK == ORDC) {
+        return make_coupled<T>(*a.coupling, backward ? nullptr : a.target);
+    } else if constexpr (MASK == ORDN) {
+        return make_vort_resid<T>(*a.vort, backward ? nullptr : a.target, a.aux);
+    } else {
+        return Resid<T>{(T)a.resid[0], {(T)a.resid[1], (T)a.resid[2]}, (T)a.resid[3], backward ? nullptr : (const T*)a.target};
+    }
+}
 
 // the coefficients of the general residual at one point
 template <typename T, int D> struct TermsAt {

@@ -3484,10 +3484,19 @@ int plan_build(void* ws, size_t ws_bytes, void* sws, size_t sws_bytes, int flags
 // the masks the fused first forward is compiled for (the rest: the list launch, then the forward launch)
 template <int C> static bool fused_first_compiled(int mask) { return C == 1 ? (mask == 1 || mask == 7 || mask == 19 || mask == 32) : mask == 7; }
 
+// a fused output whose coefficient block the caller left out (SampleArgs: terms, coupling, vort)
+static bool block_missing(int mask, const SampleArgs& a) {
+    switch (mask) {
+        case ORDG: return !a.terms;
+        case ORDC: return !a.coupling;
+        case ORDN: return !a.vort;
+        default: return false;
+    }
+}
+
 template <int C>
-static int plan_forward_c(const PlanView& pv_in, const SamplesView& sv, int mask, float* const* out, hipStream_t stream,
-                          const Resid<float>& rz, const ListArgs* first = nullptr, const Terms<float>* tz = nullptr,
-                          const Coupled<float>* cz = nullptr, const VortResid<float>* vz = nullptr) {
+static int plan_forward_c(const PlanView& pv_in, const SamplesView& sv, int mask, float* const* out, const SampleArgs& a,
+                          hipStream_t stream, const ListArgs* first) {
     // + the helper workgroups of the TILE_MODE_POINTS tiles (they leave at once when the plan queued none)
     const dim3 grid((sv.ntiles + PIGS_FWD_WG_WAVES - 1) / PIGS_FWD_WG_WAVES + POINT_HELPER_BLOCKS * 4 / PIGS_FWD_WG_WAVES),
         block(64 * PIGS_FWD_WG_WAVES);
@@ -3506,7 +3515,7 @@ static int plan_forward_c(const PlanView& pv_in, const SamplesView& sv, int mask
 #define PIGS_FUSED(MK)                                                                                                  \
     case MK:                                                                                                            \
         hipLaunchKernelGGL((plan_lists_forward_kernel<C, MK>), lgrid, dim3(256), 0, stream, la, out[0], out[1], out[2], \
-                           out[3], rz);                                                                                 \
+                           out[3], rz_of<float, MK>(a, false));                                                         \
         done = true;                                                                                                    \
         break;
         if (fused_first_compiled<C>(mask) && !getenv("PIGS_NO_FUSED_FIRST") && !plan_expects_points(pv.N, sv.M, stream)) {
@@ -3519,39 +3528,28 @@ static int plan_forward_c(const PlanView& pv_in, const SamplesView& sv, int mask
 #undef PIGS_FUSED
         if (!done) launch_lists(sv.ntiles, la, stream);
     }
-#define PIGS_CASE(MK)                                                                                          \
-    case MK:                                                                                                   \
+    if (block_missing(mask, a)) return PIGS_ERR_INVALID;
+    // every compiled mask (the fused outputs are never fused with the list launch, the linear residual apart)
+#define PIGS_CASE(MK)                                                                                            \
+    case MK:                                                                                                     \
         hipLaunchKernelGGL((tile_forward_kernel<C, MK>), grid, block, 0, stream, pv, sv, out[0], out[1], out[2], \
-                           out[3], rz);                                                                        \
+                           out[3], rz_of<float, MK>(a, false));                                                  \
+        done = true;                                                                                             \
         break;
-    if (mask == ORDG) {      // the general residual: its own coefficient block (never fused with the list launch)
-        if (!tz) return PIGS_ERR_INVALID;
-        hipLaunchKernelGGL((tile_forward_kernel<C, ORDG>), grid, block, 0, stream, pv, sv, out[0], out[1], out[2], out[3], *tz);
-    } else if (mask == ORDC) {      // the coupled residual: two channels, its own coefficient block (never fused either)
-        if (!cz) return PIGS_ERR_INVALID;
-        if constexpr (C == 2) {
-            hipLaunchKernelGGL((tile_forward_kernel<C, ORDC>), grid, block, 0, stream, pv, sv, out[0], out[1], out[2], out[3], *cz);
-        } else {
-            return PIGS_ERR_UNSUPPORTED;
+    if (!done) switch (mask) {
+        PIGS_CASE(1) PIGS_CASE(2) PIGS_CASE(4) PIGS_CASE(8) PIGS_CASE(7) PIGS_CASE(15) PIGS_CASE(16) PIGS_CASE(19)
+        PIGS_CASE(ORDR) PIGS_CASE(ORDG)
+        default: break;
+    }
+    // the vorticity terms and residual and the coupled residual: two channels, the only instantiations compiled
+    if constexpr (C == 2) {
+        switch (mask) {
+            PIGS_CASE(ORDV) PIGS_CASE(ORDC) PIGS_CASE(ORDN)
+            default: break;
         }
-    } else if (mask == ORDV) {      // the vorticity terms: two channels only (never fused with the list launch)
-        if constexpr (C == 2) {
-            hipLaunchKernelGGL((tile_forward_kernel<C, ORDV>), grid, block, 0, stream, pv, sv, out[0], out[1], out[2], out[3], rz);
-        } else {
-            return PIGS_ERR_UNSUPPORTED;
-        }
-    } else if (mask == ORDN) {      // the vorticity residual: two channels only, its own coefficient block (never fused either)
-        if (!vz) return PIGS_ERR_INVALID;
-        if constexpr (C == 2) {
-            hipLaunchKernelGGL((tile_forward_kernel<C, ORDN>), grid, block, 0, stream, pv, sv, out[0], out[1], out[2], out[3], *vz);
-        } else {
-            return PIGS_ERR_UNSUPPORTED;
-        }
-    } else if (!done) switch (mask) {
-        PIGS_CASE(1) PIGS_CASE(2) PIGS_CASE(4) PIGS_CASE(8) PIGS_CASE(7) PIGS_CASE(15) PIGS_CASE(16) PIGS_CASE(19) PIGS_CASE(32)
-        default: return PIGS_ERR_UNSUPPORTED;
     }
 #undef PIGS_CASE
+    if (!done) return PIGS_ERR_UNSUPPORTED;
     if (staged) {
         const dim3 g2((sv.M + 255) / 256), b2(256);
         if (mask == 7) hipLaunchKernelGGL(stage_to_outputs_kernel<7>, g2, b2, 0, stream, pv.stage, sv.M, out[0], out[1], out[2]);
@@ -3561,10 +3559,15 @@ static int plan_forward_c(const PlanView& pv_in, const SamplesView& sv, int mask
 }
 
 template <int C>
-static int plan_backward_c(const PlanView& pv_in, const SamplesView& sv, int mask, const float* const* g, float* gm,
-                           float* gc, float* gv, hipStream_t stream, const Resid<float>& rz, const Terms<float>* tz = nullptr,
-                           const Coupled<float>* cz = nullptr, const VortResid<float>* vz = nullptr) {
+static int plan_backward_c(const PlanView& pv_in, const SamplesView& sv, int mask, const float* const* g, const SampleArgs& a,
+                           hipStream_t stream) {
+#if PIGS_BWD_BLOCK      // one wave = four tiles
+#define PIGS_BWD_KERNEL block_backward_kernel
+    const dim3 grid((((sv.ntiles + 3) / 4) + 3) / 4 + POINT_HELPER_BLOCKS), block(256);
+#else
+#define PIGS_BWD_KERNEL tile_backward_kernel
     const dim3 grid((sv.ntiles + 3) / 4 + POINT_HELPER_BLOCKS), block(256);
+#endif
     // points that arrive in no order fetch their incoming gradients from the staging records (PlanView::stage)
     PlanView pv = pv_in;
     const bool staged = C == 1 && (mask == 7 || mask == 19) && !PIGS_BWD_BLOCK && points_unordered(sv.M, stream);
@@ -3575,115 +3578,60 @@ static int plan_backward_c(const PlanView& pv_in, const SamplesView& sv, int mas
         if (mask == 7) hipLaunchKernelGGL(gradients_to_stage_kernel<7>, g2, b2, 0, stream, pv.stage, sv.M, g[0], g[1], g[2]);
         else hipLaunchKernelGGL(gradients_to_stage_kernel<19>, g2, b2, 0, stream, pv.stage, sv.M, g[0], g[1], g[2]);
     }
-#if PIGS_BWD_BLOCK
-    const dim3 bgrid((((sv.ntiles + 3) / 4) + 3) / 4 + POINT_HELPER_BLOCKS);
-#define PIGS_CASE(MK)                                                                                             \
-    case MK:                                                                                                      \
-        hipLaunchKernelGGL((block_backward_kernel<C, MK>), bgrid, block, 0, stream, pv, sv, g[0], g[1], g[2], g[3], rz); \
+    if (block_missing(mask, a)) return PIGS_ERR_INVALID;
+    bool done = false;
+#define PIGS_CASE(MK)                                                                                                \
+    case MK:                                                                                                         \
+        hipLaunchKernelGGL((PIGS_BWD_KERNEL<C, MK>), grid, block, 0, stream, pv, sv, g[0], g[1], g[2], g[3],         \
+                           rz_of<float, MK>(a, true));                                                               \
+        done = true;                                                                                                 \
         break;
-#else
-#define PIGS_CASE(MK)                                                                                             \
-    case MK:                                                                                                      \
-        hipLaunchKernelGGL((tile_backward_kernel<C, MK>), grid, block, 0, stream, pv, sv, g[0], g[1], g[2], g[3], rz); \
-        break;
-#endif
-    if (mask == ORDG) {
-        if (!tz) return PIGS_ERR_INVALID;
-#if PIGS_BWD_BLOCK
-        hipLaunchKernelGGL((block_backward_kernel<C, ORDG>), bgrid, block, 0, stream, pv, sv, g[0], g[1], g[2], g[3], *tz);
-#else
-        hipLaunchKernelGGL((tile_backward_kernel<C, ORDG>), grid, block, 0, stream, pv, sv, g[0], g[1], g[2], g[3], *tz);
-#endif
-    } else if (mask == ORDC) {
-        if (!cz) return PIGS_ERR_INVALID;
-        if constexpr (C == 2) {
-#if PIGS_BWD_BLOCK
-            hipLaunchKernelGGL((block_backward_kernel<C, ORDC>), bgrid, block, 0, stream, pv, sv, g[0], g[1], g[2], g[3], *cz);
-#else
-            hipLaunchKernelGGL((tile_backward_kernel<C, ORDC>), grid, block, 0, stream, pv, sv, g[0], g[1], g[2], g[3], *cz);
-#endif
-        } else {
-            return PIGS_ERR_UNSUPPORTED;
+    switch (mask) {
+        PIGS_CASE(1) PIGS_CASE(2) PIGS_CASE(4) PIGS_CASE(8) PIGS_CASE(7) PIGS_CASE(15) PIGS_CASE(16) PIGS_CASE(19)
+        PIGS_CASE(ORDR) PIGS_CASE(ORDG)
+        default: break;
+    }
+    if constexpr (C == 2) {      // as in plan_forward_c
+        switch (mask) {
+            PIGS_CASE(ORDV) PIGS_CASE(ORDC) PIGS_CASE(ORDN)
+            default: break;
         }
-    } else if (mask == ORDV) {
-        if constexpr (C == 2) {
-#if PIGS_BWD_BLOCK
-            hipLaunchKernelGGL((block_backward_kernel<C, ORDV>), bgrid, block, 0, stream, pv, sv, g[0], g[1], g[2], g[3], rz);
-#else
-            hipLaunchKernelGGL((tile_backward_kernel<C, ORDV>), grid, block, 0, stream, pv, sv, g[0], g[1], g[2], g[3], rz);
-#endif
-        } else {
-            return PIGS_ERR_UNSUPPORTED;
-        }
-    } else if (mask == ORDN) {
-        if (!vz) return PIGS_ERR_INVALID;
-        if constexpr (C == 2) {
-#if PIGS_BWD_BLOCK
-            hipLaunchKernelGGL((block_backward_kernel<C, ORDN>), bgrid, block, 0, stream, pv, sv, g[0], g[1], g[2], g[3], *vz);
-#else
-            hipLaunchKernelGGL((tile_backward_kernel<C, ORDN>), grid, block, 0, stream, pv, sv, g[0], g[1], g[2], g[3], *vz);
-#endif
-        } else {
-            return PIGS_ERR_UNSUPPORTED;
-        }
-    } else switch (mask) {
-        PIGS_CASE(1) PIGS_CASE(2) PIGS_CASE(4) PIGS_CASE(8) PIGS_CASE(7) PIGS_CASE(15) PIGS_CASE(16) PIGS_CASE(19) PIGS_CASE(32)
-        default: return PIGS_ERR_UNSUPPORTED;
     }
 #undef PIGS_CASE
-    hipLaunchKernelGGL((plan_unpermute_kernel<C>), dim3((pv.N + 255) / 256), dim3(256), 0, stream, pv, gm, gc, gv);
+#undef PIGS_BWD_KERNEL
+    if (!done) return PIGS_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL((plan_unpermute_kernel<C>), dim3((pv.N + 255) / 256), dim3(256), 0, stream, pv, (float*)a.g_means,
+                       (float*)a.g_conics, (float*)a.g_values);
     return launch_status();
 }
 
-static Terms<float> terms_of(const PigsResidualTerms* t, const void* target, const void* aux) {
-    return t ? make_terms<float>(*t, target, aux) : Terms<float>{};
-}
-
-static Resid<float> resid_of(const double* r, const void* target) {
-    Resid<float> rz{};
-    if (r) { rz.a0 = (float)r[0]; rz.a1[0] = (float)r[1]; rz.a1[1] = (float)r[2]; rz.aL = (float)r[3]; }
-    rz.target = (const float*)target;
-    return rz;
-}
-
-int plan_forward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, int64_t N, int64_t M, int c,
-                 float q_max, int mask, void* const* out, hipStream_t stream, const double* resid, const void* target,
-                 const PigsResidualTerms* terms, void* aux, const PigsResidualCoupling* coupling,
-                 const PigsVorticityResidual* vort) {
-    if (!plan_supported(N, M, c)) return PIGS_ERR_UNSUPPORTED;
-    const PlanLayout p = make_plan_layout(N, M, c);
-    const SamplesLayout s = make_samples_layout(M);
+int plan_forward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, float q_max, const SampleArgs& a,
+                 hipStream_t stream) {
+    if (!plan_supported(a.N, a.M, a.c)) return PIGS_ERR_UNSUPPORTED;
+    const PlanLayout p = make_plan_layout(a.N, a.M, a.c);
+    const SamplesLayout s = make_samples_layout(a.M);
     if (!ws || ws_bytes < p.total_bytes || !sws || sws_bytes < s.total_bytes) return PIGS_ERR_WORKSPACE;
     const PlanView pv = make_view(p, ws, q_max);
     const SamplesView sv = make_samples_view(s, sws);
     float* o[4];
-    for (int k = 0; k < 4; ++k) o[k] = mask_uses_slot(mask, k) ? (float*)out[k] : nullptr;
-    const int cm = covering_mask_of(mask);
-    if (c != 1 && c != 2) return PIGS_ERR_UNSUPPORTED;
+    for (int k = 0; k < 4; ++k) o[k] = mask_uses_slot(a.orders_mask, k) ? (float*)a.out[k] : nullptr;
+    const int cm = covering_mask_of(a.orders_mask);
+    if (a.c != 1 && a.c != 2) return PIGS_ERR_UNSUPPORTED;
     DeferredLists d{};
     ListArgs la{};
     const bool first = defer_take(ws, d);
     if (first) la = make_list_args(p, s, ws, sws, d.q_f, d.q_wide);
-    const Terms<float> tz = terms_of(terms, target, aux);
-    const Terms<float>* tp = terms ? &tz : nullptr;
-    const Coupled<float> cz = coupling ? make_coupled<float>(*coupling, target) : Coupled<float>{};
-    const Coupled<float>* cp = coupling ? &cz : nullptr;
-    // the vorticity residual: `target` is the previous level's rows [M][7]
-    const VortResid<float> vz = vort ? make_vort_resid<float>(*vort, target, aux) : VortResid<float>{};
-    const VortResid<float>* vp = vort ? &vz : nullptr;
-    const int rc = c == 1 ? plan_forward_c<1>(pv, sv, cm, o, stream, resid_of(resid, target), first ? &la : nullptr, tp, cp, vp)
-                          : plan_forward_c<2>(pv, sv, cm, o, stream, resid_of(resid, target), first ? &la : nullptr, tp, cp, vp);
+    const int rc = a.c == 1 ? plan_forward_c<1>(pv, sv, cm, o, a, stream, first ? &la : nullptr)
+                            : plan_forward_c<2>(pv, sv, cm, o, a, stream, first ? &la : nullptr);
     if (first && rc == PIGS_OK) plan_note_points(p, ws, stream);
     return rc;
 }
 
-int plan_backward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, int64_t N, int64_t M, int c,
-                  float q_max, int mask, const void* const* gout, void* g_means, void* g_conics, void* g_values,
-                  hipStream_t stream, const double* resid, const PigsResidualTerms* terms, const void* aux,
-                  const PigsResidualCoupling* coupling, const PigsVorticityResidual* vort) {
-    if (!plan_supported(N, M, c)) return PIGS_ERR_UNSUPPORTED;
-    const PlanLayout p = make_plan_layout(N, M, c);
-    const SamplesLayout s = make_samples_layout(M);
+int plan_backward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, float q_max, const SampleArgs& a,
+                  hipStream_t stream) {
+    if (!plan_supported(a.N, a.M, a.c)) return PIGS_ERR_UNSUPPORTED;
+    const PlanLayout p = make_plan_layout(a.N, a.M, a.c);
+    const SamplesLayout s = make_samples_layout(a.M);
     if (!ws || ws_bytes < p.total_bytes || !sws || sws_bytes < s.total_bytes) return PIGS_ERR_WORKSPACE;
     const PlanView pv = make_view(p, ws, q_max);
     const SamplesView sv = make_samples_view(s, sws);
@@ -3698,17 +3646,11 @@ int plan_backward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, 
         }
     }
     const float* g[4];
-    for (int k = 0; k < 4; ++k) g[k] = mask_uses_slot(mask, k) ? (const float*)gout[k] : nullptr;
-    const int cm = covering_mask_of(mask);
-    const Terms<float> tz = terms_of(terms, nullptr, aux);
-    const Terms<float>* tp = terms ? &tz : nullptr;
-    const Coupled<float> cz = coupling ? make_coupled<float>(*coupling, nullptr) : Coupled<float>{};
-    const Coupled<float>* cp = coupling ? &cz : nullptr;
-    const VortResid<float> vz = vort ? make_vort_resid<float>(*vort, nullptr, aux) : VortResid<float>{};
-    const VortResid<float>* vp = vort ? &vz : nullptr;
-    switch (c) {
-        case 1: return plan_backward_c<1>(pv, sv, cm, g, (float*)g_means, (float*)g_conics, (float*)g_values, stream, resid_of(resid, nullptr), tp, cp, vp);
-        case 2: return plan_backward_c<2>(pv, sv, cm, g, (float*)g_means, (float*)g_conics, (float*)g_values, stream, resid_of(resid, nullptr), tp, cp, vp);
+    for (int k = 0; k < 4; ++k) g[k] = mask_uses_slot(a.orders_mask, k) ? (const float*)a.gout[k] : nullptr;
+    const int cm = covering_mask_of(a.orders_mask);
+    switch (a.c) {
+        case 1: return plan_backward_c<1>(pv, sv, cm, g, a, stream);
+        case 2: return plan_backward_c<2>(pv, sv, cm, g, a, stream);
     }
     return PIGS_ERR_UNSUPPORTED;
 }

@@ -32,6 +32,7 @@
 #include <sstream>
 #include <string>
 #include <tuple>
+#include <variant>
 #include <vector>
 
 #include "../../include/pigs_amd.h"
@@ -423,8 +424,11 @@ std::array<at::Tensor, 3> periodic_images_apply(const at::Tensor& means, const a
 }
 
 // ---------------------------------------------------------------------------------------------
-// residual(): r = a0 u + a1 . grad u + aL lap u - target in one launch (pigs_residual_*); the node owns its
-// inputs and plan like SampleBackward.
+// The fused outputs -- residual() in its three forms, vorticity_terms(), vorticity_residual() -- each one launch
+// forward and one backward (pigs_residual_*, pigs_residual_terms_*, pigs_residual_coupled_*, pigs_vorticity_*,
+// pigs_vorticity_residual_*).  ONE node and ONE apply function serve them, told apart by a FusedOp; the node owns its
+// inputs and plan like SampleBackward, plus the operator's coefficient fields and, where the backward reads one, the
+// record `aux` the forward left.
 // ---------------------------------------------------------------------------------------------
 struct PlanPtrs {
     void *pw, *sw;
@@ -437,90 +441,9 @@ PlanPtrs plan_ptrs(Plan* plan, hipStream_t stream) {
             (size_t)plan->samples->workspace.numel()};
 }
 
-struct ResidualBackward : public torch::autograd::Node {
-    at::Tensor means, values, conics, samples;
-    uint32_t versions[4] = {0, 0, 0, 0};
-    double coeffs[4] = {0, 0, 0, 0};
-    bool debug = false, has_target = false;
-    at::ScalarType target_dtype = at::kFloat;
-    std::shared_ptr<Plan> plan;
+using ResidualCoeffs = std::array<double, 4>;      // the linear residual: a0, a1x, a1y, aL
 
-    std::string name() const override { return "PigsResidualBackward"; }
-    void release_variables() override {}
-
-    torch::autograd::variable_list apply(torch::autograd::variable_list&& grads) override {
-        if (means._version() != versions[0] || values._version() != versions[1] || conics._version() != versions[2] ||
-            samples._version() != versions[3])
-            throw std::runtime_error(
-                "one of the tensors handed to GaussianSampler.preprocess() has been modified in place before the "
-                "backward of a residual() output that was computed from it");
-        torch::autograd::variable_list res(has_target ? 4 : 3);
-        if (grads.empty() || !grads[0].defined()) return res;
-        at::AutoGradMode no_grad(false);
-        if (grads[0].requires_grad()) throw std::runtime_error("GaussianSampler.residual() is differentiable once");
-        if (debug && plan && plan->forward_only) throw std::logic_error("a residual() node holds a forward-only plan");
-        const at::Tensor gout = grads[0].contiguous();
-        const int64_t N = means.size(0), d = means.size(1), c = values.size(1), M = samples.size(0);
-        auto gv3 = gradient_views(means, values, conics);
-        at::Tensor g_means = gv3[0], g_values = gv3[1], g_conics = gv3[2];
-        if (N > 0 && M > 0) {
-            c10::DeviceGuard guard(means.device());
-            const hipStream_t stream = current_stream(means);
-            const PlanPtrs pp = plan_ptrs(plan.get(), stream);
-            check(pigs_residual_backward(dtype_code(means), (int)d, (int)c, N, M, ptr(means), ptr(conics), ptr(values), ptr(samples),
-                                         coeffs, ptr(gout), ptr(g_means), ptr(g_conics), ptr(g_values), pp.pw, pp.pb, pp.sw, pp.sb,
-                                         stream),
-                  "pigs_residual_backward");
-        } else {
-            g_means.zero_(); g_values.zero_(); g_conics.zero_();
-        }
-        if (debug) device_sync(means);
-        res[0] = g_means; res[1] = g_values; res[2] = g_conics;
-        if (has_target && task_should_compute_output(3)) res[3] = gout.neg().to(target_dtype);
-        return res;
-    }
-};
-
-at::Tensor residual_apply(const at::Tensor& means, const at::Tensor& values, const at::Tensor& conics, const at::Tensor& samples,
-                          const std::array<double, 4>& coeffs, const c10::optional<at::Tensor>& target, bool debug,
-                          const std::shared_ptr<Plan>& plan) {
-    const int64_t N = means.size(0), d = means.size(1), c = values.size(1), M = samples.size(0);
-    at::Tensor tgt;
-    if (target.has_value()) {
-        at::AutoGradMode no_grad(false);
-        tgt = target->detach().to(means.scalar_type()).contiguous();
-    }
-    at::Tensor out = at::empty({M, c}, means.options());
-    if (M > 0) {
-        c10::DeviceGuard guard(means.device());
-        const hipStream_t stream = current_stream(means);
-        const PlanPtrs pp = plan_ptrs(plan.get(), stream);
-        check(pigs_residual_forward(dtype_code(means), (int)d, (int)c, N, M, ptr(means), ptr(conics), ptr(values), ptr(samples),
-                                    coeffs.data(), ptr(tgt), ptr(out), pp.pw, pp.pb, pp.sw, pp.sb, stream),
-              "pigs_residual_forward");
-    }
-    if (debug) device_sync(means);
-    const bool tgrad = target.has_value() && target->requires_grad();
-    if (at::GradMode::is_enabled() && (means.requires_grad() || values.requires_grad() || conics.requires_grad() || tgrad)) {
-        std::shared_ptr<ResidualBackward> node(new ResidualBackward(), torch::autograd::deleteNode);
-        if (target.has_value()) node->set_next_edges(torch::autograd::collect_next_edges(means, values, conics, *target));
-        else node->set_next_edges(torch::autograd::collect_next_edges(means, values, conics));
-        node->means = means; node->values = values; node->conics = conics; node->samples = samples;
-        node->versions[0] = means._version(); node->versions[1] = values._version();
-        node->versions[2] = conics._version(); node->versions[3] = samples._version();
-        for (int k = 0; k < 4; ++k) node->coeffs[k] = coeffs[k];
-        node->debug = debug; node->plan = plan;
-        node->has_target = target.has_value();
-        if (target.has_value()) node->target_dtype = target->scalar_type();
-        torch::autograd::create_gradient_edge(out, node);
-    }
-    return out;
-}
-
-// ---------------------------------------------------------------------------------------------
-// residual() with per-point coefficients and an advection term (pigs_residual_terms_*): one launch each way; the node
-// owns inputs, plan, coefficient fields and aux (u, grad u of the forward: what the advection term's backward reads).
-// ---------------------------------------------------------------------------------------------
+// the general residual: per-point coefficients and an advection term; aux = (u, grad u) of the forward
 struct TermsHost {
     at::Tensor fields[4];                  // a0 [M], a1 [M, d], aL [M], adv [M]: detached, contiguous, or undefined
     double consts[5] = {0, 0, 0, 0, 0};    // a0, a1x, a1y, aL, adv where the field is undefined
@@ -536,96 +459,7 @@ struct TermsHost {
     }
 };
 
-struct ResidualTermsBackward : public torch::autograd::Node {
-    at::Tensor means, values, conics, samples, aux;
-    uint32_t versions[4] = {0, 0, 0, 0};
-    TermsHost terms;
-    bool debug = false, has_target = false;
-    at::ScalarType target_dtype = at::kFloat;
-    std::shared_ptr<Plan> plan;
-
-    std::string name() const override { return "PigsResidualTermsBackward"; }
-    void release_variables() override {}
-
-    torch::autograd::variable_list apply(torch::autograd::variable_list&& grads) override {
-        if (means._version() != versions[0] || values._version() != versions[1] || conics._version() != versions[2] ||
-            samples._version() != versions[3])
-            throw std::runtime_error(
-                "one of the tensors handed to GaussianSampler.preprocess() has been modified in place before the "
-                "backward of a residual() output that was computed from it");
-        torch::autograd::variable_list res(has_target ? 4 : 3);
-        if (grads.empty() || !grads[0].defined()) return res;
-        at::AutoGradMode no_grad(false);
-        if (grads[0].requires_grad()) throw std::runtime_error("GaussianSampler.residual() is differentiable once");
-        if (debug && plan && plan->forward_only) throw std::logic_error("a residual() node holds a forward-only plan");
-        const at::Tensor gout = grads[0].contiguous();
-        const int64_t N = means.size(0), d = means.size(1), c = values.size(1), M = samples.size(0);
-        auto gv3 = gradient_views(means, values, conics);
-        at::Tensor g_means = gv3[0], g_values = gv3[1], g_conics = gv3[2];
-        if (N > 0 && M > 0) {
-            c10::DeviceGuard guard(means.device());
-            const hipStream_t stream = current_stream(means);
-            const PlanPtrs pp = plan_ptrs(plan.get(), stream);
-            const PigsResidualTerms t = terms.abi();
-            check(pigs_residual_terms_backward(dtype_code(means), (int)d, (int)c, N, M, ptr(means), ptr(conics), ptr(values),
-                                               ptr(samples), &t, ptr(gout), ptr(aux), ptr(g_means), ptr(g_conics), ptr(g_values),
-                                               pp.pw, pp.pb, pp.sw, pp.sb, stream),
-                  "pigs_residual_terms_backward");
-        } else {
-            g_means.zero_(); g_values.zero_(); g_conics.zero_();
-        }
-        if (debug) device_sync(means);
-        res[0] = g_means; res[1] = g_values; res[2] = g_conics;
-        if (has_target && task_should_compute_output(3)) res[3] = gout.neg().to(target_dtype);
-        return res;
-    }
-};
-
-at::Tensor residual_terms_apply(const at::Tensor& means, const at::Tensor& values, const at::Tensor& conics,
-                                const at::Tensor& samples, const TermsHost& terms, const c10::optional<at::Tensor>& target,
-                                bool debug, const std::shared_ptr<Plan>& plan) {
-    const int64_t N = means.size(0), d = means.size(1), c = values.size(1), M = samples.size(0);
-    at::Tensor tgt;
-    if (target.has_value()) {
-        at::AutoGradMode no_grad(false);
-        tgt = target->detach().to(means.scalar_type()).contiguous();
-    }
-    const bool tgrad = target.has_value() && target->requires_grad();
-    const bool differentiable =
-        at::GradMode::is_enabled() && (means.requires_grad() || values.requires_grad() || conics.requires_grad() || tgrad);
-    at::Tensor out = at::empty({M, c}, means.options());
-    at::Tensor aux;      // only when advection is active and a backward can follow
-    if (terms.advects() && differentiable && M > 0) aux = at::empty({M, 1 + d, c}, means.options());
-    if (M > 0) {
-        c10::DeviceGuard guard(means.device());
-        const hipStream_t stream = current_stream(means);
-        const PlanPtrs pp = plan_ptrs(plan.get(), stream);
-        const PigsResidualTerms t = terms.abi();
-        check(pigs_residual_terms_forward(dtype_code(means), (int)d, (int)c, N, M, ptr(means), ptr(conics), ptr(values),
-                                          ptr(samples), &t, ptr(tgt), ptr(out), ptr(aux), pp.pw, pp.pb, pp.sw, pp.sb, stream),
-              "pigs_residual_terms_forward");
-    }
-    if (debug) device_sync(means);
-    if (differentiable) {
-        std::shared_ptr<ResidualTermsBackward> node(new ResidualTermsBackward(), torch::autograd::deleteNode);
-        if (target.has_value()) node->set_next_edges(torch::autograd::collect_next_edges(means, values, conics, *target));
-        else node->set_next_edges(torch::autograd::collect_next_edges(means, values, conics));
-        node->means = means; node->values = values; node->conics = conics; node->samples = samples; node->aux = aux;
-        node->versions[0] = means._version(); node->versions[1] = values._version();
-        node->versions[2] = conics._version(); node->versions[3] = samples._version();
-        node->terms = terms;
-        node->debug = debug; node->plan = plan;
-        node->has_target = target.has_value();
-        if (target.has_value()) node->target_dtype = target->scalar_type();
-        torch::autograd::create_gradient_edge(out, node);
-    }
-    return out;
-}
-
-// ---------------------------------------------------------------------------------------------
-// residual() with coupled channels (pigs_residual_coupled_*): one launch each way; the node owns inputs, plan and
-// coefficient fields.  The residual is linear in the field: nothing of the forward is kept for the backward.
-// ---------------------------------------------------------------------------------------------
+// the coupled residual: linear in the field, nothing of the forward is kept for the backward
 struct CouplingHost {
     at::Tensor fields[3];                  // a0, aL, cw [M]: detached, contiguous, or undefined
     double consts[3] = {0, 0, 1};          // a0, aL, cw where the field is undefined
@@ -640,165 +474,7 @@ struct CouplingHost {
     }
 };
 
-struct ResidualCoupledBackward : public torch::autograd::Node {
-    at::Tensor means, values, conics, samples;
-    uint32_t versions[4] = {0, 0, 0, 0};
-    CouplingHost coupling;
-    bool debug = false, has_target = false;
-    at::ScalarType target_dtype = at::kFloat;
-    std::shared_ptr<Plan> plan;
-
-    std::string name() const override { return "PigsResidualCoupledBackward"; }
-    void release_variables() override {}
-
-    torch::autograd::variable_list apply(torch::autograd::variable_list&& grads) override {
-        if (means._version() != versions[0] || values._version() != versions[1] || conics._version() != versions[2] ||
-            samples._version() != versions[3])
-            throw std::runtime_error(
-                "one of the tensors handed to GaussianSampler.preprocess() has been modified in place before the "
-                "backward of a residual() output that was computed from it");
-        torch::autograd::variable_list res(has_target ? 4 : 3);
-        if (grads.empty() || !grads[0].defined()) return res;
-        at::AutoGradMode no_grad(false);
-        if (grads[0].requires_grad()) throw std::runtime_error("GaussianSampler.residual() is differentiable once");
-        if (debug && plan && plan->forward_only) throw std::logic_error("a residual() node holds a forward-only plan");
-        const at::Tensor gout = grads[0].contiguous();
-        const int64_t N = means.size(0), d = means.size(1), c = values.size(1), M = samples.size(0);
-        auto gv3 = gradient_views(means, values, conics);
-        at::Tensor g_means = gv3[0], g_values = gv3[1], g_conics = gv3[2];
-        if (N > 0 && M > 0) {
-            c10::DeviceGuard guard(means.device());
-            const hipStream_t stream = current_stream(means);
-            const PlanPtrs pp = plan_ptrs(plan.get(), stream);
-            const PigsResidualCoupling t = coupling.abi();
-            check(pigs_residual_coupled_backward(dtype_code(means), (int)d, (int)c, N, M, ptr(means), ptr(conics), ptr(values),
-                                                 ptr(samples), &t, ptr(gout), ptr(g_means), ptr(g_conics), ptr(g_values),
-                                                 pp.pw, pp.pb, pp.sw, pp.sb, stream),
-                  "pigs_residual_coupled_backward");
-        } else {
-            g_means.zero_(); g_values.zero_(); g_conics.zero_();
-        }
-        if (debug) device_sync(means);
-        res[0] = g_means; res[1] = g_values; res[2] = g_conics;
-        if (has_target && task_should_compute_output(3)) res[3] = gout.neg().to(target_dtype);
-        return res;
-    }
-};
-
-at::Tensor residual_coupled_apply(const at::Tensor& means, const at::Tensor& values, const at::Tensor& conics,
-                                  const at::Tensor& samples, const CouplingHost& coupling,
-                                  const c10::optional<at::Tensor>& target, bool debug, const std::shared_ptr<Plan>& plan) {
-    const int64_t N = means.size(0), d = means.size(1), c = values.size(1), M = samples.size(0);
-    at::Tensor tgt;
-    if (target.has_value()) {
-        at::AutoGradMode no_grad(false);
-        tgt = target->detach().to(means.scalar_type()).contiguous();
-    }
-    const bool tgrad = target.has_value() && target->requires_grad();
-    const bool differentiable =
-        at::GradMode::is_enabled() && (means.requires_grad() || values.requires_grad() || conics.requires_grad() || tgrad);
-    at::Tensor out = at::empty({M, c}, means.options());
-    if (M > 0) {
-        c10::DeviceGuard guard(means.device());
-        const hipStream_t stream = current_stream(means);
-        const PlanPtrs pp = plan_ptrs(plan.get(), stream);
-        const PigsResidualCoupling t = coupling.abi();
-        check(pigs_residual_coupled_forward(dtype_code(means), (int)d, (int)c, N, M, ptr(means), ptr(conics), ptr(values),
-                                            ptr(samples), &t, ptr(tgt), ptr(out), pp.pw, pp.pb, pp.sw, pp.sb, stream),
-              "pigs_residual_coupled_forward");
-    }
-    if (debug) device_sync(means);
-    if (differentiable) {
-        std::shared_ptr<ResidualCoupledBackward> node(new ResidualCoupledBackward(), torch::autograd::deleteNode);
-        if (target.has_value()) node->set_next_edges(torch::autograd::collect_next_edges(means, values, conics, *target));
-        else node->set_next_edges(torch::autograd::collect_next_edges(means, values, conics));
-        node->means = means; node->values = values; node->conics = conics; node->samples = samples;
-        node->versions[0] = means._version(); node->versions[1] = values._version();
-        node->versions[2] = conics._version(); node->versions[3] = samples._version();
-        node->coupling = coupling;
-        node->debug = debug; node->plan = plan;
-        node->has_target = target.has_value();
-        if (target.has_value()) node->target_dtype = target->scalar_type();
-        torch::autograd::create_gradient_edge(out, node);
-    }
-    return out;
-}
-
-// ---------------------------------------------------------------------------------------------
-// vorticity_terms(): (u_x, u_y, div, w, w_x, w_y, lap w) as [M, 7] in one launch (pigs_vorticity_*); the node owns its
-// inputs and plan like ResidualBackward.
-// ---------------------------------------------------------------------------------------------
-constexpr int64_t VORTICITY_COLUMNS = 7;
-
-struct VorticityBackward : public torch::autograd::Node {
-    at::Tensor means, values, conics, samples;
-    uint32_t versions[4] = {0, 0, 0, 0};
-    bool debug = false;
-    std::shared_ptr<Plan> plan;
-
-    std::string name() const override { return "PigsVorticityBackward"; }
-    void release_variables() override {}
-
-    torch::autograd::variable_list apply(torch::autograd::variable_list&& grads) override {
-        if (means._version() != versions[0] || values._version() != versions[1] || conics._version() != versions[2] ||
-            samples._version() != versions[3])
-            throw std::runtime_error(
-                "one of the tensors handed to GaussianSampler.preprocess() has been modified in place before the "
-                "backward of a vorticity_terms() output that was computed from it");
-        torch::autograd::variable_list res(3);
-        if (grads.empty() || !grads[0].defined()) return res;
-        at::AutoGradMode no_grad(false);
-        if (grads[0].requires_grad()) throw std::runtime_error("GaussianSampler.vorticity_terms() is differentiable once");
-        if (debug && plan && plan->forward_only) throw std::logic_error("a vorticity_terms() node holds a forward-only plan");
-        const at::Tensor gout = grads[0].contiguous();
-        const int64_t N = means.size(0), M = samples.size(0);
-        auto gv3 = gradient_views(means, values, conics);
-        at::Tensor g_means = gv3[0], g_values = gv3[1], g_conics = gv3[2];
-        if (N > 0 && M > 0) {
-            c10::DeviceGuard guard(means.device());
-            const hipStream_t stream = current_stream(means);
-            const PlanPtrs pp = plan_ptrs(plan.get(), stream);
-            check(pigs_vorticity_backward(dtype_code(means), N, M, ptr(means), ptr(conics), ptr(values), ptr(samples), ptr(gout),
-                                          ptr(g_means), ptr(g_conics), ptr(g_values), pp.pw, pp.pb, pp.sw, pp.sb, stream),
-                  "pigs_vorticity_backward");
-        } else {
-            g_means.zero_(); g_values.zero_(); g_conics.zero_();
-        }
-        if (debug) device_sync(means);
-        res[0] = g_means; res[1] = g_values; res[2] = g_conics;
-        return res;
-    }
-};
-
-at::Tensor vorticity_apply(const at::Tensor& means, const at::Tensor& values, const at::Tensor& conics, const at::Tensor& samples,
-                           bool debug, const std::shared_ptr<Plan>& plan) {
-    const int64_t N = means.size(0), M = samples.size(0);
-    at::Tensor out = at::empty({M, VORTICITY_COLUMNS}, means.options());
-    if (M > 0) {
-        c10::DeviceGuard guard(means.device());
-        const hipStream_t stream = current_stream(means);
-        const PlanPtrs pp = plan_ptrs(plan.get(), stream);
-        check(pigs_vorticity_forward(dtype_code(means), N, M, ptr(means), ptr(conics), ptr(values), ptr(samples), ptr(out), pp.pw,
-                                     pp.pb, pp.sw, pp.sb, stream),
-              "pigs_vorticity_forward");
-    }
-    if (debug) device_sync(means);
-    if (at::GradMode::is_enabled() && (means.requires_grad() || values.requires_grad() || conics.requires_grad())) {
-        std::shared_ptr<VorticityBackward> node(new VorticityBackward(), torch::autograd::deleteNode);
-        node->set_next_edges(torch::autograd::collect_next_edges(means, values, conics));
-        node->means = means; node->values = values; node->conics = conics; node->samples = samples;
-        node->versions[0] = means._version(); node->versions[1] = values._version();
-        node->versions[2] = conics._version(); node->versions[3] = samples._version();
-        node->debug = debug; node->plan = plan;
-        torch::autograd::create_gradient_edge(out, node);
-    }
-    return out;
-}
-
-// ---------------------------------------------------------------------------------------------
-// vorticity_residual(): (div_b, r) of the Navier-Stokes residual as [M, 2] in one launch (pigs_vorticity_residual_*); the
-// node owns inputs, plan, tau, prev and aux (the blended u and grad w of the forward: what the backward reads).
-// ---------------------------------------------------------------------------------------------
+// the vorticity residual; aux = the blended u and grad w of the forward
 struct VorticityResidualHost {
     double nu = 0, dt = 0, time_term = 1, tau = 1;      // tau where the field is undefined
     at::Tensor tau_field;                               // [M, 1]: detached, contiguous, or undefined
@@ -810,80 +486,191 @@ struct VorticityResidualHost {
     }
 };
 
-struct VorticityResidualBackward : public torch::autograd::Node {
+using FusedParams = std::variant<std::monostate, ResidualCoeffs, TermsHost, CouplingHost, VorticityResidualHost>;
+
+// what one C call of a fused output receives
+struct FusedLaunch {
+    int dtype, d, c;
+    int64_t N, M;
+    void *means, *conics, *values, *samples;
+    void *side, *out;                       // forward: the target (or the previous level) and the output
+    void* gout;                             // backward: the incoming gradient
+    void* aux;
+    void *g_means, *g_conics, *g_values;
+    PlanPtrs pp;
+    hipStream_t stream;
+};
+
+struct FusedOp {
+    const char *label, *node_name;          // "residual()" in messages; node->name()
+    const char *forward_name, *backward_name;
+    int64_t width;                          // columns of the output; 0: the channels
+    bool has_target;                        // `side` is a target: a fourth edge, its gradient is -gout
+    // shape of the record the backward reads (empty: these parameters need none); null: the operator keeps none
+    std::vector<int64_t> (*aux_shape)(const FusedParams&, int64_t M, int64_t d, int64_t c);
+    int (*forward)(const FusedParams&, const FusedLaunch&);
+    int (*backward)(const FusedParams&, const FusedLaunch&);
+};
+
+#define PIGS_HEAD l.dtype, l.N, l.M, l.means, l.conics, l.values, l.samples
+#define PIGS_HEAD_DC l.dtype, l.d, l.c, l.N, l.M, l.means, l.conics, l.values, l.samples
+#define PIGS_GRADS l.g_means, l.g_conics, l.g_values
+#define PIGS_TAIL l.pp.pw, l.pp.pb, l.pp.sw, l.pp.sb, l.stream
+const FusedOp RESIDUAL{
+    "residual()", "PigsResidualBackward", "pigs_residual_forward", "pigs_residual_backward", 0, true, nullptr,
+    [](const FusedParams& p, const FusedLaunch& l) {
+        return pigs_residual_forward(PIGS_HEAD_DC, std::get<ResidualCoeffs>(p).data(), l.side, l.out, PIGS_TAIL);
+    },
+    [](const FusedParams& p, const FusedLaunch& l) {
+        return pigs_residual_backward(PIGS_HEAD_DC, std::get<ResidualCoeffs>(p).data(), l.gout, PIGS_GRADS, PIGS_TAIL);
+    }};
+const FusedOp RESIDUAL_TERMS{
+    "residual()", "PigsResidualTermsBackward", "pigs_residual_terms_forward", "pigs_residual_terms_backward", 0, true,
+    [](const FusedParams& p, int64_t M, int64_t d, int64_t c) {      // only when the advection term is active
+        return std::get<TermsHost>(p).advects() ? std::vector<int64_t>{M, 1 + d, c} : std::vector<int64_t>{};
+    },
+    [](const FusedParams& p, const FusedLaunch& l) {
+        const PigsResidualTerms t = std::get<TermsHost>(p).abi();
+        return pigs_residual_terms_forward(PIGS_HEAD_DC, &t, l.side, l.out, l.aux, PIGS_TAIL);
+    },
+    [](const FusedParams& p, const FusedLaunch& l) {
+        const PigsResidualTerms t = std::get<TermsHost>(p).abi();
+        return pigs_residual_terms_backward(PIGS_HEAD_DC, &t, l.gout, l.aux, PIGS_GRADS, PIGS_TAIL);
+    }};
+const FusedOp RESIDUAL_COUPLED{
+    "residual()", "PigsResidualCoupledBackward", "pigs_residual_coupled_forward", "pigs_residual_coupled_backward", 0, true,
+    nullptr,
+    [](const FusedParams& p, const FusedLaunch& l) {
+        const PigsResidualCoupling t = std::get<CouplingHost>(p).abi();
+        return pigs_residual_coupled_forward(PIGS_HEAD_DC, &t, l.side, l.out, PIGS_TAIL);
+    },
+    [](const FusedParams& p, const FusedLaunch& l) {
+        const PigsResidualCoupling t = std::get<CouplingHost>(p).abi();
+        return pigs_residual_coupled_backward(PIGS_HEAD_DC, &t, l.gout, PIGS_GRADS, PIGS_TAIL);
+    }};
+// (u_x, u_y, div, w, w_x, w_y, lap w) as [M, 7]
+const FusedOp VORTICITY{
+    "vorticity_terms()", "PigsVorticityBackward", "pigs_vorticity_forward", "pigs_vorticity_backward", 7, false, nullptr,
+    [](const FusedParams&, const FusedLaunch& l) { return pigs_vorticity_forward(PIGS_HEAD, l.out, PIGS_TAIL); },
+    [](const FusedParams&, const FusedLaunch& l) { return pigs_vorticity_backward(PIGS_HEAD, l.gout, PIGS_GRADS, PIGS_TAIL); }};
+// (div_b, r) of the Navier-Stokes residual as [M, 2]; `side` is the previous level's vorticity terms, a constant
+const FusedOp VORTICITY_RESIDUAL{
+    "vorticity_residual()", "PigsVorticityResidualBackward", "pigs_vorticity_residual_forward",
+    "pigs_vorticity_residual_backward", 2, false,
+    [](const FusedParams&, int64_t M, int64_t, int64_t) { return std::vector<int64_t>{M, 4}; },
+    [](const FusedParams& p, const FusedLaunch& l) {
+        const PigsVorticityResidual t = std::get<VorticityResidualHost>(p).abi();
+        return pigs_vorticity_residual_forward(PIGS_HEAD, &t, l.side, l.out, l.aux, PIGS_TAIL);
+    },
+    [](const FusedParams& p, const FusedLaunch& l) {
+        const PigsVorticityResidual t = std::get<VorticityResidualHost>(p).abi();
+        return pigs_vorticity_residual_backward(PIGS_HEAD, &t, l.gout, l.aux, PIGS_GRADS, PIGS_TAIL);
+    }};
+#undef PIGS_HEAD
+#undef PIGS_HEAD_DC
+#undef PIGS_GRADS
+#undef PIGS_TAIL
+
+FusedLaunch fused_launch_of(const at::Tensor& means, const at::Tensor& values, const at::Tensor& conics,
+                            const at::Tensor& samples, Plan* plan, hipStream_t stream) {
+    FusedLaunch l{};
+    l.dtype = dtype_code(means); l.d = (int)means.size(1); l.c = (int)values.size(1);
+    l.N = means.size(0); l.M = samples.size(0);
+    l.means = ptr(means); l.conics = ptr(conics); l.values = ptr(values); l.samples = ptr(samples);
+    l.pp = plan_ptrs(plan, stream);
+    l.stream = stream;
+    return l;
+}
+
+struct FusedBackward : public torch::autograd::Node {
+    const FusedOp* op = nullptr;
     at::Tensor means, values, conics, samples, prev, aux;
     uint32_t versions[4] = {0, 0, 0, 0};
-    VorticityResidualHost params;
-    bool debug = false;
+    FusedParams params;
+    bool debug = false, has_target = false;
+    at::ScalarType target_dtype = at::kFloat;
     std::shared_ptr<Plan> plan;
 
-    std::string name() const override { return "PigsVorticityResidualBackward"; }
+    std::string name() const override { return op->node_name; }
     void release_variables() override {}
 
     torch::autograd::variable_list apply(torch::autograd::variable_list&& grads) override {
+        const std::string label = op->label;
         if (means._version() != versions[0] || values._version() != versions[1] || conics._version() != versions[2] ||
             samples._version() != versions[3])
             throw std::runtime_error(
                 "one of the tensors handed to GaussianSampler.preprocess() has been modified in place before the "
-                "backward of a vorticity_residual() output that was computed from it");
-        torch::autograd::variable_list res(3);
+                "backward of a " + label + " output that was computed from it");
+        torch::autograd::variable_list res(has_target ? 4 : 3);
         if (grads.empty() || !grads[0].defined()) return res;
         at::AutoGradMode no_grad(false);
-        if (grads[0].requires_grad()) throw std::runtime_error("GaussianSampler.vorticity_residual() is differentiable once");
-        if (debug && plan && plan->forward_only) throw std::logic_error("a vorticity_residual() node holds a forward-only plan");
+        if (grads[0].requires_grad()) throw std::runtime_error("GaussianSampler." + label + " is differentiable once");
+        if (debug && plan && plan->forward_only) throw std::logic_error("a " + label + " node holds a forward-only plan");
         const at::Tensor gout = grads[0].contiguous();
-        const int64_t N = means.size(0), M = samples.size(0);
-        if (!aux.defined() && M > 0)
-            throw std::runtime_error("this vorticity_residual() output was computed without the record its backward needs "
+        const int64_t N = means.size(0), d = means.size(1), c = values.size(1), M = samples.size(0);
+        if (op->aux_shape && !aux.defined() && M > 0 && !op->aux_shape(params, M, d, c).empty())
+            throw std::runtime_error("this " + label + " output was computed without the record its backward needs "
                                      "(no input required grad when it ran)");
         auto gv3 = gradient_views(means, values, conics);
         at::Tensor g_means = gv3[0], g_values = gv3[1], g_conics = gv3[2];
         if (N > 0 && M > 0) {
             c10::DeviceGuard guard(means.device());
             const hipStream_t stream = current_stream(means);
-            const PlanPtrs pp = plan_ptrs(plan.get(), stream);
-            const PigsVorticityResidual t = params.abi();
-            check(pigs_vorticity_residual_backward(dtype_code(means), N, M, ptr(means), ptr(conics), ptr(values), ptr(samples), &t,
-                                                   ptr(gout), ptr(aux), ptr(g_means), ptr(g_conics), ptr(g_values), pp.pw, pp.pb,
-                                                   pp.sw, pp.sb, stream),
-                  "pigs_vorticity_residual_backward");
+            FusedLaunch l = fused_launch_of(means, values, conics, samples, plan.get(), stream);
+            l.gout = ptr(gout); l.aux = ptr(aux);
+            l.g_means = ptr(g_means); l.g_conics = ptr(g_conics); l.g_values = ptr(g_values);
+            check(op->backward(params, l), op->backward_name);
         } else {
             g_means.zero_(); g_values.zero_(); g_conics.zero_();
         }
         if (debug) device_sync(means);
         res[0] = g_means; res[1] = g_values; res[2] = g_conics;
+        if (has_target && task_should_compute_output(3)) res[3] = gout.neg().to(target_dtype);
         return res;
     }
 };
 
-at::Tensor vorticity_residual_apply(const at::Tensor& means, const at::Tensor& values, const at::Tensor& conics,
-                                    const at::Tensor& samples, const VorticityResidualHost& params, const at::Tensor& prev,
-                                    bool debug, const std::shared_ptr<Plan>& plan) {
-    const int64_t N = means.size(0), M = samples.size(0);
-    const bool differentiable =
-        at::GradMode::is_enabled() && (means.requires_grad() || values.requires_grad() || conics.requires_grad());
-    at::Tensor out = at::empty({M, 2}, means.options());
+// `side`: the target of a residual (any dtype; may require grad) or the previous level of the vorticity residual (a
+// constant, already in the means' dtype and contiguous), or nothing
+at::Tensor fused_apply(const FusedOp& op, const at::Tensor& means, const at::Tensor& values, const at::Tensor& conics,
+                       const at::Tensor& samples, const FusedParams& params, const c10::optional<at::Tensor>& side, bool debug,
+                       const std::shared_ptr<Plan>& plan) {
+    const int64_t d = means.size(1), c = values.size(1), M = samples.size(0);
+    const bool has_target = op.has_target && side.has_value();
+    at::Tensor side_in = side.has_value() ? *side : at::Tensor();
+    if (has_target) {
+        at::AutoGradMode no_grad(false);
+        side_in = side->detach().to(means.scalar_type()).contiguous();
+    }
+    const bool differentiable = at::GradMode::is_enabled() && (means.requires_grad() || values.requires_grad() ||
+                                                               conics.requires_grad() || (has_target && side->requires_grad()));
+    at::Tensor out = at::empty({M, op.width ? op.width : c}, means.options());
     at::Tensor aux;      // only when a backward can follow
-    if (differentiable && M > 0) aux = at::empty({M, 4}, means.options());
+    if (op.aux_shape && differentiable && M > 0) {
+        const std::vector<int64_t> shape = op.aux_shape(params, M, d, c);
+        if (!shape.empty()) aux = at::empty(shape, means.options());
+    }
     if (M > 0) {
         c10::DeviceGuard guard(means.device());
         const hipStream_t stream = current_stream(means);
-        const PlanPtrs pp = plan_ptrs(plan.get(), stream);
-        const PigsVorticityResidual t = params.abi();
-        check(pigs_vorticity_residual_forward(dtype_code(means), N, M, ptr(means), ptr(conics), ptr(values), ptr(samples), &t,
-                                              ptr(prev), ptr(out), ptr(aux), pp.pw, pp.pb, pp.sw, pp.sb, stream),
-              "pigs_vorticity_residual_forward");
+        FusedLaunch l = fused_launch_of(means, values, conics, samples, plan.get(), stream);
+        l.side = ptr(side_in); l.out = ptr(out); l.aux = ptr(aux);
+        check(op.forward(params, l), op.forward_name);
     }
     if (debug) device_sync(means);
     if (differentiable) {
-        std::shared_ptr<VorticityResidualBackward> node(new VorticityResidualBackward(), torch::autograd::deleteNode);
-        node->set_next_edges(torch::autograd::collect_next_edges(means, values, conics));
-        node->means = means; node->values = values; node->conics = conics; node->samples = samples;
-        node->prev = prev; node->aux = aux;
+        std::shared_ptr<FusedBackward> node(new FusedBackward(), torch::autograd::deleteNode);
+        if (has_target) node->set_next_edges(torch::autograd::collect_next_edges(means, values, conics, *side));
+        else node->set_next_edges(torch::autograd::collect_next_edges(means, values, conics));
+        node->op = &op;
+        node->means = means; node->values = values; node->conics = conics; node->samples = samples; node->aux = aux;
+        if (!op.has_target) node->prev = side_in;
         node->versions[0] = means._version(); node->versions[1] = values._version();
         node->versions[2] = conics._version(); node->versions[3] = samples._version();
         node->params = params;
         node->debug = debug; node->plan = plan;
+        node->has_target = has_target;
+        if (has_target) node->target_dtype = side->scalar_type();
         torch::autograd::create_gradient_edge(out, node);
     }
     return out;
@@ -1319,7 +1106,7 @@ struct Core {
 
     at::Tensor residual(const std::array<double, 4>& coeffs, const c10::optional<at::Tensor>& target) {
         require_inputs();
-        return residual_apply(means, values, conics, samples, coeffs, target, debug, plan_for(0, target));
+        return fused_apply(RESIDUAL, means, values, conics, samples, coeffs, target, debug, plan_for(0, target));
     }
 
     // fields: a0, a1, aL, adv as validated, detached, contiguous tensors (or None); consts: a0, a1x, a1y, aL, adv;
@@ -1332,7 +1119,7 @@ struct Core {
             if (fields[k].has_value()) t.fields[k] = *fields[k];
         for (int k = 0; k < 5; ++k) t.consts[k] = consts[k];
         for (int k = 0; k < 8; ++k) t.by[k] = advect_by[k];
-        return residual_terms_apply(means, values, conics, samples, t, target, debug, plan_for(0, target));
+        return fused_apply(RESIDUAL_TERMS, means, values, conics, samples, t, target, debug, plan_for(0, target));
     }
 
     // fields: a0, aL, cw as validated, detached, contiguous tensors (or None); consts: the same three where no field;
@@ -1347,7 +1134,7 @@ struct Core {
             t.consts[k] = consts[k];
         }
         for (int k = 0; k < 16; ++k) { t.q0[k] = couple0[k]; t.qL[k] = couple_lap[k]; }
-        return residual_coupled_apply(means, values, conics, samples, t, target, debug, plan_for(0, target));
+        return fused_apply(RESIDUAL_COUPLED, means, values, conics, samples, t, target, debug, plan_for(0, target));
     }
 
     // (u_x, u_y, div, w, w_x, w_y, lap w) [M, 7]; on the order-3 plan where there is one
@@ -1358,7 +1145,7 @@ struct Core {
                                                     std::to_string(means.size(1)) + ", c = " + std::to_string(values.size(1)));
         // (a result computed where no backward could follow is not handed to a later differentiable call)
         if (!vorticity.defined() || (needs_backward() && !vorticity.requires_grad()))
-            vorticity = vorticity_apply(means, values, conics, samples, debug, plan_for(8));
+            vorticity = fused_apply(VORTICITY, means, values, conics, samples, {}, c10::nullopt, debug, plan_for(8));
         return vorticity;
     }
 
@@ -1370,8 +1157,7 @@ struct Core {
         VorticityResidualHost t;
         t.nu = nu; t.dt = dt; t.time_term = time_term; t.tau = tau;
         if (tau_field.has_value()) t.tau_field = *tau_field;
-        return vorticity_residual_apply(means, values, conics, samples, t, prev.has_value() ? *prev : at::Tensor(), debug,
-                                        plan_for(8));
+        return fused_apply(VORTICITY_RESIDUAL, means, values, conics, samples, t, prev, debug, plan_for(8));
     }
 
     void preprocess_aggregate(int64_t cap) {

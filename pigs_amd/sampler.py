@@ -390,72 +390,120 @@ def backward_raw(means, values, conics, samples, gouts, mask, plan=None):
     return g_means, g_values, g_conics
 
 
-def _residual_call(backward, means, values, conics, samples, coeffs, plan, target=None, gout=None):
-    """pigs_residual_forward / _backward on contiguous device tensors (through the plan when given)."""
+class _FusedOp:
+    """What tells the fused outputs -- residual() in its three forms, vorticity_terms(), vorticity_residual() -- apart
+    between the Python call and their pair of C entry points: ``label`` names the call in messages, ``entry`` the pair
+    (``<entry>_forward`` / ``<entry>_backward``), ``width`` the output's columns (None: the channels), ``dims`` whether
+    the entry points take d and c, ``has_params`` a coefficient block (an object with ``struct()``), ``has_side`` the
+    forward's constant input (a residual's target, the previous level of the vorticity residual), ``has_target`` that
+    this input is a target (differentiable: its gradient is ``-gout``), ``aux_shape`` the record that the forward
+    leaves for the backward, a function of (params, M, d, c) that returns None where these parameters need none."""
+
+    def __init__(self, label, entry, width=None, dims=True, has_params=True, has_side=True, has_target=True, aux_shape=None):
+        self.label, self.width, self.dims = label, width, dims
+        self.forward_name, self.backward_name = entry + "_forward", entry + "_backward"
+        self.has_params, self.has_side, self.has_target, self.aux_shape = has_params, has_side, has_target, aux_shape
+
+
+def _fused_call(op, backward, means, values, conics, samples, params, plan, side=None, gout=None, aux=None):
+    """The forward or backward entry point of the fused output ``op`` on contiguous device tensors (through the plan
+    when given).  Returns the output, or (g_means, g_values, g_conics)."""
     lib = _lib.load()
     N, d = means.shape
     c = values.shape[1]
     M = samples.shape[0]
-    cf = (ctypes.c_double * 4)(*coeffs)
     if backward and plan is not None and M > 0 and getattr(plan, "forward_only", False):
         plan = plan.full_for_backward(means, values, conics, samples)
     pw = (_ptr(plan.workspace), plan.workspace.numel(), _ptr(plan.samples.workspace), plan.samples.workspace.numel()) \
         if plan is not None else (ctypes.c_void_p(0), 0, ctypes.c_void_p(0), 0)
+    args = [_DTYPES[means.dtype], d, c, N, M] if op.dims else [_DTYPES[means.dtype], N, M]
+    args += [_ptr(means), _ptr(conics), _ptr(values), _ptr(samples)]
+    if op.has_params:
+        args.append(params.struct())
     with _on_device(means.device):
         stream = _stream(means.device)
         if plan is not None and hasattr(plan, "note_stream"):
             plan.note_stream(stream.value)
         if not backward:
-            out = torch.empty((M, c), dtype=means.dtype, device=means.device)
+            out = torch.empty((M, c if op.width is None else op.width), dtype=means.dtype, device=means.device)
             if M > 0:
-                rc = lib.pigs_residual_forward(_DTYPES[means.dtype], d, c, N, M, _ptr(means), _ptr(conics), _ptr(values),
-                                               _ptr(samples), cf, _ptr(target), _ptr(out), *pw, stream)
-                _lib.check(rc, "pigs_residual_forward")
+                if op.has_side:
+                    args.append(_ptr(side))
+                args.append(_ptr(out))
+                if op.aux_shape is not None:
+                    args.append(_ptr(aux))
+                _lib.check(getattr(lib, op.forward_name)(*args, *pw, stream), op.forward_name)
             return out
         g_means, g_values, g_conics = _gradient_views(means, values, conics)
         if N > 0:
             if M > 0:
-                rc = lib.pigs_residual_backward(_DTYPES[means.dtype], d, c, N, M, _ptr(means), _ptr(conics), _ptr(values),
-                                                _ptr(samples), cf, _ptr(gout), _ptr(g_means), _ptr(g_conics), _ptr(g_values),
-                                                *pw, stream)
-                _lib.check(rc, "pigs_residual_backward")
+                args.append(_ptr(gout))
+                if op.aux_shape is not None:
+                    args.append(_ptr(aux))
+                rc = getattr(lib, op.backward_name)(*args, _ptr(g_means), _ptr(g_conics), _ptr(g_values), *pw, stream)
+                _lib.check(rc, op.backward_name)
             else:
                 for g in (g_means, g_values, g_conics):
                     g.zero_()
         return g_means, g_values, g_conics
 
 
-class _ResidualFunction(torch.autograd.Function):
-    """r = a0 u + a1 . grad u + aL lap u - target in one launch; its backward is one launch too.  The node
-    owns its inputs and plan like :class:`_SampleFunction`."""
+class _FusedFunction(torch.autograd.Function):
+    """One fused output in one launch; its backward is one launch too.  The node owns its inputs and plan like
+    :class:`_SampleFunction`, and with them the coefficient block ``params`` (its fields), the constant ``side`` and the
+    record ``aux`` of the forward where the backward reads one.  The subclasses carry their :class:`_FusedOp` alone."""
+    op = None
 
-    @staticmethod
-    def forward(ctx, means, values, conics, samples, target, coeffs, debug, plan):
-        tgt = None if target is None else target.detach().to(means.dtype).contiguous()
-        out = _residual_call(False, means, values, conics, samples, coeffs, plan, target=tgt)
+    @classmethod
+    def forward(cls, ctx, means, values, conics, samples, side, params, debug, plan, want_aux):
+        op = cls.op
+        target_dtype = side.dtype if op.has_target and side is not None else None
+        if target_dtype is not None:
+            side = side.detach().to(means.dtype).contiguous()
+        M = samples.shape[0]
+        shape = op.aux_shape(params, M, means.shape[1], values.shape[1]) if want_aux and M > 0 else None
+        aux = None if shape is None else torch.empty(shape, dtype=means.dtype, device=means.device)
+        out = _fused_call(op, False, means, values, conics, samples, params, plan, side=side, aux=aux)
         if debug:
             torch.cuda.synchronize(means.device)
         ctx.inputs = (means, values, conics, samples)
         ctx.versions = (means._version, values._version, conics._version, samples._version)
-        ctx.coeffs, ctx.debug, ctx.plan = coeffs, debug, plan
-        ctx.target_dtype = None if target is None else target.dtype
+        ctx.params, ctx.aux, ctx.debug, ctx.plan, ctx.target_dtype = params, aux, debug, plan, target_dtype
+        ctx.side = None if op.has_target else side
         return out
 
-    @staticmethod
+    @classmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, gout):
+    def backward(cls, ctx, gout):
+        op = cls.op
         means, values, conics, samples = ctx.inputs
         if (means._version, values._version, conics._version, samples._version) != ctx.versions:
             raise RuntimeError("one of the tensors handed to GaussianSampler.preprocess() has been modified in place "
-                               "before the backward of a residual() output that was computed from it")
+                               f"before the backward of a {op.label} output that was computed from it")
+        M = samples.shape[0]
+        if (op.aux_shape is not None and ctx.aux is None and M > 0
+                and op.aux_shape(ctx.params, M, means.shape[1], values.shape[1]) is not None):
+            raise RuntimeError(f"this {op.label} output was computed without the record its backward needs "
+                               "(no input required grad when it ran)")
         gout = gout.contiguous()
         if ctx.debug:
-            assert ctx.plan is None or not ctx.plan.forward_only, "a residual() node holds a forward-only plan"
-        g_means, g_values, g_conics = _residual_call(True, means, values, conics, samples, ctx.coeffs, ctx.plan, gout=gout)
+            assert ctx.plan is None or not ctx.plan.forward_only, f"a {op.label} node holds a forward-only plan"
+        g_means, g_values, g_conics = _fused_call(op, True, means, values, conics, samples, ctx.params, ctx.plan,
+                                                  gout=gout, aux=ctx.aux)
         if ctx.debug:
             torch.cuda.synchronize(means.device)
         g_target = None if ctx.target_dtype is None or not ctx.needs_input_grad[4] else (-gout).to(ctx.target_dtype)
-        return g_means, g_values, g_conics, None, g_target, None, None, None
+        return g_means, g_values, g_conics, None, g_target, None, None, None, None
+
+
+class ResidualCoeffs:
+    """The coefficients of a linear residual() call: the four floats a0, a1x, a1y, aL."""
+
+    def __init__(self, coeffs):
+        self.coeffs = coeffs
+
+    def struct(self):
+        return (ctypes.c_double * 4)(*self.coeffs)
 
 
 class ResidualTerms:
@@ -484,82 +532,6 @@ class ResidualTerms:
         return t
 
 
-def _residual_terms_call(backward, means, values, conics, samples, terms, plan, target=None, gout=None, aux=None):
-    """pigs_residual_terms_forward / _backward on contiguous device tensors (through the plan when given)."""
-    lib = _lib.load()
-    N, d = means.shape
-    c = values.shape[1]
-    M = samples.shape[0]
-    tz = terms.struct()
-    if backward and plan is not None and M > 0 and getattr(plan, "forward_only", False):
-        plan = plan.full_for_backward(means, values, conics, samples)
-    pw = (_ptr(plan.workspace), plan.workspace.numel(), _ptr(plan.samples.workspace), plan.samples.workspace.numel()) \
-        if plan is not None else (ctypes.c_void_p(0), 0, ctypes.c_void_p(0), 0)
-    with _on_device(means.device):
-        stream = _stream(means.device)
-        if plan is not None and hasattr(plan, "note_stream"):
-            plan.note_stream(stream.value)
-        if not backward:
-            out = torch.empty((M, c), dtype=means.dtype, device=means.device)
-            if M > 0:
-                rc = lib.pigs_residual_terms_forward(_DTYPES[means.dtype], d, c, N, M, _ptr(means), _ptr(conics), _ptr(values),
-                                                     _ptr(samples), ctypes.byref(tz), _ptr(target), _ptr(out), _ptr(aux), *pw,
-                                                     stream)
-                _lib.check(rc, "pigs_residual_terms_forward")
-            return out
-        g_means, g_values, g_conics = _gradient_views(means, values, conics)
-        if N > 0:
-            if M > 0:
-                rc = lib.pigs_residual_terms_backward(_DTYPES[means.dtype], d, c, N, M, _ptr(means), _ptr(conics), _ptr(values),
-                                                      _ptr(samples), ctypes.byref(tz), _ptr(gout), _ptr(aux), _ptr(g_means),
-                                                      _ptr(g_conics), _ptr(g_values), *pw, stream)
-                _lib.check(rc, "pigs_residual_terms_backward")
-            else:
-                for g in (g_means, g_values, g_conics):
-                    g.zero_()
-        return g_means, g_values, g_conics
-
-
-class _ResidualTermsFunction(torch.autograd.Function):
-    """The general residual (per-point coefficients, advection term) in one launch; its backward is one launch too.
-    The node owns its inputs, plan, coefficient fields and ``aux`` (u and grad u of the forward, which the backward
-    of the advection term reads) like :class:`_ResidualFunction`."""
-
-    @staticmethod
-    def forward(ctx, means, values, conics, samples, target, terms, debug, plan, want_aux):
-        tgt = None if target is None else target.detach().to(means.dtype).contiguous()
-        M, d, c = samples.shape[0], means.shape[1], values.shape[1]
-        aux = torch.empty((M, 1 + d, c), dtype=means.dtype, device=means.device) if want_aux and M > 0 else None
-        out = _residual_terms_call(False, means, values, conics, samples, terms, plan, target=tgt, aux=aux)
-        if debug:
-            torch.cuda.synchronize(means.device)
-        ctx.inputs = (means, values, conics, samples)
-        ctx.versions = (means._version, values._version, conics._version, samples._version)
-        ctx.terms, ctx.aux, ctx.debug, ctx.plan = terms, aux, debug, plan
-        ctx.target_dtype = None if target is None else target.dtype
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gout):
-        means, values, conics, samples = ctx.inputs
-        if (means._version, values._version, conics._version, samples._version) != ctx.versions:
-            raise RuntimeError("one of the tensors handed to GaussianSampler.preprocess() has been modified in place "
-                               "before the backward of a residual() output that was computed from it")
-        if ctx.terms.advects and ctx.aux is None and samples.shape[0] > 0:
-            raise RuntimeError("this residual() output was computed without the record its backward needs "
-                               "(no input required grad when it ran)")
-        gout = gout.contiguous()
-        if ctx.debug:
-            assert ctx.plan is None or not ctx.plan.forward_only, "a residual() node holds a forward-only plan"
-        g_means, g_values, g_conics = _residual_terms_call(True, means, values, conics, samples, ctx.terms, ctx.plan,
-                                                           gout=gout, aux=ctx.aux)
-        if ctx.debug:
-            torch.cuda.synchronize(means.device)
-        g_target = None if ctx.target_dtype is None or not ctx.needs_input_grad[4] else (-gout).to(ctx.target_dtype)
-        return g_means, g_values, g_conics, None, g_target, None, None, None, None
-
-
 class ResidualCoupling:
     """The coefficients of a coupled residual() call: a0, aL, cw as floats or detached device fields [M], and the two
     c x c constant matrices (row = output channel, column = input channel)."""
@@ -581,140 +553,6 @@ class ResidualCoupling:
         return t
 
 
-def _residual_coupled_call(backward, means, values, conics, samples, coupling, plan, target=None, gout=None):
-    """pigs_residual_coupled_forward / _backward on contiguous device tensors (through the plan when given)."""
-    lib = _lib.load()
-    N, d = means.shape
-    c = values.shape[1]
-    M = samples.shape[0]
-    cz = coupling.struct()
-    if backward and plan is not None and M > 0 and getattr(plan, "forward_only", False):
-        plan = plan.full_for_backward(means, values, conics, samples)
-    pw = (_ptr(plan.workspace), plan.workspace.numel(), _ptr(plan.samples.workspace), plan.samples.workspace.numel()) \
-        if plan is not None else (ctypes.c_void_p(0), 0, ctypes.c_void_p(0), 0)
-    with _on_device(means.device):
-        stream = _stream(means.device)
-        if plan is not None and hasattr(plan, "note_stream"):
-            plan.note_stream(stream.value)
-        if not backward:
-            out = torch.empty((M, c), dtype=means.dtype, device=means.device)
-            if M > 0:
-                rc = lib.pigs_residual_coupled_forward(_DTYPES[means.dtype], d, c, N, M, _ptr(means), _ptr(conics),
-                                                       _ptr(values), _ptr(samples), ctypes.byref(cz), _ptr(target), _ptr(out),
-                                                       *pw, stream)
-                _lib.check(rc, "pigs_residual_coupled_forward")
-            return out
-        g_means, g_values, g_conics = _gradient_views(means, values, conics)
-        if N > 0:
-            if M > 0:
-                rc = lib.pigs_residual_coupled_backward(_DTYPES[means.dtype], d, c, N, M, _ptr(means), _ptr(conics),
-                                                        _ptr(values), _ptr(samples), ctypes.byref(cz), _ptr(gout),
-                                                        _ptr(g_means), _ptr(g_conics), _ptr(g_values), *pw, stream)
-                _lib.check(rc, "pigs_residual_coupled_backward")
-            else:
-                for g in (g_means, g_values, g_conics):
-                    g.zero_()
-        return g_means, g_values, g_conics
-
-
-class _ResidualCoupledFunction(torch.autograd.Function):
-    """The coupled residual (two constant matrices mix the channels under a per-point weight) in one launch; its
-    backward is one launch too.  The node owns its inputs, plan and coefficient fields like
-    :class:`_ResidualTermsFunction`; the residual is linear in the field, so no record of the forward is kept."""
-
-    @staticmethod
-    def forward(ctx, means, values, conics, samples, target, coupling, debug, plan):
-        tgt = None if target is None else target.detach().to(means.dtype).contiguous()
-        out = _residual_coupled_call(False, means, values, conics, samples, coupling, plan, target=tgt)
-        if debug:
-            torch.cuda.synchronize(means.device)
-        ctx.inputs = (means, values, conics, samples)
-        ctx.versions = (means._version, values._version, conics._version, samples._version)
-        ctx.coupling, ctx.debug, ctx.plan = coupling, debug, plan
-        ctx.target_dtype = None if target is None else target.dtype
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gout):
-        means, values, conics, samples = ctx.inputs
-        if (means._version, values._version, conics._version, samples._version) != ctx.versions:
-            raise RuntimeError("one of the tensors handed to GaussianSampler.preprocess() has been modified in place "
-                               "before the backward of a residual() output that was computed from it")
-        gout = gout.contiguous()
-        if ctx.debug:
-            assert ctx.plan is None or not ctx.plan.forward_only, "a residual() node holds a forward-only plan"
-        g_means, g_values, g_conics = _residual_coupled_call(True, means, values, conics, samples, ctx.coupling, ctx.plan,
-                                                             gout=gout)
-        if ctx.debug:
-            torch.cuda.synchronize(means.device)
-        g_target = None if ctx.target_dtype is None or not ctx.needs_input_grad[4] else (-gout).to(ctx.target_dtype)
-        return g_means, g_values, g_conics, None, g_target, None, None, None
-
-
-def _vorticity_call(backward, means, values, conics, samples, plan, gout=None):
-    """pigs_vorticity_forward / _backward on contiguous device tensors (through the plan when given)."""
-    lib = _lib.load()
-    N, M = means.shape[0], samples.shape[0]
-    ncol = len(VORTICITY_COLUMNS)
-    if backward and plan is not None and M > 0 and getattr(plan, "forward_only", False):
-        plan = plan.full_for_backward(means, values, conics, samples)
-    pw = (_ptr(plan.workspace), plan.workspace.numel(), _ptr(plan.samples.workspace), plan.samples.workspace.numel()) \
-        if plan is not None else (ctypes.c_void_p(0), 0, ctypes.c_void_p(0), 0)
-    with _on_device(means.device):
-        stream = _stream(means.device)
-        if plan is not None and hasattr(plan, "note_stream"):
-            plan.note_stream(stream.value)
-        if not backward:
-            out = torch.empty((M, ncol), dtype=means.dtype, device=means.device)
-            if M > 0:
-                rc = lib.pigs_vorticity_forward(_DTYPES[means.dtype], N, M, _ptr(means), _ptr(conics), _ptr(values),
-                                                _ptr(samples), _ptr(out), *pw, stream)
-                _lib.check(rc, "pigs_vorticity_forward")
-            return out
-        g_means, g_values, g_conics = _gradient_views(means, values, conics)
-        if N > 0:
-            if M > 0:
-                rc = lib.pigs_vorticity_backward(_DTYPES[means.dtype], N, M, _ptr(means), _ptr(conics), _ptr(values),
-                                                 _ptr(samples), _ptr(gout), _ptr(g_means), _ptr(g_conics), _ptr(g_values),
-                                                 *pw, stream)
-                _lib.check(rc, "pigs_vorticity_backward")
-            else:
-                for g in (g_means, g_values, g_conics):
-                    g.zero_()
-        return g_means, g_values, g_conics
-
-
-class _VorticityFunction(torch.autograd.Function):
-    """(u_x, u_y, div, w, w_x, w_y, lap w) as [M, 7] in one launch; its backward is one launch too.  The node owns
-    its inputs and plan like :class:`_ResidualFunction`."""
-
-    @staticmethod
-    def forward(ctx, means, values, conics, samples, debug, plan):
-        out = _vorticity_call(False, means, values, conics, samples, plan)
-        if debug:
-            torch.cuda.synchronize(means.device)
-        ctx.inputs = (means, values, conics, samples)
-        ctx.versions = (means._version, values._version, conics._version, samples._version)
-        ctx.debug, ctx.plan = debug, plan
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gout):
-        means, values, conics, samples = ctx.inputs
-        if (means._version, values._version, conics._version, samples._version) != ctx.versions:
-            raise RuntimeError("one of the tensors handed to GaussianSampler.preprocess() has been modified in place "
-                               "before the backward of a vorticity_terms() output that was computed from it")
-        gout = gout.contiguous()
-        if ctx.debug:
-            assert ctx.plan is None or not ctx.plan.forward_only, "a vorticity_terms() node holds a forward-only plan"
-        g_means, g_values, g_conics = _vorticity_call(True, means, values, conics, samples, ctx.plan, gout=gout)
-        if ctx.debug:
-            torch.cuda.synchronize(means.device)
-        return g_means, g_values, g_conics, None, None, None
-
-
 class VorticityResidual:
     """The coefficients of a vorticity_residual() call: three floats and ``tau``, a float or a detached device field
     [M, 1]."""
@@ -732,75 +570,35 @@ class VorticityResidual:
         return t
 
 
-def _vorticity_residual_call(backward, means, values, conics, samples, params, plan, prev=None, gout=None, aux=None):
-    """pigs_vorticity_residual_forward / _backward on contiguous device tensors (through the plan when given)."""
-    lib = _lib.load()
-    N, M = means.shape[0], samples.shape[0]
-    vz = params.struct()
-    if backward and plan is not None and M > 0 and getattr(plan, "forward_only", False):
-        plan = plan.full_for_backward(means, values, conics, samples)
-    pw = (_ptr(plan.workspace), plan.workspace.numel(), _ptr(plan.samples.workspace), plan.samples.workspace.numel()) \
-        if plan is not None else (ctypes.c_void_p(0), 0, ctypes.c_void_p(0), 0)
-    with _on_device(means.device):
-        stream = _stream(means.device)
-        if plan is not None and hasattr(plan, "note_stream"):
-            plan.note_stream(stream.value)
-        if not backward:
-            out = torch.empty((M, len(VORTICITY_RESIDUAL_COLUMNS)), dtype=means.dtype, device=means.device)
-            if M > 0:
-                rc = lib.pigs_vorticity_residual_forward(_DTYPES[means.dtype], N, M, _ptr(means), _ptr(conics), _ptr(values),
-                                                         _ptr(samples), ctypes.byref(vz), _ptr(prev), _ptr(out), _ptr(aux),
-                                                         *pw, stream)
-                _lib.check(rc, "pigs_vorticity_residual_forward")
-            return out
-        g_means, g_values, g_conics = _gradient_views(means, values, conics)
-        if N > 0:
-            if M > 0:
-                rc = lib.pigs_vorticity_residual_backward(_DTYPES[means.dtype], N, M, _ptr(means), _ptr(conics), _ptr(values),
-                                                          _ptr(samples), ctypes.byref(vz), _ptr(gout), _ptr(aux),
-                                                          _ptr(g_means), _ptr(g_conics), _ptr(g_values), *pw, stream)
-                _lib.check(rc, "pigs_vorticity_residual_backward")
-            else:
-                for g in (g_means, g_values, g_conics):
-                    g.zero_()
-        return g_means, g_values, g_conics
+class _ResidualFunction(_FusedFunction):
+    """r = a0 u + a1 . grad u + aL lap u - target."""
+    op = _FusedOp("residual()", "pigs_residual")
 
 
-class _VorticityResidualFunction(torch.autograd.Function):
-    """(div_b, r) of the Navier-Stokes residual as [M, 2] in one launch; its backward is one launch too.  The node owns
-    its inputs, plan, ``tau``, ``prev`` and ``aux`` (the blended u and grad w of the forward, which the backward of the
-    advection term reads) like :class:`_ResidualTermsFunction`."""
+class _ResidualTermsFunction(_FusedFunction):
+    """The general residual (per-point coefficients, advection term); ``aux`` = u and grad u of the forward, which the
+    backward of the advection term reads (kept only when that term is active)."""
+    op = _FusedOp("residual()", "pigs_residual_terms",
+                  aux_shape=lambda terms, M, d, c: (M, 1 + d, c) if terms.advects else None)
 
-    @staticmethod
-    def forward(ctx, means, values, conics, samples, params, prev, debug, plan, want_aux):
-        M = samples.shape[0]
-        aux = torch.empty((M, 4), dtype=means.dtype, device=means.device) if want_aux and M > 0 else None
-        out = _vorticity_residual_call(False, means, values, conics, samples, params, plan, prev=prev, aux=aux)
-        if debug:
-            torch.cuda.synchronize(means.device)
-        ctx.inputs = (means, values, conics, samples)
-        ctx.versions = (means._version, values._version, conics._version, samples._version)
-        ctx.params, ctx.prev, ctx.aux, ctx.debug, ctx.plan = params, prev, aux, debug, plan
-        return out
 
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gout):
-        means, values, conics, samples = ctx.inputs
-        if (means._version, values._version, conics._version, samples._version) != ctx.versions:
-            raise RuntimeError("one of the tensors handed to GaussianSampler.preprocess() has been modified in place "
-                               "before the backward of a vorticity_residual() output that was computed from it")
-        if ctx.aux is None and samples.shape[0] > 0:
-            raise RuntimeError("this vorticity_residual() output was computed without the record its backward needs "
-                               "(no input required grad when it ran)")
-        gout = gout.contiguous()
-        if ctx.debug:
-            assert ctx.plan is None or not ctx.plan.forward_only, "a vorticity_residual() node holds a forward-only plan"
-        g_means, g_values, g_conics = _vorticity_residual_call(True, means, values, conics, samples, ctx.params, ctx.plan,
-                                                               gout=gout, aux=ctx.aux)
-        if ctx.debug:
-            torch.cuda.synchronize(means.device)
-        return g_means, g_values, g_conics, None, None, None, None, None, None
+class _ResidualCoupledFunction(_FusedFunction):
+    """The coupled residual (two constant matrices mix the channels under a per-point weight): linear in the field, so
+    no record of the forward is kept."""
+    op = _FusedOp("residual()", "pigs_residual_coupled")
+
+
+class _VorticityFunction(_FusedFunction):
+    """(u_x, u_y, div, w, w_x, w_y, lap w) as [M, 7]."""
+    op = _FusedOp("vorticity_terms()", "pigs_vorticity", width=len(VORTICITY_COLUMNS), dims=False, has_params=False,
+                  has_side=False, has_target=False)
+
+
+class _VorticityResidualFunction(_FusedFunction):
+    """(div_b, r) of the Navier-Stokes residual as [M, 2]; ``side`` = the previous level's vorticity terms (a constant),
+    ``aux`` = the blended u and grad w of the forward, which the backward of the advection term reads."""
+    op = _FusedOp("vorticity_residual()", "pigs_vorticity_residual", width=len(VORTICITY_RESIDUAL_COLUMNS), dims=False,
+                  has_target=False, aux_shape=lambda params, M, d, c: (M, 4))
 
 
 class _SampleFunction(torch.autograd.Function):
@@ -1391,7 +1189,7 @@ class GaussianSampler:
             consts = [0.0 if isinstance(v, torch.Tensor) else v for v in (f0, fL, fW)]
             return self._core.residual_coupled(fields, consts, flat0, flatL, target)
         return _ResidualCoupledFunction.apply(means, values, conics, samples, target, ResidualCoupling(f0, fL, fW, Q0, QL),
-                                              self.debug, self._plan_for(0, target))
+                                              self.debug, self._plan_for(0, target), False)
 
     def residual(self, a0=0.0, a1=None, lap=0.0, target=None, *, advect=None, advect_by=None,
                  couple0=None, couple_lap=None, couple_weight=None):
@@ -1481,7 +1279,8 @@ class GaussianSampler:
                                                 self._plan_for(0, target), want_aux)
         if self._core is not None:
             return self._core.residual(coeffs, target)
-        return _ResidualFunction.apply(means, values, conics, samples, target, coeffs, self.debug, self._plan_for(0, target))
+        return _ResidualFunction.apply(means, values, conics, samples, target, ResidualCoeffs(coeffs), self.debug,
+                                       self._plan_for(0, target), False)
 
     def vorticity_terms(self):
         """Extension of the reference API: the seven numbers per point that the reference's Navier-Stokes problem keeps
@@ -1505,7 +1304,8 @@ class GaussianSampler:
         if self._core is not None:
             return self._core.vorticity_terms()
         if self._vorticity is None or (self._needs_backward() and not self._vorticity.requires_grad):
-            self._vorticity = _VorticityFunction.apply(means, values, conics, samples, self.debug, self._plan_for(8))
+            self._vorticity = _VorticityFunction.apply(means, values, conics, samples, None, None, self.debug,
+                                                       self._plan_for(8), False)
         return self._vorticity
 
     def vorticity_residual(self, nu, dt, prev=None, tau=1.0, *, time_term=1.0):
@@ -1549,8 +1349,8 @@ class GaussianSampler:
         if self._core is not None:
             field = f_tau if isinstance(f_tau, torch.Tensor) else None
             return self._core.vorticity_residual(nu, dt, time_term, 0.0 if field is not None else f_tau, field, prev)
-        return _VorticityResidualFunction.apply(means, values, conics, samples, VorticityResidual(nu, dt, time_term, f_tau),
-                                                prev, self.debug, self._plan_for(8), self._needs_backward())
+        return _VorticityResidualFunction.apply(means, values, conics, samples, prev, VorticityResidual(nu, dt, time_term, f_tau),
+                                                self.debug, self._plan_for(8), self._needs_backward())
 
     def sample_gaussians(self):
         """u [M, c]"""

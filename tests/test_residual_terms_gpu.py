@@ -374,7 +374,7 @@ def test_floats_alone_stay_on_the_linear_kernel(hip_lib, backend):
     with torch.no_grad():
         s.preprocess(m, v, None, con, pts)
         r = s.residual(a0=1.7, a1=(0.3, -0.1), lap=-0.01)
-        raw = S._residual_call(False, m, v, con, pts, (1.7, 0.3, -0.1, -0.01), s._plan)
+        raw = S._fused_call(S._ResidualFunction.op, False, m, v, con, pts, S.ResidualCoeffs((1.7, 0.3, -0.1, -0.01)), s._plan)
     assert (s._plan is not None) == (backend == "binned")
     assert torch.equal(r, raw)
     assert r.grad_fn is None

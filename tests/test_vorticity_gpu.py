@@ -370,8 +370,9 @@ def test_backward_on_forward_only_workspace_writes_nan(hip_lib):
     plan = S.Plan(m, v, c, pts, 44.0, q_max_backward=44.0, forward_only=True)
     full = S.Plan(m, v, c, pts, 44.0, q_max_backward=44.0)
     assert plan.forward_only and not full.forward_only
-    out = S._vorticity_call(False, m, v, c, pts, plan)
-    assert torch.isfinite(out).all() and rel(out, S._vorticity_call(False, m, v, c, pts, full)) < 1e-6
+    op = S._VorticityFunction.op
+    out = S._fused_call(op, False, m, v, c, pts, None, plan)
+    assert torch.isfinite(out).all() and rel(out, S._fused_call(op, False, m, v, c, pts, None, full)) < 1e-6
     gm, gv, gc = (torch.zeros_like(x) for x in (m, v, c))
     p, sws = ctypes.c_void_p, plan.samples.workspace
     rc = hip_lib.pigs_vorticity_backward(0, N, M, p(m.data_ptr()), p(c.data_ptr()), p(v.data_ptr()), p(pts.data_ptr()),
@@ -380,7 +381,8 @@ def test_backward_on_forward_only_workspace_writes_nan(hip_lib):
     assert rc == 0
     torch.cuda.synchronize()
     assert bool(gm.isnan().all()) and bool(gv.isnan().all()) and bool(gc.isnan().all())
-    for x, y in zip(S._vorticity_call(True, m, v, c, pts, full, gout=w), S._vorticity_call(True, m, v, c, pts, plan, gout=w)):
+    for x, y in zip(S._fused_call(op, True, m, v, c, pts, None, full, gout=w),
+                    S._fused_call(op, True, m, v, c, pts, None, plan, gout=w)):
         assert torch.isfinite(x).all() and rel(y, x) < 1e-5
 
 

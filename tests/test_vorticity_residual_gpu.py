@@ -359,14 +359,14 @@ def test_no_grad_call_allocates_no_aux(hip_lib):
     from diff_gaussian_sampling import GaussianSampler
     t, pts, w, tau, prev = small()
     seen = []
-    real = S._vorticity_residual_call
+    real = S._fused_call
 
-    def spy(backward, *a, **k):
+    def spy(op, backward, *a, **k):
         seen.append((backward, k.get("aux")))
-        return real(backward, *a, **k)
+        return real(op, backward, *a, **k)
 
     s = GaussianSampler(False, backend="dense", host="ctypes")
-    S._vorticity_residual_call = spy
+    S._fused_call = spy
     try:
         with torch.no_grad():
             s.preprocess(t[0], t[1], None, t[2], pts)
@@ -376,7 +376,7 @@ def test_no_grad_call_allocates_no_aux(hip_lib):
         out = residual_of(s, prev, tau)
         assert seen[1][1] is not None and tuple(seen[1][1].shape) == (700, 4) and out.grad_fn is not None
     finally:
-        S._vorticity_residual_call = real
+        S._fused_call = real
 
 
 def test_backward_on_forward_only_workspace_writes_nan(hip_lib):
@@ -392,8 +392,9 @@ def test_backward_on_forward_only_workspace_writes_nan(hip_lib):
     assert plan.forward_only and not full.forward_only
     params = S.VorticityResidual(NU, DT, TT, tau.reshape(-1, 1).contiguous())
     aux = torch.empty((M, 4), device="cuda")
-    out = S._vorticity_residual_call(False, m, v, c, pts, params, plan, prev=prev, aux=aux)
-    ref = S._vorticity_residual_call(False, m, v, c, pts, params, full, prev=prev)
+    op = S._VorticityResidualFunction.op
+    out = S._fused_call(op, False, m, v, c, pts, params, plan, side=prev, aux=aux)
+    ref = S._fused_call(op, False, m, v, c, pts, params, full, side=prev)
     assert torch.isfinite(out).all() and torch.isfinite(aux).all() and rel(out, ref) < 1e-6
     gm, gv, gc = (torch.zeros_like(x) for x in (m, v, c))
     p, sws, vz = ctypes.c_void_p, plan.samples.workspace, params.struct()
@@ -405,8 +406,8 @@ def test_backward_on_forward_only_workspace_writes_nan(hip_lib):
     torch.cuda.synchronize()
     assert bool(gm.isnan().all()) and bool(gv.isnan().all()) and bool(gc.isnan().all())
     assert isinstance(vz, _lib.PigsVorticityResidual)
-    for x, y in zip(S._vorticity_residual_call(True, m, v, c, pts, params, full, gout=w, aux=aux),
-                    S._vorticity_residual_call(True, m, v, c, pts, params, plan, gout=w, aux=aux)):
+    for x, y in zip(S._fused_call(op, True, m, v, c, pts, params, full, gout=w, aux=aux),
+                    S._fused_call(op, True, m, v, c, pts, params, plan, gout=w, aux=aux)):
         assert torch.isfinite(x).all() and rel(y, x) < 1e-5
 
 
