@@ -107,8 +107,9 @@ def test_residual_and_backward_as_first_calls(Sampler, hip_lib):
 
 
 def test_every_tile_mode_through_the_fused_launch(Sampler):
-    """Thin outskirts (per-point walk), very wide Gaussians (record ranges), scattered points (group lists only):
-    the fused launch must sample them all itself."""
+    """Thin outskirts (per-point walk) and very wide Gaussians (record ranges): the fused launch must sample them itself.
+    Tiles that keep their group lists only, and the other four fused instantiations in every mode, run in
+    tests/test_binned_matrix_gpu.py::test_fused_first."""
     from tools.prof_step import list_stats
     rng = np.random.default_rng(12)
     cases = []
