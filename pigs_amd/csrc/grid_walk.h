@@ -1,5 +1,5 @@
 // Walking the multi-level Gaussian grid of a plan workspace (plan.h): wave-level helpers, the exact
-// ellipse / rectangle test and `traverse()`.  Shared by the tile-list build (plan.hip) and the neighbour-
+// ellipse / rectangle test and `traverse()`.  Shared by the tile-list build (plan_lists.h) and the neighbour-
 // list build of aggregate_neighbors (aggregate.hip).
 #pragma once
 #include "plan.h"

@@ -46,7 +46,7 @@
 namespace pigs {
 
 constexpr int PLAN_MAX_LEVELS = 12;
-constexpr int PLAN_BAR_WORDS = 2 * 17 + 1;   // two barriers of 17 words + the exit counter (plan.hip, grid_barrier)
+constexpr int PLAN_BAR_WORDS = 2 * 17 + 1;   // two barriers of 17 words + the exit counter (plan_build.h, grid_barrier)
 constexpr uint32_t PLAN_SCAN_BLOCK = 256 * 4;     // counters scanned per workgroup (one uint4 per thread)
 
 constexpr int TILE_POINTS = 64;            // one wave
@@ -137,7 +137,7 @@ struct SampleParams {
     // points -- the sampling kernels read them where the caller keeps them, through the index arithmetic -- so the
     // array must stay valid and unmodified for as long as the workspace is used (the hosts keep the tensor).
     uint64_t src;
-    // two device-wide barriers among the samples' workgroups of the count launch (plan.hip, samples_sort_in_count:
+    // two device-wide barriers among the samples' workgroups of the count launch (plan_build.h, samples_sort_in_count:
     // points that were expected to be a lattice and are none are counted, scanned and scattered in that one launch);
     // zeroed by the first launch of every samples build
     uint32_t bar[2 * 17];
@@ -175,9 +175,9 @@ struct PlanParams {
                                                // the traversal indexes it by lane)
     uint32_t scan_error;
     float q_f, q_b;        // the plan's two cut-offs (forward / backward of order >= 2 gradients), q_b >= q_f
-    uint32_t bar[PLAN_BAR_WORDS];   // device-wide barriers of the one-launch Gaussian chain (zero between builds)
+    uint32_t bar[PLAN_BAR_WORDS];   // no kernel meets here any more (the one-launch Gaussian chain was removed): zeroed by every build, kept for the layout
     uint32_t n_points;              // tiles in TILE_MODE_POINTS (queued in `ptiles` by the list build)
-    // STRIPS (round 4; plan.hip, gauss_pack_part).  Gaussians that arrive in an order in which neighbours in the array are
+    // STRIPS (round 4; plan_build.h, gauss_pack_part).  Gaussians that arrive in an order in which neighbours in the array are
     // neighbours in space (the reference lays them out on a meshgrid, model_pn.py:338-342, and training moves them by
     // fractions of a spacing) are not binned at all: records stay in the CALLER's order, every STRIP = 16 consecutive
     // ones are a strip with a bounding box (`pbox`), every 16 strips a super-strip (`sbox`), and the list build tests
@@ -370,7 +370,7 @@ __device__ inline PointOrder point_order(const SamplesView& sv) {
     po.src = (const float2*)(uintptr_t)sv.params->src;
     return po;
 }
-// The same in two steps, for the forward (plan.hip, forward_tile): first the three words as loaded -- through the
+// The same in two steps, for the forward (plan_forward.h, forward_tile): first the three words as loaded -- through the
 // constant address space (the sampling kernels never write SampleParams), which makes them ONE scalar load beside the
 // wave's vector loads instead of a vector load + v_readfirstlane in their queue; nothing is derived from them here, or
 // the wave would wait for them here -- then, where the first point is addressed, the order they spell.

@@ -1,5 +1,5 @@
-"""GPU: every instantiation of the binned kernels (pigs_amd/csrc/plan.hip: tile_forward_kernel<C, MASK> and
-tile_backward_kernel<C, MASK>, 23 per direction, and the five plan_lists_forward_kernel<C, MASK> of the fused first
+"""GPU: every instantiation of the binned kernels (pigs_amd/csrc/plan_forward.h and plan_backward.h:
+tile_forward_kernel<C, MASK> and tile_backward_kernel<C, MASK>, 23 per direction, and the five plan_lists_forward_kernel<C, MASK> of the fused first
 launch) through every tile mode a header word can carry -- LIST, GROUPS, RANGES, POINTS -- against the float64 oracle.
 
 A scene is Gaussians, points and the tile mode they must produce; it is built for c = 1 and c = 2 with the same geometry,
@@ -9,7 +9,7 @@ test LIST again.  tests/test_binned_matrix.py reads SCENES, RUNS and FUSED_FIRST
 (c, mask, mode, direction) cell is left out.
 
 The scenes (N Gaussians x M points; the sizes were tuned on an MI355X from the list build's thresholds, plan.h and
-build_block_lists of plan.hip; the tile counts are those of that run, the plans of both cut-offs alike unless noted):
+build_block_lists of plan_lists.h; the tile counts are those of that run, the plans of both cut-offs alike unless noted):
   L-lattice  576 x 4 096    synthetic.grid_samples(64): the smallest index-tiled point set; all 64 tiles LIST; streamed stores
   L-sorted   600 x 1 481    random points (sorted into cells: plain stores, the staging records for c = 1) and Gaussians
                             wide enough for group lists of up to 149 entries (five 32-record chunks) and tile lists of up
@@ -69,7 +69,7 @@ another bar:
   points         0.033     0.269      0.017         0.221
   general residual with advection against its own composition: forward 5.9e-8 of the term scale (bar 2e-6), gradients
   4.1e-7 of the largest entry (bar 5e-6)
-The matrix catches what it is for -- three value-only edits of plan.hip, one run each, never committed:
+The matrix catches what it is for -- three value-only edits of plan_forward.h, one run each, never committed:
   (a) forward_points_quad tests q against a quarter of the cut-off: the forward cells of P and P-stride fail (both
       channel counts, every order set and fused output, 33 outputs) and P's fused first launches, and with them the
       gradients of vorticity_residual() there, whose backward reads the record that forward left; nothing else.

@@ -206,7 +206,7 @@ def run_matrix_case(dtype, d, c, name, N, M):
     # ---- sample(): every covering mask alone, requests with holes, a backward with holes the forward did not have
     for orders, reads in ORDER_SETS:
         reads = orders if reads is None else reads
-        fmask, bmask = mirror.masks_of(orders, reads)
+        fmask, _ = mirror.masks_of(orders, reads)
         fvar = mirror.forward_variant(dtype, d, c, fmask, N, M)
         s.preprocess(cs.t[0], cs.t[1], None, cs.t[2], cs.t[3])          # forget the outputs of the previous set
         outs = s.sample(orders)

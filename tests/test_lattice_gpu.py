@@ -232,7 +232,7 @@ def test_a_rank_s_rows_of_the_weak_scaling_grid_are_index_tiled(Sampler, hip_lib
 @pytest.mark.parametrize("strips", ["0", "1"])
 def test_gaussians_one_launch_ahead_and_points_that_break_the_expectation(Sampler, hip_lib, monkeypatch, strips):
     """With a lattice expected and the same bounding box in the last two completed builds of a size, the Gaussians are
-    binned on the REMEMBERED box in the launch that looks at the points (plan.hip, BuildArgs::ahead): three launches
+    binned on the REMEMBERED box in the launch that looks at the points (plan_build.h, BuildArgs::ahead): three launches
     in front of the tile lists instead of four.  Results must not depend on it -- not when the Gaussians change, not
     when the next point set of that size lies elsewhere (the Gaussians' grid then covers the wrong domain: slower,
     never wrong), not when it is no lattice at all (its workgroups scan and scatter in the third launch)."""
@@ -240,7 +240,7 @@ def test_gaussians_one_launch_ahead_and_points_that_break_the_expectation(Sample
     monkeypatch.setenv("PIGS_LATTICE", "1")
     # strips = "1": the Gaussians keep the caller's order (PIGS_GAUSS_STRIPS) -- nothing of them is left for the second and
     # third launch then, there is no third, and points that are no lattice after all are counted, scanned and scattered
-    # inside the second, behind device-wide barriers (plan.hip, samples_sort_in_count)
+    # inside the second, behind device-wide barriers (plan_build.h, samples_sort_in_count)
     monkeypatch.setenv("PIGS_GAUSS_STRIPS", strips)
     rng = np.random.default_rng(31)
     g = grid(96, 64)
