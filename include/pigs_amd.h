@@ -393,6 +393,16 @@ size_t pigs_plan_strips_offset(void);
  * Returns PIGS_ERR_UNSUPPORTED for sizes the binned path does not take (N >= 2^24 among them). */
 int pigs_plan_layout_info(int64_t N, int64_t M, int c, int64_t info[6]);
 
+/* The same for a samples workspace (additive to ABI 10): where the points sit in the order the sampling kernels take
+ * them.  info[0] = tiles (64 consecutive sorted points each, four groups of 16), info[1] = byte offset of the sorted
+ * points, info[2] = bytes per sorted point ({float x, y; uint32 m}: the coordinates and the point's index in the
+ * caller's array; positions behind the last point of a ragged last tile are not written), info[3] = 0.  Meaningful
+ * when the build sorted the points into cells: in index-tiled order ({rf, rs} at pigs_samples_lattice_offset non-zero)
+ * the workspace holds no points, tile t is the 8 x 8 index patch the serpentine of pair-rows puts at position t and
+ * group g of it the 4 x 4 patch (g & 1, g >> 1).
+ * Returns PIGS_ERR_UNSUPPORTED for sizes the binned path does not take. */
+int pigs_samples_layout_info(int64_t M, int64_t info[4]);
+
 /*
  * ABI 10.  Periodic domain [lo, lo + period)^2, d = 2, f32 / f64, c in 1..4.  A periodic sampler sums, for every
  * point x, the 3 x 3 images of every Gaussian:

@@ -67,8 +67,13 @@ def _pair_terms(means, conics, samples):
     return x, p, g
 
 
-def forward(means, conics, values, samples, orders=(0, 1, 2, 3), chunk=None):
-    """Returns {order: array}.  ``conics`` is the full [N, d, d] matrix."""
+def forward(means, conics, values, samples, orders=(0, 1, 2, 3), chunk=None, pair_mask=None, absolute=False):
+    """Returns {order: array}.  ``conics`` is the full [N, d, d] matrix.
+    ``pair_mask`` [M, N] bool: the terms of the unmasked (sample, Gaussian) pairs are zero (a sampler that evaluates only
+    some pairs: oracle/plan_lists.py).  ``absolute`` (with a mask): every pair's term enters in absolute value."""
+    if pair_mask is not None:
+        return _forward_pairs(means, conics, values, samples, orders, np.asarray(pair_mask, dtype=bool), absolute)
+    assert not absolute
     means = np.asarray(means)
     N, d = means.shape
     conics = np.asarray(conics).reshape(N, d, d)
@@ -99,12 +104,16 @@ def forward(means, conics, values, samples, orders=(0, 1, 2, 3), chunk=None):
     return out
 
 
-def backward(means, conics, values, samples, grads, chunk=None):
+def backward(means, conics, values, samples, grads, chunk=None, pair_mask=None, absolute=False):
     """Closed-form VJP.  ``grads`` = {order: grad_output}.  Returns
     (g_means [N,d], g_conics_full [N,d,d], g_values [N,c]); the conic gradient treats the
     d*d matrix entries as independent (what autograd through the reference's
     ``full_conics`` gives); use :func:`flat_grad_from_full` for the sampler's flat layout.
+    ``pair_mask`` / ``absolute``: as in :func:`forward` (absolute: per-pair contributions to every entry).
     """
+    if pair_mask is not None:
+        return _backward_pairs(means, conics, values, samples, grads, np.asarray(pair_mask, dtype=bool), absolute)
+    assert not absolute
     means = np.asarray(means)
     N, d = means.shape
     conics = np.asarray(conics).reshape(N, d, d)
@@ -162,3 +171,80 @@ def backward(means, conics, values, samples, grads, chunk=None):
                      + np.einsum("mn,mnk,mnl->nkl", g, dA, x)
                      + np.einsum("mn,mnkl->nkl", g, E))
     return g_means, g_conics, g_values
+
+
+# ---- the same sums over a list of pairs (pair_mask=): one row z per masked (sample, Gaussian) pair.  The einsums are
+# those of forward() / backward() with the sample axis m, the Gaussian axis n and the pair axes mn all replaced by z.
+def _segment_sum(terms, keys, size):
+    """out[k] = sum of the rows of ``terms`` whose key is k (keys ascending)"""
+    out = np.zeros((size,) + terms.shape[1:], dtype=terms.dtype)
+    if len(keys):
+        starts = np.flatnonzero(np.r_[True, keys[1:] != keys[:-1]])
+        out[keys[starts]] = np.add.reduceat(terms, starts, axis=0)
+    return out
+
+
+def _pairs(means, conics, values, samples, pair_mask, by_gaussian):
+    means = np.asarray(means)
+    N, d = means.shape
+    conics = np.asarray(conics).reshape(N, d, d)
+    values = np.asarray(values).reshape(N, -1)
+    samples = np.asarray(samples).reshape(-1, d)
+    assert pair_mask.shape == (samples.shape[0], N)
+    if by_gaussian:
+        zn, zm = np.nonzero(pair_mask.T)        # ascending in n
+    else:
+        zm, zn = np.nonzero(pair_mask)          # ascending in m
+    x = samples[zm] - means[zn]
+    C, v = conics[zn], values[zn]
+    p = np.einsum("zij,zj->zi", C, x)
+    g = np.exp(-0.5 * np.einsum("zi,zi->z", x, p))
+    return zm, zn, x, p, g, C, v, (N, d, values.shape[1], samples.shape[0])
+
+
+def _forward_pairs(means, conics, values, samples, orders, pair_mask, absolute):
+    zm, zn, x, p, g, C, v, (N, d, c, M) = _pairs(means, conics, values, samples, pair_mask, False)
+    terms = {}
+    if 0 in orders:
+        terms[0] = np.einsum("z,zc->zc", g, v)
+    if 1 in orders:
+        terms[1] = -np.einsum("z,zi,zc->zic", g, p, v)
+    if 2 in orders:
+        terms[2] = np.einsum("z,zi,zj,zc->zijc", g, p, p, v) - np.einsum("z,zij,zc->zijc", g, C, v)
+    if 3 in orders:
+        terms[3] = (np.einsum("z,zij,zk,zc->zijkc", g, C, p, v) + np.einsum("z,zik,zj,zc->zijkc", g, C, p, v)
+                    + np.einsum("z,zjk,zi,zc->zijkc", g, C, p, v) - np.einsum("z,zi,zj,zk,zc->zijkc", g, p, p, p, v))
+    return {o: _segment_sum(np.abs(t) if absolute else t, zm, M) for o, t in terms.items()}
+
+
+def _backward_pairs(means, conics, values, samples, grads, pair_mask, absolute):
+    zm, zn, x, p, g, C, v, (N, d, c, M) = _pairs(means, conics, values, samples, pair_mask, True)
+    gr = {o: np.asarray(G).reshape(ORDER_SHAPES[o](M, d, c))[zm] for o, G in grads.items() if G is not None}
+    Z = len(zm)
+    F, dA, E = np.zeros((Z, c)), np.zeros((Z, d)), np.zeros((Z, d, d))
+    if 0 in gr:
+        F += gr[0]
+    if 1 in gr:
+        g1 = gr[1]
+        F -= np.einsum("zic,zi->zc", g1, p)
+        dA -= np.einsum("zlc,zc->zl", g1, v)
+    if 2 in gr:
+        g2 = gr[2]
+        F += np.einsum("zijc,zi,zj->zc", g2, p, p) - np.einsum("zijc,zij->zc", g2, C)
+        dA += np.einsum("zljc,zj,zc->zl", g2, p, v) + np.einsum("zilc,zi,zc->zl", g2, p, v)
+        E -= np.einsum("zklc,zc->zkl", g2, v)
+    if 3 in gr:
+        g3 = gr[3]
+        F += (np.einsum("zijkc,zij,zk->zc", g3, C, p) + np.einsum("zijkc,zik,zj->zc", g3, C, p)
+              + np.einsum("zijkc,zjk,zi->zc", g3, C, p) - np.einsum("zijkc,zi,zj,zk->zc", g3, p, p, p))
+        dA += (np.einsum("zijlc,zij,zc->zl", g3, C, v) + np.einsum("zilkc,zik,zc->zl", g3, C, v)
+               + np.einsum("zljkc,zjk,zc->zl", g3, C, v) - np.einsum("zljkc,zj,zk,zc->zl", g3, p, p, v)
+               - np.einsum("zilkc,zi,zk,zc->zl", g3, p, p, v) - np.einsum("zijlc,zi,zj,zc->zl", g3, p, p, v))
+        E += (np.einsum("zklrc,zr,zc->zkl", g3, p, v) + np.einsum("zkrlc,zr,zc->zkl", g3, p, v)
+              + np.einsum("zrklc,zr,zc->zkl", g3, p, v))
+    A = np.einsum("zc,zc->z", F, v)
+    t_values = g[:, None] * F
+    t_means = (g * A)[:, None] * p - g[:, None] * np.einsum("zi,zil->zl", dA, C)
+    t_conics = (-0.5 * np.einsum("z,zk,zl->zkl", g * A, x, x) + np.einsum("z,zk,zl->zkl", g, dA, x)
+                + g[:, None, None] * E)
+    return tuple(_segment_sum(np.abs(t) if absolute else t, zn, N) for t in (t_means, t_conics, t_values))

@@ -35,7 +35,16 @@
 //
 // Cut-off: a (point, Gaussian) pair is evaluated iff the Gaussian's ellipse q <= q_max reaches
 // the bounding box of the point's 16-point group.  Dropped terms are < exp(-q_max/2) of the
-// term's scale (q_max = 36: 1.5e-8; see DESIGN.md "Cut-off").
+// term's scale (q_max = 36: 1.5e-8; see DESIGN.md "Cut-off").  Held entry by entry against a brute-force statement of
+// that sentence by tests/test_plan_lists_gpu.py (oracle/plan_lists.py).  Where the code deliberately evaluates MORE
+// than the sentence says: the group lists of a TILE_MODE_GROUPS tile hold the wide set, so the forward evaluates pairs
+// up to q_b there (plan_lists.h, the rebuild); record ranges hold every Gaussian near the tile, and the sampling
+// kernels test their records against the group boxes themselves; a TILE_MODE_POINTS tile tests every pair's own q,
+// not the group box's (fewer pairs: exactly those with q <= q_max).
+// Which of the two cut-offs a backward takes is decided by the INSTANTIATION that runs it (plan_backward.h, WIDE), and
+// a request runs its covering instantiation (launch.h, covering_mask_of): gradients that arrive at orders 0 and 1
+// together run the (0, 1, 2) kernel and read the wide masks; only a backward of order 0 or order 1 alone reads the
+// narrow ones.
 //
 // Correctness never depends on the grid domains: out-of-domain coordinates clamp to border
 // cells and queries clamp the same (monotone) way; only speed depends on them.

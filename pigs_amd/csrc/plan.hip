@@ -82,6 +82,13 @@ int plan_layout_info(int64_t N, int64_t M, int c, int64_t* info) {
     return PIGS_OK;
 }
 
+int samples_layout_info(int64_t M, int64_t* info) {
+    if (!samples_supported(M)) return PIGS_ERR_UNSUPPORTED;
+    const SamplesLayout s = make_samples_layout(M);
+    info[0] = s.ntiles; info[1] = (int64_t)s.off_spts; info[2] = (int64_t)sizeof(SPoint); info[3] = 0;
+    return PIGS_OK;
+}
+
 size_t samples_workspace_bytes(int64_t M) {
     if (!samples_supported(M)) return 0;
     return make_samples_layout(M).total_bytes;
