@@ -547,6 +547,48 @@ int pigs_aggregate_backward_periodic(int dtype, int64_t N, int64_t cap, int L, i
                                      void* g_features, void* g_transform, void* g_queries, void* g_keys,
                                      void* g_frequencies, void* g_distance_transform, void* stream);
 
+/*
+ * All H heads of an attention layer in one launch (additive to ABI 10: the number does not change).  The heads share
+ * `features`, `frequencies` and the lists; head h has transform_h, distance_transform_h and its own queries and keys:
+ *   out[:, h, :] = pigs_aggregate_forward(features, transforms[h], queries[:, h], keys[:, h], frequencies,
+ *                                         distance_transforms[h])          for h < H,
+ * what a pair's geometry gives (list entry, q, g, the 4F sin / cos values, the features row) being computed once.
+ * Layouts (row-major): features [N][L]; transforms [H][L][L]; queries, keys [N][H][K] (a Gaussian's H rows are
+ *   contiguous); frequencies [F]; distance_transforms [H][L][2E].  The forward writes out [N][H][L], lse [N][H] and
+ *   acc [N][H][L + 2E].  The backward takes gout [N][H][L] and writes g_features [N][L] and g_frequencies [F] (both
+ *   the sums over the heads), g_transforms [H][L][L], g_queries, g_keys [N][H][K], g_distance_transforms [H][L][2E];
+ *   `scratch` (pigs_aggregate_heads_backward_scratch_bytes(dtype, N, H, L, F) bytes) holds dacc [N][H][L + 2E],
+ *   D [N][H] and the per-row shares of the frequency gradient [N][F].  Launches and the sums over N as in
+ *   pigs_aggregate_backward.
+ * `period` = 0: lists of pigs_aggregate_lists; > 0: lists of pigs_aggregate_lists_periodic on a torus of that period
+ *   (its preconditions hold); anything else is PIGS_ERR_INVALID.
+ * Sizes: 1 <= H <= PIGS_AGGREGATE_HEADS_MAX (else PIGS_ERR_UNSUPPORTED).  H = 1 runs the single-head kernels under their own rule.  For
+ *   H >= 2 at most 128 components per kernel -- L + 2E <= 128, H K + F <= 128, H (L + K) <= 128 -- and the dynamic LDS
+ *   of each kernel, sizeof(T) * 4 * region values, within PIGS_AGGREGATE_LDS_MAX: region = max(64 ((L + 4F) | 1), 136 H)
+ *   in the forward, 136 H + max(64 ((H K + F) | 1), 136) in the backward by rows, max(64 ((H (L + K)) | 1), 136) in the
+ *   backward by columns.  pigs_aggregate_heads_lds_bytes is the whole rule in one call: the largest of the three, or 0
+ *   when an argument, H or a component count is out of range -- a shape is admitted when 0 < bytes <= PIGS_AGGREGATE_LDS_MAX.
+ *   Both entries check all of it before any HIP call (PIGS_ERR_UNSUPPORTED; the forward refuses a shape whose
+ *   backward could not run) and return after the check when N = 0.  H separate pigs_aggregate_forward calls remain
+ *   available for a refused shape.
+ */
+#define PIGS_AGGREGATE_HEADS_MAX 4
+size_t pigs_aggregate_heads_lds_bytes(int dtype, int H, int L, int K, int F);
+size_t pigs_aggregate_heads_backward_scratch_bytes(int dtype, int64_t N, int H, int L, int F);
+int pigs_aggregate_heads_forward(int dtype, int64_t N, int64_t cap, int H, int L, int K, int F, double period,
+                                 const void* means, const void* conics, const int32_t* row_counts,
+                                 const int32_t* row_lists, const void* features, const void* transforms,
+                                 const void* queries, const void* keys, const void* frequencies,
+                                 const void* distance_transforms, void* out, void* lse, void* acc, void* stream);
+int pigs_aggregate_heads_backward(int dtype, int64_t N, int64_t cap, int H, int L, int K, int F, double period,
+                                  const void* means, const void* conics, const int32_t* row_counts,
+                                  const int32_t* row_lists, const int32_t* col_counts, const int32_t* col_lists,
+                                  const void* features, const void* transforms, const void* queries, const void* keys,
+                                  const void* frequencies, const void* distance_transforms, const void* lse,
+                                  const void* acc, const void* gout, void* scratch, size_t scratch_bytes,
+                                  void* g_features, void* g_transforms, void* g_queries, void* g_keys,
+                                  void* g_frequencies, void* g_distance_transforms, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

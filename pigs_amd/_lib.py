@@ -117,6 +117,13 @@ SIGNATURES = {
                                         + [_vp]),
     "pigs_aggregate_backward_periodic": (_i, [_i, _i64, _i64, _i, _i, _i, ctypes.c_double] + [_vp] * 6 + [_vp] * 6 + [_vp] * 3
                                          + [_vp, ctypes.c_size_t] + [_vp] * 6 + [_vp]),
+    # all heads of a layer in one launch (additive to ABI 10): + H, period (0 = plain lists)
+    "pigs_aggregate_heads_lds_bytes": (ctypes.c_size_t, [_i, _i, _i, _i, _i]),
+    "pigs_aggregate_heads_backward_scratch_bytes": (ctypes.c_size_t, [_i, _i64, _i, _i, _i]),
+    "pigs_aggregate_heads_forward": (_i, [_i, _i64, _i64, _i, _i, _i, _i, ctypes.c_double] + [_vp] * 4 + [_vp] * 6 + [_vp] * 3
+                                     + [_vp]),
+    "pigs_aggregate_heads_backward": (_i, [_i, _i64, _i64, _i, _i, _i, _i, ctypes.c_double] + [_vp] * 6 + [_vp] * 6 + [_vp] * 3
+                                      + [_vp, ctypes.c_size_t] + [_vp] * 6 + [_vp]),
 }
 
 _lib = None

@@ -195,3 +195,102 @@ def aggregate(nb, features, transform, queries, keys, frequencies, distance_tran
         raise NotImplementedError(f"{str(dt).replace('torch.', '')} with L = {L}, K = {K}, F = {F} needs {lds} bytes of LDS "
                                   f"in one of the forward's or the backward's kernels; the limit is {LDS_MAX}")
     return _Aggregate.apply(nb, features, transform, queries, keys, frequencies, distance_transform)
+
+
+# ---- all heads of a layer in one launch ----------------------------------------------------------------------------
+MAX_HEADS = 4        # PIGS_AGGREGATE_HEADS_MAX of include/pigs_amd.h
+
+
+def heads_refusal(dtype, H, L, K, F):
+    """None when the heads' kernels admit the shape, else the reason.  The rule is the library's
+    (pigs_aggregate_heads_lds_bytes: 0 = more than 128 components in one kernel, else the LDS the kernels ask for)."""
+    lds = _lib.load().pigs_aggregate_heads_lds_bytes(_DTYPES[dtype], H, L, K, F)
+    shape = f"{str(dtype).replace('torch.', '')} with H = {H}, L = {L}, K = {K}, F = {F}"
+    if lds == 0:
+        return f"{shape} has more than 128 components in one kernel (L + 2E, H K + F, H (L + K) <= 128)"
+    if lds > LDS_MAX:
+        return f"{shape} needs {lds} bytes of LDS in one of the forward's or the backward's kernels; the limit is {LDS_MAX}"
+    return None
+
+
+class _AggregateHeads(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, nb, features, transforms, queries, keys, frequencies, distance_transforms):
+        lib = _lib.load()
+        N, L = features.shape
+        H, K, F = queries.shape[1], queries.shape[2], frequencies.shape[0]
+        E = 4 * F + 1
+        dt = nb.means.dtype
+        ins = (features, transforms, queries, keys, frequencies, distance_transforms)
+        f, tr, q, k, fr, dist = (a.detach().to(dt).contiguous() for a in ins)
+        out = torch.empty((N, H, L), dtype=dt, device=f.device)
+        lse = torch.empty((N, H), dtype=dt, device=f.device)
+        acc = torch.empty((N, H, L + 2 * E), dtype=dt, device=f.device)
+        with torch.cuda.device(f.device):
+            rc = lib.pigs_aggregate_heads_forward(
+                _DTYPES[dt], N, nb.cap, H, L, K, F, nb.period, _ptr(nb.means), _ptr(nb.conics), _ptr(nb.row_counts),
+                _ptr(nb.row_lists), _ptr(f), _ptr(tr), _ptr(q), _ptr(k), _ptr(fr), _ptr(dist), _ptr(out), _ptr(lse), _ptr(acc),
+                _stream(f.device))
+        _lib.check(rc, "pigs_aggregate_heads_forward")
+        ctx.nb = nb
+        ctx.save_for_backward(f, tr, q, k, fr, dist, lse, acc)
+        ctx.dims = (N, H, L, K, F)
+        ctx.in_dtypes = tuple(a.dtype for a in ins)
+        return out.to(features.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        lib = _lib.load()
+        nb = ctx.nb
+        f, tr, q, k, fr, dist, lse, acc = ctx.saved_tensors
+        N, H, L, K, F = ctx.dims
+        dt = f.dtype
+        gout = gout.to(dt).contiguous()
+        g_f, g_tr, g_q, g_k, g_fr, g_dist = (torch.empty_like(t) for t in (f, tr, q, k, fr, dist))
+        nbytes = lib.pigs_aggregate_heads_backward_scratch_bytes(_DTYPES[dt], N, H, L, F)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=f.device)
+        with torch.cuda.device(f.device):
+            rc = lib.pigs_aggregate_heads_backward(
+                _DTYPES[dt], N, nb.cap, H, L, K, F, nb.period, _ptr(nb.means), _ptr(nb.conics), _ptr(nb.row_counts),
+                _ptr(nb.row_lists), _ptr(nb.col_counts), _ptr(nb.col_lists), _ptr(f), _ptr(tr), _ptr(q), _ptr(k), _ptr(fr),
+                _ptr(dist), _ptr(lse), _ptr(acc), _ptr(gout), _ptr(scratch), nbytes, _ptr(g_f), _ptr(g_tr), _ptr(g_q), _ptr(g_k),
+                _ptr(g_fr), _ptr(g_dist), _stream(f.device))
+        _lib.check(rc, "pigs_aggregate_heads_backward")
+        if N == 0:
+            for g in (g_tr, g_fr, g_dist):
+                g.zero_()
+        grads = (g_f, g_tr, g_q, g_k, g_fr, g_dist)
+        return (None,) + tuple(g.to(d) for g, d in zip(grads, ctx.in_dtypes))
+
+
+def aggregate_heads(nb, features, transforms, queries, keys, frequencies, distance_transforms):
+    """out[:, h] = aggregate(nb, features, transforms[h], queries[:, h], keys[:, h], frequencies, distance_transforms[h])
+    for every head h in one forward launch (features, frequencies and the lists are the heads' common part).
+    transforms [H, L, L], queries / keys [N, H, K], distance_transforms [H, L, 2E] -> [N, H, L]."""
+    N = nb.N
+    if features.dim() != 2 or features.shape[0] != N:
+        raise ValueError(f"features must be [N={N}, L], got {tuple(features.shape)}")
+    if queries.dim() != 3 or frequencies.dim() != 1:
+        raise ValueError(f"aggregate_neighbors_heads: queries must be [N={N}, H, K] and frequencies [F], got "
+                         f"{tuple(queries.shape)} and {tuple(frequencies.shape)}")
+    L, H, K, F = features.shape[1], queries.shape[1], queries.shape[2], frequencies.shape[0]
+    E = 4 * F + 1
+    if (transforms.shape != (H, L, L) or queries.shape != (N, H, K) or keys.shape != (N, H, K)
+            or distance_transforms.shape != (H, L, 2 * E)):
+        raise ValueError(f"aggregate_neighbors_heads: expected transforms [{H},{L},{L}], queries/keys [{N},{H},{K}], "
+                         f"distance_transforms [{H},{L},{2 * E}] (E = 2*d*F + 1 = {E})")
+    ins = (("features", features), ("transforms", transforms), ("queries", queries), ("keys", keys),
+           ("frequencies", frequencies), ("distance_transforms", distance_transforms))
+    for name, t in ins:
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} is on {t.device}: aggregate_neighbors_heads runs on the GPU only (no CPU fallback)")
+    if H < 1 or H > MAX_HEADS:
+        raise NotImplementedError(f"H = {H} heads: one launch serves 1 <= H <= {MAX_HEADS}; H separate aggregate_neighbors "
+                                  f"calls remain available")
+    if H == 1:       # the single-head entry points
+        return aggregate(nb, features, transforms[0], queries[:, 0], keys[:, 0], frequencies, distance_transforms[0])[:, None]
+    why = heads_refusal(nb.means.dtype, H, L, K, F)
+    if why is not None:
+        raise NotImplementedError(f"aggregate_neighbors_heads: {why}; H separate aggregate_neighbors calls remain available")
+    return _AggregateHeads.apply(nb, features, transforms, queries, keys, frequencies, distance_transforms)

@@ -679,6 +679,446 @@ __global__ __launch_bounds__(256) void aggregate_zero_kernel(T* a, int64_t na, T
 }
 
 // ------------------------------------------------------------------------------------------
+// All H heads of an attention layer in one launch (pigs_aggregate_heads_*; 2 <= H <= HMAX, H = 1 is the kernels
+// above).  The heads share features, frequencies and the lists, so everything a pair's geometry gives -- the list
+// entry, q, g, the 4F sin / cos values, the features row -- is computed once per pair; a head owns its key dot, its
+// softmax state and its accumulators.  Same shape as above (wpg waves per Gaussian, phase 1 lane = pair, phase 2
+// lane = component).  H is a wave-uniform bound: every per-head array is indexed by the fully unrolled h < HMAX
+// only, so that it stays in registers.
+//   queries, keys [N][H][K]; transforms [H][L][L]; distance_transforms [H][L][2E];
+//   out [N][H][L]; lse [N][H]; acc [N][H][L + 2E]; dacc [N][H][L + 2E]; D [N][H]
+// ------------------------------------------------------------------------------------------
+constexpr int HMAX = PIGS_AGGREGATE_HEADS_MAX;
+#define PIGS_FOR_HEADS(h) _Pragma("unroll") for (int h = 0; h < HMAX; ++h) if (h < H)
+
+// phase 2 of the forward: a parked value is read once and feeds H accumulators; `scale_of(h, t)` returns head h's two
+// candidates (wave-uniform, from lane t), `second` chooses per lane
+template <typename T, typename Scale>
+__device__ __forceinline__ void run_rows_heads(const T* X, int xs, int idx, int cnt, int H, bool second, T* acc, Scale&& scale_of) {
+    int t = 0;
+    for (; t + 4 <= cnt; t += 4) {
+        T x[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) x[u] = X[(size_t)(t + u) * xs + idx];
+        PIGS_FOR_HEADS(h) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                T sA, sB;
+                scale_of(h, t + u, &sA, &sB);
+                acc[h] += (second ? sB : sA) * x[u];
+            }
+        }
+    }
+    for (; t < cnt; ++t) {
+        const T x = X[(size_t)t * xs + idx];
+        PIGS_FOR_HEADS(h) {
+            T sA, sB;
+            scale_of(h, t, &sA, &sB);
+            acc[h] += (second ? sB : sA) * x;
+        }
+    }
+}
+
+// phase 2 of the two backward kernels: one accumulator per lane, `pick(t)` returns the lane's own scale of row t
+// (chosen by the lane's head among the heads' wave-uniform candidates)
+template <typename T, typename Pick>
+__device__ __forceinline__ T run_rows_pick(const T* X, int xs, int idx, int cnt, Pick&& pick) {
+    T acc = 0;
+    int t = 0;
+    for (; t + 4 <= cnt; t += 4) {
+        T x[4], s[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            x[u] = X[(size_t)(t + u) * xs + idx];
+            s[u] = pick(t + u);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc += s[u] * x[u];
+    }
+    for (; t < cnt; ++t) acc += pick(t) * X[(size_t)t * xs + idx];
+    return acc;
+}
+
+// forward.  LDS row of a pair: unchanged (nothing in it depends on the head).  A wave's partial result: H blocks
+// [acc (128) ; m ; sum w ; sum w g] of PART values.
+template <typename T, bool PER>
+__global__ __launch_bounds__(256) void aggregate_heads_forward_kernel(
+    int64_t N, int H, int L, int K, int F, int64_t cap, int wpg, const T* __restrict__ means, const T* __restrict__ conics,
+    const int32_t* __restrict__ counts, const int32_t* __restrict__ lists, const T* __restrict__ features,
+    const T* __restrict__ transforms, const T* __restrict__ queries, const T* __restrict__ keys,
+    const T* __restrict__ freq, const T* __restrict__ dists, T* __restrict__ out, T* __restrict__ lse,
+    T* __restrict__ acc_out, T period) {
+    extern __shared__ unsigned char smem_raw[];
+    const WaveSlot ws = wave_slot(N, wpg);
+    const int lane = ws.lane;
+    const int64_t i = ws.valid ? ws.i : 0;
+    const int C4 = 4 * F, E = C4 + 1, W = L + 2 * E;
+    const int WC = L + 2 * C4;
+    const int xs = (L + C4) | 1;
+    const int region = 64 * xs > H * PART ? 64 * xs : H * PART;
+    T* X = (T*)smem_raw + (size_t)ws.wave * region;
+    const T inv_sqrt_k = T(1) / sqrt((T)K);
+    const int n = ws.valid ? counts[i] : 0;
+    const int32_t* row = lists + i * cap;
+    const T* qi = queries + i * H * K;           // wave-uniform: scalar loads
+    T m[HMAX], l[HMAX], lg[HMAX], acc0[HMAX], acc1[HMAX];      // a softmax state and two components per head
+#pragma unroll
+    for (int h = 0; h < HMAX; ++h) { m[h] = -INFINITY; l[h] = 0; lg[h] = 0; acc0[h] = 0; acc1[h] = 0; }
+    const int c0 = lane, c1 = lane + 64;
+    const int idx0 = c0 < L + C4 ? c0 : c0 - C4, idx1 = c1 < L + C4 ? c1 : c1 - C4;
+    const bool dens0 = c0 >= L + C4, dens1 = c1 >= L + C4;
+    for (int j0 = ws.g * 64; j0 < n; j0 += 64 * wpg) {
+        const bool have = j0 + lane < n;
+        int64_t j = i;
+        int kim = 0;
+        if (have) decode_entry<PER>(row[j0 + lane], &j, &kim);
+        T dx, dy;
+        const T q = q_of<T, PER>(means, conics, i, j, &dx, &dy, kim, period);
+        const T g = exp_<T>(T(-0.5) * q);
+        const T* kj = keys + j * H * K;          // the H key rows of a Gaussian are contiguous
+        T w[HMAX], wg[HMAX];
+#pragma unroll
+        for (int h = 0; h < HMAX; ++h) { w[h] = 0; wg[h] = 0; }
+        PIGS_FOR_HEADS(h) {
+            T s = 0;
+            for_row<T>(kj + h * K, K, [&](int k, T v) { s += qi[h * K + k] * v; });
+            s = have ? s * inv_sqrt_k : -INFINITY;
+            const T mnew = fmax(m[h], wave_max(s));      // a running maximum of the head's own
+            const T resc = exp_<T>(m[h] - mnew);
+            w[h] = have ? exp_<T>(s - mnew) : T(0);
+            wg[h] = w[h] * g;
+            l[h] = l[h] * resc + w[h];
+            lg[h] = lg[h] * resc + wg[h];
+            acc0[h] *= resc; acc1[h] *= resc;
+            m[h] = mnew;
+        }
+        wave_lds_fence();
+        T* xr = X + (size_t)lane * xs;
+        for_row<T>(features + j * L, L, [&](int c, T v) { xr[c] = v; });
+        for (int k = 0; k < F; ++k) {
+            T sx, cx, sy, cy;
+            sincos_<T>(freq[k] * dx, &sx, &cx);
+            sincos_<T>(freq[k] * dy, &sy, &cy);
+            xr[L + 4 * k] = sx; xr[L + 4 * k + 1] = cx; xr[L + 4 * k + 2] = sy; xr[L + 4 * k + 3] = cy;
+        }
+        wave_lds_fence();
+        const int cnt = n - j0 < 64 ? n - j0 : 64;
+        auto scale_of = [&](int h, int t, T* a, T* b) { *a = lane_value(w[h], t); *b = lane_value(wg[h], t); };
+        if (c0 < WC) run_rows_heads<T>(X, xs, idx0, cnt, H, dens0, acc0, scale_of);
+        if (WC > 64 && c1 < WC) run_rows_heads<T>(X, xs, idx1, cnt, H, dens1, acc1, scale_of);
+    }
+    PIGS_FOR_HEADS(h) { l[h] = wave_sum(l[h]); lg[h] = wave_sum(lg[h]); }
+    wave_lds_fence();
+    PIGS_FOR_HEADS(h) {
+        T* P = X + h * PART;
+        P[c0] = acc0[h]; P[c1] = acc1[h];
+        if (lane == 0) { P[128] = m[h]; P[129] = l[h]; P[130] = lg[h]; }
+    }
+    __syncthreads();
+    if (ws.g != 0 || !ws.valid) return;
+    T lse_h[HMAX], ag[HMAX];                     // per head: log-sum-exp, sum a g
+    PIGS_FOR_HEADS(h) {
+        const T* P = X + h * PART;
+        T mstar = -INFINITY;
+        for (int w = 0; w < wpg; ++w) mstar = fmax(mstar, P[(size_t)w * region + 128]);
+        T lt = 0, lgt = 0, a0 = 0, a1 = 0;
+        for (int w = 0; w < wpg; ++w) {
+            const T* Pw = P + (size_t)w * region;
+            const T f = exp_<T>(Pw[128] - mstar);        // a wave without a round: m = -inf, factor 0
+            lt += f * Pw[129]; lgt += f * Pw[130];
+            a0 += f * Pw[c0]; a1 += f * Pw[c1];
+        }
+        const T inv_l = T(1) / lt;               // n >= 1: every Gaussian is its own neighbour (q_ii = 0)
+        acc0[h] = a0 * inv_l; acc1[h] = a1 * inv_l;
+        ag[h] = lgt * inv_l;
+        lse_h[h] = mstar + log(lt);
+    }
+    // layout of a head's acc: [fbar (L) ; e (4F), 1 ; g e (4F), sum a g]
+    wave_lds_fence();                            // this wave's partials have been read by every lane above
+    PIGS_FOR_HEADS(h) {
+        T* sh = X + h * PART;
+        T* ao = acc_out + (i * H + h) * W;
+        auto put = [&](int c, T v) {
+            const int o = c < L + C4 ? c : c + 1;
+            sh[o] = v;
+            ao[o] = v;
+        };
+        if (c0 < WC) put(c0, acc0[h]);
+        if (c1 < WC) put(c1, acc1[h]);
+        if (lane == 0) {
+            sh[L + E - 1] = T(1); ao[L + E - 1] = T(1);
+            sh[L + 2 * E - 1] = ag[h]; ao[L + 2 * E - 1] = ag[h];
+            lse[i * H + h] = lse_h[h];
+        }
+    }
+    wave_lds_fence();
+    for (int r = lane; r < H * L; r += 64) {     // out_{i,h} = transform_h fbar_h + distance_transform_h ebar_h
+        const int h = r / L, rr = r - h * L;
+        const T* sh = X + h * PART;
+        const T* tr = transforms + ((size_t)h * L + rr) * L;
+        const T* di = dists + ((size_t)h * L + rr) * 2 * E;
+        T o = 0;
+        for (int c = 0; c < L; ++c) o += tr[c] * sh[c];
+        for (int c = 0; c < 2 * E; ++c) o += di[c] * sh[L + c];
+        out[i * H * L + r] = o;
+    }
+}
+
+// backward by rows.  Prologue: dacc_{i,h} and D_{i,h} per head (H PART values of LDS).  The sin / cos values of a pair
+// are computed once and consumed by every head; a pair's frequency share is summed over the heads in phase 1.
+// LDS row of a pair: [keys_j of the H heads (H K) ; frequency terms (F)]; components [d queries (H K) ; d frequencies (F)].
+template <typename T, bool PER>
+__global__ __launch_bounds__(256) void aggregate_heads_backward_rows_kernel(
+    int64_t N, int H, int L, int K, int F, int64_t cap, int wpg, const T* __restrict__ means, const T* __restrict__ conics,
+    const int32_t* __restrict__ counts, const int32_t* __restrict__ lists, const T* __restrict__ features,
+    const T* __restrict__ transforms, const T* __restrict__ queries, const T* __restrict__ keys, const T* __restrict__ freq,
+    const T* __restrict__ dists, const T* __restrict__ lse, const T* __restrict__ acc_in, const T* __restrict__ gout,
+    T* __restrict__ dacc_out, T* __restrict__ D_out, T* __restrict__ g_queries, T* __restrict__ g_freq_rows, T period) {
+    extern __shared__ unsigned char smem_raw[];
+    const WaveSlot ws = wave_slot(N, wpg);
+    const int lane = ws.lane;
+    const int64_t i = ws.valid ? ws.i : 0;
+    const int E = 4 * F + 1, W = L + 2 * E;
+    const int HK = H * K, WC = HK + F;
+    const int xs = WC | 1;
+    const int region = H * PART + (64 * xs > PART ? 64 * xs : PART);     // per wave: the heads' dacc_i, then the parked rows / the partial
+    T* DA = (T*)smem_raw + (size_t)ws.wave * region;
+    T* X = DA + H * PART;
+    const bool first = ws.g == 0 && ws.valid;
+    T D[HMAX], lse_i[HMAX];
+    PIGS_FOR_HEADS(h) {
+        const T* gh = gout + (i * H + h) * L;
+        const T* tr = transforms + (size_t)h * L * L;
+        const T* di = dists + (size_t)h * L * 2 * E;
+        const T* ai = acc_in + (i * H + h) * W;
+        T Dp = 0;
+        for (int c = lane; c < W; c += 64) {
+            T v = 0;
+            for (int r = 0; r < L; ++r) v += gh[r] * (c < L ? tr[r * L + c] : di[r * 2 * E + (c - L)]);
+            DA[h * PART + c] = v;
+            if (first) dacc_out[(i * H + h) * W + c] = v;
+            Dp += v * ai[c];
+        }
+        D[h] = wave_sum(Dp);
+        if (lane == 0 && first) D_out[i * H + h] = D[h];
+        lse_i[h] = lse[i * H + h];
+    }
+    wave_lds_fence();
+    const T inv_sqrt_k = T(1) / sqrt((T)K);
+    const int n = ws.valid ? counts[i] : 0;
+    const int32_t* row = lists + i * cap;
+    const T* qi = queries + i * HK;
+    T acc0 = 0, acc1 = 0;                        // components lane, lane + 64
+    const int c0 = lane, c1 = lane + 64;
+    const int hd0 = c0 < HK ? c0 / K : -1, hd1 = c1 < HK ? c1 / K : -1;      // the lane's head; -1: a frequency (scale 1)
+    for (int j0 = ws.g * 64; j0 < n; j0 += 64 * wpg) {
+        const bool have = j0 + lane < n;
+        int64_t j = i;
+        int kim = 0;
+        if (have) decode_entry<PER>(row[j0 + lane], &j, &kim);
+        T dx, dy;
+        const T q = q_of<T, PER>(means, conics, i, j, &dx, &dy, kim, period);
+        const T g = exp_<T>(T(-0.5) * q);
+        wave_lds_fence();
+        T* xr = X + (size_t)lane * xs;
+        const T* kj = keys + j * HK;
+        T a[HMAX], da[HMAX], ds[HMAX];
+#pragma unroll
+        for (int h = 0; h < HMAX; ++h) { a[h] = 0; da[h] = 0; ds[h] = 0; }
+        PIGS_FOR_HEADS(h) {
+            T s = 0;
+            for_row<T>(kj + h * K, K, [&](int k, T v) { xr[h * K + k] = v; s += qi[h * K + k] * v; });
+            a[h] = exp_<T>(s * inv_sqrt_k - lse_i[h]);
+        }
+        for_row<T>(features + j * L, L, [&](int c, T v) { PIGS_FOR_HEADS(h) da[h] += DA[h * PART + c] * v; });
+        for (int k = 0; k < F; ++k) {
+            T sx, cx, sy, cy;
+            sincos_<T>(freq[k] * dx, &sx, &cx);
+            sincos_<T>(freq[k] * dy, &sy, &cy);
+            T ft = 0;
+            PIGS_FOR_HEADS(h) {
+                const T* de = DA + h * PART + L;
+                const T e0 = de[4 * k] + g * de[E + 4 * k], e1 = de[4 * k + 1] + g * de[E + 4 * k + 1];
+                const T e2 = de[4 * k + 2] + g * de[E + 4 * k + 2], e3 = de[4 * k + 3] + g * de[E + 4 * k + 3];
+                da[h] += e0 * sx + e1 * cx + e2 * sy + e3 * cy;
+                ft += a[h] * (dx * (e0 * cx - e1 * sx) + dy * (e2 * cy - e3 * sy));
+            }
+            xr[HK + k] = ft;
+        }
+        PIGS_FOR_HEADS(h) {
+            const T* de = DA + h * PART + L;
+            da[h] += de[E - 1] + g * de[2 * E - 1];
+            ds[h] = have ? a[h] * (da[h] - D[h]) : T(0);
+        }
+        wave_lds_fence();
+        const int cnt = n - j0 < 64 ? n - j0 : 64;
+        auto pick_for = [&](int hd) {
+            return [&, hd](int t) {
+                T s = T(1);
+                PIGS_FOR_HEADS(h) {
+                    const T v = lane_value(ds[h], t);
+                    s = hd == h ? v : s;
+                }
+                return s;
+            };
+        };
+        if (c0 < WC) acc0 += run_rows_pick<T>(X, xs, c0, cnt, pick_for(hd0));
+        if (WC > 64 && c1 < WC) acc1 += run_rows_pick<T>(X, xs, c1, cnt, pick_for(hd1));
+    }
+    wave_lds_fence();
+    X[c0] = acc0; X[c1] = acc1;
+    __syncthreads();
+    if (!first) return;
+    acc0 = 0; acc1 = 0;
+    for (int w = 0; w < wpg; ++w) { acc0 += X[(size_t)w * region + c0]; acc1 += X[(size_t)w * region + c1]; }
+    auto put = [&](int c, T v) {
+        if (c < HK) g_queries[i * HK + c] = v * inv_sqrt_k;
+        else g_freq_rows[i * F + (c - HK)] = v;
+    };
+    if (c0 < WC) put(c0, acc0);
+    if (c1 < WC) put(c1, acc1);
+}
+
+// backward by columns, a gather (no atomics): d features_j [L] = sum over the heads, d keys_j [H][K] per head.
+// LDS row of a pair: [dfbar_{i,h} of the H heads (H L) ; queries_i of the H heads (H K)]; components = the same
+// H (L + K): the heads' shares of d features_j meet in the epilogue.
+template <typename T, bool PER>
+__global__ __launch_bounds__(256) void aggregate_heads_backward_cols_kernel(
+    int64_t N, int H, int L, int K, int F, int64_t cap, int wpg, const T* __restrict__ means, const T* __restrict__ conics,
+    const int32_t* __restrict__ counts, const int32_t* __restrict__ lists, const T* __restrict__ features,
+    const T* __restrict__ queries, const T* __restrict__ keys, const T* __restrict__ freq, const T* __restrict__ lse,
+    const T* __restrict__ dacc, const T* __restrict__ D, T* __restrict__ g_features, T* __restrict__ g_keys, T period) {
+    extern __shared__ unsigned char smem_raw[];
+    const WaveSlot ws = wave_slot(N, wpg);
+    const int lane = ws.lane;
+    const int64_t j = ws.valid ? ws.i : 0;
+    const int E = 4 * F + 1, W = L + 2 * E;
+    const int HL = H * L, HK = H * K, WC = HL + HK;
+    const int xs = WC | 1;
+    const int region = 64 * xs > PART ? 64 * xs : PART;
+    T* X = (T*)smem_raw + (size_t)ws.wave * region;
+    const T inv_sqrt_k = T(1) / sqrt((T)K);
+    const int n = ws.valid ? counts[j] : 0;
+    const int32_t* col = lists + j * cap;
+    const T* kj = keys + j * HK;                 // wave-uniform
+    const T* fj = features + j * L;
+    T acc0 = 0, acc1 = 0;                        // components lane, lane + 64
+    const int c0 = lane, c1 = lane + 64;
+    const int hd0 = c0 < HL ? c0 / L : (c0 - HL) / K, hd1 = c1 < HL ? c1 / L : (c1 - HL) / K;
+    for (int s0 = ws.g * 64; s0 < n; s0 += 64 * wpg) {
+        const bool have = s0 + lane < n;
+        int64_t i = j;
+        int kim = 0;
+        if (have) decode_entry<PER>(col[s0 + lane], &i, &kim);
+        T dx, dy;
+        const T q = q_of<T, PER>(means, conics, i, j, &dx, &dy, kim, period);
+        const T g = exp_<T>(T(-0.5) * q);
+        wave_lds_fence();
+        T* xr = X + (size_t)lane * xs;
+        T a[HMAX], da[HMAX], ds[HMAX];
+#pragma unroll
+        for (int h = 0; h < HMAX; ++h) { a[h] = 0; da[h] = 0; ds[h] = 0; }
+        PIGS_FOR_HEADS(h) {
+            T s = 0;
+            for_row<T>(dacc + (i * H + h) * W, L, [&](int c, T v) { xr[h * L + c] = v; da[h] += v * fj[c]; });
+            for_row<T>(queries + (i * H + h) * K, K, [&](int k, T v) { xr[HL + h * K + k] = v; s += v * kj[h * K + k]; });
+            a[h] = exp_<T>(s * inv_sqrt_k - lse[i * H + h]);
+        }
+        for (int k = 0; k < F; ++k) {
+            T sx, cx, sy, cy;
+            sincos_<T>(freq[k] * dx, &sx, &cx);
+            sincos_<T>(freq[k] * dy, &sy, &cy);
+            PIGS_FOR_HEADS(h) {
+                const T* de = dacc + (i * H + h) * W + L;
+                const T e0 = de[4 * k] + g * de[E + 4 * k], e1 = de[4 * k + 1] + g * de[E + 4 * k + 1];
+                const T e2 = de[4 * k + 2] + g * de[E + 4 * k + 2], e3 = de[4 * k + 3] + g * de[E + 4 * k + 3];
+                da[h] += e0 * sx + e1 * cx + e2 * sy + e3 * cy;
+            }
+        }
+        PIGS_FOR_HEADS(h) {
+            const T* de = dacc + (i * H + h) * W + L;
+            da[h] += de[E - 1] + g * de[2 * E - 1];
+            ds[h] = have ? a[h] * (da[h] - D[i * H + h]) : T(0);
+            if (!have) a[h] = 0;
+        }
+        wave_lds_fence();
+        const int cnt = n - s0 < 64 ? n - s0 : 64;
+        auto pick_for = [&](int hd, bool second) {
+            return [&, hd, second](int t) {
+                T s = 0;
+                PIGS_FOR_HEADS(h) {
+                    const T va = lane_value(a[h], t), vd = lane_value(ds[h], t);
+                    s = hd == h ? (second ? vd : va) : s;
+                }
+                return s;
+            };
+        };
+        if (c0 < WC) acc0 += run_rows_pick<T>(X, xs, c0, cnt, pick_for(hd0, c0 >= HL));
+        if (WC > 64 && c1 < WC) acc1 += run_rows_pick<T>(X, xs, c1, cnt, pick_for(hd1, c1 >= HL));
+    }
+    wave_lds_fence();
+    X[c0] = acc0; X[c1] = acc1;
+    __syncthreads();
+    if (ws.g != 0 || !ws.valid) return;
+    for (int c = lane; c < L; c += 64) {         // d features_j: the waves' and the heads' shares
+        T v = 0;
+        for (int w = 0; w < wpg; ++w)
+            for (int h = 0; h < H; ++h) v += X[(size_t)w * region + h * L + c];
+        g_features[j * L + c] = v;
+    }
+    for (int c = lane; c < HK; c += 64) {
+        T v = 0;
+        for (int w = 0; w < wpg; ++w) v += X[(size_t)w * region + HL + c];
+        g_keys[j * HK + c] = v * inv_sqrt_k;
+    }
+}
+
+// the sums over the Gaussians, per head: d [transform_h | distance_transform_h] = gout_h^T acc_h; d frequencies =
+// column sums of the per-row shares (which already hold the heads' sum).  Structure and `splits` as above.
+template <typename T>
+__global__ __launch_bounds__(256) void aggregate_heads_outer_kernel(int64_t N, int H, int L, int F, int splits,
+                                                                    const T* __restrict__ gout, const T* __restrict__ acc,
+                                                                    const T* __restrict__ g_freq_rows, T* __restrict__ g_transforms,
+                                                                    T* __restrict__ g_dists, T* __restrict__ g_freq) {
+    __shared__ T sh[256];
+    const int E = 4 * F + 1, W = L + 2 * E;
+    const int col = blockIdx.x / splits, sp = blockIdx.x % splits;
+    const bool is_freq = col >= H * W;
+    const int h = is_freq ? 0 : col / W, c = is_freq ? col - H * W : col - h * W;
+    const int64_t per = (N + splits - 1) / splits;
+    const int64_t i0 = sp * per, i1 = i0 + per < N ? i0 + per : N;
+    const int R = is_freq ? 1 : L;
+    int Rp = 1;
+    while (Rp < R) Rp <<= 1;
+    const int S = 256 / Rp;
+    const int r = threadIdx.x % Rp, sl = threadIdx.x / Rp;
+    T v = 0;
+    if (r < R) {
+        if (!is_freq) {
+            const T* gh = gout + (size_t)h * L + r;
+            const T* ah = acc + (size_t)h * W + c;
+#pragma unroll 8
+            for (int64_t i = i0 + sl; i < i1; i += S) v += gh[i * H * L] * ah[i * H * W];
+        } else {
+#pragma unroll 8
+            for (int64_t i = i0 + sl; i < i1; i += S) v += g_freq_rows[i * F + c];
+        }
+    }
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    if (threadIdx.x < R) {
+        T tot = 0;
+        for (int k = 0; k < S; ++k) tot += sh[k * Rp + threadIdx.x];
+        T* dst = is_freq ? g_freq + c
+                 : c < L ? g_transforms + ((size_t)h * L + threadIdx.x) * L + c
+                         : g_dists + ((size_t)h * L + threadIdx.x) * 2 * E + (c - L);
+        if (splits == 1) *dst = tot;
+        else atomicAdd(dst, tot);
+    }
+}
+#undef PIGS_FOR_HEADS
+
+// ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
 static size_t cast_bytes(int dtype, int64_t N) {       // float32 copies of centres and conics (float64 callers)
@@ -783,6 +1223,30 @@ size_t aggregate_lds_bytes(int dtype, int L, int K, int F) {
     const size_t a = forward_region(L, F), b = backward_rows_region(K, F), c = backward_cols_region(L, K);
     return (dtype == PIGS_F64 ? 8 : 4) * 4 * (a > b ? (a > c ? a : c) : (b > c ? b : c));
 }
+// The heads' kernels (2 <= H <= HMAX): the forward's row is unchanged and its merge region holds H partials; the
+// backward by rows keeps H dacc blocks and parks [H K keys ; F]; the backward by columns parks H (L + K) values.
+static size_t heads_forward_region(int H, int L, int F) {
+    const size_t r = forward_region(L, F);
+    return r > (size_t)H * PART ? r : (size_t)H * PART;
+}
+static size_t heads_backward_rows_region(int H, int K, int F) { return (size_t)H * PART + rows_region((H * K + F) | 1); }
+static size_t heads_backward_cols_region(int H, int L, int K) { return rows_region((H * (L + K)) | 1); }
+// THE size rule of the heads' entry points, in one place: 1 <= H <= HMAX, at most 128 components per kernel (two per
+// lane) and every kernel's LDS within a CU's.  Returns the most dynamic LDS any of the three kernels asks for, or 0
+// when H or a component count is out of range; a shape is admitted when 0 < bytes <= AGG_LDS_MAX.  Anything beyond is
+// refused, not attempted.  (H = 1: the single-head kernels and, by the same formulas, their rule.)
+size_t aggregate_heads_lds_bytes(int dtype, int H, int L, int K, int F) {
+    if (H < 1 || H > HMAX) return 0;
+    if (L + 2 * (4 * F + 1) > 128 || H * K + F > 128 || H * (L + K) > 128) return 0;
+    if (H == 1) return aggregate_lds_bytes(dtype, L, K, F);
+    const size_t a = heads_forward_region(H, L, F), b = heads_backward_rows_region(H, K, F), c = heads_backward_cols_region(H, L, K);
+    return (dtype == PIGS_F64 ? 8 : 4) * 4 * (a > b ? (a > c ? a : c) : (b > c ? b : c));
+}
+bool aggregate_heads_admitted(int dtype, int H, int L, int K, int F) {
+    const size_t bytes = aggregate_heads_lds_bytes(dtype, H, L, K, F);
+    return bytes != 0 && bytes <= AGG_LDS_MAX;
+}
+
 // waves per Gaussian: a launch of few Gaussians is one generation of waves bound by a wave's serial life
 // (split every Gaussian's rounds over four waves); many Gaussians are a throughput problem (no idle waves)
 static int waves_per_gaussian(int64_t N) { return N <= 4096 ? 4 : N <= 8192 ? 2 : 1; }
@@ -853,6 +1317,98 @@ int aggregate_backward(const AggregateArgs& a, hipStream_t stream) {
     if (a.N == 0) return PIGS_OK;
     if (a.period > 0) return a.dtype == PIGS_F32 ? aggregate_backward_t<float, true>(a, stream) : aggregate_backward_t<double, true>(a, stream);
     return a.dtype == PIGS_F32 ? aggregate_backward_t<float, false>(a, stream) : aggregate_backward_t<double, false>(a, stream);
+}
+
+// Waves per Gaussian of a heads' kernel.  Up to AGG_BRUTE_MAX Gaussians (the model's sizes) a launch is bound by a
+// wave's serial life, and the heads' kernels ask for more LDS than the single-head ones, so fewer of their workgroups
+// are resident at once: the waves per Gaussian are halved while the launch's workgroups exceed what the device holds
+// (AGG_CUS compute units, per CU what the LDS request admits, at most the eight workgroups of 32 waves).
+// What stands behind the rule is ONE sweep (profiles/aggregate_heads.txt "waves per Gaussian"):
+// the model's shape, H = 2, N = 1 600, 4 / 2 / 1 waves, float32 and float64.  There it picks 1 wave for all three
+// kernels in both dtypes; that is the best or within 1 us of it for the kernel by rows and for float64's forward and
+// rows, and it passes over the better 2-wave launch of float32's forward (25.5 against 27.9 us), float32's columns
+// (60.1 against 65.5) and float64's columns (117.7 against 123.9): 800 workgroups against 768 resident.  It is
+// applied unmeasured to H = 3, 4 and to other shapes.  Beyond AGG_BRUTE_MAX: the single-head rule, as measured there.
+constexpr int AGG_CUS = 256;                     // compute units of an MI355X (the one device this library is built for)
+static int heads_waves_per_gaussian(int64_t N, size_t lds_bytes) {
+    int wpg = waves_per_gaussian(N);
+    if (N > AGG_BRUTE_MAX) return wpg;
+    size_t per_cu = AGG_LDS_MAX / (lds_bytes > 0 ? lds_bytes : 1);
+    per_cu = per_cu > 8 ? 8 : per_cu < 1 ? 1 : per_cu;      // 32 waves a CU: eight workgroups of four
+    const int64_t resident = (int64_t)AGG_CUS * (int64_t)per_cu;
+    while (wpg > 1 && (N * wpg + 3) / 4 > resident) wpg >>= 1;
+    return wpg;
+}
+
+// ---- the heads' launchers (2 <= a.H <= HMAX and an admitted shape: capi.hip checks; H = 1 goes to the ones above)
+template <typename T, bool PER>
+static int aggregate_heads_forward_t(const AggregateArgs& a, hipStream_t stream) {
+    int rc = PIGS_OK;
+    const size_t lds = sampling_lds(aggregate_heads_forward_kernel<T, PER>, sizeof(T), heads_forward_region(a.H, a.L, a.F), &rc);
+    if (rc != PIGS_OK) return rc;
+    const int wpg = heads_waves_per_gaussian(a.N, lds), gpw = 4 / wpg;
+    clear_hip_error();
+    hipLaunchKernelGGL((aggregate_heads_forward_kernel<T, PER>), dim3((unsigned)((a.N + gpw - 1) / gpw)), dim3(256), lds, stream, a.N,
+                       a.H, a.L, a.K, a.F, a.cap, wpg, (const T*)a.means, (const T*)a.conics, a.row_counts, a.row_lists,
+                       (const T*)a.features, (const T*)a.transform, (const T*)a.queries, (const T*)a.keys, (const T*)a.frequencies,
+                       (const T*)a.distance_transform, (T*)a.out, (T*)a.lse, (T*)a.acc, (T)a.period);
+    return launch_status();
+}
+
+size_t aggregate_heads_backward_scratch_bytes(int dtype, int64_t N, int H, int L, int F) {
+    const size_t e = dtype == PIGS_F64 ? 8 : 4;
+    const int W = L + 2 * (4 * F + 1);
+    return align_up(e * (size_t)N * (size_t)(H * (W + 1) + F), 256);      // dacc [N][H][W], D [N][H], per-row d frequencies [N][F]
+}
+
+template <typename T, bool PER>
+static int aggregate_heads_backward_t(const AggregateArgs& a, hipStream_t stream) {
+    const int H = a.H, E = 4 * a.F + 1, W = a.L + 2 * E;
+    T* dacc = (T*)a.scratch;
+    T* D = dacc + (size_t)a.N * H * W;
+    T* gfr = D + (size_t)a.N * H;
+    int rc = PIGS_OK;
+    const size_t lds_r = sampling_lds(aggregate_heads_backward_rows_kernel<T, PER>, sizeof(T), heads_backward_rows_region(H, a.K, a.F), &rc);
+    const size_t lds_c = sampling_lds(aggregate_heads_backward_cols_kernel<T, PER>, sizeof(T), heads_backward_cols_region(H, a.L, a.K), &rc);
+    if (rc != PIGS_OK) return rc;
+    const int wpgr = heads_waves_per_gaussian(a.N, lds_r), wpgc = heads_waves_per_gaussian(a.N, lds_c);
+    const dim3 gridr((unsigned)((a.N + 4 / wpgr - 1) / (4 / wpgr))), gridc((unsigned)((a.N + 4 / wpgc - 1) / (4 / wpgc))), block(256);
+    int splits = (int)((a.N + 2047) / 2048);     // the rule of aggregate_backward_t
+    splits = splits < 1 ? 1 : splits > 64 ? 64 : splits;
+    clear_hip_error();
+    if (splits > 1) {
+        const int64_t mx = (int64_t)H * a.L * (2 * E > a.L ? 2 * E : a.L);
+        hipLaunchKernelGGL((aggregate_zero_kernel<T>), dim3((unsigned)((mx + 255) / 256)), dim3(256), 0, stream, (T*)a.g_transform,
+                           (int64_t)H * a.L * a.L, (T*)a.g_distance_transform, (int64_t)H * a.L * 2 * E, (T*)a.g_frequencies,
+                           (int64_t)a.F);
+    }
+    hipLaunchKernelGGL((aggregate_heads_backward_rows_kernel<T, PER>), gridr, block, lds_r, stream, a.N, H, a.L, a.K, a.F,
+                       a.cap, wpgr, (const T*)a.means, (const T*)a.conics, a.row_counts, a.row_lists, (const T*)a.features,
+                       (const T*)a.transform, (const T*)a.queries, (const T*)a.keys, (const T*)a.frequencies,
+                       (const T*)a.distance_transform, (const T*)a.lse, (const T*)a.acc, (const T*)a.gout, dacc, D,
+                       (T*)a.g_queries, gfr, (T)a.period);
+    hipLaunchKernelGGL((aggregate_heads_backward_cols_kernel<T, PER>), gridc, block, lds_c, stream, a.N, H, a.L, a.K, a.F,
+                       a.cap, wpgc, (const T*)a.means, (const T*)a.conics, a.col_counts, a.col_lists, (const T*)a.features,
+                       (const T*)a.queries, (const T*)a.keys, (const T*)a.frequencies, (const T*)a.lse, (const T*)dacc,
+                       (const T*)D, (T*)a.g_features, (T*)a.g_keys, (T)a.period);
+    hipLaunchKernelGGL((aggregate_heads_outer_kernel<T>), dim3((unsigned)((H * W + a.F) * splits)), dim3(256), 0, stream, a.N, H, a.L,
+                       a.F, splits, (const T*)a.gout, (const T*)a.acc, (const T*)gfr, (T*)a.g_transform,
+                       (T*)a.g_distance_transform, (T*)a.g_frequencies);
+    return launch_status();
+}
+
+int aggregate_heads_forward(const AggregateArgs& a, hipStream_t stream) {
+    if (a.H == 1) return aggregate_forward(a, stream);       // [N][1][K] is [N][K]: the single-head kernels
+    if (a.N == 0) return PIGS_OK;
+    if (a.period > 0) return a.dtype == PIGS_F32 ? aggregate_heads_forward_t<float, true>(a, stream) : aggregate_heads_forward_t<double, true>(a, stream);
+    return a.dtype == PIGS_F32 ? aggregate_heads_forward_t<float, false>(a, stream) : aggregate_heads_forward_t<double, false>(a, stream);
+}
+
+int aggregate_heads_backward(const AggregateArgs& a, hipStream_t stream) {
+    if (a.H == 1) return aggregate_backward(a, stream);
+    if (a.N == 0) return PIGS_OK;
+    if (a.period > 0) return a.dtype == PIGS_F32 ? aggregate_heads_backward_t<float, true>(a, stream) : aggregate_heads_backward_t<double, true>(a, stream);
+    return a.dtype == PIGS_F32 ? aggregate_heads_backward_t<float, false>(a, stream) : aggregate_heads_backward_t<double, false>(a, stream);
 }
 
 }  // namespace pigs

@@ -482,4 +482,69 @@ int pigs_aggregate_backward_periodic(int dtype, int64_t N, int64_t cap, int L, i
                                       g_distance_transform, stream);
 }
 
+// ---- all heads of a layer in one launch (additive to ABI 10).  period = 0: plain lists; > 0: the torus's
+static int aggregate_heads_sizes_ok(int dtype, int64_t N, int64_t cap, int H, int L, int K, int F, double period) {
+    if (dtype != PIGS_F32 && dtype != PIGS_F64) return PIGS_ERR_UNSUPPORTED;
+    if (H < 1 || H > PIGS_AGGREGATE_HEADS_MAX) return PIGS_ERR_UNSUPPORTED;
+    if (N < 0 || cap < 1 || L < 1 || K < 1 || F < 0) return PIGS_ERR_INVALID;
+    if (L > 128 || K > 128 || F > 128 || N > 0x7fffffffLL) return PIGS_ERR_UNSUPPORTED;
+    // the forward, too, refuses a shape whose backward could not run
+    if (!aggregate_heads_admitted(dtype, H, L, K, F)) return PIGS_ERR_UNSUPPORTED;
+    if (period != 0.0) return periodic_box_ok(dtype, N, 0.0, period);
+    return PIGS_OK;
+}
+
+size_t pigs_aggregate_heads_lds_bytes(int dtype, int H, int L, int K, int F) {
+    if ((dtype != PIGS_F32 && dtype != PIGS_F64) || L < 1 || K < 1 || F < 0 || L > 128 || K > 128 || F > 128) return 0;
+    return aggregate_heads_lds_bytes(dtype, H, L, K, F);         // 0: H or a component count out of range
+}
+
+size_t pigs_aggregate_heads_backward_scratch_bytes(int dtype, int64_t N, int H, int L, int F) {
+    if ((dtype != PIGS_F32 && dtype != PIGS_F64) || N < 0 || H < 1 || H > PIGS_AGGREGATE_HEADS_MAX || L < 1 || F < 0) return 0;
+    return aggregate_heads_backward_scratch_bytes(dtype, N, H, L, F);
+}
+
+int pigs_aggregate_heads_forward(int dtype, int64_t N, int64_t cap, int H, int L, int K, int F, double period, const void* means,
+                                 const void* conics, const int32_t* row_counts, const int32_t* row_lists, const void* features,
+                                 const void* transforms, const void* queries, const void* keys, const void* frequencies,
+                                 const void* distance_transforms, void* out, void* lse, void* acc, void* stream) {
+    const int rc = aggregate_heads_sizes_ok(dtype, N, cap, H, L, K, F, period);
+    if (rc != PIGS_OK) return rc;
+    if (N > 0 && (!means || !conics || !row_counts || !row_lists || !features || !transforms || !queries || !keys ||
+                  (F > 0 && !frequencies) || !distance_transforms || !out || !lse || !acc))
+        return PIGS_ERR_INVALID;
+    AggregateArgs a{};
+    a.dtype = dtype; a.N = N; a.cap = cap; a.H = H; a.L = L; a.K = K; a.F = F; a.period = period;
+    a.means = means; a.conics = conics; a.row_counts = row_counts; a.row_lists = row_lists;
+    a.features = features; a.transform = transforms; a.queries = queries; a.keys = keys; a.frequencies = frequencies;
+    a.distance_transform = distance_transforms; a.out = out; a.lse = lse; a.acc = acc;
+    return aggregate_heads_forward(a, (hipStream_t)stream);
+}
+
+int pigs_aggregate_heads_backward(int dtype, int64_t N, int64_t cap, int H, int L, int K, int F, double period, const void* means,
+                                  const void* conics, const int32_t* row_counts, const int32_t* row_lists,
+                                  const int32_t* col_counts, const int32_t* col_lists, const void* features,
+                                  const void* transforms, const void* queries, const void* keys, const void* frequencies,
+                                  const void* distance_transforms, const void* lse, const void* acc, const void* gout,
+                                  void* scratch, size_t scratch_bytes, void* g_features, void* g_transforms, void* g_queries,
+                                  void* g_keys, void* g_frequencies, void* g_distance_transforms, void* stream) {
+    const int rc = aggregate_heads_sizes_ok(dtype, N, cap, H, L, K, F, period);
+    if (rc != PIGS_OK) return rc;
+    if (N > 0 && (!means || !conics || !row_counts || !row_lists || !col_counts || !col_lists || !features || !transforms ||
+                  !queries || !keys || (F > 0 && !frequencies) || !distance_transforms || !lse || !acc || !gout || !scratch ||
+                  !g_features || !g_transforms || !g_queries || !g_keys || (F > 0 && !g_frequencies) || !g_distance_transforms))
+        return PIGS_ERR_INVALID;
+    if (N > 0 && scratch_bytes < aggregate_heads_backward_scratch_bytes(dtype, N, H, L, F)) return PIGS_ERR_WORKSPACE;
+    AggregateArgs a{};
+    a.dtype = dtype; a.N = N; a.cap = cap; a.H = H; a.L = L; a.K = K; a.F = F; a.period = period;
+    a.means = means; a.conics = conics; a.row_counts = row_counts; a.row_lists = row_lists;
+    a.col_counts = col_counts; a.col_lists = col_lists;
+    a.features = features; a.transform = transforms; a.queries = queries; a.keys = keys; a.frequencies = frequencies;
+    a.distance_transform = distance_transforms;
+    a.lse = const_cast<void*>(lse); a.acc = const_cast<void*>(acc); a.gout = gout; a.scratch = scratch;
+    a.g_features = g_features; a.g_transform = g_transforms; a.g_queries = g_queries; a.g_keys = g_keys;
+    a.g_frequencies = g_frequencies; a.g_distance_transform = g_distance_transforms;
+    return aggregate_heads_backward(a, (hipStream_t)stream);
+}
+
 }  // extern "C"

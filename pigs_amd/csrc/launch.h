@@ -48,6 +48,9 @@ struct AggregateArgs {
     const void* gout;                              // backward: incoming gradient [N][L]
     void* scratch;                                 // backward: dacc [N][W], D [N], per-row d frequencies [N][F]
     void *g_features, *g_transform, *g_queries, *g_keys, *g_frequencies, *g_distance_transform;
+    // the heads' entries (aggregate_heads_*): transform [H][L][L], queries / keys [N][H][K], distance_transform [H][L][2E],
+    // out [N][H][L], lse [N][H], acc [N][H][W], gout [N][H][L], scratch dacc [N][H][W], D [N][H], d frequencies [N][F]
+    int H;
 };
 size_t aggregate_backward_scratch_bytes(int dtype, int64_t N, int L, int F);
 size_t aggregate_workspace_bytes(int dtype, int64_t N);
@@ -58,6 +61,11 @@ int aggregate_lists(int dtype, int64_t N, int64_t cap, const void* means, const 
                     int32_t* col_lists, int32_t* overflow, hipStream_t stream, double lo = 0.0, double period = 0.0);
 int aggregate_forward(const AggregateArgs& a, hipStream_t stream);
 int aggregate_backward(const AggregateArgs& a, hipStream_t stream);
+size_t aggregate_heads_lds_bytes(int dtype, int H, int L, int K, int F);
+bool aggregate_heads_admitted(int dtype, int H, int L, int K, int F);         // the heads' size rule (1 <= H <= 4)
+size_t aggregate_heads_backward_scratch_bytes(int dtype, int64_t N, int H, int L, int F);
+int aggregate_heads_forward(const AggregateArgs& a, hipStream_t stream);
+int aggregate_heads_backward(const AggregateArgs& a, hipStream_t stream);
 
 // plan.hip
 size_t samples_workspace_bytes(int64_t M);

@@ -863,6 +863,126 @@ at::Tensor aggregate_apply(const std::shared_ptr<NeighborLists>& nb, const at::T
     return out;
 }
 
+// ---- all heads of a layer in one launch (pigs_aggregate_heads_*).  Same structure as aggregate_heads of
+// pigs_amd/aggregate.py: transforms [H,L,L], queries / keys [N,H,K], distance_transforms [H,L,2E] -> [N,H,L]
+struct AggregateHeadsBackward : public torch::autograd::Node {
+    std::shared_ptr<NeighborLists> nb;
+    at::Tensor f, tr, q, k, fr, dist, lse, acc;     // converted, contiguous, detached
+    uint32_t versions[6] = {0, 0, 0, 0, 0, 0};
+    at::ScalarType in_dtypes[6];
+    int64_t N = 0;
+    int H = 0, L = 0, K = 0, F = 0;
+
+    std::string name() const override { return "PigsAggregateHeadsBackward"; }
+
+    torch::autograd::variable_list apply(torch::autograd::variable_list&& grads) override {
+        if (!f.defined()) throw std::runtime_error("aggregate_neighbors_heads: backward through the graph a second time (saved tensors were freed)");
+        const at::Tensor* saved[6] = {&f, &tr, &q, &k, &fr, &dist};
+        for (int x = 0; x < 6; ++x)
+            if (saved[x]->_version() != versions[x])
+                throw std::runtime_error("one of the tensors handed to aggregate_neighbors_heads() has been modified in place before its backward");
+        if (grads.empty() || !grads[0].defined()) return torch::autograd::variable_list(6);
+        at::AutoGradMode no_grad(false);
+        if (grads[0].requires_grad()) throw std::runtime_error("aggregate_neighbors_heads is differentiable once");
+        const at::Tensor gout = grads[0].to(f.scalar_type()).contiguous();
+        at::Tensor g_f = at::empty_like(f), g_tr = at::empty_like(tr), g_q = at::empty_like(q), g_k = at::empty_like(k),
+                   g_fr = at::empty_like(fr), g_dist = at::empty_like(dist);
+        const int dt = dtype_code(f);
+        if (N > 0) {
+            const size_t nbytes = pigs_aggregate_heads_backward_scratch_bytes(dt, N, H, L, F);
+            at::Tensor scratch = at::empty({(int64_t)nbytes}, f.options().dtype(at::kByte));
+            c10::DeviceGuard guard(f.device());
+            check(pigs_aggregate_heads_backward(dt, N, nb->cap, H, L, K, F, nb->periodic ? nb->period : 0.0, ptr(nb->means),
+                                                ptr(nb->conics), (const int32_t*)ptr(nb->row_counts),
+                                                (const int32_t*)ptr(nb->row_lists), (const int32_t*)ptr(nb->col_counts),
+                                                (const int32_t*)ptr(nb->col_lists), ptr(f), ptr(tr), ptr(q), ptr(k), ptr(fr),
+                                                ptr(dist), ptr(lse), ptr(acc), ptr(gout), scratch.data_ptr(), nbytes, ptr(g_f),
+                                                ptr(g_tr), ptr(g_q), ptr(g_k), ptr(g_fr), ptr(g_dist), current_stream(f)),
+                  "pigs_aggregate_heads_backward");
+        } else {
+            g_tr.zero_(); g_fr.zero_(); g_dist.zero_();
+        }
+        return {g_f.to(in_dtypes[0]), g_tr.to(in_dtypes[1]), g_q.to(in_dtypes[2]), g_k.to(in_dtypes[3]), g_fr.to(in_dtypes[4]),
+                g_dist.to(in_dtypes[5])};
+    }
+    void release_variables() override {
+        f = tr = q = k = fr = dist = lse = acc = at::Tensor();
+    }
+};
+
+at::Tensor aggregate_heads_apply(const std::shared_ptr<NeighborLists>& nb, const at::Tensor& features, const at::Tensor& transforms,
+                                 const at::Tensor& queries, const at::Tensor& keys, const at::Tensor& frequencies,
+                                 const at::Tensor& distance_transforms) {
+    const int64_t N = nb->N;
+    if (features.dim() != 2 || features.size(0) != N)
+        raise_py(PyExc_ValueError, "features must be [N=" + std::to_string(N) + ", L], got " + shape_str(features));
+    if (queries.dim() != 3 || frequencies.dim() != 1)
+        raise_py(PyExc_ValueError, "aggregate_neighbors_heads: queries must be [N=" + std::to_string(N) + ", H, K] and frequencies [F], got " +
+                                       shape_str(queries) + " and " + shape_str(frequencies));
+    const int64_t L = features.size(1), H = queries.size(1), K = queries.size(2), F = frequencies.size(0), E = 4 * F + 1;
+    auto is = [](const at::Tensor& t, std::initializer_list<int64_t> want) { return t.sizes() == at::IntArrayRef(want); };
+    if (!is(transforms, {H, L, L}) || !is(queries, {N, H, K}) || !is(keys, {N, H, K}) || !is(distance_transforms, {H, L, 2 * E}))
+        raise_py(PyExc_ValueError, "aggregate_neighbors_heads: expected transforms [" + std::to_string(H) + "," + std::to_string(L) + "," +
+                                       std::to_string(L) + "], queries/keys [" + std::to_string(N) + "," + std::to_string(H) + "," +
+                                       std::to_string(K) + "], distance_transforms [" + std::to_string(H) + "," + std::to_string(L) + "," +
+                                       std::to_string(2 * E) + "] (E = 2*d*F + 1 = " + std::to_string(E) + ")");
+    const at::Tensor* ins[6] = {&features, &transforms, &queries, &keys, &frequencies, &distance_transforms};
+    const char* names[6] = {"features", "transforms", "queries", "keys", "frequencies", "distance_transforms"};
+    for (int x = 0; x < 6; ++x)
+        if (!ins[x]->is_cuda())
+            raise_py(PyExc_RuntimeError, std::string(names[x]) + " is on " + ins[x]->device().str() +
+                                             ": aggregate_neighbors_heads runs on the GPU only (no CPU fallback)");
+    const std::string remain = "; H separate aggregate_neighbors calls remain available";
+    if (H < 1 || H > PIGS_AGGREGATE_HEADS_MAX)
+        raise_py(PyExc_NotImplementedError, "H = " + std::to_string(H) + " heads: one launch serves 1 <= H <= " +
+                                                std::to_string(PIGS_AGGREGATE_HEADS_MAX) + remain);
+    if (H == 1)      // the single-head entry points
+        return aggregate_apply(nb, features, transforms.select(0, 0), queries.select(1, 0), keys.select(1, 0), frequencies,
+                               distance_transforms.select(0, 0)).unsqueeze(1);
+    const auto dt = nb->means.scalar_type();
+    const int dc = dt == at::kDouble ? PIGS_F64 : PIGS_F32;
+    const std::string shape = std::string(dt == at::kDouble ? "float64" : "float32") + " with H = " + std::to_string(H) + ", L = " +
+                              std::to_string(L) + ", K = " + std::to_string(K) + ", F = " + std::to_string(F);
+    // the size rule is the library's (pigs_aggregate_heads_lds_bytes: 0 = a component count out of range)
+    const size_t lds = pigs_aggregate_heads_lds_bytes(dc, (int)H, (int)L, (int)K, (int)F);
+    if (lds == 0)
+        raise_py(PyExc_NotImplementedError, "aggregate_neighbors_heads: " + shape + " has more than 128 components in one kernel "
+                                                "(L + 2E, H K + F, H (L + K) <= 128)" + remain);
+    if (lds > PIGS_AGGREGATE_LDS_MAX)
+        raise_py(PyExc_NotImplementedError, "aggregate_neighbors_heads: " + shape + " needs " + std::to_string(lds) +
+                                                " bytes of LDS in one of the forward's or the backward's kernels; the limit is " +
+                                                std::to_string(PIGS_AGGREGATE_LDS_MAX) + remain);
+    at::Tensor c[6];
+    {
+        at::AutoGradMode no_grad(false);
+        for (int x = 0; x < 6; ++x) c[x] = ins[x]->detach().to(dt).contiguous();
+    }
+    const auto opt = c[0].options();
+    at::Tensor out = at::empty({N, H, L}, opt), lse = at::empty({N, H}, opt), acc = at::empty({N, H, L + 2 * E}, opt);
+    if (N > 0) {
+        c10::DeviceGuard guard(c[0].device());
+        check(pigs_aggregate_heads_forward(dc, N, nb->cap, (int)H, (int)L, (int)K, (int)F, nb->periodic ? nb->period : 0.0,
+                                           ptr(nb->means), ptr(nb->conics), (const int32_t*)ptr(nb->row_counts),
+                                           (const int32_t*)ptr(nb->row_lists), ptr(c[0]), ptr(c[1]), ptr(c[2]), ptr(c[3]), ptr(c[4]),
+                                           ptr(c[5]), ptr(out), ptr(lse), ptr(acc), current_stream(c[0])),
+              "pigs_aggregate_heads_forward");
+    }
+    if (out.scalar_type() != features.scalar_type()) out = out.to(features.scalar_type());
+    bool need = false;
+    for (int x = 0; x < 6; ++x) need = need || ins[x]->requires_grad();
+    if (at::GradMode::is_enabled() && need) {
+        std::shared_ptr<AggregateHeadsBackward> node(new AggregateHeadsBackward(), torch::autograd::deleteNode);
+        node->set_next_edges(torch::autograd::collect_next_edges(features, transforms, queries, keys, frequencies, distance_transforms));
+        node->nb = nb;
+        node->f = c[0]; node->tr = c[1]; node->q = c[2]; node->k = c[3]; node->fr = c[4]; node->dist = c[5];
+        node->lse = lse; node->acc = acc;
+        for (int x = 0; x < 6; ++x) { node->versions[x] = c[x]._version(); node->in_dtypes[x] = ins[x]->scalar_type(); }
+        node->N = N; node->H = (int)H; node->L = (int)L; node->K = (int)K; node->F = (int)F;
+        torch::autograd::create_gradient_edge(out, node);
+    }
+    return out;
+}
+
 // ---------------------------------------------------------------------------------------------
 // the state behind GaussianSampler
 // ---------------------------------------------------------------------------------------------
@@ -1180,6 +1300,11 @@ struct Core {
         if (!neighbors) raise_py(PyExc_RuntimeError, "preprocess_aggregate() must be called before aggregate_neighbors()");
         return aggregate_apply(neighbors, features, transform, queries, keys, frequencies, distance_transform);
     }
+    at::Tensor aggregate_neighbors_heads(const at::Tensor& features, const at::Tensor& transforms, const at::Tensor& queries,
+                                         const at::Tensor& keys, const at::Tensor& frequencies, const at::Tensor& distance_transforms) {
+        if (!neighbors) raise_py(PyExc_RuntimeError, "preprocess_aggregate() must be called before aggregate_neighbors_heads()");
+        return aggregate_heads_apply(neighbors, features, transforms, queries, keys, frequencies, distance_transforms);
+    }
 
     py::object inputs() const {
         if (!bound) return py::none();
@@ -1292,6 +1417,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              py::arg("tau_field") = c10::optional<at::Tensor>(), py::arg("prev") = c10::optional<at::Tensor>())
         .def("preprocess_aggregate", &Core::preprocess_aggregate, py::arg("cap") = -1)
         .def("aggregate_neighbors", &Core::aggregate_neighbors)
+        .def("aggregate_neighbors_heads", &Core::aggregate_neighbors_heads)
         .def_readonly("neighbors", &Core::neighbors)
         .def_readonly("plan", &Core::plan)
         .def_readonly("plan3", &Core::plan3)

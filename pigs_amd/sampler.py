@@ -1415,3 +1415,18 @@ class GaussianSampler:
         if self._neighbors is None:
             raise RuntimeError("preprocess_aggregate() must be called before aggregate_neighbors()")
         return aggregate.aggregate(self._neighbors, features, transform, queries, keys, frequencies, distance_transform)
+
+    def aggregate_neighbors_heads(self, features, transforms, queries, keys, frequencies, distance_transforms):
+        """All H attention heads of a layer in one call (extension): ``out[:, h] = aggregate_neighbors(features,
+        transforms[h], queries[:, h], keys[:, h], frequencies, distance_transforms[h])``.  features [N, L] and
+        frequencies [F] are the heads' common part; transforms [H, L, L], queries / keys [N, H, K] (``torch.stack(...,
+        dim=1)``), distance_transforms [H, L, 2E] -> [N, H, L]; ``out.reshape(N, H * L)`` is the ``torch.cat`` of the
+        heads' results.  Differentiable once wrt all six arguments.  1 <= H <= 4; a shape the kernels do not admit
+        raises ``NotImplementedError`` (H separate calls remain available).  pigs_amd/aggregate.py."""
+        if self._core is not None:
+            return self._core.aggregate_neighbors_heads(features, transforms, queries, keys, frequencies, distance_transforms)
+        from . import aggregate
+        if self._neighbors is None:
+            raise RuntimeError("preprocess_aggregate() must be called before aggregate_neighbors_heads()")
+        return aggregate.aggregate_heads(self._neighbors, features, transforms, queries, keys, frequencies,
+                                         distance_transforms)
