@@ -589,6 +589,61 @@ int pigs_aggregate_heads_backward(int dtype, int64_t N, int64_t cap, int H, int 
                                   void* g_features, void* g_transforms, void* g_queries, void* g_keys,
                                   void* g_frequencies, void* g_distance_transforms, void* stream);
 
+/*
+ * Refinement: prune and split (or clone) Gaussians on the device (additive to ABI 10: the number does not change).
+ * d = 2, float32 / float64.  Replaces the boolean indexing, torch.linalg.eig, repeat_interleave and cat of
+ * Model.forward(split=True) / Model.split (model_pn.py:703-714, :578-605; PIGS_REFINE_SPLIT) and of the
+ * densification block of test_no_mlp.py:198-240 (PIGS_REFINE_CLONE).
+ *
+ * Inputs: means [N][2], scaling [N][2] (variances), transforms [N] (raw correlation t), values [N][c], and two masks
+ *   of one byte per row, nonzero = true: keep (NULL = all rows) and split (NULL = none).  The effective split set is
+ *   split & keep.  With n_k kept rows and n_s effective split rows both modes give n_k + n_s output rows:
+ *   PIGS_REFINE_SPLIT  the rows with keep & ~split in input order, then for every split parent in input order its two
+ *                      children (mean - e, mean + e), adjacent, values = value_scale * v, scaling and transforms copied.
+ *                      e = lambda_max * v of the covariance [[s0, tau], [tau, s1]], tau = tanh(t) sqrt(s0 s1): the UNIT
+ *                      eigenvector times the eigenVALUE (model_pn.py:587-589), signed so that e_x > 0, or e_x = 0 and
+ *                      e_y > 0; an exactly isotropic covariance gives e = (lambda, 0).
+ *   PIGS_REFINE_CLONE  all kept rows in input order, then one unchanged copy of every split parent in input order.
+ *
+ * pigs_refine_index classifies and ranks the rows: kept_pos [N] (int64) = the output row of a row's kept copy, child_pos
+ *   [N] (int64) = the output row of its first child or of its copy, -1 where there is none; counts [2] (int64, device) =
+ *   {n_k, n_s}.  The caller reads `counts` to size the outputs; that read is the path's only host wait.  Three launches:
+ *   totals per workgroup of PIGS_REFINE_ROWS rows, their exclusive scan by ONE workgroup that takes
+ *   PIGS_REFINE_SCAN_WIDTH totals per pass, the ranks.  `workspace`: pigs_refine_workspace_bytes(N) bytes, 8-byte
+ *   aligned (16 bytes per workgroup; a pure function of N; 0 for N <= 0 and for sizes the path does not take, N >= 2^31).
+ * pigs_refine_apply writes the output rows and the two maps source [rows] (int64: the input row of every output row)
+ *   and child [rows] (int32: -1 kept row, 0 / 1 the -e / +e child, 0 a copy).  `rows` is the length of the output
+ *   arrays: every store is guarded by position < rows, so a `rows` smaller than n_k + n_s truncates the result and
+ *   nothing is written behind it.  An output may be NULL (not wanted: source and child alone are the maps for arrays
+ *   the library does not know); a wanted output needs its input, out_means in PIGS_REFINE_SPLIT needs scaling and
+ *   transforms as well.  One launch, one thread per input row.
+ * pigs_refine_backward gathers the gradients of the inputs, one thread per input row, no atomics: a pruned row 0, a kept
+ *   row its output row's, a split parent the sum of its two children's (times value_scale for values), a clone parent
+ *   its kept row's plus its copy's.  e is a constant (the reference computes it under no_grad, model_pn.py:584-585).
+ *   Any incoming gradient may be NULL (zero), any outgoing one NULL (not wanted).  Positions >= rows count as zero.
+ * Rows of means and scaling are read and written as one 8-byte (float32) / 16-byte (float64) access: those arrays
+ *   are aligned to a row.
+ * Arguments are checked before any HIP call: a bad dtype or mode, or N >= 2^31, is PIGS_ERR_UNSUPPORTED; a negative N or
+ *   rows, c < 1, a null required array or a misaligned one with N > 0 is PIGS_ERR_INVALID; a short workspace is
+ *   PIGS_ERR_WORKSPACE.  N = 0 (and rows = 0 in apply) returns PIGS_OK without a launch -- pigs_refine_index then leaves
+ *   `counts` unwritten: both totals are 0.  Nothing allocates, frees or synchronises.
+ */
+#define PIGS_REFINE_SPLIT 0
+#define PIGS_REFINE_CLONE 1
+#define PIGS_REFINE_ROWS 1024
+#define PIGS_REFINE_SCAN_WIDTH 256
+size_t pigs_refine_workspace_bytes(int64_t N);
+int pigs_refine_index(int mode, int64_t N, const uint8_t* keep, const uint8_t* split, void* workspace,
+                      size_t workspace_bytes, int64_t* kept_pos, int64_t* child_pos, int64_t* counts, void* stream);
+int pigs_refine_apply(int dtype, int mode, int c, int64_t N, int64_t rows, double value_scale, const int64_t* kept_pos,
+                      const int64_t* child_pos, const void* means, const void* scaling, const void* transforms,
+                      const void* values, void* out_means, void* out_scaling, void* out_transforms, void* out_values,
+                      int64_t* source, int32_t* child, void* stream);
+int pigs_refine_backward(int dtype, int mode, int c, int64_t N, int64_t rows, double value_scale, const int64_t* kept_pos,
+                         const int64_t* child_pos, const void* g_out_means, const void* g_out_scaling,
+                         const void* g_out_transforms, const void* g_out_values, void* g_means, void* g_scaling,
+                         void* g_transforms, void* g_values, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

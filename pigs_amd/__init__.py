@@ -5,6 +5,9 @@ Public surface:
     VORTICITY_COLUMNS       the column names of ``GaussianSampler.vorticity_terms()``
     VORTICITY_RESIDUAL_COLUMNS  the column names of ``GaussianSampler.vorticity_residual()``
     covariances             fused ``build_covariances`` / ``build_full_covariances`` (gaussians.py:163-193)
+    split_gaussians         prune and split / clone Gaussians in HIP with one host read (pigs_amd.refine;
+                            model_pn.py:578-605, :703-714 and test_no_mlp.py:198-240)
+    refine_index            its (source, child) maps alone, for optimiser state and other per-Gaussian arrays
     build()                 compile the HIP library (hipcc, gfx950) and the native host extension in-tree
 """
 from .build import build_all as build  # noqa: F401  (libpigs_amd.so + the native host extension)
@@ -21,4 +24,7 @@ def __getattr__(name):
     if name == "VORTICITY_RESIDUAL_COLUMNS":
         from .sampler import VORTICITY_RESIDUAL_COLUMNS
         return VORTICITY_RESIDUAL_COLUMNS
+    if name in ("split_gaussians", "refine_index"):
+        from . import refine
+        return getattr(refine, name)
     raise AttributeError(name)

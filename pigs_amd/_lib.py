@@ -124,6 +124,12 @@ SIGNATURES = {
                                      + [_vp]),
     "pigs_aggregate_heads_backward": (_i, [_i, _i64, _i64, _i, _i, _i, _i, ctypes.c_double] + [_vp] * 6 + [_vp] * 6 + [_vp] * 3
                                       + [_vp, ctypes.c_size_t] + [_vp] * 6 + [_vp]),
+    # refinement (additive to ABI 10): prune and split / clone Gaussians; masks, workspace, maps, counts / maps, arrays
+    "pigs_refine_workspace_bytes": (ctypes.c_size_t, [_i64]),
+    "pigs_refine_index": (_i, [_i, _i64, _vp, _vp, _vp, ctypes.c_size_t] + [_vp] * 3 + [_vp]),
+    "pigs_refine_apply": (_i, [_i, _i, _i, _i64, _i64, ctypes.c_double] + [_vp] * 2 + [_vp] * 4 + [_vp] * 4 + [_vp] * 2
+                          + [_vp]),
+    "pigs_refine_backward": (_i, [_i, _i, _i, _i64, _i64, ctypes.c_double] + [_vp] * 2 + [_vp] * 4 + [_vp] * 4 + [_vp]),
 }
 
 _lib = None

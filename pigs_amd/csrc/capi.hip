@@ -547,4 +547,67 @@ int pigs_aggregate_heads_backward(int dtype, int64_t N, int64_t cap, int H, int 
     return aggregate_heads_backward(a, (hipStream_t)stream);
 }
 
+size_t pigs_refine_workspace_bytes(int64_t N) { return refine_workspace_bytes(N); }
+
+static int refine_sizes_ok(int dtype, int mode, int c, int64_t N, int64_t rows) {
+    if (dtype != PIGS_F32 && dtype != PIGS_F64) return PIGS_ERR_UNSUPPORTED;
+    if (mode != PIGS_REFINE_SPLIT && mode != PIGS_REFINE_CLONE) return PIGS_ERR_UNSUPPORTED;
+    if (N < 0 || rows < 0 || c < 1) return PIGS_ERR_INVALID;
+    if (N > REFINE_MAX_N) return PIGS_ERR_UNSUPPORTED;
+    return PIGS_OK;
+}
+static bool refine_misaligned(const void* p, int dtype) {      // a row of two values is one access
+    return ((uintptr_t)p & (dtype == PIGS_F64 ? 15u : 7u)) != 0;
+}
+
+int pigs_refine_index(int mode, int64_t N, const uint8_t* keep, const uint8_t* split, void* workspace,
+                      size_t workspace_bytes, int64_t* kept_pos, int64_t* child_pos, int64_t* counts, void* stream) {
+    const int rc = refine_sizes_ok(PIGS_F32, mode, 1, N, 0);
+    if (rc != PIGS_OK) return rc;
+    if (N == 0) return PIGS_OK;
+    if (!workspace || !kept_pos || !child_pos || !counts || ((uintptr_t)workspace & 7u)) return PIGS_ERR_INVALID;
+    if (workspace_bytes < refine_workspace_bytes(N)) return PIGS_ERR_WORKSPACE;
+    return refine_index(mode, N, keep, split, workspace, kept_pos, child_pos, counts, (hipStream_t)stream);
+}
+
+int pigs_refine_apply(int dtype, int mode, int c, int64_t N, int64_t rows, double value_scale, const int64_t* kept_pos,
+                      const int64_t* child_pos, const void* means, const void* scaling, const void* transforms,
+                      const void* values, void* out_means, void* out_scaling, void* out_transforms, void* out_values,
+                      int64_t* source, int32_t* child, void* stream) {
+    const int rc = refine_sizes_ok(dtype, mode, c, N, rows);
+    if (rc != PIGS_OK) return rc;
+    if (N == 0 || rows == 0) return PIGS_OK;
+    if (!kept_pos || !child_pos) return PIGS_ERR_INVALID;
+    if ((out_means && !means) || (out_scaling && !scaling) || (out_transforms && !transforms) || (out_values && !values))
+        return PIGS_ERR_INVALID;
+    if (out_means && mode == PIGS_REFINE_SPLIT && (!scaling || !transforms)) return PIGS_ERR_INVALID;
+    if (!out_means && !out_scaling && !out_transforms && !out_values && !source && !child) return PIGS_ERR_INVALID;
+    if ((out_means && (refine_misaligned(means, dtype) || refine_misaligned(out_means, dtype))) ||
+        ((out_scaling || out_means) && refine_misaligned(scaling, dtype)) || refine_misaligned(out_scaling, dtype))
+        return PIGS_ERR_INVALID;
+    RefineRows r{};
+    r.dtype = dtype; r.mode = mode; r.c = c; r.N = N; r.rows = rows; r.value_scale = value_scale;
+    r.kept_pos = kept_pos; r.child_pos = child_pos;
+    r.in[0] = means; r.in[1] = scaling; r.in[2] = transforms; r.in[3] = values;
+    r.out[0] = out_means; r.out[1] = out_scaling; r.out[2] = out_transforms; r.out[3] = out_values;
+    r.source = source; r.child = child;
+    return refine_rows(false, r, (hipStream_t)stream);
+}
+
+int pigs_refine_backward(int dtype, int mode, int c, int64_t N, int64_t rows, double value_scale, const int64_t* kept_pos,
+                         const int64_t* child_pos, const void* g_out_means, const void* g_out_scaling,
+                         const void* g_out_transforms, const void* g_out_values, void* g_means, void* g_scaling,
+                         void* g_transforms, void* g_values, void* stream) {
+    const int rc = refine_sizes_ok(dtype, mode, c, N, rows);
+    if (rc != PIGS_OK) return rc;
+    if (N == 0) return PIGS_OK;
+    if (!kept_pos || !child_pos || (!g_means && !g_scaling && !g_transforms && !g_values)) return PIGS_ERR_INVALID;
+    RefineRows r{};
+    r.dtype = dtype; r.mode = mode; r.c = c; r.N = N; r.rows = rows; r.value_scale = value_scale;
+    r.kept_pos = kept_pos; r.child_pos = child_pos;
+    r.in[0] = g_out_means; r.in[1] = g_out_scaling; r.in[2] = g_out_transforms; r.in[3] = g_out_values;
+    r.out[0] = g_means; r.out[1] = g_scaling; r.out[2] = g_transforms; r.out[3] = g_values;
+    return refine_rows(true, r, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -30,6 +30,25 @@ int dense_dispatch(bool backward, const SampleArgs& a, hipStream_t stream);
 int covariances_dispatch(bool backward, int dtype, int64_t N, const void* scaling, const void* transform,
                          const void* a, const void* b, void* o0, void* o1, hipStream_t stream);
 
+// refine.hip
+constexpr int REFINE_ROWS = PIGS_REFINE_ROWS;                // rows per workgroup of the index kernels
+constexpr int REFINE_SCAN_WIDTH = PIGS_REFINE_SCAN_WIDTH;    // block totals per pass of the one-workgroup scan
+constexpr int64_t REFINE_MAX_N = 0x7fffffffLL;
+struct RefineRows {        // apply: in = inputs, out = outputs; backward: in = incoming gradients, out = gradients
+    int dtype, mode, c;
+    int64_t N, rows;
+    double value_scale;
+    const int64_t *kept_pos, *child_pos;
+    const void* in[4];     // means, scaling, transforms, values
+    void* out[4];
+    int64_t* source;       // apply only
+    int32_t* child;
+};
+size_t refine_workspace_bytes(int64_t N);
+int refine_index(int mode, int64_t N, const uint8_t* keep, const uint8_t* split, void* workspace, int64_t* kept_pos,
+                 int64_t* child_pos, int64_t* counts, hipStream_t stream);
+int refine_rows(bool backward, const RefineRows& r, hipStream_t stream);
+
 // periodic.hip: images (fold = false; a = means, conics, values; o = image arrays) or the fold of their gradients
 // (fold = true; a = image gradients, null = zero; o = gradients)
 int periodic_dispatch(bool fold, int dtype, int c, int64_t N, double lo, double period, double q_cut, const void* a0,
