@@ -408,6 +408,8 @@ int pigs_samples_layout_info(int64_t M, int64_t info[4]);
  * point x, the 3 x 3 images of every Gaussian:
  *     u(x) = sum_n sum_{k in {-1,0,1}^2} v_n exp(-1/2 (x - mu'_n - k period)^T C_n (x - mu'_n - k period)),
  *     mu'_n = lo + (mu_n - lo) - period floor((mu_n - lo) / period)     (the mean wrapped into the box; d mu'/d mu = 1).
+ * In floating point mu'_n lies in the CLOSED box [lo, lo + period]: a mean just below lo lands on lo + period, the same
+ * point of the torus (a remainder that comes out negative -- (mu - lo) / period underflowing to -0 -- gets one period).
  * Sample points are not wrapped.  For x in the closed box this is the periodic field exactly (up to the cut-off)
  * when every Gaussian's q <= q_cut ellipse spans less than one period on each axis: q_cut Sigma_ii < period^2,
  * Sigma = C^-1, with q_cut the widest cut-off the caller samples with.
@@ -516,7 +518,8 @@ int pigs_aggregate_backward(int dtype, int64_t N, int64_t cap, int L, int K, int
  * i.e. the definition above applied to the 9N images, rows of block 0.  One j may appear through several images
  * (half extents between L/2 and L), so a list can be LONGER THAN N: `cap` = N is not safe here, take the counting
  * pass (lists == NULL) or check *overflow.
- * PRECONDITIONS, neither of which is checked here: (1) `means` are already wrapped into [lo, lo + period) -- block 0
+ * PRECONDITIONS, neither of which is checked here: (1) `means` are already wrapped into [lo, lo + period] (the closed
+ * box: a centre on lo + period is admitted, the culls carry a margin for it) -- block 0
  * of pigs_periodic_images (with its conics); nothing is wrapped here.  (2) Every Gaussian's q <= q_max ellipse spans
  * less than one period on each axis, sqrt(q_max Sigma_ii) < period -- what the flag of pigs_periodic_images reports
  * for q_cut >= q_max.  The all-pairs build (N <= 2048) relies on both: it tests only the four shifts that can then

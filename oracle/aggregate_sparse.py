@@ -48,22 +48,27 @@ def brute_pairs(means, conics, q_max, band_units=BAND_UNITS, block=512, u=U[torc
     return tuple(torch.cat(v) for v in out)
 
 
-def periodic_images(means, conics, lo, period):
-    """The 9N images of the wrapped centres in the block order of pigs_periodic_images: means [9N, 2], conics [9N, 3]."""
+def periodic_images(means, conics, lo, period, wrap=True):
+    """The 9N images of the wrapped centres in the block order of pigs_periodic_images: means [9N, 2], conics [9N, 3].
+    ``wrap=False`` takes the centres as they are -- block 0 of pigs_periodic_images, which lies in the CLOSED box: a
+    centre on lo + period is the same point of the torus as one on lo, but it meets its neighbours through other
+    images k, and the lists name k."""
     m = means.detach().double().cpu()
-    m = lo + torch.remainder(m - lo, period)
+    if wrap:
+        m = lo + torch.remainder(m - lo, period)
     sh = torch.tensor(SHIFTS, dtype=torch.float64) * period
     return (m[None] + sh[:, None, :]).reshape(-1, 2), conics.detach().double().cpu().reshape(-1, 3).repeat(9, 1)
 
 
-def brute_pairs_periodic(means, conics, q_max, lo, period, band_units=BAND_UNITS, block=512, u=U[torch.float32]):
+def brute_pairs_periodic(means, conics, q_max, lo, period, band_units=BAND_UNITS, block=512, u=U[torch.float32], wrap=True):
     """The same on the torus [lo, lo + period)^2: rows of block 0 against the 9N images, (i, j, k, q, S) ordered by
     (i, k, j).  The kernels take delta = (mu'_j - mu'_i) + s_k L: the difference is rounded (by at most u |mu'_j -
     mu'_i| per axis) before the shift makes it small, which moves q by up to |dq/d delta| times that, so S carries
-    that term too (divided by band_units, so that band_units * u * S bounds the sum of both)."""
+    that term too (divided by band_units, so that band_units * u * S bounds the sum of both).  ``wrap``: see
+    periodic_images."""
     means, conics = means.detach().double().cpu(), conics.detach().double().cpu().reshape(-1, 3)
     N = means.shape[0]
-    m9, c9 = periodic_images(means, conics, lo, period)
+    m9, c9 = periodic_images(means, conics, lo, period, wrap)
     shift = (torch.tensor(SHIFTS, dtype=torch.float64) * period).repeat_interleave(N, 0)     # [9N, 2]
 
     def extra(j, dx, dy, a, b, c):

@@ -6,6 +6,8 @@
 // right at the seam.  A periodic sampler sums, for every point, the 3 x 3 shifted copies of every Gaussian:
 //   u(x) = sum_n sum_{k in {-1,0,1}^2} v_n exp(-1/2 (x - mu'_n - kL)^T C_n (x - mu'_n - kL)),
 //   mu'_n = lo + (mu_n - lo) - L floor((mu_n - lo) / L)          (d mu' / d mu = 1).
+// In floating point mu'_n lies in the closed box [lo, lo + L]: a mean just below lo lands on lo + L, and a remainder
+// that comes out negative ((mu - lo) / L underflowing to -0) gets one period.
 // Nothing downstream changes: the images are an ordinary set of 9N Gaussians that preprocess() binds in place of
 // the caller's N, and every sampling path (dense, binned, residual, captures) runs on them unchanged.
 //
@@ -83,7 +85,12 @@ __global__ __launch_bounds__(256) void periodic_images_kernel(int64_t N, T lo, T
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
             const T r = m[a] - lo;
-            m[a] = lo + (r - period * floor(r / period));
+            T w = r - period * floor(r / period);
+            // r / period of a mean a few denormals below lo underflows to -0 (lo = 0, L > 1): w = r < 0 and the
+            // mean stayed outside the closed box.  One period more puts it on hi, where the rounding puts every
+            // other mean just below lo.
+            if (w < T(0)) w += period;
+            m[a] = lo + w;
         }
         // the images suffice when the cut-off ellipse spans less than one period on each axis:
         // q_cut Sigma_xx = q_cut C_yy / det < L^2 (and likewise for y); the negated form fails on NaN too

@@ -761,7 +761,11 @@ class GaussianSampler:
     Sigma_ii) < L with q_cut = max(q_max, q_max_backward, q_max_order3) -- debug mode (``flag``) checks this and
     raises ``ValueError``.  d = 2 only (d = 1 raises ``NotImplementedError``); dense and binned alike, the ``auto``
     rule counting the 9N images.  ``preprocess_aggregate`` / ``aggregate_neighbors`` keep working on the caller's N
-    Gaussians with the non-periodic neighbour definition unless ``periodic_aggregate`` is set.
+    Gaussians with the non-periodic neighbour definition unless ``periodic_aggregate`` is set.  ``lo`` and ``hi - lo``
+    reach the kernels as doubles and are cast to the tensors' dtype there: a float32 sampler lives on the torus of
+    float32(hi - lo) from float32(lo).  For (0, 2 pi) that period is 1.7e-7 away from 2 pi -- for narrow Gaussians a
+    visible change of q next to the seam, and no error: wrap means and points with the same float32 period.  The
+    wrapped means lie in the closed box [lo, lo + L] (a mean just below lo lands on hi, the same point of the torus).
 
     ``periodic_aggregate`` (extension, keyword only; default False; settable like ``periodic``; True without
     ``periodic`` raises ``ValueError``): ``preprocess_aggregate`` builds the neighbour lists of the torus from the

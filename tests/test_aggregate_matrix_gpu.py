@@ -171,7 +171,27 @@ def gen_offset(g, N):
     return means, conics_of(sd[:, 0], sd[:, 1], rand(g, N) - 0.5)       # smallest axis >= 0.0085 sqrt(1 - 0.5) = 6.0e-3
 
 
-def gen_torus(g, N):
+def to_box(means, conics, box):
+    """x -> lo + (x + 1) a, a = (hi - lo) / 2, applied to a problem stated on (-1, 1): means (or points) mapped,
+    conics / a^2 (None for points); torch tensors or numpy arrays.  ``box`` = (lo, hi); None leaves the problem as it is.  The one
+    statement of the map: every box test goes through it."""
+    if box is None:
+        return means, conics
+    a = (float(box[1]) - float(box[0])) / 2.0
+    return float(box[0]) + (means + 1.0) * a, None if conics is None else conics / (a * a)
+
+
+def lo_period_as_held(box, dtype):
+    """(lo, period) of ``box`` = (lo, hi) as a kernel of ``dtype`` holds them (both are cast to T); None: (-1, 1)."""
+    if box is None:
+        return LO, PERIOD
+    lo, period = float(box[0]), float(box[1]) - float(box[0])
+    if DTYPES[dtype] == torch.float32:
+        lo, period = float(torch.tensor(lo, dtype=torch.float32)), float(torch.tensor(period, dtype=torch.float32))
+    return lo, period
+
+
+def gen_torus(g, N, box=None):
     """A jittered lattice that fills the box; part of the means start outside it (the caller wraps)."""
     n = math.isqrt(N)
     cell = PERIOD / n
@@ -179,10 +199,10 @@ def gen_torus(g, N):
     gx, gy = torch.meshgrid((t, t), indexing="ij")
     means = torch.stack((gx, gy), dim=-1).reshape(N, 2) + (rand(g, N, 2) - 0.5) * 0.7 * cell + 0.31
     sd = (0.06 + 0.04 * rand(g, N, 2)) * (8.0 / n)
-    return means, conics_of(sd[:, 0], sd[:, 1], torch.tanh(randn(g, N) * 0.5) * 0.5)
+    return to_box(means, conics_of(sd[:, 0], sd[:, 1], torch.tanh(randn(g, N) * 0.5) * 0.5), box)
 
 
-def gen_torus_small(g, N):
+def gen_torus_small(g, N, box=None):
     """Every half extent small (at most 6 * 0.004): the top grid level stays empty and the row walk culls by reach
     (asserted from the grid's level mask by the test)."""
     means = rand(g, N, 2) * 2 - 1
@@ -193,15 +213,15 @@ def gen_torus_small(g, N):
     means[128:160, 1] = LO + rand(g, 32) * 0.004
     means[160:192, 1] = LO + PERIOD - rand(g, 32) * 0.004
     means[128:192, 0] = means[128, 0] + (rand(g, 64) - 0.5) * 0.01
-    return means, conics_of(sd[:, 0], sd[:, 1], rand(g, N) - 0.5)
+    return to_box(means, conics_of(sd[:, 0], sd[:, 1], rand(g, N) - 0.5), box)
 
 
-def gen_torus_wide(g, N):
+def gen_torus_wide(g, N, box=None):
     """gen_torus with one Gaussian whose q <= q_max half extents are just under the period (0.98 and 0.9 of it): the
     top grid level is occupied and the row walk's reach unbounded (asserted from the grid's level mask by the test)."""
     means, conics = gen_torus(g, N)
     conics[N // 2] = conics_of(torch.tensor(0.98 * PERIOD / 6), torch.tensor(0.9 * PERIOD / 6), torch.tensor(0.3))
-    return means, conics
+    return to_box(means, conics, box)
 
 
 def gen_shapes(g, N):
@@ -220,15 +240,17 @@ PERIODIC_GENERATORS = ("torus", "torus_small", "torus_wide")
 
 
 @functools.lru_cache(maxsize=None)
-def inputs(dtype, gen, N):
+def inputs(dtype, gen, N, box=None):
     """means [N, 2] and conics [N, 3] rounded to ``dtype`` (float64 on the CPU).  The periodic generators' means are
-    wrapped into the box after the rounding, as the sampler hands them to the lists."""
+    wrapped into the box after the rounding, as the sampler hands them to the lists.  ``box`` = (lo, hi), periodic
+    generators only: the problem moved onto that box, wrapped on the box as ``dtype`` holds it."""
     g = torch.Generator().manual_seed(1000 * sorted(GENERATORS).index(gen) + N)
-    means, conics = GENERATORS[gen](g, N)
+    means, conics = GENERATORS[gen](g, N) if box is None else GENERATORS[gen](g, N, box=box)
     means, conics = means.to(DTYPES[dtype]), conics.to(DTYPES[dtype])
     if gen in PERIODIC_GENERATORS:
-        means = LO + torch.remainder(means - LO, PERIOD)
-        means = torch.where(means >= LO + PERIOD, torch.full_like(means, LO), means)
+        lo, period = lo_period_as_held(box, dtype)
+        means = lo + torch.remainder(means - lo, period)
+        means = torch.where(means >= lo + period, torch.full_like(means, lo), means)
     return means, conics
 
 
@@ -236,11 +258,12 @@ class Relation:
     """The brute-force relation of one case: sorted keys i * M + column of the sure-in pairs and of the band pairs
     (M = N columns, or 9N with column = k * N + j on the torus)."""
 
-    def __init__(self, dtype, gen, N):
-        means, conics = inputs(dtype, gen, N)
+    def __init__(self, dtype, gen, N, box=None):
+        means, conics = inputs(dtype, gen, N, box)
         self.N, self.periodic = N, gen in PERIODIC_GENERATORS
         if self.periodic:
-            i, j, k, q, S = sparse.brute_pairs_periodic(means, conics, Q_MAX, LO, PERIOD)
+            lo, period = lo_period_as_held(box, dtype)
+            i, j, k, q, S = sparse.brute_pairs_periodic(means, conics, Q_MAX, lo, period)
             self.M = 9 * N
             key = i * self.M + k * N + j
         else:
@@ -251,12 +274,13 @@ class Relation:
         self.sure, self.band = key[sure].sort().values, key[band].sort().values
         self.band_fraction = self.band.numel() / max(1, self.sure.numel())
         self.images_used = bool((k[sure] != 0).any()) if self.periodic else False
+        self.images_seen = set(k[sure].unique().tolist()) if self.periodic else set()
         self.row_counts = torch.bincount(key[sure] // self.M, minlength=N)
 
 
 @functools.lru_cache(maxsize=None)
-def relation(dtype, gen, N):
-    return Relation(dtype, gen, N)
+def relation(dtype, gen, N, box=None):
+    return Relation(dtype, gen, N, box)
 
 
 def contains(sorted_keys, keys):
@@ -303,11 +327,12 @@ def check_lists(nb, rel, dtype, clamped=False):
     return rows
 
 
-def build_lists(dtype, gen, N, cap=None):
+def build_lists(dtype, gen, N, cap=None, box=None):
+    """``box`` = (lo, hi): the lists get (lo, hi - lo) as doubles, the way the sampler hands them over."""
     from pigs_amd.aggregate import NeighborLists
-    means, conics = inputs(dtype, gen, N)
-    box = (LO, PERIOD) if gen in PERIODIC_GENERATORS else None
-    return NeighborLists(means.cuda(), conics.cuda(), Q_MAX, cap=cap, periodic=box)
+    means, conics = inputs(dtype, gen, N, box)
+    per = (LO, PERIOD) if box is None else (float(box[0]), float(box[1]) - float(box[0]))
+    return NeighborLists(means.cuda(), conics.cuda(), Q_MAX, cap=cap, periodic=per if gen in PERIODIC_GENERATORS else None)
 
 
 # ---- (a)

@@ -27,10 +27,11 @@ NAMES = ("features", "transform", "queries", "keys", "frequencies", "distance_tr
 HOSTS = ("native", "ctypes")
 
 
-def lattice(n_side, seed=0, sigma=(0.06, 0.10), scale=1.0):
+def lattice(n_side, seed=0, sigma=(0.06, 0.10), scale=1.0, box=None):
     """A jittered n_side x n_side lattice that fills [-1, 1)^2, float64 on the CPU: means [N, 2], conics [N, 3].
     ``sigma`` is the range of the standard deviations at n_side = 8 (it shrinks with the cell); ``scale`` < 1 pulls
-    all means towards the middle of the box."""
+    all means towards the middle of the box.  ``box`` = (lo, hi): the same lattice moved by x -> lo + (x + 1) a,
+    a = (hi - lo) / 2 (conics / a^2)."""
     g = torch.Generator().manual_seed(seed)
     N = n_side * n_side
     cell = PERIOD / n_side
@@ -42,6 +43,9 @@ def lattice(n_side, seed=0, sigma=(0.06, 0.10), scale=1.0):
     sxx, syy, sxy = sd[:, 0] ** 2, sd[:, 1] ** 2, rho * sd[:, 0] * sd[:, 1]
     det = sxx * syy - sxy * sxy
     conics = torch.stack((syy / det, -sxy / det, sxx / det), dim=-1)
+    if box is not None:
+        from test_aggregate_matrix_gpu import to_box
+        return to_box(means * scale, conics, box)
     return means * scale, conics
 
 
@@ -77,19 +81,19 @@ def run(s, args, r):
     return [out.detach()] + [g.detach() for g in torch.autograd.grad((out * r).sum(), args)]
 
 
-def images64(means, conics):
+def images64(means, conics, lo=LO, period=PERIOD):
     """The wrapped 9N image system in float64 on the CPU, from the (rounded) inputs."""
     m = means.detach().double().cpu()
-    m = LO + torch.remainder(m - LO, PERIOD)
-    sh = torch.tensor(SHIFTS, dtype=torch.float64) * PERIOD
+    m = lo + torch.remainder(m - lo, period)
+    sh = torch.tensor(SHIFTS, dtype=torch.float64) * period
     return (m[None] + sh[:, None, :]).reshape(-1, 2), conics.detach().double().cpu().repeat(9, 1)
 
 
-def checker(means, conics, args, r, q_max):
+def checker(means, conics, args, r, q_max, lo=LO, period=PERIOD):
     """The dense checker on the 9N images, rows of block 0: [out, six gradients], the mask [N, 9N] and q - q_max of
     every (row of block 0, image) pair."""
     N = means.shape[0]
-    m9, c9 = images64(means, conics)
+    m9, c9 = images64(means, conics, lo, period)
     a64 = [a.detach().double().cpu().requires_grad_(True) for a in args]
     f, tr, q, k, fr, dist = a64
     mask, delta, g = aggregate_torch.neighbor_structure(m9, c9, q_max)

@@ -8,6 +8,7 @@ import torch
 
 from oracle import c_oracle
 from pigs_amd import synthetic
+from test_aggregate_matrix_gpu import to_box
 
 pytestmark = pytest.mark.gpu
 HOSTS = ("native", "ctypes")
@@ -38,40 +39,66 @@ def fold(g, N):
     return g.reshape((9, N) + g.shape[1:]).sum(0)
 
 
-def periodic_forward(means, conics, values, samples, orders=(0, 1, 2, 3)):
-    return c_oracle.forward(*images(means, conics, values), samples, orders=orders)
+def box_as_held(box, dtype):
+    """The box as a kernel of ``dtype`` holds it: both hosts hand over lo and hi - lo as doubles and the kernels cast
+    them to T, so a float32 run lives on the torus of float32(hi - lo) from float32(lo).  Returned as (lo, hi) in
+    float64 with hi - lo that period."""
+    lo, period = float(box[0]), float(box[1]) - float(box[0])
+    if dtype == torch.float32:
+        lo, period = float(np.float32(lo)), float(np.float32(period))
+    return lo, lo + period
 
 
-def periodic_backward(means, conics, values, samples, grads):
+def periodic_forward(means, conics, values, samples, orders=(0, 1, 2, 3), box=(LO, HI)):
+    return c_oracle.forward(*images(means, conics, values, *box), samples, orders=orders)
+
+
+def periodic_backward(means, conics, values, samples, grads, box=(LO, HI)):
     N = len(means)
-    return tuple(fold(g, N) for g in c_oracle.backward(*images(means, conics, values), samples, grads))
+    return tuple(fold(g, N) for g in c_oracle.backward(*images(means, conics, values, *box), samples, grads))
 
 
-def check_grads(got, means, conics, values, samples, grads, dtype):
+def check_grads(got, means, conics, values, samples, grads, dtype, box=(LO, HI)):
     """got = (g_means, g_conics, g_values).  float64: 1e-11 of each tensor's largest entry.  float32: the suite's bars
     (conftest.grads_within_accumulation_bound) restated for the folded gradients -- every entry within 1e-6 of the sum
     of the ABSOLUTE per-pair contributions to it (over all nine images) plus 1e-6 of the folded tensor's largest
-    entry -- and the tensor-scale bar, 1e-5 of that largest entry."""
+    entry -- and the tensor-scale bar, 1e-5 of that largest entry.  Returns the worst figure in units of its bar."""
     N = len(means)
     if dtype == torch.float64:
-        want = periodic_backward(means, conics, values, samples, grads)
+        want = periodic_backward(means, conics, values, samples, grads, box=box)
         for name, g, w in zip(("means", "conics", "values"), got, want):
             assert rel(g, w) < 1e-11, (name, rel(g, w))
-        return
-    img = images(means, conics, values)
+        return max(rel(g, w) for g, w in zip(got, want)) / 1e-11
+    img = images(means, conics, values, *box)
     want = [fold(w, N) for w in c_oracle.backward(*img, samples, grads)]
     mag = [fold(m, N) for m in c_oracle.backward(*img, samples, grads, absolute=True)]
+    worst = 0.0
     for name, g, w, m in zip(("means", "conics", "values"), got, want, mag):
         g = np64(g).reshape(w.shape)
         ratio = np.abs(g - w) / (1e-6 * m + 1e-6 * np.abs(w).max())
         assert (ratio <= 1.0).all(), (name, float(ratio.max()))
         assert rel(g, w) < 1e-5, (name, rel(g, w))
+        worst = max(worst, float(ratio.max()), rel(g, w) / 1e-5)
+    return worst
 
 
-def problem(N=200, c=1, seed=0, dtype=torch.float32, unwrapped=True, res=64):
+def planted_means(box, dtype):
+    """Means exactly on lo, on hi and one representable number to either side of each, in ``dtype`` (12 rows: six on
+    each axis, the other coordinate inside the box; then (lo, hi) and (hi, lo), the corners)."""
+    npt = np.float32 if dtype == torch.float32 else np.float64
+    lo, hi = (npt(v) for v in box_as_held(box, dtype))
+    edge = [lo, hi, np.nextafter(lo, npt(-np.inf)), np.nextafter(lo, npt(np.inf)), np.nextafter(hi, npt(-np.inf)),
+            np.nextafter(hi, npt(np.inf))]
+    mid = [float(lo) + f * (float(hi) - float(lo)) for f in (0.13, 0.29, 0.41, 0.58, 0.77, 0.92)]
+    rows = [(float(e), m) for e, m in zip(edge, mid)] + [(m, float(e)) for e, m in zip(edge, mid)]
+    return np.array(rows + [(float(lo), float(hi)), (float(hi), float(lo))], dtype=np.float64)
+
+
+def problem(N=200, c=1, seed=0, dtype=torch.float32, unwrapped=True, res=64, box=None, planted=False):
     """Random Gaussians in the box, an eighth of them within one extent of each seam and a few at the corners, a quarter
     handed over unwrapped (mu +- L, mu +- 2L); variances e^-4.5 .. e^-3 (extent at q_cut = 44 below 1.48 < L = 2).
-    Samples: the linspace(-1, 1) grid, both ends included."""
+    Samples: the linspace(-1, 1) grid, both ends included.  ``box`` = (lo, hi): the same problem moved by
+    to_box (means and points mapped, conics / a^2; the samples are the box's own closed grid); ``planted``: 14 of the rows are then put exactly on the seams and next to them (planted_means)."""
     rng = np.random.default_rng(seed)
     means = rng.uniform(LO, HI, (N, 2))
     k = N // 8
@@ -87,6 +114,11 @@ def problem(N=200, c=1, seed=0, dtype=torch.float32, unwrapped=True, res=64):
     con = np.stack((s[:, 1] / det, -tau / det, s[:, 0] / det), -1)
     values = rng.uniform(-1, 1, (N, c))
     pts = synthetic.grid_samples(res).numpy()
+    if box is not None:
+        means, con = to_box(means, con, box)
+        pts = to_box(pts.astype(np.float64), None, box)[0]
+        if planted:
+            means[2 * k + 4:2 * k + 18] = planted_means(box, dtype)
     t = [torch.as_tensor(a, dtype=dtype, device="cuda") for a in (means, values, con, pts)]
     for x in t[:3]:
         x.requires_grad_(True)

@@ -204,9 +204,10 @@ def test_binned_matches_the_oracle(hip_lib, points):
 # ------------------------------------------------------------------------------------------
 # 3. periodic (-1, 1)
 # ------------------------------------------------------------------------------------------
-def periodic_problem():
+def periodic_problem(box=None):
     """N = 64: 8 means within one sigma of the x seam, 8 of the y seam, 4 at the corners, the rest anywhere in the box;
-    sigma = e^-2 .. e^-1.6 (extent at q_cut = 44 below 1.35 < L = 2)."""
+    sigma = e^-2 .. e^-1.6 (extent at q_cut = 44 below 1.35 < L = 2).  ``box`` = (lo, hi): the same problem moved by
+    x -> lo + (x + 1) a, a = (hi - lo) / 2 (means and points mapped, conics / a^2)."""
     rng = np.random.default_rng(7)
     N = 64
     s = np.exp(rng.uniform(-4.0, -3.2, (N, 2)))
@@ -218,7 +219,12 @@ def periodic_problem():
     det = s[:, 0] * s[:, 1] - tau ** 2
     con = np.stack((s[:, 1] / det, -tau / det, s[:, 0] / det), -1)
     pts = np.concatenate((synthetic.grid_samples(24).numpy(), rng.uniform(-1, 1, (423, 2))))
-    return means, rng.uniform(-1, 1, (N, 2)), con, pts, rng.uniform(-1, 1, (len(pts), 7))
+    values, gout = rng.uniform(-1, 1, (N, 2)), rng.uniform(-1, 1, (len(pts), 7))
+    if box is not None:
+        from test_aggregate_matrix_gpu import to_box
+        means, con = to_box(means, con, box)
+        pts = to_box(pts.astype(np.float64), None, box)[0]
+    return means, values, con, pts, gout
 
 
 @pytest.mark.parametrize("host", HOSTS)
