@@ -565,8 +565,8 @@ int pigs_aggregate_backward_periodic(int dtype, int64_t N, int64_t cap, int L, i
  *   pigs_aggregate_backward.
  * `period` = 0: lists of pigs_aggregate_lists; > 0: lists of pigs_aggregate_lists_periodic on a torus of that period
  *   (its preconditions hold); anything else is PIGS_ERR_INVALID.
- * Sizes: 1 <= H <= PIGS_AGGREGATE_HEADS_MAX (else PIGS_ERR_UNSUPPORTED).  H = 1 runs the single-head kernels under their own rule.  For
- *   H >= 2 at most 128 components per kernel -- L + 2E <= 128, H K + F <= 128, H (L + K) <= 128 -- and the dynamic LDS
+ * Sizes: 1 <= H <= PIGS_AGGREGATE_HEADS_MAX (else PIGS_ERR_UNSUPPORTED).  H = 1 is pigs_aggregate_forward / _backward (the same
+ *   kernels; at H = 1 the rule below is theirs).  At most 128 components per kernel -- L + 2E <= 128, H K + F <= 128, H (L + K) <= 128 -- and the dynamic LDS
  *   of each kernel, sizeof(T) * 4 * region values, within PIGS_AGGREGATE_LDS_MAX: region = max(64 ((L + 4F) | 1), 136 H)
  *   in the forward, 136 H + max(64 ((H K + F) | 1), 136) in the backward by rows, max(64 ((H (L + K)) | 1), 136) in the
  *   backward by columns.  pigs_aggregate_heads_lds_bytes is the whole rule in one call: the largest of the three, or 0

@@ -119,113 +119,23 @@ class NeighborLists:
 
 
 class _Aggregate(torch.autograd.Function):
+    """One launch path for both calls: `heads` says whether the caller's tensors carry a head axis (transforms [H, L, L],
+    queries / keys [N, H, K], distance_transforms [H, L, 2E] -> [N, H, L]) or are one head's ([L, L], [N, K], [L, 2E]
+    -> [N, L]: the same memory as H = 1)."""
+
     @staticmethod
-    def forward(ctx, nb, features, transform, queries, keys, frequencies, distance_transform):
+    def forward(ctx, nb, heads, features, transforms, queries, keys, frequencies, distance_transforms):
         lib = _lib.load()
         N, L = features.shape
-        K, F = queries.shape[1], frequencies.shape[0]
-        E = 4 * F + 1
-        dt = nb.means.dtype
-        args = [a.detach().to(dt).contiguous() for a in (features, transform, queries, keys, frequencies, distance_transform)]
-        f, tr, q, k, fr, dist = args
-        out = torch.empty((N, L), dtype=dt, device=f.device)
-        lse = torch.empty(N, dtype=dt, device=f.device)
-        acc = torch.empty((N, L + 2 * E), dtype=dt, device=f.device)
-        tail = (_ptr(nb.means), _ptr(nb.conics), _ptr(nb.row_counts), _ptr(nb.row_lists), _ptr(f), _ptr(tr), _ptr(q), _ptr(k),
-                _ptr(fr), _ptr(dist), _ptr(out), _ptr(lse), _ptr(acc), _stream(f.device))
-        with torch.cuda.device(f.device):
-            if nb.periodic is None:
-                rc = lib.pigs_aggregate_forward(_DTYPES[dt], N, nb.cap, L, K, F, *tail)
-            else:
-                rc = lib.pigs_aggregate_forward_periodic(_DTYPES[dt], N, nb.cap, L, K, F, nb.period, *tail)
-        _lib.check(rc, "pigs_aggregate_forward_periodic" if nb.periodic else "pigs_aggregate_forward")
-        ctx.nb = nb
-        ctx.save_for_backward(f, tr, q, k, fr, dist, lse, acc)
-        ctx.dims = (N, L, K, F, E)
-        ctx.in_dtypes = tuple(a.dtype for a in (features, transform, queries, keys, frequencies, distance_transform))
-        return out.to(features.dtype)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gout):
-        lib = _lib.load()
-        nb = ctx.nb
-        f, tr, q, k, fr, dist, lse, acc = ctx.saved_tensors
-        N, L, K, F, E = ctx.dims
-        dt = f.dtype
-        gout = gout.to(dt).contiguous()
-        g_f, g_tr, g_q, g_k, g_fr, g_dist = (torch.empty_like(t) for t in (f, tr, q, k, fr, dist))
-        nbytes = lib.pigs_aggregate_backward_scratch_bytes(_DTYPES[dt], N, L, F)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=f.device)
-        tail = (_ptr(nb.means), _ptr(nb.conics), _ptr(nb.row_counts), _ptr(nb.row_lists), _ptr(nb.col_counts),
-                _ptr(nb.col_lists), _ptr(f), _ptr(tr), _ptr(q), _ptr(k), _ptr(fr), _ptr(dist), _ptr(lse), _ptr(acc), _ptr(gout),
-                _ptr(scratch), nbytes, _ptr(g_f), _ptr(g_tr), _ptr(g_q), _ptr(g_k), _ptr(g_fr), _ptr(g_dist), _stream(f.device))
-        with torch.cuda.device(f.device):
-            if nb.periodic is None:
-                rc = lib.pigs_aggregate_backward(_DTYPES[dt], N, nb.cap, L, K, F, *tail)
-            else:
-                rc = lib.pigs_aggregate_backward_periodic(_DTYPES[dt], N, nb.cap, L, K, F, nb.period, *tail)
-        _lib.check(rc, "pigs_aggregate_backward_periodic" if nb.periodic else "pigs_aggregate_backward")
-        if N == 0:
-            for g in (g_tr, g_fr, g_dist):
-                g.zero_()
-        grads = (g_f, g_tr, g_q, g_k, g_fr, g_dist)
-        return (None,) + tuple(g.to(d) for g, d in zip(grads, ctx.in_dtypes))
-
-
-def aggregate(nb, features, transform, queries, keys, frequencies, distance_transform):
-    N = nb.N
-    if features.dim() != 2 or features.shape[0] != N:
-        raise ValueError(f"features must be [N={N}, L], got {tuple(features.shape)}")
-    L, K, F = features.shape[1], queries.shape[1], frequencies.shape[0]
-    E = 4 * F + 1
-    if (transform.shape != (L, L) or queries.shape != (N, K) or keys.shape != (N, K)
-            or distance_transform.shape != (L, 2 * E)):
-        raise ValueError(f"aggregate_neighbors: expected transform [{L},{L}], queries/keys [{N},{K}], "
-                         f"distance_transform [{L},{2 * E}] (E = 2*d*F + 1 = {E})")
-    for name, t in (("features", features), ("transform", transform), ("queries", queries), ("keys", keys),
-                    ("frequencies", frequencies), ("distance_transform", distance_transform)):
-        if not t.is_cuda:
-            raise RuntimeError(f"{name} is on {t.device}: aggregate_neighbors runs on the GPU only (no CPU fallback)")
-    if L + 2 * E > 128:
-        raise NotImplementedError(f"L + 2E = {L + 2 * E} > 128 is not supported")
-    dt = nb.means.dtype
-    lds = _lib.load().pigs_aggregate_lds_bytes(_DTYPES[dt], L, K, F)
-    if lds > LDS_MAX:      # the backward's kernels included: a forward that cannot be differentiated is refused
-        raise NotImplementedError(f"{str(dt).replace('torch.', '')} with L = {L}, K = {K}, F = {F} needs {lds} bytes of LDS "
-                                  f"in one of the forward's or the backward's kernels; the limit is {LDS_MAX}")
-    return _Aggregate.apply(nb, features, transform, queries, keys, frequencies, distance_transform)
-
-
-# ---- all heads of a layer in one launch ----------------------------------------------------------------------------
-MAX_HEADS = 4        # PIGS_AGGREGATE_HEADS_MAX of include/pigs_amd.h
-
-
-def heads_refusal(dtype, H, L, K, F):
-    """None when the heads' kernels admit the shape, else the reason.  The rule is the library's
-    (pigs_aggregate_heads_lds_bytes: 0 = more than 128 components in one kernel, else the LDS the kernels ask for)."""
-    lds = _lib.load().pigs_aggregate_heads_lds_bytes(_DTYPES[dtype], H, L, K, F)
-    shape = f"{str(dtype).replace('torch.', '')} with H = {H}, L = {L}, K = {K}, F = {F}"
-    if lds == 0:
-        return f"{shape} has more than 128 components in one kernel (L + 2E, H K + F, H (L + K) <= 128)"
-    if lds > LDS_MAX:
-        return f"{shape} needs {lds} bytes of LDS in one of the forward's or the backward's kernels; the limit is {LDS_MAX}"
-    return None
-
-
-class _AggregateHeads(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, nb, features, transforms, queries, keys, frequencies, distance_transforms):
-        lib = _lib.load()
-        N, L = features.shape
-        H, K, F = queries.shape[1], queries.shape[2], frequencies.shape[0]
+        H, K, F = queries.shape[1] if heads else 1, queries.shape[-1], frequencies.shape[0]
         E = 4 * F + 1
         dt = nb.means.dtype
         ins = (features, transforms, queries, keys, frequencies, distance_transforms)
         f, tr, q, k, fr, dist = (a.detach().to(dt).contiguous() for a in ins)
-        out = torch.empty((N, H, L), dtype=dt, device=f.device)
-        lse = torch.empty((N, H), dtype=dt, device=f.device)
-        acc = torch.empty((N, H, L + 2 * E), dtype=dt, device=f.device)
+        lead = (N, H) if heads else (N,)
+        out = torch.empty(lead + (L,), dtype=dt, device=f.device)
+        lse = torch.empty(lead, dtype=dt, device=f.device)
+        acc = torch.empty(lead + (L + 2 * E,), dtype=dt, device=f.device)
         with torch.cuda.device(f.device):
             rc = lib.pigs_aggregate_heads_forward(
                 _DTYPES[dt], N, nb.cap, H, L, K, F, nb.period, _ptr(nb.means), _ptr(nb.conics), _ptr(nb.row_counts),
@@ -261,7 +171,52 @@ class _AggregateHeads(torch.autograd.Function):
             for g in (g_tr, g_fr, g_dist):
                 g.zero_()
         grads = (g_f, g_tr, g_q, g_k, g_fr, g_dist)
-        return (None,) + tuple(g.to(d) for g, d in zip(grads, ctx.in_dtypes))
+        return (None, None) + tuple(g.to(d) for g, d in zip(grads, ctx.in_dtypes))
+
+
+def _refuse_one_head(dt, L, K, F):
+    """The size checks of one head, in aggregate()'s words."""
+    E = 4 * F + 1
+    if L + 2 * E > 128:
+        raise NotImplementedError(f"L + 2E = {L + 2 * E} > 128 is not supported")
+    lds = _lib.load().pigs_aggregate_lds_bytes(_DTYPES[dt], L, K, F)
+    if lds > LDS_MAX:      # the backward's kernels included: a forward that cannot be differentiated is refused
+        raise NotImplementedError(f"{str(dt).replace('torch.', '')} with L = {L}, K = {K}, F = {F} needs {lds} bytes of LDS "
+                                  f"in one of the forward's or the backward's kernels; the limit is {LDS_MAX}")
+
+
+def aggregate(nb, features, transform, queries, keys, frequencies, distance_transform):
+    N = nb.N
+    if features.dim() != 2 or features.shape[0] != N:
+        raise ValueError(f"features must be [N={N}, L], got {tuple(features.shape)}")
+    L, K, F = features.shape[1], queries.shape[1], frequencies.shape[0]
+    E = 4 * F + 1
+    if (transform.shape != (L, L) or queries.shape != (N, K) or keys.shape != (N, K)
+            or distance_transform.shape != (L, 2 * E)):
+        raise ValueError(f"aggregate_neighbors: expected transform [{L},{L}], queries/keys [{N},{K}], "
+                         f"distance_transform [{L},{2 * E}] (E = 2*d*F + 1 = {E})")
+    for name, t in (("features", features), ("transform", transform), ("queries", queries), ("keys", keys),
+                    ("frequencies", frequencies), ("distance_transform", distance_transform)):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} is on {t.device}: aggregate_neighbors runs on the GPU only (no CPU fallback)")
+    _refuse_one_head(nb.means.dtype, L, K, F)
+    return _Aggregate.apply(nb, False, features, transform, queries, keys, frequencies, distance_transform)
+
+
+# ---- all heads of a layer in one launch ----------------------------------------------------------------------------
+MAX_HEADS = 4        # PIGS_AGGREGATE_HEADS_MAX of include/pigs_amd.h
+
+
+def heads_refusal(dtype, H, L, K, F):
+    """None when the kernels admit the shape, else the reason.  The rule is the library's
+    (pigs_aggregate_heads_lds_bytes: 0 = more than 128 components in one kernel, else the LDS the kernels ask for)."""
+    lds = _lib.load().pigs_aggregate_heads_lds_bytes(_DTYPES[dtype], H, L, K, F)
+    shape = f"{str(dtype).replace('torch.', '')} with H = {H}, L = {L}, K = {K}, F = {F}"
+    if lds == 0:
+        return f"{shape} has more than 128 components in one kernel (L + 2E, H K + F, H (L + K) <= 128)"
+    if lds > LDS_MAX:
+        return f"{shape} needs {lds} bytes of LDS in one of the forward's or the backward's kernels; the limit is {LDS_MAX}"
+    return None
 
 
 def aggregate_heads(nb, features, transforms, queries, keys, frequencies, distance_transforms):
@@ -288,9 +243,10 @@ def aggregate_heads(nb, features, transforms, queries, keys, frequencies, distan
     if H < 1 or H > MAX_HEADS:
         raise NotImplementedError(f"H = {H} heads: one launch serves 1 <= H <= {MAX_HEADS}; H separate aggregate_neighbors "
                                   f"calls remain available")
-    if H == 1:       # the single-head entry points
-        return aggregate(nb, features, transforms[0], queries[:, 0], keys[:, 0], frequencies, distance_transforms[0])[:, None]
-    why = heads_refusal(nb.means.dtype, H, L, K, F)
-    if why is not None:
-        raise NotImplementedError(f"aggregate_neighbors_heads: {why}; H separate aggregate_neighbors calls remain available")
-    return _AggregateHeads.apply(nb, features, transforms, queries, keys, frequencies, distance_transforms)
+    if H == 1:       # one head: aggregate()'s rule, in its words
+        _refuse_one_head(nb.means.dtype, L, K, F)
+    else:
+        why = heads_refusal(nb.means.dtype, H, L, K, F)
+        if why is not None:
+            raise NotImplementedError(f"aggregate_neighbors_heads: {why}; H separate aggregate_neighbors calls remain available")
+    return _Aggregate.apply(nb, True, features, transforms, queries, keys, frequencies, distance_transforms)

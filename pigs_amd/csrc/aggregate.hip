@@ -1214,47 +1214,64 @@ static size_t sampling_lds(Kernel kernel, size_t elem, size_t region, int* rc) {
     }
     return bytes;
 }
+// A wave's region, in values: the forward parks [features_j ; 4F sin / cos] and merges H partials; the backward by rows
+// keeps H dacc blocks and parks [H K keys ; F]; the backward by columns parks H (L + K) values.
 static size_t rows_region(int stride) { return (size_t)(64 * stride > PART ? 64 * stride : PART); }
-static size_t forward_region(int L, int F) { return rows_region((L + 4 * F) | 1); }
-static size_t backward_rows_region(int K, int F) { return PART + rows_region((K + F) | 1); }
-static size_t backward_cols_region(int L, int K) { return rows_region((L + K) | 1); }
-// the most dynamic LDS any of the three sampling kernels asks for at these sizes (a CU has AGG_LDS_MAX = 160 KB)
-size_t aggregate_lds_bytes(int dtype, int L, int K, int F) {
-    const size_t a = forward_region(L, F), b = backward_rows_region(K, F), c = backward_cols_region(L, K);
-    return (dtype == PIGS_F64 ? 8 : 4) * 4 * (a > b ? (a > c ? a : c) : (b > c ? b : c));
-}
-// The heads' kernels (2 <= H <= HMAX): the forward's row is unchanged and its merge region holds H partials; the
-// backward by rows keeps H dacc blocks and parks [H K keys ; F]; the backward by columns parks H (L + K) values.
-static size_t heads_forward_region(int H, int L, int F) {
-    const size_t r = forward_region(L, F);
+static size_t forward_region(int H, int L, int F) {
+    const size_t r = rows_region((L + 4 * F) | 1);
     return r > (size_t)H * PART ? r : (size_t)H * PART;
 }
-static size_t heads_backward_rows_region(int H, int K, int F) { return (size_t)H * PART + rows_region((H * K + F) | 1); }
-static size_t heads_backward_cols_region(int H, int L, int K) { return rows_region((H * (L + K)) | 1); }
-// THE size rule of the heads' entry points, in one place: 1 <= H <= HMAX, at most 128 components per kernel (two per
-// lane) and every kernel's LDS within a CU's.  Returns the most dynamic LDS any of the three kernels asks for, or 0
-// when H or a component count is out of range; a shape is admitted when 0 < bytes <= AGG_LDS_MAX.  Anything beyond is
-// refused, not attempted.  (H = 1: the single-head kernels and, by the same formulas, their rule.)
-size_t aggregate_heads_lds_bytes(int dtype, int H, int L, int K, int F) {
-    if (H < 1 || H > HMAX) return 0;
-    if (L + 2 * (4 * F + 1) > 128 || H * K + F > 128 || H * (L + K) > 128) return 0;
-    if (H == 1) return aggregate_lds_bytes(dtype, L, K, F);
-    const size_t a = heads_forward_region(H, L, F), b = heads_backward_rows_region(H, K, F), c = heads_backward_cols_region(H, L, K);
+static size_t backward_rows_region(int H, int K, int F) { return (size_t)H * PART + rows_region((H * K + F) | 1); }
+static size_t backward_cols_region(int H, int L, int K) { return rows_region((H * (L + K)) | 1); }
+// the most dynamic LDS any of the three sampling kernels asks for at these sizes (a CU has AGG_LDS_MAX = 160 KB)
+size_t aggregate_lds_bytes(int dtype, int H, int L, int K, int F) {
+    const size_t a = forward_region(H, L, F), b = backward_rows_region(H, K, F), c = backward_cols_region(H, L, K);
     return (dtype == PIGS_F64 ? 8 : 4) * 4 * (a > b ? (a > c ? a : c) : (b > c ? b : c));
 }
-bool aggregate_heads_admitted(int dtype, int H, int L, int K, int F) {
-    const size_t bytes = aggregate_heads_lds_bytes(dtype, H, L, K, F);
-    return bytes != 0 && bytes <= AGG_LDS_MAX;
+// THE size rule of every sampling entry point, in one place: 1 <= H <= HMAX, at most 128 components per kernel (two per
+// lane) and every kernel's LDS within a CU's.  A shape is admitted when neither H nor a component count is out of
+// range and aggregate_lds_bytes <= AGG_LDS_MAX.  Anything beyond is refused, not attempted.
+static bool components_ok(int H, int L, int K, int F) {
+    return H >= 1 && H <= HMAX && L + 2 * (4 * F + 1) <= 128 && H * K + F <= 128 && H * (L + K) <= 128;
+}
+size_t aggregate_heads_lds_bytes(int dtype, int H, int L, int K, int F) {      // 0: H or a component count out of range
+    return components_ok(H, L, K, F) ? aggregate_lds_bytes(dtype, H, L, K, F) : 0;
+}
+bool aggregate_admitted(int dtype, int H, int L, int K, int F) {
+    return components_ok(H, L, K, F) && aggregate_lds_bytes(dtype, H, L, K, F) <= AGG_LDS_MAX;
 }
 
-// waves per Gaussian: a launch of few Gaussians is one generation of waves bound by a wave's serial life
+// Waves per Gaussian, one head: a launch of few Gaussians is one generation of waves bound by a wave's serial life
 // (split every Gaussian's rounds over four waves); many Gaussians are a throughput problem (no idle waves)
 static int waves_per_gaussian(int64_t N) { return N <= 4096 ? 4 : N <= 8192 ? 2 : 1; }
+
+// Waves per Gaussian, H >= 2.  Up to AGG_BRUTE_MAX Gaussians (the model's sizes) a launch is bound by a wave's serial
+// life, and several heads ask for more LDS than one, so fewer of their workgroups are resident at once: the waves per
+// Gaussian are halved while the launch's workgroups exceed what the device holds (AGG_CUS compute units, per CU what
+// the LDS request admits, at most the eight workgroups of 32 waves).
+// What stands behind the rule is ONE sweep (DESIGN.md section 9, profiles/aggregate_heads.txt "waves per Gaussian"):
+// the model's shape, H = 2, N = 1 600, 4 / 2 / 1 waves, float32 and float64.  There it picks 1 wave for all three
+// kernels in both dtypes; that is the best or within 1 us of it for the kernel by rows and for float64's forward and
+// rows, and it passes over the better 2-wave launch of float32's forward (25.5 against 27.9 us), float32's columns
+// (60.1 against 65.5) and float64's columns (117.7 against 123.9): 800 workgroups against 768 resident.  It is
+// applied unmeasured to H = 3, 4 and to other shapes.  Beyond AGG_BRUTE_MAX: the one-head rule, as measured there.
+// It stays keyed on H: applied to H = 1 it would halve the waves at the model's N = 1 600 (1 600 workgroups against
+// 768 resident).
+constexpr int AGG_CUS = 256;                     // compute units of an MI355X (the one device this library is built for)
+static int heads_waves_per_gaussian(int64_t N, size_t lds_bytes) {
+    int wpg = waves_per_gaussian(N);
+    if (N > AGG_BRUTE_MAX) return wpg;
+    size_t per_cu = AGG_LDS_MAX / (lds_bytes > 0 ? lds_bytes : 1);
+    per_cu = per_cu > 8 ? 8 : per_cu < 1 ? 1 : per_cu;      // 32 waves a CU: eight workgroups of four
+    const int64_t resident = (int64_t)AGG_CUS * (int64_t)per_cu;
+    while (wpg > 1 && (N * wpg + 3) / 4 > resident) wpg >>= 1;
+    return wpg;
+}
 
 template <typename T, bool PER>
 static int aggregate_forward_t(const AggregateArgs& a, hipStream_t stream) {
     int rc = PIGS_OK;
-    const size_t lds = sampling_lds(aggregate_forward_kernel<T, PER>, sizeof(T), forward_region(a.L, a.F), &rc);
+    const size_t lds = sampling_lds(aggregate_forward_kernel<T, PER>, sizeof(T), forward_region(1, a.L, a.F), &rc);
     if (rc != PIGS_OK) return rc;
     const int wpg = waves_per_gaussian(a.N), gpw = 4 / wpg;
     clear_hip_error();
@@ -1265,10 +1282,10 @@ static int aggregate_forward_t(const AggregateArgs& a, hipStream_t stream) {
     return launch_status();
 }
 
-size_t aggregate_backward_scratch_bytes(int dtype, int64_t N, int L, int F) {
+size_t aggregate_backward_scratch_bytes(int dtype, int64_t N, int H, int L, int F) {
     const size_t e = dtype == PIGS_F64 ? 8 : 4;
     const int W = L + 2 * (4 * F + 1);
-    return align_up(e * (size_t)N * (size_t)(W + 1 + F), 256);      // dacc [N][W], D [N], per-row d frequencies [N][F]
+    return align_up(e * (size_t)N * (size_t)(H * (W + 1) + F), 256);      // dacc [N][H][W], D [N][H], per-row d frequencies [N][F]
 }
 
 template <typename T, bool PER>
@@ -1278,8 +1295,8 @@ static int aggregate_backward_t(const AggregateArgs& a, hipStream_t stream) {
     T* D = dacc + (size_t)a.N * W;
     T* gfr = D + a.N;
     int rc = PIGS_OK;
-    const size_t lds_r = sampling_lds(aggregate_backward_rows_kernel<T, PER>, sizeof(T), backward_rows_region(a.K, a.F), &rc);
-    const size_t lds_c = sampling_lds(aggregate_backward_cols_kernel<T, PER>, sizeof(T), backward_cols_region(a.L, a.K), &rc);
+    const size_t lds_r = sampling_lds(aggregate_backward_rows_kernel<T, PER>, sizeof(T), backward_rows_region(1, a.K, a.F), &rc);
+    const size_t lds_c = sampling_lds(aggregate_backward_cols_kernel<T, PER>, sizeof(T), backward_cols_region(1, a.L, a.K), &rc);
     if (rc != PIGS_OK) return rc;
     const int wpg = waves_per_gaussian(a.N), gpw = 4 / wpg;
     const dim3 grid((unsigned)((a.N + gpw - 1) / gpw)), block(256);
@@ -1307,44 +1324,11 @@ static int aggregate_backward_t(const AggregateArgs& a, hipStream_t stream) {
     return launch_status();
 }
 
-int aggregate_forward(const AggregateArgs& a, hipStream_t stream) {
-    if (a.N == 0) return PIGS_OK;
-    if (a.period > 0) return a.dtype == PIGS_F32 ? aggregate_forward_t<float, true>(a, stream) : aggregate_forward_t<double, true>(a, stream);
-    return a.dtype == PIGS_F32 ? aggregate_forward_t<float, false>(a, stream) : aggregate_forward_t<double, false>(a, stream);
-}
-
-int aggregate_backward(const AggregateArgs& a, hipStream_t stream) {
-    if (a.N == 0) return PIGS_OK;
-    if (a.period > 0) return a.dtype == PIGS_F32 ? aggregate_backward_t<float, true>(a, stream) : aggregate_backward_t<double, true>(a, stream);
-    return a.dtype == PIGS_F32 ? aggregate_backward_t<float, false>(a, stream) : aggregate_backward_t<double, false>(a, stream);
-}
-
-// Waves per Gaussian of a heads' kernel.  Up to AGG_BRUTE_MAX Gaussians (the model's sizes) a launch is bound by a
-// wave's serial life, and the heads' kernels ask for more LDS than the single-head ones, so fewer of their workgroups
-// are resident at once: the waves per Gaussian are halved while the launch's workgroups exceed what the device holds
-// (AGG_CUS compute units, per CU what the LDS request admits, at most the eight workgroups of 32 waves).
-// What stands behind the rule is ONE sweep (DESIGN.md section 9, profiles/aggregate_heads.txt "waves per Gaussian"):
-// the model's shape, H = 2, N = 1 600, 4 / 2 / 1 waves, float32 and float64.  There it picks 1 wave for all three
-// kernels in both dtypes; that is the best or within 1 us of it for the kernel by rows and for float64's forward and
-// rows, and it passes over the better 2-wave launch of float32's forward (25.5 against 27.9 us), float32's columns
-// (60.1 against 65.5) and float64's columns (117.7 against 123.9): 800 workgroups against 768 resident.  It is
-// applied unmeasured to H = 3, 4 and to other shapes.  Beyond AGG_BRUTE_MAX: the single-head rule, as measured there.
-constexpr int AGG_CUS = 256;                     // compute units of an MI355X (the one device this library is built for)
-static int heads_waves_per_gaussian(int64_t N, size_t lds_bytes) {
-    int wpg = waves_per_gaussian(N);
-    if (N > AGG_BRUTE_MAX) return wpg;
-    size_t per_cu = AGG_LDS_MAX / (lds_bytes > 0 ? lds_bytes : 1);
-    per_cu = per_cu > 8 ? 8 : per_cu < 1 ? 1 : per_cu;      // 32 waves a CU: eight workgroups of four
-    const int64_t resident = (int64_t)AGG_CUS * (int64_t)per_cu;
-    while (wpg > 1 && (N * wpg + 3) / 4 > resident) wpg >>= 1;
-    return wpg;
-}
-
 // ---- the heads' launchers (2 <= a.H <= HMAX and an admitted shape: capi.hip checks; H = 1 goes to the ones above)
 template <typename T, bool PER>
 static int aggregate_heads_forward_t(const AggregateArgs& a, hipStream_t stream) {
     int rc = PIGS_OK;
-    const size_t lds = sampling_lds(aggregate_heads_forward_kernel<T, PER>, sizeof(T), heads_forward_region(a.H, a.L, a.F), &rc);
+    const size_t lds = sampling_lds(aggregate_heads_forward_kernel<T, PER>, sizeof(T), forward_region(a.H, a.L, a.F), &rc);
     if (rc != PIGS_OK) return rc;
     const int wpg = heads_waves_per_gaussian(a.N, lds), gpw = 4 / wpg;
     clear_hip_error();
@@ -1355,12 +1339,6 @@ static int aggregate_heads_forward_t(const AggregateArgs& a, hipStream_t stream)
     return launch_status();
 }
 
-size_t aggregate_heads_backward_scratch_bytes(int dtype, int64_t N, int H, int L, int F) {
-    const size_t e = dtype == PIGS_F64 ? 8 : 4;
-    const int W = L + 2 * (4 * F + 1);
-    return align_up(e * (size_t)N * (size_t)(H * (W + 1) + F), 256);      // dacc [N][H][W], D [N][H], per-row d frequencies [N][F]
-}
-
 template <typename T, bool PER>
 static int aggregate_heads_backward_t(const AggregateArgs& a, hipStream_t stream) {
     const int H = a.H, E = 4 * a.F + 1, W = a.L + 2 * E;
@@ -1368,8 +1346,8 @@ static int aggregate_heads_backward_t(const AggregateArgs& a, hipStream_t stream
     T* D = dacc + (size_t)a.N * H * W;
     T* gfr = D + (size_t)a.N * H;
     int rc = PIGS_OK;
-    const size_t lds_r = sampling_lds(aggregate_heads_backward_rows_kernel<T, PER>, sizeof(T), heads_backward_rows_region(H, a.K, a.F), &rc);
-    const size_t lds_c = sampling_lds(aggregate_heads_backward_cols_kernel<T, PER>, sizeof(T), heads_backward_cols_region(H, a.L, a.K), &rc);
+    const size_t lds_r = sampling_lds(aggregate_heads_backward_rows_kernel<T, PER>, sizeof(T), backward_rows_region(H, a.K, a.F), &rc);
+    const size_t lds_c = sampling_lds(aggregate_heads_backward_cols_kernel<T, PER>, sizeof(T), backward_cols_region(H, a.L, a.K), &rc);
     if (rc != PIGS_OK) return rc;
     const int wpgr = heads_waves_per_gaussian(a.N, lds_r), wpgc = heads_waves_per_gaussian(a.N, lds_c);
     const dim3 gridr((unsigned)((a.N + 4 / wpgr - 1) / (4 / wpgr))), gridc((unsigned)((a.N + 4 / wpgc - 1) / (4 / wpgc))), block(256);
@@ -1397,18 +1375,18 @@ static int aggregate_heads_backward_t(const AggregateArgs& a, hipStream_t stream
     return launch_status();
 }
 
-int aggregate_heads_forward(const AggregateArgs& a, hipStream_t stream) {
-    if (a.H == 1) return aggregate_forward(a, stream);       // [N][1][K] is [N][K]: the single-head kernels
-    if (a.N == 0) return PIGS_OK;
-    if (a.period > 0) return a.dtype == PIGS_F32 ? aggregate_heads_forward_t<float, true>(a, stream) : aggregate_heads_forward_t<double, true>(a, stream);
-    return a.dtype == PIGS_F32 ? aggregate_heads_forward_t<float, false>(a, stream) : aggregate_heads_forward_t<double, false>(a, stream);
+// dtype, period > 0 and the head count (one head: the single-head kernels, [N][1][K] is [N][K]) pick the launcher
+#define PIGS_AGG_H(fn, T, PER) (a.H == 1 ? aggregate_##fn##_t<T, PER>(a, stream) : aggregate_heads_##fn##_t<T, PER>(a, stream))
+#define PIGS_AGG_DISPATCH(fn)                                                                                   \
+    (a.period > 0 ? (a.dtype == PIGS_F32 ? PIGS_AGG_H(fn, float, true) : PIGS_AGG_H(fn, double, true))            \
+                  : (a.dtype == PIGS_F32 ? PIGS_AGG_H(fn, float, false) : PIGS_AGG_H(fn, double, false)))
+int aggregate_forward(const AggregateArgs& a, hipStream_t stream) {
+    return a.N == 0 ? PIGS_OK : PIGS_AGG_DISPATCH(forward);
 }
-
-int aggregate_heads_backward(const AggregateArgs& a, hipStream_t stream) {
-    if (a.H == 1) return aggregate_backward(a, stream);
-    if (a.N == 0) return PIGS_OK;
-    if (a.period > 0) return a.dtype == PIGS_F32 ? aggregate_heads_backward_t<float, true>(a, stream) : aggregate_heads_backward_t<double, true>(a, stream);
-    return a.dtype == PIGS_F32 ? aggregate_heads_backward_t<float, false>(a, stream) : aggregate_heads_backward_t<double, false>(a, stream);
+int aggregate_backward(const AggregateArgs& a, hipStream_t stream) {
+    return a.N == 0 ? PIGS_OK : PIGS_AGG_DISPATCH(backward);
 }
+#undef PIGS_AGG_DISPATCH
+#undef PIGS_AGG_H
 
 }  // namespace pigs

@@ -323,18 +323,29 @@ int pigs_periodic_images_backward(int dtype, int c, int64_t N, const void* g_img
                              g_conics, g_values, nullptr, (hipStream_t)stream);
 }
 
-static int aggregate_sizes_ok(int dtype, int64_t N, int64_t cap, int L, int K, int F) {
+// the periodic entry points: argument checks before any HIP call (a list entry is j | k << 28)
+static int periodic_box_ok(int dtype, int64_t N, double lo, double period) {
     if (dtype != PIGS_F32 && dtype != PIGS_F64) return PIGS_ERR_UNSUPPORTED;
+    if (!std::isfinite(lo) || !std::isfinite(period) || !(period > 0) || !std::isfinite(lo + period)) return PIGS_ERR_INVALID;
+    if (N >= (1LL << 28)) return PIGS_ERR_UNSUPPORTED;
+    return PIGS_OK;
+}
+
+// THE argument rule of the sampling entry points (pigs_aggregate_*: H = 1, period = 0 or, checked by the entry, > 0)
+static int aggregate_sizes_ok(int dtype, int64_t N, int64_t cap, int H, int L, int K, int F, double period) {
+    if (dtype != PIGS_F32 && dtype != PIGS_F64) return PIGS_ERR_UNSUPPORTED;
+    if (H < 1 || H > PIGS_AGGREGATE_HEADS_MAX) return PIGS_ERR_UNSUPPORTED;
     if (N < 0 || cap < 1 || L < 1 || K < 1 || F < 0) return PIGS_ERR_INVALID;
-    if (L + 2 * (4 * F + 1) > 128 || L + K > 128 || K + F > 128 || N > 0x7fffffffLL) return PIGS_ERR_UNSUPPORTED;   // two components per lane
-    // the forward, too, refuses a shape whose backward could not run: all three kernels' LDS must fit a CU
-    if (aggregate_lds_bytes(dtype, L, K, F) > AGG_LDS_MAX) return PIGS_ERR_UNSUPPORTED;
+    if (L > 128 || K > 128 || F > 128 || N > 0x7fffffffLL) return PIGS_ERR_UNSUPPORTED;
+    // two components per lane; the forward, too, refuses a shape whose backward could not run: all three kernels' LDS must fit a CU
+    if (!aggregate_admitted(dtype, H, L, K, F)) return PIGS_ERR_UNSUPPORTED;
+    if (period != 0.0) return periodic_box_ok(dtype, N, 0.0, period);
     return PIGS_OK;
 }
 
 size_t pigs_aggregate_lds_bytes(int dtype, int L, int K, int F) {
     if ((dtype != PIGS_F32 && dtype != PIGS_F64) || L < 1 || K < 1 || F < 0 || L > 128 || K > 128 || F > 128) return 0;
-    return aggregate_lds_bytes(dtype, L, K, F);
+    return aggregate_lds_bytes(dtype, 1, L, K, F);
 }
 
 int pigs_aggregate_grid_info(int dtype, int64_t N, int64_t info[2]) {
@@ -346,14 +357,6 @@ int pigs_aggregate_grid_info(int dtype, int64_t N, int64_t info[2]) {
 size_t pigs_aggregate_workspace_bytes(int dtype, int64_t N) {
     if ((dtype != PIGS_F32 && dtype != PIGS_F64) || N < 0) return 0;
     return aggregate_workspace_bytes(dtype, N);
-}
-
-// the periodic entry points: argument checks before any HIP call (a list entry is j | k << 28)
-static int periodic_box_ok(int dtype, int64_t N, double lo, double period) {
-    if (dtype != PIGS_F32 && dtype != PIGS_F64) return PIGS_ERR_UNSUPPORTED;
-    if (!std::isfinite(lo) || !std::isfinite(period) || !(period > 0) || !std::isfinite(lo + period)) return PIGS_ERR_INVALID;
-    if (N >= (1LL << 28)) return PIGS_ERR_UNSUPPORTED;
-    return PIGS_OK;
 }
 
 static int aggregate_lists_checked(int dtype, int64_t N, int64_t cap, const void* means, const void* conics, double q_max,
@@ -385,21 +388,22 @@ int pigs_aggregate_lists_periodic(int dtype, int64_t N, int64_t cap, const void*
                                    row_lists, col_counts, col_lists, overflow, stream);
 }
 
-static int aggregate_forward_checked(int dtype, int64_t N, int64_t cap, int L, int K, int F, double period, const void* means,
-                                     const void* conics, const int32_t* row_counts, const int32_t* row_lists,
-                                     const void* features, const void* transform, const void* queries, const void* keys,
-                                     const void* frequencies, const void* distance_transform, void* out, void* lse, void* acc,
-                                     void* stream) {
-    const int rc = aggregate_sizes_ok(dtype, N, cap, L, K, F);
+// ---- all heads of a layer in one launch; pigs_aggregate_{forward,backward}[_periodic] are H = 1 of it.
+// period = 0: plain lists; > 0: the torus's
+int pigs_aggregate_heads_forward(int dtype, int64_t N, int64_t cap, int H, int L, int K, int F, double period, const void* means,
+                                 const void* conics, const int32_t* row_counts, const int32_t* row_lists, const void* features,
+                                 const void* transforms, const void* queries, const void* keys, const void* frequencies,
+                                 const void* distance_transforms, void* out, void* lse, void* acc, void* stream) {
+    const int rc = aggregate_sizes_ok(dtype, N, cap, H, L, K, F, period);
     if (rc != PIGS_OK) return rc;
-    if (N > 0 && (!means || !conics || !row_counts || !row_lists || !features || !transform || !queries || !keys ||
-                  (F > 0 && !frequencies) || !distance_transform || !out || !lse || !acc))
+    if (N > 0 && (!means || !conics || !row_counts || !row_lists || !features || !transforms || !queries || !keys ||
+                  (F > 0 && !frequencies) || !distance_transforms || !out || !lse || !acc))
         return PIGS_ERR_INVALID;
     AggregateArgs a{};
-    a.dtype = dtype; a.N = N; a.cap = cap; a.L = L; a.K = K; a.F = F; a.period = period;
+    a.dtype = dtype; a.N = N; a.cap = cap; a.H = H; a.L = L; a.K = K; a.F = F; a.period = period;
     a.means = means; a.conics = conics; a.row_counts = row_counts; a.row_lists = row_lists;
-    a.features = features; a.transform = transform; a.queries = queries; a.keys = keys; a.frequencies = frequencies;
-    a.distance_transform = distance_transform; a.out = out; a.lse = lse; a.acc = acc;
+    a.features = features; a.transform = transforms; a.queries = queries; a.keys = keys; a.frequencies = frequencies;
+    a.distance_transform = distance_transforms; a.out = out; a.lse = lse; a.acc = acc;
     return aggregate_forward(a, (hipStream_t)stream);
 }
 
@@ -407,8 +411,8 @@ int pigs_aggregate_forward(int dtype, int64_t N, int64_t cap, int L, int K, int 
                            const int32_t* row_counts, const int32_t* row_lists, const void* features,
                            const void* transform, const void* queries, const void* keys, const void* frequencies,
                            const void* distance_transform, void* out, void* lse, void* acc, void* stream) {
-    return aggregate_forward_checked(dtype, N, cap, L, K, F, 0.0, means, conics, row_counts, row_lists, features, transform,
-                                     queries, keys, frequencies, distance_transform, out, lse, acc, stream);
+    return pigs_aggregate_heads_forward(dtype, N, cap, 1, L, K, F, 0.0, means, conics, row_counts, row_lists, features, transform,
+                                        queries, keys, frequencies, distance_transform, out, lse, acc, stream);
 }
 
 int pigs_aggregate_forward_periodic(int dtype, int64_t N, int64_t cap, int L, int K, int F, double period, const void* means,
@@ -418,38 +422,47 @@ int pigs_aggregate_forward_periodic(int dtype, int64_t N, int64_t cap, int L, in
                                     void* stream) {
     const int rc = periodic_box_ok(dtype, N, 0.0, period);
     if (rc != PIGS_OK) return rc;
-    return aggregate_forward_checked(dtype, N, cap, L, K, F, period, means, conics, row_counts, row_lists, features, transform,
-                                     queries, keys, frequencies, distance_transform, out, lse, acc, stream);
+    return pigs_aggregate_heads_forward(dtype, N, cap, 1, L, K, F, period, means, conics, row_counts, row_lists, features, transform,
+                                        queries, keys, frequencies, distance_transform, out, lse, acc, stream);
+}
+
+size_t pigs_aggregate_heads_lds_bytes(int dtype, int H, int L, int K, int F) {
+    if ((dtype != PIGS_F32 && dtype != PIGS_F64) || L < 1 || K < 1 || F < 0 || L > 128 || K > 128 || F > 128) return 0;
+    return aggregate_heads_lds_bytes(dtype, H, L, K, F);         // 0: H or a component count out of range
+}
+
+size_t pigs_aggregate_heads_backward_scratch_bytes(int dtype, int64_t N, int H, int L, int F) {
+    if ((dtype != PIGS_F32 && dtype != PIGS_F64) || N < 0 || H < 1 || H > PIGS_AGGREGATE_HEADS_MAX || L < 1 || F < 0) return 0;
+    return aggregate_backward_scratch_bytes(dtype, N, H, L, F);
 }
 
 size_t pigs_aggregate_backward_scratch_bytes(int dtype, int64_t N, int L, int F) {
-    if ((dtype != PIGS_F32 && dtype != PIGS_F64) || N < 0 || L < 1 || F < 0) return 0;
-    return aggregate_backward_scratch_bytes(dtype, N, L, F);
+    return pigs_aggregate_heads_backward_scratch_bytes(dtype, N, 1, L, F);
 }
 
-static int aggregate_backward_checked(int dtype, int64_t N, int64_t cap, int L, int K, int F, double period, const void* means,
-                            const void* conics, const int32_t* row_counts, const int32_t* row_lists,
-                            const int32_t* col_counts, const int32_t* col_lists, const void* features,
-                            const void* transform, const void* queries, const void* keys, const void* frequencies,
-                            const void* distance_transform, const void* lse, const void* acc, const void* gout,
-                            void* scratch, size_t scratch_bytes, void* g_features, void* g_transform, void* g_queries,
-                            void* g_keys, void* g_frequencies, void* g_distance_transform, void* stream) {
-    const int rc = aggregate_sizes_ok(dtype, N, cap, L, K, F);
+int pigs_aggregate_heads_backward(int dtype, int64_t N, int64_t cap, int H, int L, int K, int F, double period, const void* means,
+                                  const void* conics, const int32_t* row_counts, const int32_t* row_lists,
+                                  const int32_t* col_counts, const int32_t* col_lists, const void* features,
+                                  const void* transforms, const void* queries, const void* keys, const void* frequencies,
+                                  const void* distance_transforms, const void* lse, const void* acc, const void* gout,
+                                  void* scratch, size_t scratch_bytes, void* g_features, void* g_transforms, void* g_queries,
+                                  void* g_keys, void* g_frequencies, void* g_distance_transforms, void* stream) {
+    const int rc = aggregate_sizes_ok(dtype, N, cap, H, L, K, F, period);
     if (rc != PIGS_OK) return rc;
-    if (N > 0 && (!means || !conics || !row_counts || !row_lists || !col_counts || !col_lists || !features || !transform ||
-                  !queries || !keys || (F > 0 && !frequencies) || !distance_transform || !lse || !acc || !gout || !scratch ||
-                  !g_features || !g_transform || !g_queries || !g_keys || (F > 0 && !g_frequencies) || !g_distance_transform))
+    if (N > 0 && (!means || !conics || !row_counts || !row_lists || !col_counts || !col_lists || !features || !transforms ||
+                  !queries || !keys || (F > 0 && !frequencies) || !distance_transforms || !lse || !acc || !gout || !scratch ||
+                  !g_features || !g_transforms || !g_queries || !g_keys || (F > 0 && !g_frequencies) || !g_distance_transforms))
         return PIGS_ERR_INVALID;
-    if (N > 0 && scratch_bytes < aggregate_backward_scratch_bytes(dtype, N, L, F)) return PIGS_ERR_WORKSPACE;
+    if (N > 0 && scratch_bytes < aggregate_backward_scratch_bytes(dtype, N, H, L, F)) return PIGS_ERR_WORKSPACE;
     AggregateArgs a{};
-    a.dtype = dtype; a.N = N; a.cap = cap; a.L = L; a.K = K; a.F = F; a.period = period;
+    a.dtype = dtype; a.N = N; a.cap = cap; a.H = H; a.L = L; a.K = K; a.F = F; a.period = period;
     a.means = means; a.conics = conics; a.row_counts = row_counts; a.row_lists = row_lists;
     a.col_counts = col_counts; a.col_lists = col_lists;
-    a.features = features; a.transform = transform; a.queries = queries; a.keys = keys; a.frequencies = frequencies;
-    a.distance_transform = distance_transform;
+    a.features = features; a.transform = transforms; a.queries = queries; a.keys = keys; a.frequencies = frequencies;
+    a.distance_transform = distance_transforms;
     a.lse = const_cast<void*>(lse); a.acc = const_cast<void*>(acc); a.gout = gout; a.scratch = scratch;
-    a.g_features = g_features; a.g_transform = g_transform; a.g_queries = g_queries; a.g_keys = g_keys;
-    a.g_frequencies = g_frequencies; a.g_distance_transform = g_distance_transform;
+    a.g_features = g_features; a.g_transform = g_transforms; a.g_queries = g_queries; a.g_keys = g_keys;
+    a.g_frequencies = g_frequencies; a.g_distance_transform = g_distance_transforms;
     return aggregate_backward(a, (hipStream_t)stream);
 }
 
@@ -460,10 +473,10 @@ int pigs_aggregate_backward(int dtype, int64_t N, int64_t cap, int L, int K, int
                             const void* distance_transform, const void* lse, const void* acc, const void* gout,
                             void* scratch, size_t scratch_bytes, void* g_features, void* g_transform, void* g_queries,
                             void* g_keys, void* g_frequencies, void* g_distance_transform, void* stream) {
-    return aggregate_backward_checked(dtype, N, cap, L, K, F, 0.0, means, conics, row_counts, row_lists, col_counts, col_lists,
-                                      features, transform, queries, keys, frequencies, distance_transform, lse, acc, gout, scratch,
-                                      scratch_bytes, g_features, g_transform, g_queries, g_keys, g_frequencies,
-                                      g_distance_transform, stream);
+    return pigs_aggregate_heads_backward(dtype, N, cap, 1, L, K, F, 0.0, means, conics, row_counts, row_lists, col_counts, col_lists,
+                                         features, transform, queries, keys, frequencies, distance_transform, lse, acc, gout, scratch,
+                                         scratch_bytes, g_features, g_transform, g_queries, g_keys, g_frequencies,
+                                         g_distance_transform, stream);
 }
 
 int pigs_aggregate_backward_periodic(int dtype, int64_t N, int64_t cap, int L, int K, int F, double period, const void* means,
@@ -476,75 +489,10 @@ int pigs_aggregate_backward_periodic(int dtype, int64_t N, int64_t cap, int L, i
                                      void* stream) {
     const int rc = periodic_box_ok(dtype, N, 0.0, period);
     if (rc != PIGS_OK) return rc;
-    return aggregate_backward_checked(dtype, N, cap, L, K, F, period, means, conics, row_counts, row_lists, col_counts, col_lists,
-                                      features, transform, queries, keys, frequencies, distance_transform, lse, acc, gout, scratch,
-                                      scratch_bytes, g_features, g_transform, g_queries, g_keys, g_frequencies,
-                                      g_distance_transform, stream);
-}
-
-// ---- all heads of a layer in one launch (additive to ABI 10).  period = 0: plain lists; > 0: the torus's
-static int aggregate_heads_sizes_ok(int dtype, int64_t N, int64_t cap, int H, int L, int K, int F, double period) {
-    if (dtype != PIGS_F32 && dtype != PIGS_F64) return PIGS_ERR_UNSUPPORTED;
-    if (H < 1 || H > PIGS_AGGREGATE_HEADS_MAX) return PIGS_ERR_UNSUPPORTED;
-    if (N < 0 || cap < 1 || L < 1 || K < 1 || F < 0) return PIGS_ERR_INVALID;
-    if (L > 128 || K > 128 || F > 128 || N > 0x7fffffffLL) return PIGS_ERR_UNSUPPORTED;
-    // the forward, too, refuses a shape whose backward could not run
-    if (!aggregate_heads_admitted(dtype, H, L, K, F)) return PIGS_ERR_UNSUPPORTED;
-    if (period != 0.0) return periodic_box_ok(dtype, N, 0.0, period);
-    return PIGS_OK;
-}
-
-size_t pigs_aggregate_heads_lds_bytes(int dtype, int H, int L, int K, int F) {
-    if ((dtype != PIGS_F32 && dtype != PIGS_F64) || L < 1 || K < 1 || F < 0 || L > 128 || K > 128 || F > 128) return 0;
-    return aggregate_heads_lds_bytes(dtype, H, L, K, F);         // 0: H or a component count out of range
-}
-
-size_t pigs_aggregate_heads_backward_scratch_bytes(int dtype, int64_t N, int H, int L, int F) {
-    if ((dtype != PIGS_F32 && dtype != PIGS_F64) || N < 0 || H < 1 || H > PIGS_AGGREGATE_HEADS_MAX || L < 1 || F < 0) return 0;
-    return aggregate_heads_backward_scratch_bytes(dtype, N, H, L, F);
-}
-
-int pigs_aggregate_heads_forward(int dtype, int64_t N, int64_t cap, int H, int L, int K, int F, double period, const void* means,
-                                 const void* conics, const int32_t* row_counts, const int32_t* row_lists, const void* features,
-                                 const void* transforms, const void* queries, const void* keys, const void* frequencies,
-                                 const void* distance_transforms, void* out, void* lse, void* acc, void* stream) {
-    const int rc = aggregate_heads_sizes_ok(dtype, N, cap, H, L, K, F, period);
-    if (rc != PIGS_OK) return rc;
-    if (N > 0 && (!means || !conics || !row_counts || !row_lists || !features || !transforms || !queries || !keys ||
-                  (F > 0 && !frequencies) || !distance_transforms || !out || !lse || !acc))
-        return PIGS_ERR_INVALID;
-    AggregateArgs a{};
-    a.dtype = dtype; a.N = N; a.cap = cap; a.H = H; a.L = L; a.K = K; a.F = F; a.period = period;
-    a.means = means; a.conics = conics; a.row_counts = row_counts; a.row_lists = row_lists;
-    a.features = features; a.transform = transforms; a.queries = queries; a.keys = keys; a.frequencies = frequencies;
-    a.distance_transform = distance_transforms; a.out = out; a.lse = lse; a.acc = acc;
-    return aggregate_heads_forward(a, (hipStream_t)stream);
-}
-
-int pigs_aggregate_heads_backward(int dtype, int64_t N, int64_t cap, int H, int L, int K, int F, double period, const void* means,
-                                  const void* conics, const int32_t* row_counts, const int32_t* row_lists,
-                                  const int32_t* col_counts, const int32_t* col_lists, const void* features,
-                                  const void* transforms, const void* queries, const void* keys, const void* frequencies,
-                                  const void* distance_transforms, const void* lse, const void* acc, const void* gout,
-                                  void* scratch, size_t scratch_bytes, void* g_features, void* g_transforms, void* g_queries,
-                                  void* g_keys, void* g_frequencies, void* g_distance_transforms, void* stream) {
-    const int rc = aggregate_heads_sizes_ok(dtype, N, cap, H, L, K, F, period);
-    if (rc != PIGS_OK) return rc;
-    if (N > 0 && (!means || !conics || !row_counts || !row_lists || !col_counts || !col_lists || !features || !transforms ||
-                  !queries || !keys || (F > 0 && !frequencies) || !distance_transforms || !lse || !acc || !gout || !scratch ||
-                  !g_features || !g_transforms || !g_queries || !g_keys || (F > 0 && !g_frequencies) || !g_distance_transforms))
-        return PIGS_ERR_INVALID;
-    if (N > 0 && scratch_bytes < aggregate_heads_backward_scratch_bytes(dtype, N, H, L, F)) return PIGS_ERR_WORKSPACE;
-    AggregateArgs a{};
-    a.dtype = dtype; a.N = N; a.cap = cap; a.H = H; a.L = L; a.K = K; a.F = F; a.period = period;
-    a.means = means; a.conics = conics; a.row_counts = row_counts; a.row_lists = row_lists;
-    a.col_counts = col_counts; a.col_lists = col_lists;
-    a.features = features; a.transform = transforms; a.queries = queries; a.keys = keys; a.frequencies = frequencies;
-    a.distance_transform = distance_transforms;
-    a.lse = const_cast<void*>(lse); a.acc = const_cast<void*>(acc); a.gout = gout; a.scratch = scratch;
-    a.g_features = g_features; a.g_transform = g_transforms; a.g_queries = g_queries; a.g_keys = g_keys;
-    a.g_frequencies = g_frequencies; a.g_distance_transform = g_distance_transforms;
-    return aggregate_heads_backward(a, (hipStream_t)stream);
+    return pigs_aggregate_heads_backward(dtype, N, cap, 1, L, K, F, period, means, conics, row_counts, row_lists, col_counts, col_lists,
+                                         features, transform, queries, keys, frequencies, distance_transform, lse, acc, gout, scratch,
+                                         scratch_bytes, g_features, g_transform, g_queries, g_keys, g_frequencies,
+                                         g_distance_transform, stream);
 }
 
 size_t pigs_refine_workspace_bytes(int64_t N) { return refine_workspace_bytes(N); }

@@ -58,33 +58,28 @@ int periodic_dispatch(bool fold, int dtype, int c, int64_t N, double lo, double 
 struct AggregateArgs {
     int dtype;
     int64_t N, cap;
-    int L, K, F;
+    int H, L, K, F;                                // H heads (pigs_aggregate_*: 1; [N][1][K] is [N][K])
     double period;                                 // > 0: periodic lists (entries j | k << 28), means wrapped; 0: plain
     const void *means, *conics;
     const int32_t *row_counts, *row_lists, *col_counts, *col_lists;
+    // transform [H][L][L], queries / keys [N][H][K], distance_transform [H][L][2E]
     const void *features, *transform, *queries, *keys, *frequencies, *distance_transform;
-    void *out, *lse, *acc;                         // forward outputs (the backward reads lse and acc)
-    const void* gout;                              // backward: incoming gradient [N][L]
-    void* scratch;                                 // backward: dacc [N][W], D [N], per-row d frequencies [N][F]
+    void *out, *lse, *acc;                         // forward outputs [N][H][L], [N][H], [N][H][W] (the backward reads lse and acc)
+    const void* gout;                              // backward: incoming gradient [N][H][L]
+    void* scratch;                                 // backward: dacc [N][H][W], D [N][H], per-row d frequencies [N][F]
     void *g_features, *g_transform, *g_queries, *g_keys, *g_frequencies, *g_distance_transform;
-    // the heads' entries (aggregate_heads_*): transform [H][L][L], queries / keys [N][H][K], distance_transform [H][L][2E],
-    // out [N][H][L], lse [N][H], acc [N][H][W], gout [N][H][L], scratch dacc [N][H][W], D [N][H], d frequencies [N][F]
-    int H;
 };
-size_t aggregate_backward_scratch_bytes(int dtype, int64_t N, int L, int F);
 size_t aggregate_workspace_bytes(int dtype, int64_t N);
 constexpr size_t AGG_LDS_MAX = 160 * 1024;       // LDS of a gfx950 CU: what one workgroup can ask for
-size_t aggregate_lds_bytes(int dtype, int L, int K, int F);
+size_t aggregate_lds_bytes(int dtype, int H, int L, int K, int F);
+size_t aggregate_heads_lds_bytes(int dtype, int H, int L, int K, int F);      // the same, 0 where H or a component count is out of range
+bool aggregate_admitted(int dtype, int H, int L, int K, int F);               // the size rule (1 <= H <= 4)
+size_t aggregate_backward_scratch_bytes(int dtype, int64_t N, int H, int L, int F);
 int aggregate_lists(int dtype, int64_t N, int64_t cap, const void* means, const void* conics, double q_max, void* workspace,
                     size_t workspace_bytes, int flags, int32_t* row_counts, int32_t* row_lists, int32_t* col_counts,
                     int32_t* col_lists, int32_t* overflow, hipStream_t stream, double lo = 0.0, double period = 0.0);
 int aggregate_forward(const AggregateArgs& a, hipStream_t stream);
 int aggregate_backward(const AggregateArgs& a, hipStream_t stream);
-size_t aggregate_heads_lds_bytes(int dtype, int H, int L, int K, int F);
-bool aggregate_heads_admitted(int dtype, int H, int L, int K, int F);         // the heads' size rule (1 <= H <= 4)
-size_t aggregate_heads_backward_scratch_bytes(int dtype, int64_t N, int H, int L, int F);
-int aggregate_heads_forward(const AggregateArgs& a, hipStream_t stream);
-int aggregate_heads_backward(const AggregateArgs& a, hipStream_t stream);
 
 // plan.hip
 size_t samples_workspace_bytes(int64_t M);

@@ -745,145 +745,29 @@ struct NeighborLists {
     }
 };
 
+// One backward node for aggregate_neighbors (`heads` false: the tensors are one head's, H = 1) and
+// aggregate_neighbors_heads (transforms [H,L,L], queries / keys [N,H,K], distance_transforms [H,L,2E] -> [N,H,L])
 struct AggregateBackward : public torch::autograd::Node {
     std::shared_ptr<NeighborLists> nb;
     at::Tensor f, tr, q, k, fr, dist, lse, acc;     // converted, contiguous, detached
     uint32_t versions[6] = {0, 0, 0, 0, 0, 0};
     at::ScalarType in_dtypes[6];
+    bool heads = false;
     int64_t N = 0;
-    int L = 0, K = 0, F = 0;
+    int H = 1, L = 0, K = 0, F = 0;
 
-    std::string name() const override { return "PigsAggregateBackward"; }
+    std::string name() const override { return heads ? "PigsAggregateHeadsBackward" : "PigsAggregateBackward"; }
 
     torch::autograd::variable_list apply(torch::autograd::variable_list&& grads) override {
-        if (!f.defined()) throw std::runtime_error("aggregate_neighbors: backward through the graph a second time (saved tensors were freed)");
+        const std::string fn = heads ? "aggregate_neighbors_heads" : "aggregate_neighbors";
+        if (!f.defined()) throw std::runtime_error(fn + ": backward through the graph a second time (saved tensors were freed)");
         const at::Tensor* saved[6] = {&f, &tr, &q, &k, &fr, &dist};
         for (int x = 0; x < 6; ++x)
             if (saved[x]->_version() != versions[x])
-                throw std::runtime_error("one of the tensors handed to aggregate_neighbors() has been modified in place before its backward");
+                throw std::runtime_error("one of the tensors handed to " + fn + "() has been modified in place before its backward");
         if (grads.empty() || !grads[0].defined()) return torch::autograd::variable_list(6);
         at::AutoGradMode no_grad(false);
-        if (grads[0].requires_grad()) throw std::runtime_error("aggregate_neighbors is differentiable once");
-        const at::Tensor gout = grads[0].to(f.scalar_type()).contiguous();
-        at::Tensor g_f = at::empty_like(f), g_tr = at::empty_like(tr), g_q = at::empty_like(q), g_k = at::empty_like(k),
-                   g_fr = at::empty_like(fr), g_dist = at::empty_like(dist);
-        const int dt = dtype_code(f);
-        if (N > 0) {
-            const size_t nbytes = pigs_aggregate_backward_scratch_bytes(dt, N, L, F);
-            at::Tensor scratch = at::empty({(int64_t)nbytes}, f.options().dtype(at::kByte));
-            c10::DeviceGuard guard(f.device());
-            if (nb->periodic)
-                check(pigs_aggregate_backward_periodic(dt, N, nb->cap, L, K, F, nb->period, ptr(nb->means), ptr(nb->conics),
-                                                       (const int32_t*)ptr(nb->row_counts), (const int32_t*)ptr(nb->row_lists),
-                                                       (const int32_t*)ptr(nb->col_counts), (const int32_t*)ptr(nb->col_lists), ptr(f),
-                                                       ptr(tr), ptr(q), ptr(k), ptr(fr), ptr(dist), ptr(lse), ptr(acc), ptr(gout),
-                                                       scratch.data_ptr(), nbytes, ptr(g_f), ptr(g_tr), ptr(g_q), ptr(g_k), ptr(g_fr),
-                                                       ptr(g_dist), current_stream(f)),
-                      "pigs_aggregate_backward_periodic");
-            else
-                check(pigs_aggregate_backward(dt, N, nb->cap, L, K, F, ptr(nb->means), ptr(nb->conics), (const int32_t*)ptr(nb->row_counts),
-                                              (const int32_t*)ptr(nb->row_lists), (const int32_t*)ptr(nb->col_counts),
-                                              (const int32_t*)ptr(nb->col_lists), ptr(f), ptr(tr), ptr(q), ptr(k), ptr(fr), ptr(dist),
-                                              ptr(lse), ptr(acc), ptr(gout), scratch.data_ptr(), nbytes, ptr(g_f), ptr(g_tr), ptr(g_q),
-                                              ptr(g_k), ptr(g_fr), ptr(g_dist), current_stream(f)),
-                      "pigs_aggregate_backward");
-        } else {
-            g_tr.zero_(); g_fr.zero_(); g_dist.zero_();
-        }
-        return {g_f.to(in_dtypes[0]), g_tr.to(in_dtypes[1]), g_q.to(in_dtypes[2]), g_k.to(in_dtypes[3]), g_fr.to(in_dtypes[4]),
-                g_dist.to(in_dtypes[5])};
-    }
-    void release_variables() override {
-        f = tr = q = k = fr = dist = lse = acc = at::Tensor();
-    }
-};
-
-at::Tensor aggregate_apply(const std::shared_ptr<NeighborLists>& nb, const at::Tensor& features, const at::Tensor& transform,
-                           const at::Tensor& queries, const at::Tensor& keys, const at::Tensor& frequencies,
-                           const at::Tensor& distance_transform) {
-    const int64_t N = nb->N;
-    if (features.dim() != 2 || features.size(0) != N)
-        raise_py(PyExc_ValueError, "features must be [N=" + std::to_string(N) + ", L], got " + shape_str(features));
-    if (queries.dim() != 2 || keys.dim() != 2 || frequencies.dim() != 1 || transform.dim() != 2 || distance_transform.dim() != 2)
-        raise_py(PyExc_ValueError, "aggregate_neighbors: transform, queries, keys, distance_transform must be 2-d, frequencies 1-d");
-    const int64_t L = features.size(1), K = queries.size(1), F = frequencies.size(0), E = 4 * F + 1;
-    if (transform.size(0) != L || transform.size(1) != L || queries.size(0) != N || keys.size(0) != N || keys.size(1) != K ||
-        distance_transform.size(0) != L || distance_transform.size(1) != 2 * E)
-        raise_py(PyExc_ValueError, "aggregate_neighbors: expected transform [" + std::to_string(L) + "," + std::to_string(L) +
-                                       "], queries/keys [" + std::to_string(N) + "," + std::to_string(K) + "], distance_transform [" +
-                                       std::to_string(L) + "," + std::to_string(2 * E) + "] (E = 2*d*F + 1 = " + std::to_string(E) + ")");
-    const at::Tensor* ins[6] = {&features, &transform, &queries, &keys, &frequencies, &distance_transform};
-    const char* names[6] = {"features", "transform", "queries", "keys", "frequencies", "distance_transform"};
-    for (int x = 0; x < 6; ++x)
-        if (!ins[x]->is_cuda())
-            raise_py(PyExc_RuntimeError, std::string(names[x]) + " is on " + ins[x]->device().str() +
-                                             ": aggregate_neighbors runs on the GPU only (no CPU fallback)");
-    if (L + 2 * E > 128) raise_py(PyExc_NotImplementedError, "L + 2E = " + std::to_string(L + 2 * E) + " > 128 is not supported");
-    const auto dt = nb->means.scalar_type();
-    const size_t lds = pigs_aggregate_lds_bytes(dt == at::kDouble ? PIGS_F64 : PIGS_F32, (int)L, (int)K, (int)F);
-    if (lds > PIGS_AGGREGATE_LDS_MAX)      // the backward's kernels included: a forward that cannot be differentiated is refused
-        raise_py(PyExc_NotImplementedError, std::string(dt == at::kDouble ? "float64" : "float32") + " with L = " + std::to_string(L) +
-                                                ", K = " + std::to_string(K) + ", F = " + std::to_string(F) + " needs " +
-                                                std::to_string(lds) + " bytes of LDS in one of the forward's or the backward's kernels; "
-                                                "the limit is " + std::to_string(PIGS_AGGREGATE_LDS_MAX));
-    at::Tensor c[6];
-    {
-        at::AutoGradMode no_grad(false);
-        for (int x = 0; x < 6; ++x) c[x] = ins[x]->detach().to(dt).contiguous();
-    }
-    const auto opt = c[0].options();
-    at::Tensor out = at::empty({N, L}, opt), lse = at::empty({N}, opt), acc = at::empty({N, L + 2 * E}, opt);
-    if (N > 0) {
-        c10::DeviceGuard guard(c[0].device());
-        if (nb->periodic)
-            check(pigs_aggregate_forward_periodic(dtype_code(c[0]), N, nb->cap, (int)L, (int)K, (int)F, nb->period, ptr(nb->means),
-                                                  ptr(nb->conics), (const int32_t*)ptr(nb->row_counts),
-                                                  (const int32_t*)ptr(nb->row_lists), ptr(c[0]), ptr(c[1]), ptr(c[2]), ptr(c[3]),
-                                                  ptr(c[4]), ptr(c[5]), ptr(out), ptr(lse), ptr(acc), current_stream(c[0])),
-                  "pigs_aggregate_forward_periodic");
-        else
-            check(pigs_aggregate_forward(dtype_code(c[0]), N, nb->cap, (int)L, (int)K, (int)F, ptr(nb->means), ptr(nb->conics),
-                                         (const int32_t*)ptr(nb->row_counts), (const int32_t*)ptr(nb->row_lists), ptr(c[0]), ptr(c[1]),
-                                         ptr(c[2]), ptr(c[3]), ptr(c[4]), ptr(c[5]), ptr(out), ptr(lse), ptr(acc), current_stream(c[0])),
-                  "pigs_aggregate_forward");
-    }
-    if (out.scalar_type() != features.scalar_type()) out = out.to(features.scalar_type());
-    bool need = false;
-    for (int x = 0; x < 6; ++x) need = need || ins[x]->requires_grad();
-    if (at::GradMode::is_enabled() && need) {
-        std::shared_ptr<AggregateBackward> node(new AggregateBackward(), torch::autograd::deleteNode);
-        node->set_next_edges(torch::autograd::collect_next_edges(features, transform, queries, keys, frequencies, distance_transform));
-        node->nb = nb;
-        node->f = c[0]; node->tr = c[1]; node->q = c[2]; node->k = c[3]; node->fr = c[4]; node->dist = c[5];
-        node->lse = lse; node->acc = acc;
-        for (int x = 0; x < 6; ++x) { node->versions[x] = c[x]._version(); node->in_dtypes[x] = ins[x]->scalar_type(); }
-        node->N = N; node->L = (int)L; node->K = (int)K; node->F = (int)F;
-        torch::autograd::create_gradient_edge(out, node);
-    }
-    return out;
-}
-
-// ---- all heads of a layer in one launch (pigs_aggregate_heads_*).  Same structure as aggregate_heads of
-// pigs_amd/aggregate.py: transforms [H,L,L], queries / keys [N,H,K], distance_transforms [H,L,2E] -> [N,H,L]
-struct AggregateHeadsBackward : public torch::autograd::Node {
-    std::shared_ptr<NeighborLists> nb;
-    at::Tensor f, tr, q, k, fr, dist, lse, acc;     // converted, contiguous, detached
-    uint32_t versions[6] = {0, 0, 0, 0, 0, 0};
-    at::ScalarType in_dtypes[6];
-    int64_t N = 0;
-    int H = 0, L = 0, K = 0, F = 0;
-
-    std::string name() const override { return "PigsAggregateHeadsBackward"; }
-
-    torch::autograd::variable_list apply(torch::autograd::variable_list&& grads) override {
-        if (!f.defined()) throw std::runtime_error("aggregate_neighbors_heads: backward through the graph a second time (saved tensors were freed)");
-        const at::Tensor* saved[6] = {&f, &tr, &q, &k, &fr, &dist};
-        for (int x = 0; x < 6; ++x)
-            if (saved[x]->_version() != versions[x])
-                throw std::runtime_error("one of the tensors handed to aggregate_neighbors_heads() has been modified in place before its backward");
-        if (grads.empty() || !grads[0].defined()) return torch::autograd::variable_list(6);
-        at::AutoGradMode no_grad(false);
-        if (grads[0].requires_grad()) throw std::runtime_error("aggregate_neighbors_heads is differentiable once");
+        if (grads[0].requires_grad()) throw std::runtime_error(fn + " is differentiable once");
         const at::Tensor gout = grads[0].to(f.scalar_type()).contiguous();
         at::Tensor g_f = at::empty_like(f), g_tr = at::empty_like(tr), g_q = at::empty_like(q), g_k = at::empty_like(k),
                    g_fr = at::empty_like(fr), g_dist = at::empty_like(dist);
@@ -910,6 +794,87 @@ struct AggregateHeadsBackward : public torch::autograd::Node {
     }
 };
 
+// the launch and the backward node of both calls, after their argument checks (ins: features, transform(s), queries, keys,
+// frequencies, distance_transform(s)); out [N,L] or, with a head axis, [N,H,L]
+static at::Tensor aggregate_launch(const std::shared_ptr<NeighborLists>& nb, bool heads, int64_t H, int64_t L, int64_t K, int64_t F,
+                                   const at::Tensor* const (&ins)[6]) {
+    const int64_t N = nb->N, E = 4 * F + 1;
+    const auto dt = nb->means.scalar_type();
+    at::Tensor c[6];
+    {
+        at::AutoGradMode no_grad(false);
+        for (int x = 0; x < 6; ++x) c[x] = ins[x]->detach().to(dt).contiguous();
+    }
+    const auto opt = c[0].options();
+    at::Tensor out, lse, acc;
+    if (heads) { out = at::empty({N, H, L}, opt); lse = at::empty({N, H}, opt); acc = at::empty({N, H, L + 2 * E}, opt); }
+    else { out = at::empty({N, L}, opt); lse = at::empty({N}, opt); acc = at::empty({N, L + 2 * E}, opt); }
+    if (N > 0) {
+        c10::DeviceGuard guard(c[0].device());
+        check(pigs_aggregate_heads_forward(dtype_code(c[0]), N, nb->cap, (int)H, (int)L, (int)K, (int)F, nb->periodic ? nb->period : 0.0,
+                                           ptr(nb->means), ptr(nb->conics), (const int32_t*)ptr(nb->row_counts),
+                                           (const int32_t*)ptr(nb->row_lists), ptr(c[0]), ptr(c[1]), ptr(c[2]), ptr(c[3]), ptr(c[4]),
+                                           ptr(c[5]), ptr(out), ptr(lse), ptr(acc), current_stream(c[0])),
+              "pigs_aggregate_heads_forward");
+    }
+    if (out.scalar_type() != ins[0]->scalar_type()) out = out.to(ins[0]->scalar_type());
+    bool need = false;
+    for (int x = 0; x < 6; ++x) need = need || ins[x]->requires_grad();
+    if (at::GradMode::is_enabled() && need) {
+        std::shared_ptr<AggregateBackward> node(new AggregateBackward(), torch::autograd::deleteNode);
+        node->set_next_edges(torch::autograd::collect_next_edges(*ins[0], *ins[1], *ins[2], *ins[3], *ins[4], *ins[5]));
+        node->nb = nb;
+        node->f = c[0]; node->tr = c[1]; node->q = c[2]; node->k = c[3]; node->fr = c[4]; node->dist = c[5];
+        node->lse = lse; node->acc = acc;
+        for (int x = 0; x < 6; ++x) { node->versions[x] = c[x]._version(); node->in_dtypes[x] = ins[x]->scalar_type(); }
+        node->heads = heads;
+        node->N = N; node->H = (int)H; node->L = (int)L; node->K = (int)K; node->F = (int)F;
+        torch::autograd::create_gradient_edge(out, node);
+    }
+    return out;
+}
+
+// one head's size checks, in aggregate_neighbors' words
+static void refuse_one_head(at::ScalarType dt, int64_t L, int64_t K, int64_t F) {
+    const int64_t E = 4 * F + 1;
+    if (L + 2 * E > 128) raise_py(PyExc_NotImplementedError, "L + 2E = " + std::to_string(L + 2 * E) + " > 128 is not supported");
+    const size_t lds = pigs_aggregate_lds_bytes(dt == at::kDouble ? PIGS_F64 : PIGS_F32, (int)L, (int)K, (int)F);
+    if (lds > PIGS_AGGREGATE_LDS_MAX)      // the backward's kernels included: a forward that cannot be differentiated is refused
+        raise_py(PyExc_NotImplementedError, std::string(dt == at::kDouble ? "float64" : "float32") + " with L = " + std::to_string(L) +
+                                                ", K = " + std::to_string(K) + ", F = " + std::to_string(F) + " needs " +
+                                                std::to_string(lds) + " bytes of LDS in one of the forward's or the backward's kernels; "
+                                                "the limit is " + std::to_string(PIGS_AGGREGATE_LDS_MAX));
+}
+static void refuse_off_gpu(const at::Tensor* const (&ins)[6], const char* const (&names)[6], const char* fn) {
+    for (int x = 0; x < 6; ++x)
+        if (!ins[x]->is_cuda())
+            raise_py(PyExc_RuntimeError, std::string(names[x]) + " is on " + ins[x]->device().str() + ": " + fn +
+                                             " runs on the GPU only (no CPU fallback)");
+}
+
+at::Tensor aggregate_apply(const std::shared_ptr<NeighborLists>& nb, const at::Tensor& features, const at::Tensor& transform,
+                           const at::Tensor& queries, const at::Tensor& keys, const at::Tensor& frequencies,
+                           const at::Tensor& distance_transform) {
+    const int64_t N = nb->N;
+    if (features.dim() != 2 || features.size(0) != N)
+        raise_py(PyExc_ValueError, "features must be [N=" + std::to_string(N) + ", L], got " + shape_str(features));
+    if (queries.dim() != 2 || keys.dim() != 2 || frequencies.dim() != 1 || transform.dim() != 2 || distance_transform.dim() != 2)
+        raise_py(PyExc_ValueError, "aggregate_neighbors: transform, queries, keys, distance_transform must be 2-d, frequencies 1-d");
+    const int64_t L = features.size(1), K = queries.size(1), F = frequencies.size(0), E = 4 * F + 1;
+    if (transform.size(0) != L || transform.size(1) != L || queries.size(0) != N || keys.size(0) != N || keys.size(1) != K ||
+        distance_transform.size(0) != L || distance_transform.size(1) != 2 * E)
+        raise_py(PyExc_ValueError, "aggregate_neighbors: expected transform [" + std::to_string(L) + "," + std::to_string(L) +
+                                       "], queries/keys [" + std::to_string(N) + "," + std::to_string(K) + "], distance_transform [" +
+                                       std::to_string(L) + "," + std::to_string(2 * E) + "] (E = 2*d*F + 1 = " + std::to_string(E) + ")");
+    const at::Tensor* const ins[6] = {&features, &transform, &queries, &keys, &frequencies, &distance_transform};
+    const char* const names[6] = {"features", "transform", "queries", "keys", "frequencies", "distance_transform"};
+    refuse_off_gpu(ins, names, "aggregate_neighbors");
+    refuse_one_head(nb->means.scalar_type(), L, K, F);
+    return aggregate_launch(nb, false, 1, L, K, F, ins);
+}
+
+// ---- all heads of a layer in one launch (pigs_aggregate_heads_*).  Same structure as aggregate_heads of
+// pigs_amd/aggregate.py: transforms [H,L,L], queries / keys [N,H,K], distance_transforms [H,L,2E] -> [N,H,L]
 at::Tensor aggregate_heads_apply(const std::shared_ptr<NeighborLists>& nb, const at::Tensor& features, const at::Tensor& transforms,
                                  const at::Tensor& queries, const at::Tensor& keys, const at::Tensor& frequencies,
                                  const at::Tensor& distance_transforms) {
@@ -926,20 +891,18 @@ at::Tensor aggregate_heads_apply(const std::shared_ptr<NeighborLists>& nb, const
                                        std::to_string(L) + "], queries/keys [" + std::to_string(N) + "," + std::to_string(H) + "," +
                                        std::to_string(K) + "], distance_transforms [" + std::to_string(H) + "," + std::to_string(L) + "," +
                                        std::to_string(2 * E) + "] (E = 2*d*F + 1 = " + std::to_string(E) + ")");
-    const at::Tensor* ins[6] = {&features, &transforms, &queries, &keys, &frequencies, &distance_transforms};
-    const char* names[6] = {"features", "transforms", "queries", "keys", "frequencies", "distance_transforms"};
-    for (int x = 0; x < 6; ++x)
-        if (!ins[x]->is_cuda())
-            raise_py(PyExc_RuntimeError, std::string(names[x]) + " is on " + ins[x]->device().str() +
-                                             ": aggregate_neighbors_heads runs on the GPU only (no CPU fallback)");
+    const at::Tensor* const ins[6] = {&features, &transforms, &queries, &keys, &frequencies, &distance_transforms};
+    const char* const names[6] = {"features", "transforms", "queries", "keys", "frequencies", "distance_transforms"};
+    refuse_off_gpu(ins, names, "aggregate_neighbors_heads");
     const std::string remain = "; H separate aggregate_neighbors calls remain available";
     if (H < 1 || H > PIGS_AGGREGATE_HEADS_MAX)
         raise_py(PyExc_NotImplementedError, "H = " + std::to_string(H) + " heads: one launch serves 1 <= H <= " +
                                                 std::to_string(PIGS_AGGREGATE_HEADS_MAX) + remain);
-    if (H == 1)      // the single-head entry points
-        return aggregate_apply(nb, features, transforms.select(0, 0), queries.select(1, 0), keys.select(1, 0), frequencies,
-                               distance_transforms.select(0, 0)).unsqueeze(1);
     const auto dt = nb->means.scalar_type();
+    if (H == 1) {    // one head: aggregate_neighbors' rule, in its words
+        refuse_one_head(dt, L, K, F);
+        return aggregate_launch(nb, true, H, L, K, F, ins);
+    }
     const int dc = dt == at::kDouble ? PIGS_F64 : PIGS_F32;
     const std::string shape = std::string(dt == at::kDouble ? "float64" : "float32") + " with H = " + std::to_string(H) + ", L = " +
                               std::to_string(L) + ", K = " + std::to_string(K) + ", F = " + std::to_string(F);
@@ -952,35 +915,7 @@ at::Tensor aggregate_heads_apply(const std::shared_ptr<NeighborLists>& nb, const
         raise_py(PyExc_NotImplementedError, "aggregate_neighbors_heads: " + shape + " needs " + std::to_string(lds) +
                                                 " bytes of LDS in one of the forward's or the backward's kernels; the limit is " +
                                                 std::to_string(PIGS_AGGREGATE_LDS_MAX) + remain);
-    at::Tensor c[6];
-    {
-        at::AutoGradMode no_grad(false);
-        for (int x = 0; x < 6; ++x) c[x] = ins[x]->detach().to(dt).contiguous();
-    }
-    const auto opt = c[0].options();
-    at::Tensor out = at::empty({N, H, L}, opt), lse = at::empty({N, H}, opt), acc = at::empty({N, H, L + 2 * E}, opt);
-    if (N > 0) {
-        c10::DeviceGuard guard(c[0].device());
-        check(pigs_aggregate_heads_forward(dc, N, nb->cap, (int)H, (int)L, (int)K, (int)F, nb->periodic ? nb->period : 0.0,
-                                           ptr(nb->means), ptr(nb->conics), (const int32_t*)ptr(nb->row_counts),
-                                           (const int32_t*)ptr(nb->row_lists), ptr(c[0]), ptr(c[1]), ptr(c[2]), ptr(c[3]), ptr(c[4]),
-                                           ptr(c[5]), ptr(out), ptr(lse), ptr(acc), current_stream(c[0])),
-              "pigs_aggregate_heads_forward");
-    }
-    if (out.scalar_type() != features.scalar_type()) out = out.to(features.scalar_type());
-    bool need = false;
-    for (int x = 0; x < 6; ++x) need = need || ins[x]->requires_grad();
-    if (at::GradMode::is_enabled() && need) {
-        std::shared_ptr<AggregateHeadsBackward> node(new AggregateHeadsBackward(), torch::autograd::deleteNode);
-        node->set_next_edges(torch::autograd::collect_next_edges(features, transforms, queries, keys, frequencies, distance_transforms));
-        node->nb = nb;
-        node->f = c[0]; node->tr = c[1]; node->q = c[2]; node->k = c[3]; node->fr = c[4]; node->dist = c[5];
-        node->lse = lse; node->acc = acc;
-        for (int x = 0; x < 6; ++x) { node->versions[x] = c[x]._version(); node->in_dtypes[x] = ins[x]->scalar_type(); }
-        node->N = N; node->H = (int)H; node->L = (int)L; node->K = (int)K; node->F = (int)F;
-        torch::autograd::create_gradient_edge(out, node);
-    }
-    return out;
+    return aggregate_launch(nb, true, H, L, K, F, ins);
 }
 
 // ---------------------------------------------------------------------------------------------
