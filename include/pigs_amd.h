@@ -143,6 +143,19 @@ int pigs_samples_build(void* samples_ws, size_t samples_ws_bytes, int64_t M, con
 /* what the library currently remembers for builds of M points on the current device: 1 = coarse bins,
  * 0 = one pass, -1 = nothing yet (introspection for tools and tests) */
 int pigs_samples_order_hint(int64_t M);
+/* Introspection for tools and tests (additive to ABI 10: the number does not change).  Once point sets of M points have
+ * been the same compact lattice on the same box for 64 verified builds and three statistic copies in a row, a build
+ * with PIGS_BUILD_SAMPLES that keeps the Gaussians' order into a clean plan workspace no longer looks at the points in
+ * front of its list launch (a TRUSTED build: two launches instead of four; never inside a capture).  Results do not
+ * depend on it; the list launch checks every tile against the remembered box and the library goes back to looking
+ * within 8 builds of points that are no such lattice.  PIGS_LATTICE_TRUST=0 / 1 in the environment, read at every
+ * build: never / as soon as a row length and a stable box are remembered.
+ *   info[0] = 1 when the library's memory of M points on the current device would let the next build be trusted (the
+ *             samples' side of the decision; the Gaussians' side is the build's own), else 0
+ *   info[1] = trusted builds of this size so far
+ *   info[2] = times the list launch's check turned this size's memory around
+ *   info[3] = verified builds in the current run of agreeing statistic copies */
+int pigs_samples_trust_info(int64_t M, int64_t info[4]);
 
 /* plan workspace.  `flags`:
  *   PIGS_BUILD_SAMPLES       also (re)builds the samples workspace from `samples` in the same launches

@@ -70,6 +70,7 @@ SIGNATURES = {
     "pigs_plan_strips_offset": (ctypes.c_size_t, []),
     "pigs_samples_build": (_i, [_vp, ctypes.c_size_t, _i64, _vp, _vp]),
     "pigs_samples_order_hint": (_i, [_i64]),
+    "pigs_samples_trust_info": (_i, [_i64, ctypes.POINTER(_i64)]),              # additive to ABI 10
     "pigs_plan_build": (_i, [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _i, _i64, _i64, _i, ctypes.c_float, ctypes.c_float]
                         + [_vp] * 4 + [_vp]),
     "pigs_plan_forward": (_i, [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _i64, _i64, _i, ctypes.c_float, _i]

@@ -109,6 +109,10 @@ int pigs_samples_build(void* samples_ws, size_t samples_ws_bytes, int64_t M, con
 }
 
 int pigs_samples_order_hint(int64_t M) { return samples_order_hint(M); }
+int pigs_samples_trust_info(int64_t M, int64_t info[4]) {
+    if (!info) return PIGS_ERR_INVALID;
+    return samples_trust_info(M, info);
+}
 
 int pigs_plan_build(void* workspace, size_t workspace_bytes, void* samples_ws, size_t samples_ws_bytes,
                     int flags, int64_t N, int64_t M, int c, float q_max, float q_max_backward, const void* means,

@@ -200,6 +200,10 @@ struct PlanParams {
     uint32_t points_wanted;         // ... and met this many blocks / tiles of far-apart points, which a build through the
                                     // cells would have left to the per-point walk (TILE_MODE_POINTS needs the grid): the
                                     // library then goes back to the cells
+    uint32_t lattice_broken;        // a TRUSTED build (plan.hip, run_build: the samples' lattice taken from the library's memory,
+                                    // nobody looked at the points) met a tile wider or higher than twice its share of
+                                    // the remembered box (plan_lists.h, the guard): the lists are right, the order was not compact
+                                    // -- the library forgets the lattice (adjacent to points_wanted: the same copy carries it home)
     uint32_t fwd_only;              // PIGS_BUILD_FORWARD_ONLY: one cut-off, group lists only (no tile lists, no wide masks);
                                     // a backward on such a plan writes NaN gradients (plan_unpermute_kernel)
 };

@@ -168,9 +168,30 @@ struct OrderHint {
     bool box_seen = false;         // ... and whether the completed build before it had the same one: a box to build the
     bool box_stable = false;       //     Gaussians' grid on before this build's own is known (BuildArgs::ahead)
     uint32_t same = 0;             // completed copies in a row that said the same (row length, box): the copies get rarer
+    // TRUSTED builds (run_build): once the memory has held the same lattice for long enough, a build stops looking
+    uint32_t axis = 0;             // the fast axis that goes with `rf` (SampleParams::lat_cand[1])
+    uint32_t streak = 0;           // verified builds since a completed copy last said anything but (rf, box): builds between
+                                   // two copies are taken on the word of the copies around them
+    uint32_t trusted = 0;          // trusted builds of this (device, M) so far
+    uint32_t broken = 0;           // times the list launch's guard turned this memory around (phint_poll)
     uint64_t stamp = 0;
 };
 constexpr uint32_t HINT_WORDS = 16;
+// A build is trusted from this many verified builds in a row on: longer than any run of lattice builds after which the
+// suite switches to other points of the same count and wants them noticed by the very next build
+// (tests/test_lattice_gpu.py: 40), short next to a training run.
+constexpr uint32_t TRUST_MIN_BUILDS = 64;
+// PIGS_LATTICE_TRUST, read at every build: 0 = never (A/B: the verified chain), 1 = as soon as the memory holds a row
+// length and a stable box (tests, tools/lattice_trust_worst_case.py); otherwise the memory decides (-1)
+static int trust_mode() {
+    const char* e = getenv("PIGS_LATTICE_TRUST");
+    return !e ? -1 : e[0] == '0' ? 0 : e[0] == '1' ? 1 : -1;
+}
+static bool hint_trusts(const OrderHint& h) {      // g_hint_mu held; the samples' side of the conditions (run_build)
+    const int mode = trust_mode();
+    if (mode == 0 || h.rf == 0u || !h.box_stable) return false;
+    return mode == 1 || (h.same >= 2u && h.streak >= TRUST_MIN_BUILDS);
+}
 static_assert(offsetof(SampleParams, box) == 0 && offsetof(SampleParams, order_stat) == 40 && offsetof(SampleParams, lat) == 56,
               "the hint copy: the first 64 bytes of SampleParams");
 static std::mutex g_hint_mu;
@@ -202,6 +223,7 @@ static OrderHint* hint_entry(int device, int64_t M, bool create) {      // g_hin
     if (!lru->host && hipHostMalloc((void**)&lru->host, HINT_WORDS * sizeof(uint32_t), hipHostMallocPortable) != hipSuccess) { lru->host = nullptr; (void)hipGetLastError(); return nullptr; }
     lru->device = device; lru->M = M; lru->coarse = false; lru->pending = false; lru->builds = 0; lru->rf = 0; lru->stamp = ++g_hint_clock;
     lru->box_seen = lru->box_stable = false; lru->same = 0;
+    lru->axis = 0; lru->streak = 0; lru->trusted = 0; lru->broken = 0;
     return lru;
 }
 
@@ -219,6 +241,7 @@ static void hint_poll(OrderHint& h) {           // g_hint_mu held
         h.pending = false;
         const uint32_t rf_before = h.rf;
         h.rf = h.host[14];         // SampleParams::lat[0]
+        h.axis = h.host[13];       // SampleParams::lat_cand[1]
         if (h.rf != 0u) h.coarse = false;      // index-tiled: the points arrived in order (and left no run statistic)
         else if (h.host[11] > 0u) h.coarse = (uint64_t)h.host[10] * 100u > (uint64_t)h.host[11] * 55u;
         float b[4];
@@ -226,6 +249,7 @@ static void hint_poll(OrderHint& h) {           // g_hint_mu held
         const bool finite = fabsf(b[0]) < 3.0e38f && fabsf(b[1]) < 3.0e38f && fabsf(b[2]) < 3.0e38f && fabsf(b[3]) < 3.0e38f && b[2] > b[0] && b[3] > b[1];
         h.box_stable = finite && h.box_seen && memcmp(b, h.box, sizeof(b)) == 0;
         h.same = h.box_stable && h.rf == rf_before ? h.same + 1u : 0u;
+        if (h.rf == 0u || h.rf != rf_before || !h.box_stable) h.streak = 0u;
         h.box_seen = finite;
         memcpy(h.box, b, sizeof(b));
     }
@@ -249,17 +273,29 @@ static bool samples_take_coarse(const SamplesLayout& s, int order, hipStream_t s
 }
 
 // the row length the last completed build of M points found (index-tiled order), or 0
-// *box_ok / box: the same box in the last two completed builds
-static uint32_t samples_rf_hint(const SamplesLayout& s, hipStream_t stream, bool* box_ok = nullptr, float* box = nullptr) {
+// *box_ok / box: the same box in the last two completed builds; *axis: the fast axis; *trust: the memory would let a build
+// of this size go without looking at the points (never inside a capture)
+static uint32_t samples_rf_hint(const SamplesLayout& s, hipStream_t stream, bool* box_ok = nullptr, float* box = nullptr,
+                                uint32_t* axis = nullptr, bool* trust = nullptr) {
     if (box_ok) *box_ok = false;
+    if (trust) *trust = false;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 0u; }
     std::lock_guard<std::mutex> lock(g_hint_mu);
     OrderHint* h = hint_entry(dev, s.M, false);
     if (!h) return 0u;
-    if (!stream_capturing(stream)) hint_poll(*h);
+    const bool cap = stream_capturing(stream);
+    if (!cap) hint_poll(*h);
     if (box_ok && box && h->box_stable) { *box_ok = true; memcpy(box, h->box, 4 * sizeof(float)); }
+    if (axis) *axis = h->axis;
+    if (trust) *trust = !cap && hint_trusts(*h);
     return h->rf;
+}
+static void samples_note_trusted(const SamplesLayout& s) {      // behind a trusted build: nothing to ask for, one more to count
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return; }
+    std::lock_guard<std::mutex> lock(g_hint_mu);
+    if (OrderHint* h = hint_entry(dev, s.M, false)) ++h->trusted;
 }
 
 // behind a samples build: ask for its {runs, points}
@@ -272,6 +308,7 @@ static void samples_note_order(const SamplesLayout& s, void* sws, hipStream_t st
     OrderHint* h = hint_entry(dev, s.M, true);
     if (!h) return;
     const uint32_t nth = h->builds++;
+    if (h->rf != 0u) ++h->streak;
     // (with a row length in the memory the build runs on expectations -- an eighth of the count's workgroups, the
     // Gaussians one launch ahead -- and a point set that stopped meeting them should not be met 15 more times: every 8th
     // build then; the copy is a ~4 us blit in the build's stream)
@@ -311,6 +348,21 @@ int samples_order_hint(int64_t M) {
     if (!h) return -1;
     hint_poll(*h);
     return h->coarse ? 1 : 0;
+}
+
+static void phint_poll_size(int device, int64_t M);
+int samples_trust_info(int64_t M, int64_t* info) {
+    info[0] = info[1] = info[2] = info[3] = 0;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return PIGS_OK; }
+    std::lock_guard<std::mutex> lock(g_hint_mu);
+    phint_poll_size(dev, M);           // (the guard's word comes home with the plans' copies)
+    OrderHint* h = hint_entry(dev, M, false);
+    if (!h) return PIGS_OK;
+    hint_poll(*h);
+    info[0] = hint_trusts(*h) ? 1 : 0;
+    info[1] = h->trusted; info[2] = h->broken; info[3] = h->streak;
+    return PIGS_OK;
 }
 
 static void fill_plan_args(BuildArgs& a, const PlanLayout& p, void* ws, float q_f, float q_b, const void* means,
@@ -375,11 +427,13 @@ struct PointsHint {
     uint32_t same = 0;             // completed copies in a row that led to the same choice: the copies get rarer
     uint32_t builds = 0;
     hipEvent_t ev = nullptr;
-    uint32_t* host = nullptr;      // pinned {n_points, strip_cover, strips, points_wanted}
+    uint32_t* host = nullptr;      // pinned {n_points, strip_cover, strips, points_wanted, lattice_broken}
     uint64_t stamp = 0;
 };
+constexpr uint32_t PHINT_WORDS = 5;
 static_assert(offsetof(PlanParams, strip_cover) == offsetof(PlanParams, n_points) + 4 && offsetof(PlanParams, strips) == offsetof(PlanParams, n_points) + 8 &&
-              offsetof(PlanParams, points_wanted) == offsetof(PlanParams, n_points) + 12, "one copy: n_points, strip_cover, strips, points_wanted");
+              offsetof(PlanParams, points_wanted) == offsetof(PlanParams, n_points) + 12 && offsetof(PlanParams, lattice_broken) == offsetof(PlanParams, n_points) + 16,
+              "one copy: n_points, strip_cover, strips, points_wanted, lattice_broken");
 static PointsHint g_phints[16];
 static void phint_poll(PointsHint& h) {          // g_hint_mu held
     if (!h.pending) return;
@@ -393,7 +447,20 @@ static void phint_poll(PointsHint& h) {          // g_hint_mu held
         if (!(h.cover >= 0.f)) h.cover = 3.0e38f;      // NaN: as bad as it gets
         h.strips = h.host[2] != 0u;
         h.same = (h.cover <= STRIP_MAX_COVER && !h.has_points) == took_before ? h.same + 1u : 0u;
+        if (h.host[4] != 0u) {
+            // a trusted build met points that are no compact lattice in the remembered order (plan_lists.h, the guard): the
+            // samples' memory of this size turns around -- the next build searches, verifies and, if need be, sorts, as
+            // a first build does
+            if (OrderHint* o = hint_entry(h.device, h.M, false)) {
+                o->rf = 0u; o->same = 0u; o->box_stable = false; o->streak = 0u;
+                ++o->broken;
+            }
+        }
     }
+}
+static void phint_poll_size(int device, int64_t M) {      // g_hint_mu held: every plan size with M points
+    for (auto& h : g_phints)
+        if (h.device == device && h.M == M) phint_poll(h);
 }
 static PointsHint* phint_entry(int device, int64_t N, int64_t M, bool create) {      // g_hint_mu held
     PointsHint* lru = nullptr;
@@ -411,7 +478,7 @@ static PointsHint* phint_entry(int device, int64_t N, int64_t M, bool create) { 
     }
     if (lru->ev && lru->device != device) { (void)hipEventDestroy(lru->ev); lru->ev = nullptr; }
     if (!lru->ev && hipEventCreateWithFlags(&lru->ev, hipEventDisableTiming) != hipSuccess) { lru->ev = nullptr; (void)hipGetLastError(); return nullptr; }
-    if (!lru->host && hipHostMalloc((void**)&lru->host, 4 * sizeof(uint32_t), hipHostMallocPortable) != hipSuccess) { lru->host = nullptr; (void)hipGetLastError(); return nullptr; }
+    if (!lru->host && hipHostMalloc((void**)&lru->host, PHINT_WORDS * sizeof(uint32_t), hipHostMallocPortable) != hipSuccess) { lru->host = nullptr; (void)hipGetLastError(); return nullptr; }
     lru->device = device; lru->N = N; lru->M = M; lru->has_points = false; lru->pending = false; lru->builds = 0; lru->stamp = ++g_hint_clock;
     lru->cover = -1.f; lru->strips = false; lru->same = 0;
     return lru;
@@ -450,7 +517,8 @@ static bool plan_takes_strips(int64_t N, int64_t M, hipStream_t stream) {
     // sigma = 0.15 over lattice Gaussians, warm step 111 -> 1 126 us.)
     return h->cover >= 0.f && h->cover <= STRIP_MAX_COVER && !h->has_points;
 }
-static void plan_note_points(const PlanLayout& p, const void* ws, hipStream_t stream) {      // behind a list build
+// trusted: the build took the samples' lattice on trust (run_build) -- its guard's word is wanted home soon
+static void plan_note_points(const PlanLayout& p, const void* ws, hipStream_t stream, bool trusted = false) {      // behind a list build
     if (stream_capturing(stream)) return;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return; }
@@ -460,9 +528,10 @@ static void plan_note_points(const PlanLayout& p, const void* ws, hipStream_t st
     const uint32_t nth = h->builds++;
     // (builds that keep the caller's order run on an expectation -- strips that cover the domain a few times over -- and
     // Gaussians that stopped meeting it should not be met 15 more times)
-    if (h->pending || (nth >= 2u && (nth & (h->strips ? (h->same >= 2u ? 31u : 7u) : 15u)) != 0u)) return;
+    // ... and points that stopped being the lattice a trusted build takes them for not 31 more times either: every 8th)
+    if (h->pending || (nth >= 2u && (nth & (trusted ? 7u : h->strips ? (h->same >= 2u ? 31u : 7u) : 15u)) != 0u)) return;
     const PlanParams* pp = (const PlanParams*)((const char*)ws + p.off_params);
-    if (hipMemcpyAsync(h->host, &pp->n_points, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess &&
+    if (hipMemcpyAsync(h->host, &pp->n_points, PHINT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess &&
         hipEventRecord(h->ev, stream) == hipSuccess)
         h->pending = true;
     (void)hipGetLastError();
@@ -516,8 +585,8 @@ static int run_build(bool do_samples, bool do_plan, bool plan_ws_clean, bool no_
     a.zero_gacc = !plan_ws_clean;
     const bool coarse = do_samples && samples_take_coarse(s, order, stream);
     fill_samples_args(a, s, sws, samples, coarse);
-    bool box_ok = false;
-    a.rf_hint = do_samples ? samples_rf_hint(s, stream, &box_ok, a.hint_box) : 0u;
+    bool box_ok = false, trust = false;
+    a.rf_hint = do_samples ? samples_rf_hint(s, stream, &box_ok, a.hint_box, &a.hint_axis, &trust) : 0u;
     {
         static const char* e = getenv("PIGS_BBOX_BLOCKS");      // (A/B: 256 | 512)
         // same box, 1024^2 points: the plain pass 6.6 -> 5.9 us with 512 workgroups, the pass with a row length 7.5 -> 7.8
@@ -550,7 +619,18 @@ static int run_build(bool do_samples, bool do_plan, bool plan_ws_clean, bool no_
     const bool strips = do_plan && build_lists && !defer_lists && !no_lookback &&
                         plan_takes_strips(N, M, stream);
     a.strips = strips;
-    if (ahead && strips) {
+    // TRUSTED: point sets of this size have been the same compact lattice for TRUST_MIN_BUILDS verified builds and three
+    // copies in a row -- this build does not look again.  It launches what a build on a finished samples workspace
+    // launches, the Gaussians' pack and the lists; the pack's first workgroup writes the samples header the decision
+    // would have written, the list launch reads the points through it and holds every tile's real box against the
+    // remembered one (ListArgs::lattice_broken), and that word rides home with the plan's statistics every 8th build
+    // (phint_poll turns the memory around).  Results never depend on it: the lists come from the groups' real boxes.
+    const bool trusted = ahead && strips && trust && order == 0 && a.rf_hint >= 8u && (a.rf_hint & 7u) == 0u && M >= 64 && M % a.rf_hint == 0 &&
+                         ((M / a.rf_hint) & 7) == 0;
+    if (trusted) {
+        a.trusted = 1; a.ahead = 0; a.s_scan_in_scatter = 0;
+        hipLaunchKernelGGL(plan_count_kernel, dim3(gb), dim3(256), 0, stream, a);
+    } else if (ahead && strips) {
         // nothing of the Gaussians is left for launches 2 and 3: the samples' fall-back moves into launch 2 whole
         // (samples_sort_in_count; at most 256 workgroups: they meet at device-wide barriers) -- FOUR launches up to the forward
         a.sort_in_count = 1; a.s_scan_in_scatter = 0;
@@ -590,12 +670,23 @@ static int run_build(bool do_samples, bool do_plan, bool plan_ws_clean, bool no_
                                    s.cells_per_bin * sizeof(uint32_t), stream, a);
         }
     }
-    if (do_plan && build_lists && !defer_lists)
-        launch_lists(s.ntiles, make_list_args(p, s, ws, sws, q_max, a.q_max), stream, strips, fwd_only);
+    if (do_plan && build_lists && !defer_lists) {
+        ListArgs la = make_list_args(p, s, ws, sws, q_max, a.q_max);
+        if (trusted) {
+            la.lattice_broken = &a.params->lattice_broken;
+            const float rf = (float)a.rf_hint, rs = (float)(M / a.rf_hint);
+            la.guard_n[0] = a.hint_axis ? rs : rf; la.guard_n[1] = a.hint_axis ? rf : rs;      // points along x / along y
+            la.guard_e[0] = 16.f * (a.hint_box[2] - a.hint_box[0]) * 1.001f;
+            la.guard_e[1] = 16.f * (a.hint_box[3] - a.hint_box[1]) * 1.001f;
+        }
+        launch_lists(s.ntiles, la, stream, strips, fwd_only);
+    }
     const int rc = launch_status();
     if (do_plan) defer_set(ws, build_lists && defer_lists && rc == PIGS_OK, q_max, a.q_max);
-    if (do_plan && build_lists && !defer_lists && rc == PIGS_OK) plan_note_points(p, ws, stream);
-    if (do_samples && rc == PIGS_OK && order == 0) samples_note_order(s, sws, stream);
+    if (do_plan && build_lists && !defer_lists && rc == PIGS_OK) plan_note_points(p, ws, stream, trusted);
+    if (trusted) {      // (the samples header holds only what this build put there: nothing to ask for)
+        if (rc == PIGS_OK) samples_note_trusted(s);
+    } else if (do_samples && rc == PIGS_OK && order == 0) samples_note_order(s, sws, stream);
     return rc;
 }
 

@@ -78,6 +78,12 @@ struct BuildArgs {
     // scan and scatter; `parea` is written by builds of either kind (the statistic the library decides from)
     int strips;
     int fwd_only;         // PIGS_BUILD_FORWARD_ONLY (PlanParams::fwd_only): q_max = q_f = q_b
+    // TRUSTED build (plan.hip, run_build): point sets of this size have long been the same compact lattice, so nobody looks
+    // at the points in front of the list launch -- the count launch holds the Gaussians' pack workgroups alone, on
+    // `hint_box`, and its first workgroup writes the samples header the decision would have written (row length rf_hint,
+    // fast axis hint_axis).  The list launch checks every tile against that box (plan_lists.h, the guard).
+    int trusted;
+    uint32_t hint_axis;
     float4* pbox;
     float4* sbox;
     float* parea;
@@ -483,6 +489,7 @@ __device__ __forceinline__ void gauss_count_part(const BuildArgs& a, uint32_t bi
         a.params->n_points = 0u;
         a.params->strips = a.strips ? 1u : 0u;
         a.params->points_wanted = 0u;
+        a.params->lattice_broken = 0u;
         a.params->fwd_only = a.fwd_only ? 1u : 0u;
         if (a.strips) a.params->level_mask = 0u;
 #pragma unroll
@@ -601,8 +608,10 @@ __global__ __launch_bounds__(256) void plan_count_kernel(BuildArgs a) {
     float2 pt[4];
     uint32_t i0 = ((bid - gblocks) * 4 + (threadIdx.x >> 6)) * 256 + lane;
     // the first launch's lattice candidate (plan.h): with one, the sample workgroups most likely have nothing to do
-    const uint32_t lat_rf = a.do_samples ? a.sparams->lat_cand[0] : 0u;
-    const uint32_t lat_axis = a.do_samples ? a.sparams->lat_cand[1] : 0u;
+    // (a trusted build has no first launch and no sample workgroups: every workgroup packs Gaussians)
+    const bool looked = a.do_samples && !a.trusted;
+    const uint32_t lat_rf = looked ? a.sparams->lat_cand[0] : 0u;
+    const uint32_t lat_axis = looked ? a.sparams->lat_cand[1] : 0u;
     auto load_points = [&]() {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -615,6 +624,24 @@ __global__ __launch_bounds__(256) void plan_count_kernel(BuildArgs a) {
     else if (!a.coarse && lat_rf == 0u) load_points();
     float sbox[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     bool lattice = false;
+    if (a.trusted) {      // (launch-uniform) the remembered box, from the kernel arguments: the header is being written
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sbox[k] = a.hint_box[k];
+        if (bid == 0 && threadIdx.x == 0) {
+            // the header the decision launch would have left for a lattice of this row length on this box
+            SampleParams* sp = a.sparams;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) sp->box[k] = sbox[k];
+            sp->sg = sample_grid(sbox, a.M, a.scells_cap);
+            sp->scan_error = 0;
+            sp->order_stat[0] = 0u; sp->order_stat[1] = 0u;
+            sp->lat_cand[0] = a.rf_hint; sp->lat_cand[1] = a.hint_axis;
+            sp->lat[0] = a.rf_hint; sp->lat[1] = a.M / a.rf_hint;
+            sp->src = (uint64_t)(uintptr_t)a.samples;
+        }
+        gauss_count_part(a, bid, sbox, gld);      // (gpart: the launch is the Gaussians' workgroups)
+        return;
+    }
     if (a.do_samples) {
         reduce_boxes(a.sboxes, a.slat, a.bbox_blocks, sbox, shb);
         lattice = lattice_compact(sbox, lat_rf, lat_rf ? a.M / lat_rf : 0u, lat_axis);

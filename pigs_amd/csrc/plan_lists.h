@@ -42,6 +42,17 @@ struct ListArgs {
     float q_f;            // the narrow cut-off (pv.q_max is the wide one)
     const float* parea;   // per strip: box area / domain area (written by the build's Gaussian pass)
     float* strip_cover;   //   their sum (PlanParams::strip_cover)
+    // The guard of a TRUSTED build (plan.hip, run_build; null: none -- every other build).  Nobody looked at the points in
+    // front of this launch: they are taken in index-tiled order because point sets of this size have long been the same
+    // lattice.  The lists are right whatever the points are (they come from the groups' real boxes); what may have failed
+    // is the compactness of the order, and this launch has every tile's real box: a tile wider or higher than twice its
+    // share of the remembered box -- lattice_compact's own bound (plan_build.h), per tile -- sets PlanParams::
+    // lattice_broken, which rides home with the plan's statistics.  guard_n = points along x / y, guard_e = 16 x the
+    // remembered box's extents, with 1/1000 to spare: the decision launch bounds a tile's extent by 7 (along + across)
+    // rounded neighbour steps, this one takes the difference of two coordinates, and a lattice that one accepts on the
+    // same box must never trip the other.
+    uint32_t* lattice_broken;
+    float guard_n[2], guard_e[2];
 };
 
 // the lists of the TPW tiles from tile0 (one wave).  TPW = 4 (a 4 x 4 block of sample cells: the traversal of the grid is
@@ -221,10 +232,20 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
     const bool two_cuts = !FWD_ONLY && pv.q_max > a.q_f;
     bool any_rare = false;
     bool rebuild[TPW];
+    const bool guard = a.lattice_broken != nullptr;       // launch-uniform
+    if (guard) wave_lds_fence();                          // (the group boxes: no flush may have run)
 #pragma unroll
     for (int t = 0; t < TPW; ++t) {
         rebuild[t] = false;
         if (tile0 + (uint32_t)t >= ntiles) { overflow[t] = false; continue; }
+        if (guard) {      // the trusted build's guard (ListArgs::lattice_broken); a comparison that NaN or inf fails: broken
+            float4 gb[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) gb[g] = lds.gbox[t * 4 + g];
+            const float wx = fmaxf(fmaxf(gb[0].z, gb[1].z), fmaxf(gb[2].z, gb[3].z)) - fminf(fminf(gb[0].x, gb[1].x), fminf(gb[2].x, gb[3].x));
+            const float wy = fmaxf(fmaxf(gb[0].w, gb[1].w), fmaxf(gb[2].w, gb[3].w)) - fminf(fminf(gb[0].y, gb[1].y), fminf(gb[2].y, gb[3].y));
+            if (!(wx * a.guard_n[0] <= a.guard_e[0] && wy * a.guard_n[1] <= a.guard_e[1]) && lane == 0) *a.lattice_broken = 1u;
+        }
         const bool tl_over = FWD_ONLY ? goverflow[t] : overflow[t];      // (no tile list: its group lists decide)
         overflow[t] = tl_over && goverflow[t];            // from here on: the tile needs the ranges fallback
         rebuild[t] = tl_over && !goverflow[t] && two_cuts;
