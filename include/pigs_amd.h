@@ -660,6 +660,64 @@ int pigs_refine_backward(int dtype, int mode, int c, int64_t N, int64_t rows, do
                          const void* g_out_transforms, const void* g_out_values, void* g_means, void* g_scaling,
                          void* g_transforms, void* g_values, void* stream);
 
+/*
+ * The optimiser of the MLP-free loops: the Gaussians' parameterisation, its chain rule and Adam in one launch
+ * (additive to ABI 10: the number does not change).  d = 2, c = 1..4, float32 / float64.  Replaces, per training step,
+ * tanh(raw_means) * scale and exp(raw_scaling) (test_no_mlp.py:99-104, test_initialize.py:100-104), build_covariances
+ * (gaussians.py:163-193), the autograd backward of each, torch.optim.Adam over four tensors with zero_grad
+ * (test_no_mlp.py:146, 185-186, test_initialize.py:80-85, 151, 172-173) and the periodic wrap of the means
+ * (test_initialize.py:175-180, model_pn.py:689-693).
+ *
+ * Parameters: raw_means [N][2], values [N][c], raw_scaling [N][2], transform [N].  The Gaussians they stand for:
+ *   means        PIGS_OPTIM_MEANS_TANH: tanh(raw_means) * scale;  PIGS_OPTIM_MEANS_IDENTITY: raw_means
+ *   s = exp(raw_scaling), h = tanh(transform), covariances (s0, h sqrt(s0 s1), s1), conics their inverses, flat
+ *   (xx, xy, yy); 1 / (1 - h^2) and sech^2 are formed from exp(-2 |x|), never from a cancelling subtraction.
+ *
+ * pigs_optim_materialize writes means [N][2], covariances [N][3] and conics [N][3] from the parameters: one launch.
+ * pigs_optim_step, one launch of one thread per Gaussian (two with a device state, see below):
+ *   1. the chain rule from g_means [N][2], g_covariances [N][3], g_conics [N][3] (gradients with respect to the arrays
+ *      pigs_optim_materialize wrote) to the raw parameters; g_values [N][c] passes through;
+ *   2. Adam as torch.optim.Adam defines it, per group g in (means, values, scaling, transform):
+ *        m <- beta1 m + (1 - beta1) g,  v <- beta2 v + (1 - beta2) g^2,
+ *        p <- p - lr[g] / (1 - beta1_pow[g]) * m / (sqrt(v) / sqrt(1 - beta2_pow[g]) + eps),
+ *      in place on the parameters, exp_avg and exp_avg_sq (arrays of the parameters' shapes);
+ *   3. with hyper->wrap, a coordinate of raw_means > wrap_hi is lowered by wrap_hi - wrap_lo and one < wrap_lo raised by
+ *      it: one shift, strict inequalities;
+ *   4. means, covariances and conics of the UPDATED parameters, as pigs_optim_materialize would write them, bit for bit.
+ *   A null gradient leaves its group untouched: g_means the means, g_values the values, g_covariances and g_conics
+ *   BOTH null the scaling and the transform (one of them null counts as zero).  The outputs are always written.
+ *   beta1_pow[g] / beta2_pow[g] are beta1^t / beta2^t of the step being taken, kept by the caller as running products
+ *   in double.  With hyper->device_state (12 doubles on the device: beta1_pow[4], beta2_pow[4], steps[4]; initially
+ *   1, 1, 0) the entry ignores the two host arrays and first launches ONE thread that multiplies the products of the
+ *   groups that have a gradient by beta1 / beta2 and adds 1 to their step counts; the update reads them from there.
+ *   With hyper->device_lr (4 doubles on the device) the rates are read from there.  Nothing in the update waits for
+ *   another workgroup.  Both ways the bias corrections are formed on the device by the same double operations.
+ * Arguments are checked before any HIP call: a bad dtype or means_map, or c outside 1..4, is PIGS_ERR_UNSUPPORTED;
+ *   N <= 0, a null hyper, parameter, moment or output array, all four gradients null, or a raw_means / raw_scaling
+ *   array (or its moments, g_means, means) not aligned to a row is PIGS_ERR_INVALID.  Nothing allocates, frees or
+ *   synchronises.
+ */
+#define PIGS_OPTIM_MEANS_TANH 0
+#define PIGS_OPTIM_MEANS_IDENTITY 1
+typedef struct PigsAdamStep {
+    double lr[4];                     /* means, values, scaling, transform */
+    double beta1, beta2, eps;
+    double beta1_pow[4], beta2_pow[4];
+    double scale;                     /* PIGS_OPTIM_MEANS_TANH */
+    double wrap_lo, wrap_hi;
+    int means_map, wrap;
+    const double* device_lr;          /* [4] on the device, or NULL */
+    double* device_state;             /* [12] on the device, or NULL */
+} PigsAdamStep;
+int pigs_optim_materialize(int dtype, int means_map, int64_t N, double scale, const void* raw_means,
+                           const void* raw_scaling, const void* transform, void* means, void* covariances, void* conics,
+                           void* stream);
+int pigs_optim_step(int dtype, int c, int64_t N, const PigsAdamStep* hyper, void* raw_means, void* values,
+                    void* raw_scaling, void* transform, void* exp_avg_means, void* exp_avg_values, void* exp_avg_scaling,
+                    void* exp_avg_transform, void* exp_avg_sq_means, void* exp_avg_sq_values, void* exp_avg_sq_scaling,
+                    void* exp_avg_sq_transform, const void* g_means, const void* g_values, const void* g_covariances,
+                    const void* g_conics, void* means, void* covariances, void* conics, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

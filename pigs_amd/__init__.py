@@ -8,6 +8,8 @@ Public surface:
     split_gaussians         prune and split / clone Gaussians in HIP with one host read (pigs_amd.refine;
                             model_pn.py:578-605, :703-714 and test_no_mlp.py:198-240)
     refine_index            its (source, child) maps alone, for optimiser state and other per-Gaussian arrays
+    GaussianAdam            the Gaussians' parameterisation, its backward and Adam in one launch per step
+                            (pigs_amd.optim; test_no_mlp.py:99-104, 146, 185-186, test_initialize.py:172-180)
     build()                 compile the HIP library (hipcc, gfx950) and the native host extension in-tree
 """
 from .build import build_all as build  # noqa: F401  (libpigs_amd.so + the native host extension)
@@ -27,4 +29,7 @@ def __getattr__(name):
     if name in ("split_gaussians", "refine_index"):
         from . import refine
         return getattr(refine, name)
+    if name == "GaussianAdam":
+        from .optim import GaussianAdam
+        return GaussianAdam
     raise AttributeError(name)

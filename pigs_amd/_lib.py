@@ -51,6 +51,17 @@ class PigsVorticityResidual(ctypes.Structure):
 
 _vorticity_residual_p = ctypes.POINTER(PigsVorticityResidual)
 
+
+class PigsAdamStep(ctypes.Structure):
+    """struct PigsAdamStep of include/pigs_amd.h (the optimiser's rates, running products and parameterisation)"""
+    _fields_ = [("lr", ctypes.c_double * 4), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+                ("beta1_pow", ctypes.c_double * 4), ("beta2_pow", ctypes.c_double * 4), ("scale", ctypes.c_double),
+                ("wrap_lo", ctypes.c_double), ("wrap_hi", ctypes.c_double), ("means_map", _i), ("wrap", _i),
+                ("device_lr", _vp), ("device_state", _vp)]
+
+
+_adam_p = ctypes.POINTER(PigsAdamStep)
+
 # name -> (restype, argtypes); must list every symbol include/pigs_amd.h declares
 SIGNATURES = {
     "pigs_abi_version": (_i, []),
@@ -131,6 +142,9 @@ SIGNATURES = {
     "pigs_refine_apply": (_i, [_i, _i, _i, _i64, _i64, ctypes.c_double] + [_vp] * 2 + [_vp] * 4 + [_vp] * 4 + [_vp] * 2
                           + [_vp]),
     "pigs_refine_backward": (_i, [_i, _i, _i, _i64, _i64, ctypes.c_double] + [_vp] * 2 + [_vp] * 4 + [_vp] * 4 + [_vp]),
+    # the optimiser (additive to ABI 10): parameters, outputs / hyper, parameters, moments, gradients, outputs
+    "pigs_optim_materialize": (_i, [_i, _i, _i64, ctypes.c_double] + [_vp] * 3 + [_vp] * 3 + [_vp]),
+    "pigs_optim_step": (_i, [_i, _i, _i64, _adam_p] + [_vp] * 4 + [_vp] * 8 + [_vp] * 4 + [_vp] * 3 + [_vp]),
 }
 
 _lib = None

@@ -562,4 +562,53 @@ int pigs_refine_backward(int dtype, int mode, int c, int64_t N, int64_t rows, do
     return refine_rows(true, r, (hipStream_t)stream);
 }
 
+static int optim_sizes_ok(int dtype, int means_map, int c, int64_t N) {
+    if (dtype != PIGS_F32 && dtype != PIGS_F64) return PIGS_ERR_UNSUPPORTED;
+    if (means_map != PIGS_OPTIM_MEANS_TANH && means_map != PIGS_OPTIM_MEANS_IDENTITY) return PIGS_ERR_UNSUPPORTED;
+    if (c < 1 || c > 4) return PIGS_ERR_UNSUPPORTED;
+    if (N <= 0) return PIGS_ERR_INVALID;
+    return PIGS_OK;
+}
+
+int pigs_optim_materialize(int dtype, int means_map, int64_t N, double scale, const void* raw_means,
+                           const void* raw_scaling, const void* transform, void* means, void* covariances, void* conics,
+                           void* stream) {
+    const int rc = optim_sizes_ok(dtype, means_map, 1, N);
+    if (rc != PIGS_OK) return rc;
+    if (!raw_means || !raw_scaling || !transform || !means || !covariances || !conics) return PIGS_ERR_INVALID;
+    if (refine_misaligned(raw_means, dtype) || refine_misaligned(raw_scaling, dtype) || refine_misaligned(means, dtype))
+        return PIGS_ERR_INVALID;
+    return optim_materialize(dtype, N, means_map == PIGS_OPTIM_MEANS_TANH, scale, raw_means, raw_scaling, transform, means,
+                             covariances, conics, (hipStream_t)stream);
+}
+
+int pigs_optim_step(int dtype, int c, int64_t N, const PigsAdamStep* hyper, void* raw_means, void* values,
+                    void* raw_scaling, void* transform, void* exp_avg_means, void* exp_avg_values, void* exp_avg_scaling,
+                    void* exp_avg_transform, void* exp_avg_sq_means, void* exp_avg_sq_values, void* exp_avg_sq_scaling,
+                    void* exp_avg_sq_transform, const void* g_means, const void* g_values, const void* g_covariances,
+                    const void* g_conics, void* means, void* covariances, void* conics, void* stream) {
+    if (!hyper) return PIGS_ERR_INVALID;
+    const int rc = optim_sizes_ok(dtype, hyper->means_map, c, N);
+    if (rc != PIGS_OK) return rc;
+    OptimStep o{};
+    o.dtype = dtype; o.c = c; o.N = N; o.hyper = hyper;
+    o.params[0] = raw_means; o.params[1] = values; o.params[2] = raw_scaling; o.params[3] = transform;
+    o.exp_avg[0] = exp_avg_means; o.exp_avg[1] = exp_avg_values; o.exp_avg[2] = exp_avg_scaling;
+    o.exp_avg[3] = exp_avg_transform;
+    o.exp_avg_sq[0] = exp_avg_sq_means; o.exp_avg_sq[1] = exp_avg_sq_values; o.exp_avg_sq[2] = exp_avg_sq_scaling;
+    o.exp_avg_sq[3] = exp_avg_sq_transform;
+    o.grads[0] = g_means; o.grads[1] = g_values; o.grads[2] = g_covariances; o.grads[3] = g_conics;
+    o.out[0] = means; o.out[1] = covariances; o.out[2] = conics;
+    for (int g = 0; g < 4; ++g)
+        if (!o.params[g] || !o.exp_avg[g] || !o.exp_avg_sq[g]) return PIGS_ERR_INVALID;
+    if (!means || !covariances || !conics) return PIGS_ERR_INVALID;
+    if (!g_means && !g_values && !g_covariances && !g_conics) return PIGS_ERR_INVALID;
+    for (int g = 0; g < 4; g += 2)      // the rows of two values: one access each
+        if (refine_misaligned(o.params[g], dtype) || refine_misaligned(o.exp_avg[g], dtype) ||
+            refine_misaligned(o.exp_avg_sq[g], dtype))
+            return PIGS_ERR_INVALID;
+    if (refine_misaligned(g_means, dtype) || refine_misaligned(means, dtype)) return PIGS_ERR_INVALID;
+    return optim_step(o, (hipStream_t)stream);
+}
+
 }  // extern "C"

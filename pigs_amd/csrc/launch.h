@@ -49,6 +49,19 @@ int refine_index(int mode, int64_t N, const uint8_t* keep, const uint8_t* split,
                  int64_t* child_pos, int64_t* counts, hipStream_t stream);
 int refine_rows(bool backward, const RefineRows& r, hipStream_t stream);
 
+// optim.hip
+struct OptimStep {
+    int dtype, c;
+    int64_t N;
+    const PigsAdamStep* hyper;
+    void *params[4], *exp_avg[4], *exp_avg_sq[4];      // raw_means, values, raw_scaling, transform
+    const void* grads[4];                              // d means, d values, d covariances, d conics (null = none)
+    void* out[3];                                      // the next step's means, covariances, conics
+};
+int optim_materialize(int dtype, int64_t N, bool tanh_map, double scale, const void* raw_means, const void* raw_scaling,
+                      const void* transform, void* o_means, void* o_cov, void* o_conic, hipStream_t stream);
+int optim_step(const OptimStep& o, hipStream_t stream);
+
 // periodic.hip: images (fold = false; a = means, conics, values; o = image arrays) or the fold of their gradients
 // (fold = true; a = image gradients, null = zero; o = gradients)
 int periodic_dispatch(bool fold, int dtype, int c, int64_t N, double lo, double period, double q_cut, const void* a0,
