@@ -661,6 +661,57 @@ int pigs_refine_backward(int dtype, int mode, int c, int64_t N, int64_t rows, do
                          void* g_transforms, void* g_values, void* stream);
 
 /*
+ * The split criteria: which Gaussians to refine, as a byte mask on the device (additive to ABI 10: the number does not
+ * change).  float32 / float64.  Replaces the element-wise chain, the reductions and the full sort of torch.quantile in
+ * Model.forward(split=True) (model_pn.py:733-754; the three sampling passes of :719-737 stay the sampler's) and the
+ * threshold of the densification block (test_no_mlp.py:203-205).  The mask goes straight into pigs_refine_index.
+ *
+ * pigs_criterion_quantile_mask.  Inputs, row-major: sample_u [n][c] (the current field at the current means),
+ *   prev_sample_u [n][c] (the previous field there), density [n] (a field of ones there), boundary_mask [n] (one byte
+ *   per row, nonzero = true; NULL = all).  In the inputs' dtype, each step one IEEE operation, no contraction:
+ *     w[i]   = 1 - (D[i] - min D) / max D
+ *     m[i,k] = ((u[i,k] - u_prev[i,k]) * (u[i,k] - u_prev[i,k])) * w[i]
+ *     L = n c,  pos = q (L - 1) in double,  lo = floor(pos),  hi = min(lo + 1, L - 1),  x = sort(m)
+ *     quantile = x[lo] + (x[hi] - x[lo]) (pos - lo)        in double, rounded once: torch.quantile's linear rule
+ *     mask[i] = any_k(m[i,k] > quantile) and boundary_mask[i]        (0 / 1)
+ *   x[lo] and x[hi] are selected elements, bit for bit: a most-significant-digit-first radix select (8-bit digits) on
+ *   the order-preserving unsigned image of the float bits, so -0.0, negatives, denormals and +inf sort as IEEE
+ *   compares them.  A NaN in m (or in D: min and max propagate it) is found by a flag of its own: quantile, x_lo and
+ *   x_hi are then NaN and the mask is all 0.  L = 1: quantile = x[0], mask all 0 (the compare is strict).
+ *   metric [n][c] (m; or NULL) and stats (4 values of the dtype: quantile, x_lo, x_hi, 1 if a NaN was seen else 0; or
+ *   NULL) are optional outputs.
+ * pigs_criterion_meanstd_mask.  threshold = mean(score) + k std(score), std unbiased (n - 1) as torch.std; mean and the
+ *   sum of squared deviations in double, two passes, mean first, the threshold rounded once; mask[i] = score[i] >
+ *   threshold and keep[i] (NULL = all).  n = 1 (std NaN) and a NaN score give an all-0 mask.  stats (or NULL):
+ *   threshold, mean, std.
+ * variant: PIGS_CRITERION_AUTO; PIGS_CRITERION_ONE_WORKGROUP, ONE launch of one workgroup with the keys in LDS, for
+ *   n c <= PIGS_CRITERION_LDS_VALUES (pigs_criterion_lds_values() returns the library's; PIGS_ERR_UNSUPPORTED above);
+ *   PIGS_CRITERION_MANY_WORKGROUPS for any n c <= 2^24: quantile 6 launches in float32, 10 in float64 (min / max
+ *   partials; metric + first digit; one per remaining digit; finish), mean/std 3.  AUTO takes the first where it
+ *   fits.  The variants agree bit for bit in the quantile rule.  Cross-workgroup sums are per-workgroup partials or
+ *   integer adds on histogram bins: every output is a pure function of the inputs.
+ * workspace: pigs_criterion_workspace_bytes(dtype, n, c) bytes (c = 1 for mean/std), 8-byte aligned; read and written by
+ *   the many-workgroup variant only (the one-workgroup variant takes NULL).  A pure function, monotone in n c; 0 for
+ *   n <= 0, c < 1, a bad dtype and n c > 2^24.
+ * Arguments are checked before any HIP call: a bad dtype or variant, or n c > 2^24 (torch.quantile refuses the same),
+ *   is PIGS_ERR_UNSUPPORTED; a negative n, c < 1, q outside [0, 1] or NaN (k NaN), or a null required array with n > 0
+ *   is PIGS_ERR_INVALID; a short workspace is PIGS_ERR_WORKSPACE.  n = 0 returns PIGS_OK without a launch.  Nothing
+ *   allocates, frees, synchronises or waits for another workgroup: both entries can be captured into a graph.
+ */
+#define PIGS_CRITERION_AUTO 0
+#define PIGS_CRITERION_ONE_WORKGROUP 1
+#define PIGS_CRITERION_MANY_WORKGROUPS 2
+#define PIGS_CRITERION_LDS_VALUES 16384      /* float64 keys: 128 KiB of the 160 KiB of LDS of a CU */
+int pigs_criterion_lds_values(void);
+size_t pigs_criterion_workspace_bytes(int dtype, int64_t n, int c);
+int pigs_criterion_quantile_mask(int dtype, int variant, int c, int64_t n, double q, const void* sample_u,
+                                 const void* prev_sample_u, const void* density, const uint8_t* boundary_mask,
+                                 void* workspace, size_t workspace_bytes, void* metric, void* stats, uint8_t* mask,
+                                 void* stream);
+int pigs_criterion_meanstd_mask(int dtype, int variant, int64_t n, double k, const void* score, const uint8_t* keep,
+                                void* workspace, size_t workspace_bytes, void* stats, uint8_t* mask, void* stream);
+
+/*
  * The optimiser of the MLP-free loops: the Gaussians' parameterisation, its chain rule and Adam in one launch
  * (additive to ABI 10: the number does not change).  d = 2, c = 1..4, float32 / float64.  Replaces, per training step,
  * tanh(raw_means) * scale and exp(raw_scaling) (test_no_mlp.py:99-104, test_initialize.py:100-104), build_covariances

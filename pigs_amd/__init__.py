@@ -8,6 +8,10 @@ Public surface:
     split_gaussians         prune and split / clone Gaussians in HIP with one host read (pigs_amd.refine;
                             model_pn.py:578-605, :703-714 and test_no_mlp.py:198-240)
     refine_index            its (source, child) maps alone, for optimiser state and other per-Gaussian arrays
+    split_criterion         which Gaussians to split, as a mask on the device without a host wait: the sampling
+                            passes and the quantile rule of model_pn.py:716-754 (pigs_amd.refine)
+    split_mask              the quantile rule alone (:733-754), from the three sampled fields
+    threshold_mask          score > mean + k std, the rule of test_no_mlp.py:203-205
     GaussianAdam            the Gaussians' parameterisation, its backward and Adam in one launch per step
                             (pigs_amd.optim; test_no_mlp.py:99-104, 146, 185-186, test_initialize.py:172-180)
     build()                 compile the HIP library (hipcc, gfx950) and the native host extension in-tree
@@ -26,7 +30,7 @@ def __getattr__(name):
     if name == "VORTICITY_RESIDUAL_COLUMNS":
         from .sampler import VORTICITY_RESIDUAL_COLUMNS
         return VORTICITY_RESIDUAL_COLUMNS
-    if name in ("split_gaussians", "refine_index"):
+    if name in ("split_gaussians", "refine_index", "split_mask", "threshold_mask", "split_criterion"):
         from . import refine
         return getattr(refine, name)
     if name == "GaussianAdam":

@@ -142,6 +142,13 @@ SIGNATURES = {
     "pigs_refine_apply": (_i, [_i, _i, _i, _i64, _i64, ctypes.c_double] + [_vp] * 2 + [_vp] * 4 + [_vp] * 4 + [_vp] * 2
                           + [_vp]),
     "pigs_refine_backward": (_i, [_i, _i, _i, _i64, _i64, ctypes.c_double] + [_vp] * 2 + [_vp] * 4 + [_vp] * 4 + [_vp]),
+    # the split criteria (additive to ABI 10): inputs, masks, workspace, metric / stats, mask
+    "pigs_criterion_lds_values": (_i, []),
+    "pigs_criterion_workspace_bytes": (ctypes.c_size_t, [_i, _i64, _i]),
+    "pigs_criterion_quantile_mask": (_i, [_i, _i, _i, _i64, ctypes.c_double] + [_vp] * 4 + [_vp, ctypes.c_size_t]
+                                     + [_vp] * 3 + [_vp]),
+    "pigs_criterion_meanstd_mask": (_i, [_i, _i, _i64, ctypes.c_double] + [_vp] * 2 + [_vp, ctypes.c_size_t] + [_vp] * 2
+                                    + [_vp]),
     # the optimiser (additive to ABI 10): parameters, outputs / hyper, parameters, moments, gradients, outputs
     "pigs_optim_materialize": (_i, [_i, _i, _i64, ctypes.c_double] + [_vp] * 3 + [_vp] * 3 + [_vp]),
     "pigs_optim_step": (_i, [_i, _i, _i64, _adam_p] + [_vp] * 4 + [_vp] * 8 + [_vp] * 4 + [_vp] * 3 + [_vp]),

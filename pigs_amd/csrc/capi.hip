@@ -562,6 +562,60 @@ int pigs_refine_backward(int dtype, int mode, int c, int64_t N, int64_t rows, do
     return refine_rows(true, r, (hipStream_t)stream);
 }
 
+int pigs_criterion_lds_values(void) { return CRITERION_LDS_VALUES; }
+
+size_t pigs_criterion_workspace_bytes(int dtype, int64_t n, int c) { return criterion_workspace_bytes(dtype, n, c); }
+
+// the checks the two criteria share; *one = the variant that runs
+static int criterion_sizes_ok(int dtype, int variant, int c, int64_t n, bool* one) {
+    if (dtype != PIGS_F32 && dtype != PIGS_F64) return PIGS_ERR_UNSUPPORTED;
+    if (variant != PIGS_CRITERION_AUTO && variant != PIGS_CRITERION_ONE_WORKGROUP && variant != PIGS_CRITERION_MANY_WORKGROUPS)
+        return PIGS_ERR_UNSUPPORTED;
+    if (n < 0 || c < 1) return PIGS_ERR_INVALID;
+    if (n > CRITERION_MAX_VALUES / c) return PIGS_ERR_UNSUPPORTED;
+    const bool fits = n * c <= CRITERION_LDS_VALUES;
+    if (variant == PIGS_CRITERION_ONE_WORKGROUP && !fits) return PIGS_ERR_UNSUPPORTED;
+    *one = variant == PIGS_CRITERION_AUTO ? fits : variant == PIGS_CRITERION_ONE_WORKGROUP;
+    return PIGS_OK;
+}
+
+int pigs_criterion_quantile_mask(int dtype, int variant, int c, int64_t n, double q, const void* sample_u,
+                                 const void* prev_sample_u, const void* density, const uint8_t* boundary_mask,
+                                 void* workspace, size_t workspace_bytes, void* metric, void* stats, uint8_t* mask,
+                                 void* stream) {
+    CriterionQuantile a{};
+    const int rc = criterion_sizes_ok(dtype, variant, c, n, &a.one_workgroup);
+    if (rc != PIGS_OK) return rc;
+    if (!(q >= 0.0 && q <= 1.0)) return PIGS_ERR_INVALID;            // NaN fails both compares
+    if (n == 0) return PIGS_OK;
+    if (!sample_u || !prev_sample_u || !density || !mask) return PIGS_ERR_INVALID;
+    if (!a.one_workgroup) {
+        if (!workspace || ((uintptr_t)workspace & 7u)) return PIGS_ERR_INVALID;
+        if (workspace_bytes < criterion_workspace_bytes(dtype, n, c)) return PIGS_ERR_WORKSPACE;
+    }
+    a.dtype = dtype; a.c = c; a.n = n; a.q = q;
+    a.sample_u = sample_u; a.prev_sample_u = prev_sample_u; a.density = density; a.boundary = boundary_mask;
+    a.workspace = workspace; a.metric = metric; a.stats = stats; a.mask = mask;
+    return criterion_quantile(a, (hipStream_t)stream);
+}
+
+int pigs_criterion_meanstd_mask(int dtype, int variant, int64_t n, double k, const void* score, const uint8_t* keep,
+                                void* workspace, size_t workspace_bytes, void* stats, uint8_t* mask, void* stream) {
+    CriterionMeanStd a{};
+    const int rc = criterion_sizes_ok(dtype, variant, 1, n, &a.one_workgroup);
+    if (rc != PIGS_OK) return rc;
+    if (k != k) return PIGS_ERR_INVALID;
+    if (n == 0) return PIGS_OK;
+    if (!score || !mask) return PIGS_ERR_INVALID;
+    if (!a.one_workgroup) {
+        if (!workspace || ((uintptr_t)workspace & 7u)) return PIGS_ERR_INVALID;
+        if (workspace_bytes < criterion_workspace_bytes(dtype, n, 1)) return PIGS_ERR_WORKSPACE;
+    }
+    a.dtype = dtype; a.n = n; a.k = k; a.score = score; a.keep = keep;
+    a.workspace = workspace; a.stats = stats; a.mask = mask;
+    return criterion_meanstd(a, (hipStream_t)stream);
+}
+
 static int optim_sizes_ok(int dtype, int means_map, int c, int64_t N) {
     if (dtype != PIGS_F32 && dtype != PIGS_F64) return PIGS_ERR_UNSUPPORTED;
     if (means_map != PIGS_OPTIM_MEANS_TANH && means_map != PIGS_OPTIM_MEANS_IDENTITY) return PIGS_ERR_UNSUPPORTED;

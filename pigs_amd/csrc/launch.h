@@ -49,6 +49,35 @@ int refine_index(int mode, int64_t N, const uint8_t* keep, const uint8_t* split,
                  int64_t* child_pos, int64_t* counts, hipStream_t stream);
 int refine_rows(bool backward, const RefineRows& r, hipStream_t stream);
 
+// criterion.hip
+constexpr int CRITERION_LDS_VALUES = PIGS_CRITERION_LDS_VALUES;      // most values the one-workgroup variant takes
+constexpr int64_t CRITERION_MAX_VALUES = 1LL << 24;                  // n * c, as torch.quantile
+struct CriterionQuantile {
+    int dtype, c;
+    bool one_workgroup;
+    int64_t n;
+    double q;
+    const void *sample_u, *prev_sample_u, *density;
+    const uint8_t* boundary;
+    void* workspace;       // many workgroups only
+    void *metric, *stats;  // or null
+    uint8_t* mask;
+};
+struct CriterionMeanStd {
+    int dtype;
+    bool one_workgroup;
+    int64_t n;
+    double k;
+    const void* score;
+    const uint8_t* keep;
+    void* workspace;       // many workgroups only
+    void* stats;           // or null
+    uint8_t* mask;
+};
+size_t criterion_workspace_bytes(int dtype, int64_t n, int c);
+int criterion_quantile(const CriterionQuantile& q, hipStream_t stream);
+int criterion_meanstd(const CriterionMeanStd& m, hipStream_t stream);
+
 // optim.hip
 struct OptimStep {
     int dtype, c;

@@ -18,6 +18,12 @@ array follows with one ``index_select`` and one ``where``.  The effective split 
 
 Five HIP launches (C ABI: pigs_refine_*) and ONE host wait: the pinned read of the two row totals that size the
 outputs.  d = 2, float32 / float64, GPU only.
+
+The criteria that choose the ``split`` mask, on the device and without a host wait (C ABI: pigs_criterion_*):
+
+    split_criterion   the whole of model_pn.py:716-754: two sampling passes and the quantile rule
+    split_mask        the quantile rule alone (:733-754) from the three sampled fields
+    threshold_mask    score > mean + k std, the rule of test_no_mlp.py:203-205
 """
 import collections
 import ctypes
@@ -215,3 +221,165 @@ def split_gaussians(means, scaling, transforms, values, split, keep=None, *, mod
     keep = _check_mask("keep", keep, N, means.device)
     split = _check_mask("split", split, N, means.device)
     return Refined(*_SplitGaussians.apply(means, scaling, transforms, values, keep, split, m, float(value_scale)))
+
+
+# ---- the criteria: which rows to split -------------------------------------------------------------------------
+VARIANTS = {"auto": 0, "one": 1, "many": 2}
+CRITERION_LDS_VALUES = 16384   # PIGS_CRITERION_LDS_VALUES: most values n * c of the one-workgroup variant
+CRITERION_MAX_VALUES = 1 << 24  # n * c beyond this is refused, as torch.quantile refuses it
+
+
+def _variant(variant, values):
+    if variant not in VARIANTS:
+        raise ValueError(f"variant must be 'auto', 'one' or 'many', got {variant!r}")
+    if values > CRITERION_MAX_VALUES:
+        raise NotImplementedError(f"{values} values: the criteria take up to 2^24 (as torch.quantile)")
+    if variant == "one" and values > CRITERION_LDS_VALUES:
+        raise NotImplementedError(f"variant='one' takes up to {CRITERION_LDS_VALUES} values, got {values}")
+    return VARIANTS[variant], variant == "one" or (variant == "auto" and values <= CRITERION_LDS_VALUES)
+
+
+def _row_mask(name, mask, n, device):
+    """a bool [n] or [n, 1] on the device -> contiguous [n]"""
+    _check_mask_type(name, mask)
+    if mask is not None and mask.dim() == 2 and mask.shape[1] == 1:
+        mask = mask.reshape(-1)
+    return _check_mask(name, mask, n, device)
+
+
+def _criterion_workspace(lib, one, dtype, n, c, device):
+    if one:
+        return None, 0
+    ws_bytes = lib.pigs_criterion_workspace_bytes(_DTYPES[dtype], n, c)
+    return torch.empty(ws_bytes // 8 + 1, dtype=torch.int64, device=device), ws_bytes
+
+
+def split_mask(sample_u, prev_sample_u, density, boundary_mask=None, *, q=0.98, variant="auto", return_stats=False):
+    """The quantile rule of model_pn.py:733-754 as a torch.bool mask [n] on the device, without a host wait:
+
+        w = 1 - (density - density.min()) / density.max();   metric = (sample_u - prev_sample_u) ** 2 * w
+        mask = (metric > torch.quantile(metric, q)).any(-1) & boundary_mask
+
+    sample_u, prev_sample_u [n, c] and density [n] or [n, 1]: float32 or float64 on one GPU, all alike;
+    ``boundary_mask``: torch.bool [n] or [n, 1], or None (all).  Inputs that require a gradient are detached (the
+    reference computes the criterion under no_grad).  ``variant``: "auto", "one" (one launch of one workgroup, up to
+    CRITERION_LDS_VALUES values n * c) or "many" (6 launches in float32, 10 in float64).  With ``return_stats`` the
+    result is ``(mask, metric [n, c], stats [4])``, stats = (quantile, x_lo, x_hi, 1.0 if a NaN was seen else 0.0);
+    a NaN makes the quantile NaN and the mask all False."""
+    names = ("sample_u", "prev_sample_u", "density")
+    arrays = (sample_u, prev_sample_u, density)
+    for name, a in zip(names, arrays):
+        if not isinstance(a, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+    if sample_u.dim() != 2 or sample_u.shape[1] < 1:
+        raise ValueError(f"sample_u must be [n, c] with c >= 1, got {tuple(sample_u.shape)}")
+    n, c = sample_u.shape
+    if prev_sample_u.shape != sample_u.shape:
+        raise ValueError(f"prev_sample_u must be [n, c] = [{n}, {c}], got {tuple(prev_sample_u.shape)}")
+    if tuple(density.shape) not in ((n,), (n, 1)):
+        raise ValueError(f"density must be [n] or [n, 1] with n = {n}, got {tuple(density.shape)}")
+    for name, a in zip(names, arrays):
+        if not a.is_cuda or a.device != sample_u.device:
+            raise RuntimeError(f"{name} is on {a.device}, sample_u on {sample_u.device}: the criterion runs on one GPU "
+                               "(no CPU fallback)")
+    if sample_u.dtype not in _DTYPES or any(a.dtype != sample_u.dtype for a in arrays):
+        raise TypeError(f"dtypes {[str(a.dtype) for a in arrays]}: float32 or float64, all alike")
+    q = float(q)
+    if not 0.0 <= q <= 1.0:
+        raise ValueError(f"q must lie in [0, 1], got {q}")
+    device, dtype = sample_u.device, sample_u.dtype
+    boundary_mask = _row_mask("boundary_mask", boundary_mask, n, device)
+    code, one = _variant(variant, n * c)
+    mask = torch.empty(n, dtype=torch.bool, device=device)
+    metric = torch.empty((n, c), dtype=dtype, device=device) if return_stats else None
+    stats = torch.empty(4, dtype=dtype, device=device) if return_stats else None
+    if n > 0:
+        lib = _lib.load()
+        su, pu, dn = (a.detach().contiguous() for a in arrays)
+        workspace, ws_bytes = _criterion_workspace(lib, one, dtype, n, c, device)
+        with torch.cuda.device(device):
+            rc = lib.pigs_criterion_quantile_mask(_DTYPES[dtype], code, c, n, q, _ptr(su), _ptr(pu), _ptr(dn),
+                                                  _ptr(boundary_mask), _ptr(workspace), ws_bytes, _ptr(metric), _ptr(stats),
+                                                  _ptr(mask), _stream(device))
+        _lib.check(rc, "pigs_criterion_quantile_mask")
+    elif return_stats:
+        stats.fill_(float("nan"))
+    return (mask, metric, stats) if return_stats else mask
+
+
+def threshold_mask(score, keep=None, *, k=1.6, variant="auto", return_stats=False):
+    """The rule of test_no_mlp.py:203-205 as a torch.bool mask [n] on the device, without a host wait:
+
+        mask = (score > torch.mean(score) + k * torch.std(score)) & keep
+
+    score [n]: float32 or float64 on the GPU (detached if it requires a gradient); ``keep``: torch.bool [n] or None.
+    The mean and the squared deviations are summed in double; n = 1 (std NaN) and a NaN score give an all-False mask.
+    ``variant``: "auto", "one" (one launch, n up to CRITERION_LDS_VALUES) or "many" (three launches).  With
+    ``return_stats`` the result is ``(mask, stats [3])``, stats = (threshold, mean, std)."""
+    if not isinstance(score, torch.Tensor):
+        raise TypeError("score must be a torch.Tensor")
+    if score.dim() != 1:
+        raise ValueError(f"score must be [n], got {tuple(score.shape)}")
+    if not score.is_cuda:
+        raise RuntimeError(f"score is on {score.device}: the criterion runs on one GPU (no CPU fallback)")
+    if score.dtype not in _DTYPES:
+        raise TypeError(f"dtype {score.dtype}: float32 or float64")
+    k = float(k)
+    if k != k:
+        raise ValueError("k must not be NaN")
+    n, device, dtype = score.shape[0], score.device, score.dtype
+    keep = _check_mask("keep", keep, n, device)
+    code, one = _variant(variant, n)
+    mask = torch.empty(n, dtype=torch.bool, device=device)
+    stats = torch.empty(3, dtype=dtype, device=device) if return_stats else None
+    if n > 0:
+        lib = _lib.load()
+        sc = score.detach().contiguous()
+        workspace, ws_bytes = _criterion_workspace(lib, one, dtype, n, 1, device)
+        with torch.cuda.device(device):
+            rc = lib.pigs_criterion_meanstd_mask(_DTYPES[dtype], code, n, k, _ptr(sc), _ptr(keep), _ptr(workspace), ws_bytes,
+                                                 _ptr(stats), _ptr(mask), _stream(device))
+        _lib.check(rc, "pigs_criterion_meanstd_mask")
+    elif return_stats:
+        stats.fill_(float("nan"))
+    return (mask, stats) if return_stats else mask
+
+
+def _one_pass(sampler, n, c):
+    """values and the channel of ones in ONE preprocess: within the sampler's 4 channels, and not where the extra
+    channel would take a pass that runs binned (c <= 2 there) off that path"""
+    if c + 1 > 4:
+        return False
+    backend = getattr(sampler, "backend", "auto")
+    binned = backend == "binned" or (backend == "auto" and n * n >= getattr(sampler, "BINNED_AUTO_MIN_PAIRS", 1 << 62))
+    return c + 1 <= 2 or not binned
+
+
+def split_criterion(sampler, means, values, covariances, conics, prev_means, prev_values, prev_covariances, prev_conics,
+                    boundary_mask=None, *, q=0.98):
+    """The whole criterion of Model.forward(split=True), model_pn.py:716-754, under no_grad: the current field and the
+    density of the current Gaussians at their own means, the previous field there, then ``split_mask``.  Returns the
+    torch.bool mask [n] that goes into ``split_gaussians`` / ``refine_index``; nothing waits for the device.
+
+    The density (a field of ones, :729-732) rides as one more channel of the first pass where the sampler takes it in
+    the same path (c + 1 <= 4 channels; a pass that runs binned keeps its c <= 2), else it is a pass of its own.  The
+    sampler picks dense or binned as it always does, with either host and with ``periodic=``.  The sampler is left
+    bound to the LAST pass: the previous Gaussians at the current means."""
+    with torch.no_grad():
+        means, values = means.detach(), values.detach()
+        if values.dim() == 1:
+            values = values.reshape(-1, 1)
+        n, c = values.shape
+        ones = torch.ones((n, 1), dtype=values.dtype, device=values.device)
+        if _one_pass(sampler, n, c):
+            sampler.preprocess(means, torch.cat((values, ones), -1), covariances, conics, means)
+            both = sampler.sample_gaussians()
+            sample_u, density = both[:, :c], both[:, c]
+        else:
+            sampler.preprocess(means, values, covariances, conics, means)
+            sample_u = sampler.sample_gaussians()
+            sampler.preprocess(means, ones, covariances, conics, means)
+            density = sampler.sample_gaussians()
+        sampler.preprocess(prev_means, prev_values, prev_covariances, prev_conics, means)
+        prev_sample_u = sampler.sample_gaussians()
+        return split_mask(sample_u, prev_sample_u.reshape(n, c), density, boundary_mask, q=q)
