@@ -769,6 +769,66 @@ int pigs_optim_step(int dtype, int c, int64_t N, const PigsAdamStep* hyper, void
                     void* exp_avg_sq_transform, const void* g_means, const void* g_values, const void* g_covariances,
                     const void* g_conics, void* means, void* covariances, void* conics, void* stream);
 
+/*
+ * The model's state update: the dynamics network's deltas applied to the Gaussians, the next covariances and the
+ * conservation penalty (additive to ABI 10: the number does not change).  d = 2, c = 1..4, float32 / float64.
+ * Replaces, per time step of the loop with the network (main_pn.py:171-232 driving model_pn.Model):
+ *   model_pn.py:270-273  the four strided column slices of the network's output (and, in the backward, a zero tensor and
+ *                        an add per slice);
+ *   :677-682             six detach().clone() of the previous state: the inputs are never written, they ARE prev_*;
+ *   :684-687             means + dmeans m, scaling exp(dscaling m), transforms + dtransforms m, u + du m;
+ *   :689-693             the periodic wrap of the means, two boolean-index writes with a host wait each;
+ *   :695-698             build_full_covariances and flatten_covariances;
+ *   :878-882             mean(x[mask]^2) of the four delta blocks, a boolean indexing with a host wait each.
+ *
+ * Arrays, row-major: means [N][2], u [N][c], scaling [N][2], transforms [N], deltas [N][5 + c] in the network's own column
+ * order (dmeans 0:2, dscaling 2:4, dtransforms 4:5, du 5:5+c), boundary_mask [N] (one byte per row, nonzero = a FREE
+ * Gaussian, m = 1, as the reference uses it; zero = a boundary Gaussian, m = 0).
+ *
+ * pigs_advance_forward, two launches.  The first, one thread per Gaussian in workgroups of 256:
+ *   means' = means + dmeans m,  scaling' = scaling exp(dscaling m),  transforms' = transforms + dtransforms m,
+ *   u' = u + du m;  with `wrap`, a coordinate of means' > wrap_hi is lowered by wrap_hi - wrap_lo and one < wrap_lo
+ *   raised by it: one shift, strict inequalities.  A boundary row copies its inputs bit for bit; its deltas take part in
+ *   no arithmetic (they may be NaN or Inf).
+ *   covariances [N][3], conics [N][3] of (scaling', transforms') with the expressions of pigs_build_covariances, bit for
+ *   bit what it writes from out_scaling and out_transforms; full_covariances [N][2][2], full_conics [N][2][2] the same
+ *   values, the xy entry stored twice.
+ *   Each thread squares its row's deltas in double; a workgroup adds the four sums and the free-row count across each
+ *   wave, then across its waves through LDS, and writes one record of PIGS_ADVANCE_RECORD doubles to `scratch`.
+ * The second, one workgroup, adds the records in a fixed order and writes
+ *   penalty[k] = sum over the free rows of the squares of block k / (n_free width_k),  widths 2, 2, 1, c,
+ *   k = dmeans, dscaling, dtransforms, du, rounded once to the dtype; no free row gives NaN (0 / 0), as torch.mean of an
+ *   empty tensor.  No float atomics: the penalty is a pure function of the inputs.  n_free stays in `scratch`.
+ * pigs_advance_backward, one launch of one thread per Gaussian.  From gradients with respect to any subset of the nine
+ *   outputs (a NULL one counts as zero) to g_means [N][2], g_u [N][c], g_scaling [N][2], g_transforms [N] and ONE packed
+ *   g_deltas [N][5 + c] (a NULL one is not written).  It reads out_scaling, out_transforms, deltas, boundary_mask and the
+ *   scratch of the forward.  The covariance terms are recomputed from (scaling', transforms') with the arithmetic of
+ *   pigs_build_covariances_backward; a full-matrix gradient folds into the flat one, the xy entry receiving both
+ *   off-diagonals.  The wrap passes its gradient through.  The penalty's share of g_deltas is
+ *   2 x m g_penalty[k] / (n_free width_k).  A boundary row's g_deltas is exactly zero.
+ * scratch: pigs_advance_scratch_bytes(N) bytes, 8-byte aligned (0 for N <= 0): record 0 the totals, record 1 + b the
+ *   record of workgroup b.  The forward writes all of it; the backward reads it only with a g_penalty.
+ * Rows of means, scaling, out_means, out_scaling, g_out_means, g_out_scaling, g_means and g_scaling are one 8-byte
+ *   (float32) / 16-byte (float64) access: those arrays are aligned to a row.
+ * Arguments are checked before any HIP call: a bad dtype or c outside 1..4 is PIGS_ERR_UNSUPPORTED; N <= 0, wrap with
+ *   wrap_lo >= wrap_hi, a null required array (forward: every input, output and the scratch; backward: the four saved
+ *   arrays, the scratch with a g_penalty, and all five gradients null) or a misaligned one is PIGS_ERR_INVALID; a short
+ *   scratch is PIGS_ERR_WORKSPACE.  Nothing allocates, frees, synchronises or waits for another workgroup.
+ */
+#define PIGS_ADVANCE_RECORD 5
+size_t pigs_advance_scratch_bytes(int64_t N);
+int pigs_advance_forward(int dtype, int c, int64_t N, int wrap, double wrap_lo, double wrap_hi, const void* means,
+                         const void* u, const void* scaling, const void* transforms, const void* deltas,
+                         const uint8_t* boundary_mask, void* scratch, size_t scratch_bytes, void* out_means, void* out_u,
+                         void* out_scaling, void* out_transforms, void* covariances, void* conics, void* full_covariances,
+                         void* full_conics, void* penalty, void* stream);
+int pigs_advance_backward(int dtype, int c, int64_t N, const void* out_scaling, const void* out_transforms,
+                          const void* deltas, const uint8_t* boundary_mask, const void* scratch, const void* g_out_means,
+                          const void* g_out_u, const void* g_out_scaling, const void* g_out_transforms,
+                          const void* g_covariances, const void* g_conics, const void* g_full_covariances,
+                          const void* g_full_conics, const void* g_penalty, void* g_means, void* g_u, void* g_scaling,
+                          void* g_transforms, void* g_deltas, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

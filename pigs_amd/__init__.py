@@ -14,6 +14,10 @@ Public surface:
     threshold_mask          score > mean + k std, the rule of test_no_mlp.py:203-205
     GaussianAdam            the Gaussians' parameterisation, its backward and Adam in one launch per step
                             (pigs_amd.optim; test_no_mlp.py:99-104, 146, 185-186, test_initialize.py:172-180)
+    advance_gaussians       the dynamics network's deltas applied to the Gaussians, the next covariances and the
+                            conservation penalty in two launches, one for the backward (pigs_amd.advance;
+                            model_pn.py:270-273, 677-698, 878-882)
+    ADVANCE_PENALTY_COLUMNS the names of ``advance_gaussians(...).penalty``'s four entries
     build()                 compile the HIP library (hipcc, gfx950) and the native host extension in-tree
 """
 from .build import build_all as build  # noqa: F401  (libpigs_amd.so + the native host extension)
@@ -36,4 +40,7 @@ def __getattr__(name):
     if name == "GaussianAdam":
         from .optim import GaussianAdam
         return GaussianAdam
+    if name in ("advance_gaussians", "ADVANCE_PENALTY_COLUMNS"):
+        from . import advance
+        return getattr(advance, name)
     raise AttributeError(name)

@@ -152,6 +152,12 @@ SIGNATURES = {
     # the optimiser (additive to ABI 10): parameters, outputs / hyper, parameters, moments, gradients, outputs
     "pigs_optim_materialize": (_i, [_i, _i, _i64, ctypes.c_double] + [_vp] * 3 + [_vp] * 3 + [_vp]),
     "pigs_optim_step": (_i, [_i, _i, _i64, _adam_p] + [_vp] * 4 + [_vp] * 8 + [_vp] * 4 + [_vp] * 3 + [_vp]),
+    # the model's state update (additive to ABI 10): wrap, state, deltas, mask, scratch, the nine outputs /
+    # saved arrays, mask, scratch, the nine incoming gradients, the five gradients
+    "pigs_advance_scratch_bytes": (ctypes.c_size_t, [_i64]),
+    "pigs_advance_forward": (_i, [_i, _i, _i64, _i, ctypes.c_double, ctypes.c_double] + [_vp] * 4 + [_vp, _vp]
+                             + [_vp, ctypes.c_size_t] + [_vp] * 9 + [_vp]),
+    "pigs_advance_backward": (_i, [_i, _i, _i64] + [_vp] * 3 + [_vp, _vp] + [_vp] * 9 + [_vp] * 5 + [_vp]),
 }
 
 _lib = None

@@ -665,4 +665,64 @@ int pigs_optim_step(int dtype, int c, int64_t N, const PigsAdamStep* hyper, void
     return optim_step(o, (hipStream_t)stream);
 }
 
+size_t pigs_advance_scratch_bytes(int64_t N) { return advance_scratch_bytes(N); }
+
+static int advance_sizes_ok(int dtype, int c, int64_t N) {
+    if (dtype != PIGS_F32 && dtype != PIGS_F64) return PIGS_ERR_UNSUPPORTED;
+    if (c < 1 || c > 4) return PIGS_ERR_UNSUPPORTED;
+    if (N <= 0) return PIGS_ERR_INVALID;
+    return PIGS_OK;
+}
+
+int pigs_advance_forward(int dtype, int c, int64_t N, int wrap, double wrap_lo, double wrap_hi, const void* means,
+                         const void* u, const void* scaling, const void* transforms, const void* deltas,
+                         const uint8_t* boundary_mask, void* scratch, size_t scratch_bytes, void* out_means, void* out_u,
+                         void* out_scaling, void* out_transforms, void* covariances, void* conics, void* full_covariances,
+                         void* full_conics, void* penalty, void* stream) {
+    const int rc = advance_sizes_ok(dtype, c, N);
+    if (rc != PIGS_OK) return rc;
+    if (wrap && !(wrap_lo < wrap_hi)) return PIGS_ERR_INVALID;            // NaN fails the compare
+    AdvanceStep s{};
+    s.dtype = dtype; s.c = c; s.N = N; s.wrap = wrap != 0; s.lo = wrap_lo; s.hi = wrap_hi;
+    s.in[0] = means; s.in[1] = u; s.in[2] = scaling; s.in[3] = transforms;
+    s.deltas = deltas; s.mask = boundary_mask; s.scratch = scratch;
+    s.out[0] = out_means; s.out[1] = out_u; s.out[2] = out_scaling; s.out[3] = out_transforms;
+    s.out[4] = covariances; s.out[5] = conics; s.out[6] = full_covariances; s.out[7] = full_conics; s.out[8] = penalty;
+    for (int k = 0; k < 4; ++k)
+        if (!s.in[k]) return PIGS_ERR_INVALID;
+    for (int k = 0; k < 9; ++k)
+        if (!s.out[k]) return PIGS_ERR_INVALID;
+    if (!deltas || !boundary_mask || !scratch || ((uintptr_t)scratch & 7u)) return PIGS_ERR_INVALID;
+    if (refine_misaligned(means, dtype) || refine_misaligned(scaling, dtype) || refine_misaligned(out_means, dtype) ||
+        refine_misaligned(out_scaling, dtype))
+        return PIGS_ERR_INVALID;
+    if (scratch_bytes < advance_scratch_bytes(N)) return PIGS_ERR_WORKSPACE;
+    return advance_forward(s, (hipStream_t)stream);
+}
+
+int pigs_advance_backward(int dtype, int c, int64_t N, const void* out_scaling, const void* out_transforms,
+                          const void* deltas, const uint8_t* boundary_mask, const void* scratch, const void* g_out_means,
+                          const void* g_out_u, const void* g_out_scaling, const void* g_out_transforms,
+                          const void* g_covariances, const void* g_conics, const void* g_full_covariances,
+                          const void* g_full_conics, const void* g_penalty, void* g_means, void* g_u, void* g_scaling,
+                          void* g_transforms, void* g_deltas, void* stream) {
+    const int rc = advance_sizes_ok(dtype, c, N);
+    if (rc != PIGS_OK) return rc;
+    AdvanceStep s{};
+    s.dtype = dtype; s.c = c; s.N = N;
+    s.in[2] = out_scaling; s.in[3] = out_transforms;
+    s.deltas = deltas; s.mask = boundary_mask; s.scratch = const_cast<void*>(scratch);
+    s.gout[0] = g_out_means; s.gout[1] = g_out_u; s.gout[2] = g_out_scaling; s.gout[3] = g_out_transforms;
+    s.gout[4] = g_covariances; s.gout[5] = g_conics; s.gout[6] = g_full_covariances; s.gout[7] = g_full_conics;
+    s.gout[8] = g_penalty;
+    s.out[0] = g_means; s.out[1] = g_u; s.out[2] = g_scaling; s.out[3] = g_transforms; s.out[4] = g_deltas;
+    if (!out_scaling || !out_transforms || !deltas || !boundary_mask) return PIGS_ERR_INVALID;
+    if (g_penalty && (!scratch || ((uintptr_t)scratch & 7u))) return PIGS_ERR_INVALID;
+    if (!g_means && !g_u && !g_scaling && !g_transforms && !g_deltas) return PIGS_ERR_INVALID;
+    if (refine_misaligned(out_scaling, dtype) || refine_misaligned(g_out_means, dtype) ||
+        refine_misaligned(g_out_scaling, dtype) || refine_misaligned(g_means, dtype) || refine_misaligned(g_scaling, dtype))
+        return PIGS_ERR_INVALID;
+    return advance_backward(s, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -91,6 +91,23 @@ int optim_materialize(int dtype, int64_t N, bool tanh_map, double scale, const v
                       const void* transform, void* o_means, void* o_cov, void* o_conic, hipStream_t stream);
 int optim_step(const OptimStep& o, hipStream_t stream);
 
+// advance.hip
+struct AdvanceStep {
+    int dtype, c, wrap;
+    int64_t N;
+    double lo, hi;
+    const void* in[4];       // forward: means, u, scaling, transforms; backward: [2], [3] = the forward's scaling', transforms'
+    const void* deltas;      // [N][5 + c]
+    const uint8_t* mask;
+    void* scratch;           // the forward writes it, the backward reads n_free from its record 0
+    const void* gout[9];     // backward: incoming gradients in the order of the forward's outputs (null = none)
+    void* out[9];            // forward: means', u', scaling', transforms', covariances, conics, the two full forms, penalty;
+                             // backward: gradients of means, u, scaling, transforms, deltas (null = not wanted)
+};
+size_t advance_scratch_bytes(int64_t N);
+int advance_forward(const AdvanceStep& s, hipStream_t stream);
+int advance_backward(const AdvanceStep& s, hipStream_t stream);
+
 // periodic.hip: images (fold = false; a = means, conics, values; o = image arrays) or the fold of their gradients
 // (fold = true; a = image gradients, null = zero; o = gradients)
 int periodic_dispatch(bool fold, int dtype, int c, int64_t N, double lo, double period, double q_cut, const void* a0,
