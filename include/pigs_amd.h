@@ -829,6 +829,41 @@ int pigs_advance_backward(int dtype, int c, int64_t N, const void* out_scaling, 
                           const void* g_full_conics, const void* g_penalty, void* g_means, void* g_u, void* g_scaling,
                           void* g_transforms, void* g_deltas, void* stream);
 
+/* ---- One per-Gaussian tanh network per launch (additive to ABI 10) ----------------------------
+ * The three per-Gaussian nets of the dynamics network (model_pn.py:154-174 delta_net, :187-198 input_projection,
+ * :203-226 the query / key transforms; nn.Tanh, :425-426): nn.Linear layers with tanh between them and none after the last,
+ * applied row by row.  One net per call:
+ *   a_0 = x [N][w_0];  a_{l+1} = tanh(a_l W_l^T + b_l) for l < L - 1;  y = a_{L-1} W_{L-1}^T + b_{L-1}  [N][w_L]
+ * `widths` is a host array of L + 1 ints (w_0 .. w_L); `weights` and `biases` are host arrays of L device pointers, W_l
+ * [w_{l+1}][w_l] and b_l [w_{l+1}] row-major in nn.Linear's layout.  1 <= L <= PIGS_MLP_MAX_LAYERS, every width in
+ * 1..PIGS_MLP_MAX_WIDTH, float32 only.  The host arrays are read during the call and not kept.
+ *
+ * pigs_mlp_forward, one launch.  A wave takes 16 rows at a time and keeps the activations in the accumulator registers of
+ *   v_mfma_f32_16x16x4_f32 from x to y; the weights are staged once per workgroup in LDS, padded with zeros to multiples
+ *   of 16.  Each output is a float32 fmaf chain over the layer's inputs, started from the bias, in a fixed order.
+ * pigs_mlp_backward, one launch, and a second one when any weight or bias gradient is wanted.  From g_y [N][w_L] to g_x
+ *   [N][w_0], g_weights[l] and g_biases[l] (shapes of W_l, b_l); a NULL g_x, a NULL array or a NULL entry is not
+ *   written.  The activations are recomputed from x: the forward saves nothing.  At most PIGS_MLP_MAX_RECORDS waves walk
+ *   the row tiles in a fixed order, each adds its weight and bias gradients in registers and writes one record to
+ *   `scratch`; the second launch adds the records in a fixed order (four interleaved partial sums per parameter, then
+ *   (p0 + p1) + (p2 + p3)).  No float atomics: every output is a pure function of the inputs, bit for bit.
+ * scratch: pigs_mlp_scratch_bytes(N, L, widths) bytes = min(ceil(N / 16), PIGS_MLP_MAX_RECORDS) records of
+ *   sum_l w_{l+1} (w_l + 1) floats, 4-byte aligned; 0 for N <= 0 or an unsupported net.  Not read by the caller.
+ * Arguments are checked before any HIP call: a dtype other than PIGS_F32, L or a width out of range is
+ *   PIGS_ERR_UNSUPPORTED; N <= 0, a null required array (widths, x, weights, biases and their entries, y or g_y; the
+ *   backward with no gradient wanted), or a null, misaligned or short scratch with a weight or bias gradient wanted is
+ *   PIGS_ERR_INVALID.  Nothing allocates, frees, synchronises or waits for another workgroup.
+ */
+#define PIGS_MLP_MAX_LAYERS 6
+#define PIGS_MLP_MAX_WIDTH 48
+#define PIGS_MLP_MAX_RECORDS 256
+size_t pigs_mlp_scratch_bytes(int64_t N, int L, const int* widths);
+int pigs_mlp_forward(int dtype, int64_t N, int L, const int* widths, const void* x, const void* const* weights,
+                     const void* const* biases, void* y, void* stream);
+int pigs_mlp_backward(int dtype, int64_t N, int L, const int* widths, const void* x, const void* const* weights,
+                      const void* const* biases, const void* g_y, void* scratch, size_t scratch_bytes, void* g_x,
+                      void* const* g_weights, void* const* g_biases, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,11 @@ Public surface:
                             conservation penalty in two launches, one for the backward (pigs_amd.advance;
                             model_pn.py:270-273, 677-698, 878-882)
     ADVANCE_PENALTY_COLUMNS the names of ``advance_gaussians(...).penalty``'s four entries
+    fused_mlp               one per-Gaussian tanh network (nn.Linear layers with nn.Tanh between them, up to 6 layers
+                            of width up to 48) in one launch forward and at most two backward, on the f32 MFMA
+                            (pigs_amd.mlp; model_pn.py:154-174, 187-198, 203-226)
+    FusedMLP                ``FusedMLP.from_sequential(seq)``: the same, as a module over an existing nn.Sequential
+                            whose Parameters and state_dict keys it keeps
     build()                 compile the HIP library (hipcc, gfx950) and the native host extension in-tree
 """
 from .build import build_all as build  # noqa: F401  (libpigs_amd.so + the native host extension)
@@ -43,4 +48,7 @@ def __getattr__(name):
     if name in ("advance_gaussians", "ADVANCE_PENALTY_COLUMNS"):
         from . import advance
         return getattr(advance, name)
+    if name in ("fused_mlp", "FusedMLP"):
+        from . import mlp
+        return getattr(mlp, name)
     raise AttributeError(name)

@@ -20,6 +20,8 @@ ABI_VERSION = 10
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _i64 = ctypes.c_int64
+_ip = ctypes.POINTER(ctypes.c_int)          # a host array of ints
+_vpp = ctypes.POINTER(ctypes.c_void_p)      # a host array of device pointers
 
 
 
@@ -158,6 +160,10 @@ SIGNATURES = {
     "pigs_advance_forward": (_i, [_i, _i, _i64, _i, ctypes.c_double, ctypes.c_double] + [_vp] * 4 + [_vp, _vp]
                              + [_vp, ctypes.c_size_t] + [_vp] * 9 + [_vp]),
     "pigs_advance_backward": (_i, [_i, _i, _i64] + [_vp] * 3 + [_vp, _vp] + [_vp] * 9 + [_vp] * 5 + [_vp]),
+    # one tanh network per launch (additive to ABI 10): widths, x, weights, biases, y / ..., g_y, scratch, the gradients
+    "pigs_mlp_scratch_bytes": (ctypes.c_size_t, [_i64, _i, _ip]),
+    "pigs_mlp_forward": (_i, [_i, _i64, _i, _ip, _vp, _vpp, _vpp, _vp, _vp]),
+    "pigs_mlp_backward": (_i, [_i, _i64, _i, _ip, _vp, _vpp, _vpp, _vp, _vp, ctypes.c_size_t, _vp, _vpp, _vpp, _vp]),
 }
 
 _lib = None

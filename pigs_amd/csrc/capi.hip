@@ -725,4 +725,50 @@ int pigs_advance_backward(int dtype, int c, int64_t N, const void* out_scaling, 
     return advance_backward(s, (hipStream_t)stream);
 }
 
+size_t pigs_mlp_scratch_bytes(int64_t N, int L, const int* widths) { return mlp_scratch_bytes(N, L, widths); }
+
+static int mlp_sizes_ok(int dtype, int64_t N, int L, const int* widths) {
+    if (dtype != PIGS_F32) return PIGS_ERR_UNSUPPORTED;
+    if (L < 1 || L > PIGS_MLP_MAX_LAYERS) return PIGS_ERR_UNSUPPORTED;
+    if (!widths) return PIGS_ERR_INVALID;
+    for (int l = 0; l <= L; ++l)
+        if (widths[l] < 1 || widths[l] > PIGS_MLP_MAX_WIDTH) return PIGS_ERR_UNSUPPORTED;
+    if (N <= 0) return PIGS_ERR_INVALID;
+    return PIGS_OK;
+}
+
+static bool mlp_net_missing(int L, const void* x, const void* const* weights, const void* const* biases) {
+    if (!x || !weights || !biases) return true;
+    for (int l = 0; l < L; ++l)
+        if (!weights[l] || !biases[l]) return true;
+    return false;
+}
+
+int pigs_mlp_forward(int dtype, int64_t N, int L, const int* widths, const void* x, const void* const* weights,
+                     const void* const* biases, void* y, void* stream) {
+    const int rc = mlp_sizes_ok(dtype, N, L, widths);
+    if (rc != PIGS_OK) return rc;
+    if (mlp_net_missing(L, x, weights, biases) || !y) return PIGS_ERR_INVALID;
+    MlpStep s{};
+    s.N = N; s.L = L; s.widths = widths; s.x = x; s.weights = weights; s.biases = biases; s.y = y;
+    return mlp_forward(s, (hipStream_t)stream);
+}
+
+int pigs_mlp_backward(int dtype, int64_t N, int L, const int* widths, const void* x, const void* const* weights,
+                      const void* const* biases, const void* g_y, void* scratch, size_t scratch_bytes, void* g_x,
+                      void* const* g_weights, void* const* g_biases, void* stream) {
+    const int rc = mlp_sizes_ok(dtype, N, L, widths);
+    if (rc != PIGS_OK) return rc;
+    if (mlp_net_missing(L, x, weights, biases) || !g_y) return PIGS_ERR_INVALID;
+    bool params = false;
+    for (int l = 0; l < L; ++l) params = params || (g_weights && g_weights[l]) || (g_biases && g_biases[l]);
+    if (!g_x && !params) return PIGS_ERR_INVALID;
+    if (params && (!scratch || ((uintptr_t)scratch & 3u) || scratch_bytes < mlp_scratch_bytes(N, L, widths)))
+        return PIGS_ERR_INVALID;
+    MlpStep s{};
+    s.N = N; s.L = L; s.widths = widths; s.x = x; s.weights = weights; s.biases = biases; s.g_y = g_y;
+    s.scratch = scratch; s.g_x = g_x; s.g_weights = g_weights; s.g_biases = g_biases;
+    return mlp_backward(s, (hipStream_t)stream);
+}
+
 }  // extern "C"

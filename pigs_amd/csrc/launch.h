@@ -108,6 +108,25 @@ size_t advance_scratch_bytes(int64_t N);
 int advance_forward(const AdvanceStep& s, hipStream_t stream);
 int advance_backward(const AdvanceStep& s, hipStream_t stream);
 
+// mlp.hip
+struct MlpStep {
+    int64_t N;
+    int L;
+    const int* widths;                  // [L + 1], host
+    const void* x;                      // [N][widths[0]]
+    const void* const* weights;         // [L] device pointers, host array: W_l [widths[l + 1]][widths[l]]
+    const void* const* biases;          // [L]: b_l [widths[l + 1]]
+    void* y;                            // forward: [N][widths[L]]
+    const void* g_y;                    // backward: the incoming gradient
+    void* scratch;                      // backward: the waves' records (only with a weight or bias gradient)
+    void* g_x;                          // backward: null = not wanted
+    void* const* g_weights;             // backward: null, or [L] with null entries = not wanted
+    void* const* g_biases;
+};
+size_t mlp_scratch_bytes(int64_t N, int L, const int* widths);
+int mlp_forward(const MlpStep& s, hipStream_t stream);
+int mlp_backward(const MlpStep& s, hipStream_t stream);
+
 // periodic.hip: images (fold = false; a = means, conics, values; o = image arrays) or the fold of their gradients
 // (fold = true; a = image gradients, null = zero; o = gradients)
 int periodic_dispatch(bool fold, int dtype, int c, int64_t N, double lo, double period, double q_cut, const void* a0,
