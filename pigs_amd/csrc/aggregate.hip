@@ -31,7 +31,10 @@
 //   forward   [fbar ; ebar] from {features_j, sin/cos}; the two constant embedding entries are sum a = 1
 //             and sum a g, reduced in phase 1
 //   backward  per pair: da_ij = <dfbar_i, features_j> + <debar_i, emb_ij>, ds_ij = a_ij (da_ij - D_i) with
-//             D_i = <dacc_i, acc_i> (the softmax's inner sum, known without a pass over the pairs);
+//             D_i = sum_j a_ij da_ij / sum_j a_ij, summed over the pairs by the row pass before it forms ds
+//             (<dacc_i, acc_i> from the forward's saved means is the same number without that pass, but
+//             ds is a small difference and sum_j ds_ij must vanish with the a_ij the backward itself
+//             recomputes: DESIGN.md section 22);
 //             by rows: d queries_i and the row's share of d frequencies (from the same sin / cos values);
 //             by columns, as a gather (no atomics): d features_j, d keys_j.
 // d transform, d distance_transform and dacc = gout [transform | distance_transform] are plain
@@ -473,7 +476,7 @@ __global__ __launch_bounds__(256) void aggregate_forward_kernel(
 // rows in hand); de = the embedding part of dacc_i: [plain (4F), const ; density-weighted (4F), const].
 template <typename T, typename De, typename Fterm>
 __device__ __forceinline__ void pair_terms(int F, T dx, T dy, T g, T s, T dfeat, De&& de, const T* __restrict__ freq, T lse_i,
-                                           T D_i, T inv_sqrt_k, T* a_out, T* ds_out, Fterm&& fterm) {
+                                           T D_i, T inv_sqrt_k, T* a_out, T* ds_out, Fterm&& fterm, T* da_out = nullptr) {
     const int E = 4 * F + 1;
     const T a = exp_<T>(s * inv_sqrt_k - lse_i);
     T da = dfeat;
@@ -490,10 +493,12 @@ __device__ __forceinline__ void pair_terms(int F, T dx, T dy, T g, T s, T dfeat,
     da += de(E - 1) + g * de(2 * E - 1);
     *a_out = a;
     *ds_out = a * (da - D_i);
+    if (da_out) *da_out = da;
 }
 
-// backward by rows.  Prologue: dacc_i = gout_i [transform | distance_transform]  [W] and D_i = <dacc_i, acc_i>
-// (kept in the wave's LDS for the pairs; written out for the column pass by the Gaussian's first wave).
+// backward by rows.  Prologue: dacc_i = gout_i [transform | distance_transform]  [W] (kept in the wave's LDS for the
+// pairs; written out for the column pass by the Gaussian's first wave).  A first walk over the pairs sums D_i (the
+// Gaussian's waves exchange their partials in LDS; written out for the column pass likewise; `acc_in` is not read).
 // Then d queries_i [K] and the row's share of d frequencies [F].
 // LDS row of a pair: [keys_j (K) ; frequency terms (F)].
 template <typename T, bool PER>
@@ -513,22 +518,48 @@ __global__ __launch_bounds__(256) void aggregate_backward_rows_kernel(
     T* DA = (T*)smem_raw + (size_t)ws.wave * region;
     T* X = DA + PART;
     // ---- prologue, per wave (2 components per lane, L MACs each)
-    T Dp = 0;
     for (int c = lane; c < W; c += 64) {
         T v = 0;
         for (int r = 0; r < L; ++r) v += gout[i * L + r] * (c < L ? transform[r * L + c] : dist[r * 2 * E + (c - L)]);
         DA[c] = v;
         if (ws.g == 0 && ws.valid) dacc_out[i * W + c] = v;
-        Dp += v * acc_in[i * W + c];
     }
-    const T D_i = wave_sum(Dp);
-    if (lane == 0 && ws.g == 0 && ws.valid) D_out[i] = D_i;
     wave_lds_fence();
     const T inv_sqrt_k = T(1) / sqrt((T)K);
     const int n = ws.valid ? counts[i] : 0;
     const int32_t* row = lists + i * cap;
     const T* qi = queries + i * K;
     const T lse_i = lse[i];
+    // ---- D_i = sum a da / sum a over the row's pairs (all waves of the Gaussian add the same partials in the same order)
+    double pa = 0, pd = 0;                       // in double: D_i rounded once, so that sum_j ds_ij stays within half an ulp of D_i
+    for (int j0 = ws.g * 64; j0 < n; j0 += 64 * wpg) {
+        const bool have = j0 + lane < n;
+        int64_t j = i;
+        int kim = 0;
+        if (have) decode_entry<PER>(row[j0 + lane], &j, &kim);
+        T dx, dy;
+        const T q = q_of<T, PER>(means, conics, i, j, &dx, &dy, kim, period);
+        const T g = exp_<T>(T(-0.5) * q);
+        T s = 0, dfeat = 0;
+        for_row<T>(keys + j * K, K, [&](int k, T v) { s += qi[k] * v; });
+        for_row<T>(features + j * L, L, [&](int c, T v) { dfeat += DA[c] * v; });
+        T a, ada, da;
+        pair_terms<T>(F, dx, dy, g, s, dfeat, [&](int e) { return DA[L + e]; }, freq, lse_i, T(0), inv_sqrt_k, &a, &ada,
+                      [](int, T) {}, &da);
+        if (have) { pa += (double)a; pd += (double)a * (double)da; }
+    }
+    pa = wave_sum(pa);
+    pd = wave_sum(pd);
+    if (lane == 0) { ((double*)X)[0] = pa; ((double*)X)[1] = pd; }       // X is unused so far; a wave's region starts 8-byte aligned
+    __syncthreads();
+    double sa = 0, sd = 0;
+    for (int w = 0; w < wpg; ++w) {
+        const double* Pw = (const double*)(X + ((ptrdiff_t)w - ws.g) * region);
+        sa += Pw[0]; sd += Pw[1];
+    }
+    const T D_i = (T)(sd / sa);                       // n >= 1: every Gaussian is its own neighbour
+    __syncthreads();                             // the partials are read before a wave parks rows over them
+    if (lane == 0 && ws.g == 0 && ws.valid) D_out[i] = D_i;
     T acc0 = 0, acc1 = 0;                        // components lane, lane + 64 of [d queries (K) ; d frequencies (F)]
     const int WC = K + F;
     for (int j0 = ws.g * 64; j0 < n; j0 += 64 * wpg) {
@@ -864,7 +895,10 @@ __global__ __launch_bounds__(256) void aggregate_heads_forward_kernel(
     }
 }
 
-// backward by rows.  Prologue: dacc_{i,h} and D_{i,h} per head (H PART values of LDS).  The sin / cos values of a pair
+static_assert(4 * HMAX <= PART, "the heads' partial sums of D (2 H doubles) lie at the start of a wave's region of at least PART values");
+
+// backward by rows.  Prologue: dacc_{i,h} per head (H PART values of LDS), then D_{i,h} summed over the pairs as in the
+// one-head kernel (`acc_in` is not read).  The sin / cos values of a pair
 // are computed once and consumed by every head; a pair's frequency share is summed over the heads in phase 1.
 // LDS row of a pair: [keys_j of the H heads (H K) ; frequency terms (F)]; components [d queries (H K) ; d frequencies (F)].
 template <typename T, bool PER>
@@ -890,17 +924,12 @@ __global__ __launch_bounds__(256) void aggregate_heads_backward_rows_kernel(
         const T* gh = gout + (i * H + h) * L;
         const T* tr = transforms + (size_t)h * L * L;
         const T* di = dists + (size_t)h * L * 2 * E;
-        const T* ai = acc_in + (i * H + h) * W;
-        T Dp = 0;
         for (int c = lane; c < W; c += 64) {
             T v = 0;
             for (int r = 0; r < L; ++r) v += gh[r] * (c < L ? tr[r * L + c] : di[r * 2 * E + (c - L)]);
             DA[h * PART + c] = v;
             if (first) dacc_out[(i * H + h) * W + c] = v;
-            Dp += v * ai[c];
         }
-        D[h] = wave_sum(Dp);
-        if (lane == 0 && first) D_out[i * H + h] = D[h];
         lse_i[h] = lse[i * H + h];
     }
     wave_lds_fence();
@@ -908,6 +937,61 @@ __global__ __launch_bounds__(256) void aggregate_heads_backward_rows_kernel(
     const int n = ws.valid ? counts[i] : 0;
     const int32_t* row = lists + i * cap;
     const T* qi = queries + i * HK;
+    // ---- D_{i,h} = sum a da / sum a over the row's pairs, as in the one-head kernel
+    double pa[HMAX], pd[HMAX];
+#pragma unroll
+    for (int h = 0; h < HMAX; ++h) { pa[h] = 0; pd[h] = 0; D[h] = 0; }
+    for (int j0 = ws.g * 64; j0 < n; j0 += 64 * wpg) {
+        const bool have = j0 + lane < n;
+        int64_t j = i;
+        int kim = 0;
+        if (have) decode_entry<PER>(row[j0 + lane], &j, &kim);
+        T dx, dy;
+        const T q = q_of<T, PER>(means, conics, i, j, &dx, &dy, kim, period);
+        const T g = exp_<T>(T(-0.5) * q);
+        const T* kj = keys + j * HK;
+        T a[HMAX], da[HMAX];
+#pragma unroll
+        for (int h = 0; h < HMAX; ++h) { a[h] = 0; da[h] = 0; }
+        PIGS_FOR_HEADS(h) {
+            T s = 0;
+            for_row<T>(kj + h * K, K, [&](int k, T v) { s += qi[h * K + k] * v; });
+            a[h] = exp_<T>(s * inv_sqrt_k - lse_i[h]);
+        }
+        for_row<T>(features + j * L, L, [&](int c, T v) { PIGS_FOR_HEADS(h) da[h] += DA[h * PART + c] * v; });
+        for (int k = 0; k < F; ++k) {
+            T sx, cx, sy, cy;
+            sincos_<T>(freq[k] * dx, &sx, &cx);
+            sincos_<T>(freq[k] * dy, &sy, &cy);
+            PIGS_FOR_HEADS(h) {
+                const T* de = DA + h * PART + L;
+                const T e0 = de[4 * k] + g * de[E + 4 * k], e1 = de[4 * k + 1] + g * de[E + 4 * k + 1];
+                const T e2 = de[4 * k + 2] + g * de[E + 4 * k + 2], e3 = de[4 * k + 3] + g * de[E + 4 * k + 3];
+                da[h] += e0 * sx + e1 * cx + e2 * sy + e3 * cy;
+            }
+        }
+        PIGS_FOR_HEADS(h) {
+            const T* de = DA + h * PART + L;
+            da[h] += de[E - 1] + g * de[2 * E - 1];
+            if (have) { pa[h] += (double)a[h]; pd[h] += (double)a[h] * (double)da[h]; }
+        }
+    }
+    PIGS_FOR_HEADS(h) {
+        pa[h] = wave_sum(pa[h]);
+        pd[h] = wave_sum(pd[h]);
+        if (lane == 0) { ((double*)X)[2 * h] = pa[h]; ((double*)X)[2 * h + 1] = pd[h]; }
+    }
+    __syncthreads();
+    PIGS_FOR_HEADS(h) {
+        double sa = 0, sd = 0;
+        for (int w = 0; w < wpg; ++w) {
+            const double* Pw = (const double*)(X + ((ptrdiff_t)w - ws.g) * region);
+            sa += Pw[2 * h]; sd += Pw[2 * h + 1];
+        }
+        D[h] = (T)(sd / sa);                          // n >= 1: every Gaussian is its own neighbour
+    }
+    __syncthreads();                             // the partials are read before a wave parks rows over them
+    PIGS_FOR_HEADS(h) if (lane == 0 && first) D_out[i * H + h] = D[h];
     T acc0 = 0, acc1 = 0;                        // components lane, lane + 64
     const int c0 = lane, c1 = lane + 64;
     const int hd0 = c0 < HK ? c0 / K : -1, hd1 = c1 < HK ? c1 / K : -1;      // the lane's head; -1: a frequency (scale 1)
