@@ -133,7 +133,8 @@ size_t pigs_plan_workspace_bytes(int64_t N, int64_t M, int c);   /* 0 = unsuppor
  * behind the build (nobody waits); the next build of the same M takes the path the last completed copy
  * recommends (more than 0.55 runs per point: coarse bins).  Captured builds neither ask nor copy.
  * PIGS_SAMPLES_ORDER=ordered|unordered in the environment overrules the memory (tests), as do the
- * PIGS_BUILD_POINTS_* flags of pigs_plan_build.
+ * PIGS_BUILD_POINTS_* flags of pigs_plan_build.  (The rules: csrc/build_choice.h, choose_build and OrderState; the
+ * slot table behind the memory: csrc/build_memory.h.)
  * The same memory decides how pigs_plan_forward / pigs_plan_backward move the outputs / incoming gradients of
  * c = 1, orders (0, 1, 2) or (0, 1, trace) launches: directly through the points' original indices (lattices:
  * runs of consecutive indices), or -- points in no order -- through one 32-byte record per point in the plan
@@ -149,7 +150,8 @@ int pigs_samples_order_hint(int64_t M);
  * front of its list launch (a TRUSTED build: two launches instead of four; never inside a capture).  Results do not
  * depend on it; the list launch checks every tile against the remembered box and the library goes back to looking
  * within 8 builds of points that are no such lattice.  PIGS_LATTICE_TRUST=0 / 1 in the environment, read at every
- * build: never / as soon as a row length and a stable box are remembered.
+ * build: never / as soon as a row length and a stable box are remembered.  (csrc/build_choice.h: `trusted` in
+ * choose_build, OrderState::trusts; tests/test_build_choice.py holds both on a CPU.)
  *   info[0] = 1 when the library's memory of M points on the current device would let the next build be trusted (the
  *             samples' side of the decision; the Gaussians' side is the build's own), else 0
  *   info[1] = trusted builds of this size so far

@@ -67,6 +67,14 @@ constexpr int PLAN_POINTS_PER_CELL = 16;   // target occupancy of a fine sample 
 // stores; same-address atomics serialise at ~10 ns each, so no atomics here) and reduced again by
 // every workgroup of the second.
 constexpr int PLAN_BBOX_BLOCKS = 512;      // partials the samples workspace holds; the first launch has 256 or 512 workgroups
+// Launch shapes the host's choice of launches (build_choice.h) shares with the kernels (plan_build.h, plan_lists.h)
+constexpr uint32_t BBOX_THREADS = 256;      // (1 024-thread workgroups -- 4 096 waves to launch -- cost small point sets ~3 us)
+constexpr uint32_t BBOX_WIDE_POINTS = 1u << 19;    // from here on the first launch has 512 workgroups (no row length expected)
+constexpr uint32_t SCATTER_STAGE_MAX = 2048;       // points of a chunk the coarse-bin scatter's LDS stage holds (32 KB)
+#ifndef PIGS_LISTS_TPW
+#define PIGS_LISTS_TPW 4
+#endif
+constexpr int LISTS_TPW = PIGS_LISTS_TPW;          // tiles per wave of the list launch
 
 // tile list entries: sorted Gaussian index | WIDE group mask << 24 | NARROW group mask << 28.  Two cut-offs
 // live in one plan: the forward evaluates a pair iff the q <= q_f ellipse reaches the point's group box
@@ -455,7 +463,7 @@ struct PlanView {
     // and a streaming launch behind the forward deals the records out to the output arrays (stage_to_outputs_kernel);
     // the backward is preceded by the opposite launch (gradients_to_stage_kernel) and reads one record per point.
     // c = 1, orders (0, 1, 2) or (0, 1, trace); chosen by the library when it remembers the point set's size as
-    // unordered (plan.hip, samples_take_coarse).
+    // unordered (build_choice.h, OrderState::coarse).
     float4* stage;
 };
 

@@ -6,7 +6,8 @@
 //   plan_lists.h     the tile lists: one wave walks the Gaussian grid once for four consecutive 64-point tiles
 //   plan_forward.h   one wave = one tile; what forward and backward share, the forward, the fused list + forward launch
 //   plan_backward.h  the backward over the tile lists, the way back to the caller's order
-// This file: the host half -- workspaces, the library's memory of the last builds, launch policy, entry points.
+// This file: the host half -- workspaces, entry points, and a build in five steps (run_build).  Which launches a build
+// issues is build_choice.h's pure function; the library's memory of the last builds is build_memory.h's table.
 //
 // Build-time knobs (defaults measured on MI355X): PIGS_FWD_WAVES, PIGS_FWD_WG_WAVES,
 // PIGS_FWD_UNROLL, PIGS_GROUP_CAP (plan_forward.h), PIGS_BWD_WAVES, PIGS_BWD_STEP (plan_backward.h),
@@ -19,6 +20,8 @@
 #include "plan_lists.h"
 #include "plan_forward.h"
 #include "plan_backward.h"
+#include "build_choice.h"
+#include "build_memory.h"
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -99,19 +102,11 @@ size_t plan_workspace_bytes(int64_t N, int64_t M, int c) {
     return make_plan_layout(N, M, c).total_bytes;
 }
 
-constexpr int64_t LATTICE_MIN_POINTS = 1 << 12;
 static void fill_samples_args(BuildArgs& a, const SamplesLayout& s, void* sws, const void* samples, bool coarse) {
     char* b = (char*)sws;
     a.sparams = (SampleParams*)(b + s.off_params);
     a.sboxes = (float4*)(b + s.off_boxes);
     a.slat = (float4*)(b + s.off_lat);
-    {   // index-tiled order: from LATTICE_MIN_POINTS points on.  (Until the Gaussians ran one launch ahead -- BuildArgs::ahead
-        // -- the bar stood at 2^18 points: detecting a lattice adds ~2.5 us to the first launch, sorting one costs ~1 us of
-        // the count and scatter launches per 131 072 points.  A lattice that is expected now saves a whole launch: 128^2 ...
-        // 384^2 grids, cold step -4 ... -5 us; BASELINE configs[1] 34.1 -> 31.5 us.)  PIGS_LATTICE=1 / 0: always / never
-        const char* e = getenv("PIGS_LATTICE");
-        a.no_lattice = e ? e[0] == '0' : s.M < LATTICE_MIN_POINTS;
-    }
     a.skey = (uint2*)(b + s.off_skey);
     a.spts = (SPoint*)(b + s.off_spts);
     a.samples = (const float*)samples;
@@ -137,231 +132,148 @@ static void fill_samples_args(BuildArgs& a, const SamplesLayout& s, void* sws, c
     }
 }
 
-// ---- which way a samples build sorts its points (plan.h, SamplesLayout) ----
-// Unordered points want the coarse-bin path, points in runs the one-pass build, and the host cannot look at
-// the points without a synchronisation.  So every build of a large point set leaves {runs, points} of a sample
-// of its waves in the workspace header, the library copies that pair to pinned memory on the build's stream
-// behind the build (no wait), and the NEXT build of a point set of the same size on the same device takes what
-// the last completed copy says: a training loop that draws new random collocation points every step
-// (main_pn.py:103, test_no_mlp.py:86) switches after its first step or two, a lattice never does.  A capture
-// neither asks nor copies (it keeps the mode of the moment).  PIGS_SAMPLES_ORDER = ordered | unordered in the
-// environment, or the PIGS_BUILD_POINTS_* flags, overrule the memory; the result is the same either way
-// (order inside a fine cell aside), only the time differs.
-// Where the two mechanisms start to pay, measured on uniform random points with one Gaussian per 16 points (one box,
-// cold step / forward launches / backward launches, us): 256^2 points: one-pass 49.1 / 18.7 / 19.1, coarse-bin 51.1,
-// staged 23.0 / 22.4; 384^2: 61.1 vs 58.9 cold, staged forward 20.8 vs 14.3; 512^2: 70.8 vs 66.9 cold, staged
-// 32.2 / 45.2 vs 30.4 / 39.5; 1024^2: 162 vs 122 cold, staged 49 / 104 vs 57 / 110.  Below ~100 k points the extra
-// launch of the coarse-bin build costs more than the atomics it saves, and the staging launch more than the
-// scattered sectors up to ~500 k.
-constexpr int64_t COARSE_MIN_POINTS = 1 << 17;
-constexpr int64_t STAGE_MIN_POINTS = 1 << 19;
-struct OrderHint {
-    int device = -1;
-    int64_t M = 0;
-    bool coarse = false, pending = false;
-    uint32_t builds = 0;           // samples builds of this (device, M) so far: the statistic is asked for after the first
-                                   // two and after every 16th (the 8-byte copy is a 4 us blit in the build's stream)
-    hipEvent_t ev = nullptr;
-    uint32_t* host = nullptr;      // pinned: the first 64 bytes of SampleParams (box, grid, order_stat, lat_cand, lat)
-    uint32_t rf = 0;               // the row length of the last completed build when it took the index-tiled order (else 0)
-    float box[4] = {0.f, 0.f, 0.f, 0.f};   // the samples' bounding box of the last completed build
-    bool box_seen = false;         // ... and whether the completed build before it had the same one: a box to build the
-    bool box_stable = false;       //     Gaussians' grid on before this build's own is known (BuildArgs::ahead)
-    uint32_t same = 0;             // completed copies in a row that said the same (row length, box): the copies get rarer
-    // TRUSTED builds (run_build): once the memory has held the same lattice for long enough, a build stops looking
-    uint32_t axis = 0;             // the fast axis that goes with `rf` (SampleParams::lat_cand[1])
-    uint32_t streak = 0;           // verified builds since a completed copy last said anything but (rf, box): builds between
-                                   // two copies are taken on the word of the copies around them
-    uint32_t trusted = 0;          // trusted builds of this (device, M) so far
-    uint32_t broken = 0;           // times the list launch's guard turned this memory around (phint_poll)
-    uint64_t stamp = 0;
+// ---- the settings that steer a build (build_choice.h, BuildEnv): read here and nowhere else ----
+static int samples_order_setting() {      // PIGS_SAMPLES_ORDER
+    const char* e = getenv("PIGS_SAMPLES_ORDER");
+    return !e ? 0 : !strcmp(e, "ordered") ? 1 : !strcmp(e, "unordered") ? 2 : 0;
+}
+static BuildEnv build_env() {
+    static const char* const bbox = getenv("PIGS_BBOX_BLOCKS");      // the two A/B settings: once per process
+    static const bool no_ahead = getenv("PIGS_NO_AHEAD") != nullptr;
+    BuildEnv env;      // the others at every build: the tests flip them inside one process
+    if (const char* e = getenv("PIGS_LATTICE")) env.lattice = e[0] != '0';
+    if (const char* e = getenv("PIGS_LATTICE_TRUST")) env.lattice_trust = e[0] == '0' ? 0 : e[0] == '1' ? 1 : -1;
+    env.samples_order = samples_order_setting();
+    if (const char* e = getenv("PIGS_GAUSS_STRIPS")) env.gauss_strips = e[0] == '1';
+    if (bbox) env.bbox_blocks = atoi(bbox) == 512 ? 512 : 256;
+    env.no_ahead = no_ahead;
+    return env;
+}
+
+// ---- the library's memory of the last builds: the records and their rules in build_choice.h, the table in
+// build_memory.h.  Process-global, per device and size; one mutex for both tables (a plan's copy can turn the samples'
+// record around).
+struct OrderKey {
+    int64_t M;
+    bool operator==(const OrderKey& o) const { return M == o.M; }
 };
-constexpr uint32_t HINT_WORDS = 16;
-// A build is trusted from this many verified builds in a row on: longer than any run of lattice builds after which the
-// suite switches to other points of the same count and wants them noticed by the very next build
-// (tests/test_lattice_gpu.py: 40), short next to a training run.
-constexpr uint32_t TRUST_MIN_BUILDS = 64;
-// PIGS_LATTICE_TRUST, read at every build: 0 = never (A/B: the verified chain), 1 = as soon as the memory holds a row
-// length and a stable box (tests, tools/lattice_trust_worst_case.py); otherwise the memory decides (-1)
-static int trust_mode() {
-    const char* e = getenv("PIGS_LATTICE_TRUST");
-    return !e ? -1 : e[0] == '0' ? 0 : e[0] == '1' ? 1 : -1;
-}
-static bool hint_trusts(const OrderHint& h) {      // g_hint_mu held; the samples' side of the conditions (run_build)
-    const int mode = trust_mode();
-    if (mode == 0 || h.rf == 0u || !h.box_stable) return false;
-    return mode == 1 || (h.same >= 2u && h.streak >= TRUST_MIN_BUILDS);
-}
-static_assert(offsetof(SampleParams, box) == 0 && offsetof(SampleParams, order_stat) == 40 && offsetof(SampleParams, lat) == 56,
-              "the hint copy: the first 64 bytes of SampleParams");
-static std::mutex g_hint_mu;
-static OrderHint g_hints[16];
-static uint64_t g_hint_clock = 0;
-
-static void hint_poll(OrderHint& h);
-static OrderHint* hint_entry(int device, int64_t M, bool create) {      // g_hint_mu held; create: never inside a capture
-    OrderHint* lru = nullptr;
-    for (auto& h : g_hints) {
-        if (h.device == device && h.M == M) { h.stamp = ++g_hint_clock; return &h; }
-        if (!h.pending && (!lru || h.stamp < lru->stamp)) lru = &h;
-    }
-    if (!create) return nullptr;
-    if (!lru) {
-        // every slot waits for a copy (sizes that were built once and never came back): the copies have long
-        // landed -- take note of them and give the least recently used slot away
-        for (auto& h : g_hints) {
-            hint_poll(h);
-            if (!h.pending && (!lru || h.stamp < lru->stamp)) lru = &h;
-        }
-        if (!lru) return nullptr;
-    }
-    if (lru->ev && lru->device != device) {      // an event belongs to the device it was created on
-        (void)hipEventDestroy(lru->ev);
-        lru->ev = nullptr;
-    }
-    if (!lru->ev && hipEventCreateWithFlags(&lru->ev, hipEventDisableTiming) != hipSuccess) { lru->ev = nullptr; (void)hipGetLastError(); return nullptr; }
-    if (!lru->host && hipHostMalloc((void**)&lru->host, HINT_WORDS * sizeof(uint32_t), hipHostMallocPortable) != hipSuccess) { lru->host = nullptr; (void)hipGetLastError(); return nullptr; }
-    lru->device = device; lru->M = M; lru->coarse = false; lru->pending = false; lru->builds = 0; lru->rf = 0; lru->stamp = ++g_hint_clock;
-    lru->box_seen = lru->box_stable = false; lru->same = 0;
-    lru->axis = 0; lru->streak = 0; lru->trusted = 0; lru->broken = 0;
-    return lru;
+struct PointsKey {
+    int64_t N, M;
+    bool operator==(const PointsKey& o) const { return N == o.N && M == o.M; }
+};
+using OrderMemory = BuildMemory<OrderKey, OrderState, ORDER_WORDS>;
+using PointsMemory = BuildMemory<PointsKey, PointsState, POINTS_WORDS>;
+static void order_landed(OrderMemory::Slot& s) { s.st.absorb(s.host); }
+static void points_landed(PointsMemory::Slot& s);
+static std::mutex g_memory_mu;
+static OrderMemory g_order{order_landed};
+static PointsMemory g_points{points_landed};
+static void points_landed(PointsMemory::Slot& s) {
+    // a trusted build met points that are no compact lattice in the remembered order (plan_lists.h, the guard): the
+    // samples' memory of this size turns around
+    if (s.st.absorb(s.host))
+        if (auto* o = g_order.find(s.device, OrderKey{s.key.M})) o->st.turn_around();
 }
 
-static bool stream_capturing(hipStream_t stream) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return st != hipStreamCaptureStatusNone;
-}
-
-static void hint_poll(OrderHint& h) {           // g_hint_mu held
-    if (!h.pending) return;
-    const hipError_t q = hipEventQuery(h.ev);
-    (void)hipGetLastError();          // hipErrorNotReady is an answer, not a failure
-    if (q == hipSuccess) {
-        h.pending = false;
-        const uint32_t rf_before = h.rf;
-        h.rf = h.host[14];         // SampleParams::lat[0]
-        h.axis = h.host[13];       // SampleParams::lat_cand[1]
-        if (h.rf != 0u) h.coarse = false;      // index-tiled: the points arrived in order (and left no run statistic)
-        else if (h.host[11] > 0u) h.coarse = (uint64_t)h.host[10] * 100u > (uint64_t)h.host[11] * 55u;
-        float b[4];
-        memcpy(b, h.host, sizeof(b));
-        const bool finite = fabsf(b[0]) < 3.0e38f && fabsf(b[1]) < 3.0e38f && fabsf(b[2]) < 3.0e38f && fabsf(b[3]) < 3.0e38f && b[2] > b[0] && b[3] > b[1];
-        h.box_stable = finite && h.box_seen && memcmp(b, h.box, sizeof(b)) == 0;
-        h.same = h.box_stable && h.rf == rf_before ? h.same + 1u : 0u;
-        if (h.rf == 0u || h.rf != rf_before || !h.box_stable) h.streak = 0u;
-        h.box_seen = finite;
-        memcpy(h.box, b, sizeof(b));
-    }
-}
-// order: 0 = ask the memory, 1 = one pass, 2 = coarse bins
-static bool samples_take_coarse(const SamplesLayout& s, int order, hipStream_t stream) {
-    if (s.cells_per_bin > SAMPLES_MAX_CELLS_PER_BIN) return false;
-    if (const char* e = getenv("PIGS_SAMPLES_ORDER")) {
-        if (!strcmp(e, "ordered")) order = 1;
-        else if (!strcmp(e, "unordered")) order = 2;
-    }
-    if (order) return order == 2;
-    if (s.M < COARSE_MIN_POINTS) return false;
+// What the memories say to a build.  The samples' is asked by every build that sorts points, the plans' only where
+// its word decides (strips_asked); a capture reads what is there and looks at no copy.
+static MemoryAnswer ask_memories(const BuildRequest& r, const BuildEnv& env, hipStream_t stream) {
+    MemoryAnswer m;
+    const bool points = strips_asked(r, env);
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return false; }
-    std::lock_guard<std::mutex> lock(g_hint_mu);
-    OrderHint* h = hint_entry(dev, s.M, false);
-    if (!h) return false;
-    if (!stream_capturing(stream)) hint_poll(*h);
-    return h->coarse;
-}
-
-// the row length the last completed build of M points found (index-tiled order), or 0
-// *box_ok / box: the same box in the last two completed builds; *axis: the fast axis; *trust: the memory would let a build
-// of this size go without looking at the points (never inside a capture)
-static uint32_t samples_rf_hint(const SamplesLayout& s, hipStream_t stream, bool* box_ok = nullptr, float* box = nullptr,
-                                uint32_t* axis = nullptr, bool* trust = nullptr) {
-    if (box_ok) *box_ok = false;
-    if (trust) *trust = false;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 0u; }
-    std::lock_guard<std::mutex> lock(g_hint_mu);
-    OrderHint* h = hint_entry(dev, s.M, false);
-    if (!h) return 0u;
+    if ((!r.do_samples && !points) || !current_device(&dev)) return m;
     const bool cap = stream_capturing(stream);
-    if (!cap) hint_poll(*h);
-    if (box_ok && box && h->box_stable) { *box_ok = true; memcpy(box, h->box, 4 * sizeof(float)); }
-    if (axis) *axis = h->axis;
-    if (trust) *trust = !cap && hint_trusts(*h);
-    return h->rf;
-}
-static void samples_note_trusted(const SamplesLayout& s) {      // behind a trusted build: nothing to ask for, one more to count
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return; }
-    std::lock_guard<std::mutex> lock(g_hint_mu);
-    if (OrderHint* h = hint_entry(dev, s.M, false)) ++h->trusted;
+    std::lock_guard<std::mutex> lock(g_memory_mu);
+    if (r.do_samples)
+        if (auto* o = g_order.find(dev, OrderKey{r.M})) {
+            if (!cap) g_order.poll(*o);
+            m.coarse = o->st.coarse; m.rf = o->st.rf; m.axis = o->st.axis;
+            if (o->st.box_stable) { m.box_ok = true; memcpy(m.box, o->st.box, sizeof(m.box)); }
+            m.trust = !cap && o->st.trusts(env.lattice_trust);
+        }
+    if (points)
+        if (auto* h = g_points.find(dev, PointsKey{r.N, r.M})) {
+            if (!cap) g_points.poll(*h);
+            m.takes_strips = h->st.takes_strips();
+        }
+    return m;
 }
 
-// behind a samples build: ask for its {runs, points}
-static void samples_note_order(const SamplesLayout& s, void* sws, hipStream_t stream) {
-    if (s.M < 64) return;          // (the same record carries the lattice row length: wanted for every size)
-    if (stream_capturing(stream)) return;
+// behind a samples build: count it and, when one is due, ask for its header's words (a trusted build left none)
+static void note_order(const SamplesLayout& s, const void* sws, hipStream_t stream, bool trusted) {
+    if (!trusted && (s.M < 64 || stream_capturing(stream))) return;
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return; }
-    std::lock_guard<std::mutex> lock(g_hint_mu);
-    OrderHint* h = hint_entry(dev, s.M, true);
+    if (!current_device(&dev)) return;
+    std::lock_guard<std::mutex> lock(g_memory_mu);
+    auto* o = g_order.find(dev, OrderKey{s.M}, !trusted);
+    if (!o) return;
+    if (trusted) { ++o->st.trusted; return; }
+    const uint32_t nth = o->st.builds++;
+    if (o->st.rf != 0u) ++o->st.streak;
+    if (!o->pending && o->st.copy_due(nth)) g_order.request(*o, (const char*)sws + s.off_params, stream);
+}
+// behind a list build.  trusted: its guard's word is wanted home soon
+static void note_points(const PlanLayout& p, const void* ws, hipStream_t stream, bool trusted = false) {
+    int dev = 0;
+    if (stream_capturing(stream) || !current_device(&dev)) return;
+    std::lock_guard<std::mutex> lock(g_memory_mu);
+    auto* h = g_points.find(dev, PointsKey{p.N, p.M}, true);
     if (!h) return;
-    const uint32_t nth = h->builds++;
-    if (h->rf != 0u) ++h->streak;
-    // (with a row length in the memory the build runs on expectations -- an eighth of the count's workgroups, the
-    // Gaussians one launch ahead -- and a point set that stopped meeting them should not be met 15 more times: every 8th
-    // build then; the copy is a ~4 us blit in the build's stream)
-    // ... every 32nd once three copies in a row have said the same)
-    if (h->pending || (nth >= 2u && (nth & (h->rf ? (h->same >= 2u ? 31u : 7u) : 15u)) != 0u)) return;
-    const SampleParams* sp = (const SampleParams*)((const char*)sws + s.off_params);
-    if (hipMemcpyAsync(h->host, sp, HINT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess &&
-        hipEventRecord(h->ev, stream) == hipSuccess)
-        h->pending = true;
-    (void)hipGetLastError();
+    const uint32_t nth = h->st.builds++;
+    if (!h->pending && h->st.copy_due(nth, trusted))
+        g_points.request(*h, &((const PlanParams*)((const char*)ws + p.off_params))->n_points, stream);
 }
 
 // The sampling launches' question (staging, PlanView::stage): did the point set of this size arrive in no order?
 // A pending statistic is looked at here too -- a point set that is built once and sampled many times (fixed random
-// collocation points) never comes back to samples_take_coarse -- unless the stream is being captured.
+// collocation points) never comes back to a build -- unless the stream is being captured.
 static bool points_unordered(int64_t M, hipStream_t stream) {
     if (const char* e = getenv("PIGS_STAGE")) return e[0] == '1';          // tests / A-B runs: staging on or off whatever the memory and the size
     if (M < STAGE_MIN_POINTS) return false;
-    if (const char* e = getenv("PIGS_SAMPLES_ORDER")) return !strcmp(e, "unordered");
+    if (getenv("PIGS_SAMPLES_ORDER")) return samples_order_setting() == 2;
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (!current_device(&dev)) return false;
     const bool cap = stream_capturing(stream);
-    std::lock_guard<std::mutex> lock(g_hint_mu);
-    for (auto& h : g_hints)
-        if (h.device == dev && h.M == M) {
-            if (!cap) hint_poll(h);
-            return h.coarse;
-        }
-    return false;
+    std::lock_guard<std::mutex> lock(g_memory_mu);
+    auto* o = g_order.peek(dev, OrderKey{M});
+    if (!o) return false;
+    if (!cap) g_order.poll(*o);
+    return o->st.coarse;
+}
+// a first forward takes the fused launch unless the last completed copy for its sizes showed TILE_MODE_POINTS tiles
+static bool plan_expects_points(int64_t N, int64_t M, hipStream_t stream) {
+    int dev = 0;
+    if (!current_device(&dev)) return false;
+    const bool cap = stream_capturing(stream);
+    std::lock_guard<std::mutex> lock(g_memory_mu);
+    auto* h = g_points.find(dev, PointsKey{N, M});
+    if (!h) return false;
+    if (!cap) g_points.poll(*h);
+    return h->st.has_points;
 }
 
 int samples_order_hint(int64_t M) {
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return -1; }
-    std::lock_guard<std::mutex> lock(g_hint_mu);
-    OrderHint* h = hint_entry(dev, M, false);
-    if (!h) return -1;
-    hint_poll(*h);
-    return h->coarse ? 1 : 0;
+    if (!current_device(&dev)) return -1;
+    std::lock_guard<std::mutex> lock(g_memory_mu);
+    auto* o = g_order.find(dev, OrderKey{M});
+    if (!o) return -1;
+    g_order.poll(*o);
+    return o->st.coarse ? 1 : 0;
 }
 
-static void phint_poll_size(int device, int64_t M);
 int samples_trust_info(int64_t M, int64_t* info) {
     info[0] = info[1] = info[2] = info[3] = 0;
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return PIGS_OK; }
-    std::lock_guard<std::mutex> lock(g_hint_mu);
-    phint_poll_size(dev, M);           // (the guard's word comes home with the plans' copies)
-    OrderHint* h = hint_entry(dev, M, false);
-    if (!h) return PIGS_OK;
-    hint_poll(*h);
-    info[0] = hint_trusts(*h) ? 1 : 0;
-    info[1] = h->trusted; info[2] = h->broken; info[3] = h->streak;
+    if (!current_device(&dev)) return PIGS_OK;
+    std::lock_guard<std::mutex> lock(g_memory_mu);
+    for (auto& h : g_points.slots)      // (the guard's word comes home with the copies of every plan size with M points)
+        if (h.device == dev && h.key.M == M) g_points.poll(h);
+    auto* o = g_order.find(dev, OrderKey{M});
+    if (!o) return PIGS_OK;
+    g_order.poll(*o);
+    info[0] = o->st.trusts(build_env().lattice_trust) ? 1 : 0;
+    info[1] = o->st.trusted; info[2] = o->st.broken; info[3] = o->st.streak;
     return PIGS_OK;
 }
 
@@ -410,132 +322,6 @@ static bool defer_take(const void* ws, DeferredLists& d) {
     g_deferred.erase(it);
     return true;
 }
-// ---- does a plan of these sizes hold tiles in TILE_MODE_POINTS? ----
-// The fused first forward walks such tiles in their own list wave (right, and slow when there are hundreds: the
-// thin outskirts of a clustered cloud), the two-launch path spreads them over helper workgroups.  Which one a plan
-// wants is known on the device only, so -- like the order of the points (OrderHint above) -- the library remembers,
-// per device and (N, M): behind the list build of the first two plans of a size and of every 16th, PlanParams::
-// n_points is copied to pinned memory on the build's stream (nobody waits); a first forward takes the fused launch
-// unless the last completed copy for its sizes showed such tiles.  Never inside a capture.
-constexpr float STRIP_MAX_COVER = 64.f;      // (plan_takes_strips below)
-struct PointsHint {
-    int device = -1;
-    int64_t N = 0, M = 0;
-    bool has_points = false, pending = false;
-    float cover = -1.f;            // PlanParams::strip_cover of the last completed build (< 0: none yet)
-    bool strips = false;           // ... and whether that build kept the caller's order
-    uint32_t same = 0;             // completed copies in a row that led to the same choice: the copies get rarer
-    uint32_t builds = 0;
-    hipEvent_t ev = nullptr;
-    uint32_t* host = nullptr;      // pinned {n_points, strip_cover, strips, points_wanted, lattice_broken}
-    uint64_t stamp = 0;
-};
-constexpr uint32_t PHINT_WORDS = 5;
-static_assert(offsetof(PlanParams, strip_cover) == offsetof(PlanParams, n_points) + 4 && offsetof(PlanParams, strips) == offsetof(PlanParams, n_points) + 8 &&
-              offsetof(PlanParams, points_wanted) == offsetof(PlanParams, n_points) + 12 && offsetof(PlanParams, lattice_broken) == offsetof(PlanParams, n_points) + 16,
-              "one copy: n_points, strip_cover, strips, points_wanted, lattice_broken");
-static PointsHint g_phints[16];
-static void phint_poll(PointsHint& h) {          // g_hint_mu held
-    if (!h.pending) return;
-    const hipError_t q = hipEventQuery(h.ev);
-    (void)hipGetLastError();
-    if (q == hipSuccess) {
-        h.pending = false;
-        const bool took_before = h.cover >= 0.f && h.cover <= STRIP_MAX_COVER && !h.has_points;
-        h.has_points = h.host[0] != 0u || h.host[3] != 0u;
-        memcpy(&h.cover, &h.host[1], sizeof(float));
-        if (!(h.cover >= 0.f)) h.cover = 3.0e38f;      // NaN: as bad as it gets
-        h.strips = h.host[2] != 0u;
-        h.same = (h.cover <= STRIP_MAX_COVER && !h.has_points) == took_before ? h.same + 1u : 0u;
-        if (h.host[4] != 0u) {
-            // a trusted build met points that are no compact lattice in the remembered order (plan_lists.h, the guard): the
-            // samples' memory of this size turns around -- the next build searches, verifies and, if need be, sorts, as
-            // a first build does
-            if (OrderHint* o = hint_entry(h.device, h.M, false)) {
-                o->rf = 0u; o->same = 0u; o->box_stable = false; o->streak = 0u;
-                ++o->broken;
-            }
-        }
-    }
-}
-static void phint_poll_size(int device, int64_t M) {      // g_hint_mu held: every plan size with M points
-    for (auto& h : g_phints)
-        if (h.device == device && h.M == M) phint_poll(h);
-}
-static PointsHint* phint_entry(int device, int64_t N, int64_t M, bool create) {      // g_hint_mu held
-    PointsHint* lru = nullptr;
-    for (auto& h : g_phints) {
-        if (h.device == device && h.N == N && h.M == M) { h.stamp = ++g_hint_clock; return &h; }
-        if (!h.pending && (!lru || h.stamp < lru->stamp)) lru = &h;
-    }
-    if (!create) return nullptr;
-    if (!lru) {
-        for (auto& h : g_phints) {
-            phint_poll(h);
-            if (!h.pending && (!lru || h.stamp < lru->stamp)) lru = &h;
-        }
-        if (!lru) return nullptr;
-    }
-    if (lru->ev && lru->device != device) { (void)hipEventDestroy(lru->ev); lru->ev = nullptr; }
-    if (!lru->ev && hipEventCreateWithFlags(&lru->ev, hipEventDisableTiming) != hipSuccess) { lru->ev = nullptr; (void)hipGetLastError(); return nullptr; }
-    if (!lru->host && hipHostMalloc((void**)&lru->host, PHINT_WORDS * sizeof(uint32_t), hipHostMallocPortable) != hipSuccess) { lru->host = nullptr; (void)hipGetLastError(); return nullptr; }
-    lru->device = device; lru->N = N; lru->M = M; lru->has_points = false; lru->pending = false; lru->builds = 0; lru->stamp = ++g_hint_clock;
-    lru->cover = -1.f; lru->strips = false; lru->same = 0;
-    return lru;
-}
-static bool plan_expects_points(int64_t N, int64_t M, hipStream_t stream) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return false; }
-    const bool cap = stream_capturing(stream);
-    std::lock_guard<std::mutex> lock(g_hint_mu);
-    PointsHint* h = phint_entry(dev, N, M, false);
-    if (!h) return false;
-    if (!cap) phint_poll(*h);
-    return h->has_points;
-}
-// Does the next build of these sizes keep the caller's order (PlanParams::strips)?  Yes when the last completed build's
-// strips covered the samples' domain at most STRIP_MAX_COVER times -- that number is about how many strips a block of
-// tiles meets (a lattice in row order, a strip of 1 x 16 widened by its ellipses' reach on every side: ~10 times at
-// kappa = 0.5, ~17 at 0.8, ~33 at 1.3; Gaussians in no order: every strip covers the domain, N / 16 times).
-// PIGS_GAUSS_STRIPS=0 / 1: never / always.
-constexpr int64_t STRIP_MIN_GAUSSIANS = 1024;      // (below, the chain it replaces is not what a step waits for)
-static bool plan_takes_strips(int64_t N, int64_t M, hipStream_t stream) {
-    if (const char* e = getenv("PIGS_GAUSS_STRIPS")) return e[0] == '1';
-    // (a build that also sorts or looks at the samples saves no launch by it -- the Gaussians' count, scan and scatter ride
-    // along in launches that exist anyway -- but the lists from strips are the faster ones since the survivors wait for a
-    // full buffer: 20.0 against 21.3 us at C3, 55 against 60 at kappa 1.3, and the scan / scatter launches carry less)
-    if (N < STRIP_MIN_GAUSSIANS) return false;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return false; }
-    const bool cap = stream_capturing(stream);
-    std::lock_guard<std::mutex> lock(g_hint_mu);
-    PointsHint* h = phint_entry(dev, N, M, false);
-    if (!h) return false;
-    if (!cap) phint_poll(*h);
-    // (tiles of far-apart points -- a cloud's thin outskirts -- are walked point by point through the GRID at sampling
-    // time, TILE_MODE_POINTS: a plan that had such tiles keeps the cells.  Measured without this line: clamped normals
-    // sigma = 0.15 over lattice Gaussians, warm step 111 -> 1 126 us.)
-    return h->cover >= 0.f && h->cover <= STRIP_MAX_COVER && !h->has_points;
-}
-// trusted: the build took the samples' lattice on trust (run_build) -- its guard's word is wanted home soon
-static void plan_note_points(const PlanLayout& p, const void* ws, hipStream_t stream, bool trusted = false) {      // behind a list build
-    if (stream_capturing(stream)) return;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return; }
-    std::lock_guard<std::mutex> lock(g_hint_mu);
-    PointsHint* h = phint_entry(dev, p.N, p.M, true);
-    if (!h) return;
-    const uint32_t nth = h->builds++;
-    // (builds that keep the caller's order run on an expectation -- strips that cover the domain a few times over -- and
-    // Gaussians that stopped meeting it should not be met 15 more times)
-    // ... and points that stopped being the lattice a trusted build takes them for not 31 more times either: every 8th)
-    if (h->pending || (nth >= 2u && (nth & (trusted ? 7u : h->strips ? (h->same >= 2u ? 31u : 7u) : 15u)) != 0u)) return;
-    const PlanParams* pp = (const PlanParams*)((const char*)ws + p.off_params);
-    if (hipMemcpyAsync(h->host, &pp->n_points, PHINT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess &&
-        hipEventRecord(h->ev, stream) == hipSuccess)
-        h->pending = true;
-    (void)hipGetLastError();
-}
 
 static ListArgs make_list_args(const PlanLayout& p, const SamplesLayout& s, void* ws, const void* sws, float q_f, float q_wide) {
     ListArgs la{};
@@ -552,141 +338,88 @@ static ListArgs make_list_args(const PlanLayout& p, const SamplesLayout& s, void
     la.strip_cover = &((PlanParams*)((char*)ws + p.off_params))->strip_cover;
     return la;
 }
-// Small point sets (a list launch of fewer tiles than this is one sparse generation of waves): one tile per wave.
-constexpr uint32_t LISTS_SMALL_TILES = 4096;
-// fwd_only: PIGS_BUILD_FORWARD_ONLY (build_block_lists<..., FWD_ONLY>)
-static void launch_lists(uint32_t ntiles, const ListArgs& la, hipStream_t stream, bool strips = false, bool fwd_only = false) {
-    const bool small = ntiles <= LISTS_SMALL_TILES && LISTS_TPW != 1;
-    const dim3 grid(small ? (ntiles + 3) / 4 : (ntiles + 4 * LISTS_TPW - 1) / (4 * LISTS_TPW));
+// the list launch (build_choice.h, list_launch); fwd_only: PIGS_BUILD_FORWARD_ONLY (build_block_lists<..., FWD_ONLY>)
+static void launch_lists(const BuildLaunch& l, const ListArgs& la, hipStream_t stream, bool strips = false, bool fwd_only = false) {
+    const bool small = l.kernel == K_LISTS_SMALL;
+    const dim3 grid(l.grid), block(l.block);
     if (fwd_only) {
-        if (small && strips) hipLaunchKernelGGL((plan_lists_kernel<1, true, true>), grid, dim3(256), 0, stream, la);
-        else if (small) hipLaunchKernelGGL((plan_lists_kernel<1, false, true>), grid, dim3(256), 0, stream, la);
-        else if (strips) hipLaunchKernelGGL((plan_lists_kernel<LISTS_TPW, true, true>), grid, dim3(256), 0, stream, la);
-        else hipLaunchKernelGGL((plan_lists_kernel<LISTS_TPW, false, true>), grid, dim3(256), 0, stream, la);
+        if (small && strips) hipLaunchKernelGGL((plan_lists_kernel<1, true, true>), grid, block, 0, stream, la);
+        else if (small) hipLaunchKernelGGL((plan_lists_kernel<1, false, true>), grid, block, 0, stream, la);
+        else if (strips) hipLaunchKernelGGL((plan_lists_kernel<LISTS_TPW, true, true>), grid, block, 0, stream, la);
+        else hipLaunchKernelGGL((plan_lists_kernel<LISTS_TPW, false, true>), grid, block, 0, stream, la);
         return;
     }
-    if (small && strips) hipLaunchKernelGGL((plan_lists_kernel<1, true>), grid, dim3(256), 0, stream, la);
-    else if (small) hipLaunchKernelGGL((plan_lists_kernel<1, false>), grid, dim3(256), 0, stream, la);
-    else if (strips) hipLaunchKernelGGL((plan_lists_kernel<LISTS_TPW, true>), grid, dim3(256), 0, stream, la);
-    else hipLaunchKernelGGL((plan_lists_kernel<LISTS_TPW, false>), grid, dim3(256), 0, stream, la);
+    if (small && strips) hipLaunchKernelGGL((plan_lists_kernel<1, true>), grid, block, 0, stream, la);
+    else if (small) hipLaunchKernelGGL((plan_lists_kernel<1, false>), grid, block, 0, stream, la);
+    else if (strips) hipLaunchKernelGGL((plan_lists_kernel<LISTS_TPW, true>), grid, block, 0, stream, la);
+    else hipLaunchKernelGGL((plan_lists_kernel<LISTS_TPW, false>), grid, block, 0, stream, la);
 }
 
-// The chain bbox -> count -> scan -> scatter for the samples (build_samples), the Gaussians
-// (build_plan) or both in the same four launches, then the tile lists.
-static int run_build(bool do_samples, bool do_plan, bool plan_ws_clean, bool no_lookback, void* sws, size_t sws_bytes, void* ws, size_t ws_bytes, int64_t N,
-                     int64_t M, int c, float q_max, float q_max_b, const void* means, const void* conics, const void* values,
-                     const void* samples, hipStream_t stream, bool build_lists = true, int order = 0, bool defer_lists = false,
-                     bool fwd_only = false) {
-    if (!samples_supported(M)) return PIGS_ERR_UNSUPPORTED;
-    const SamplesLayout s = make_samples_layout(M);
+// The chain bbox -> count -> scan -> scatter for the samples (build_samples), the Gaussians (build_plan) or both in
+// the same launches, then the tile lists.  Which launches: build_choice.h.
+static int run_build(const BuildRequest& r, void* sws, size_t sws_bytes, void* ws, size_t ws_bytes, const void* means,
+                     const void* conics, const void* values, const void* samples, hipStream_t stream) {
+    // 1. what cannot be built
+    if (!samples_supported(r.M)) return PIGS_ERR_UNSUPPORTED;
+    const SamplesLayout s = make_samples_layout(r.M);
     if (!sws || sws_bytes < s.total_bytes) return PIGS_ERR_WORKSPACE;
-    BuildArgs a{};
-    a.do_samples = do_samples; a.do_plan = do_plan; a.no_lookback = no_lookback;
-    a.zero_gacc = !plan_ws_clean;
-    const bool coarse = do_samples && samples_take_coarse(s, order, stream);
-    fill_samples_args(a, s, sws, samples, coarse);
-    bool box_ok = false, trust = false;
-    a.rf_hint = do_samples ? samples_rf_hint(s, stream, &box_ok, a.hint_box, &a.hint_axis, &trust) : 0u;
-    {
-        static const char* e = getenv("PIGS_BBOX_BLOCKS");      // (A/B: 256 | 512)
-        // same box, 1024^2 points: the plain pass 6.6 -> 5.9 us with 512 workgroups, the pass with a row length 7.5 -> 7.8
-        a.bbox_blocks = e ? (uint32_t)atoi(e) : (M >= (int64_t)BBOX_WIDE_POINTS && a.rf_hint == 0u ? 512u : 256u);
-        if (a.bbox_blocks != 512u) a.bbox_blocks = 256u;
-    }
     PlanLayout p{};
-    if (do_plan) {
-        if (!plan_supported(N, M, c)) return PIGS_ERR_UNSUPPORTED;
-        if (!(q_max > 0.f)) return PIGS_ERR_INVALID;
-        if (!(q_max_b >= q_max)) q_max_b = q_max;      // <= 0 / NaN: one cut-off
-        // a plan for the forward alone is sized with the forward's cut-off throughout (boxes, levels, strips, the walk)
-        fwd_only = fwd_only && build_lists && !defer_lists;
-        if (fwd_only) q_max_b = q_max;
-        p = make_plan_layout(N, M, c);
+    if (r.do_plan) {
+        if (!plan_supported(r.N, r.M, r.c)) return PIGS_ERR_UNSUPPORTED;
+        if (!(r.q_max > 0.f)) return PIGS_ERR_INVALID;
+        p = make_plan_layout(r.N, r.M, r.c);
         if (!ws || ws_bytes < p.total_bytes) return PIGS_ERR_WORKSPACE;
-        fill_plan_args(a, p, ws, q_max, q_max_b, means, conics, values);
-        a.fwd_only = fwd_only;
     }
-    clear_hip_error();
-    const uint32_t gb = do_plan ? (uint32_t)((N + 255) / 256) : 0u;
-    // The Gaussians one launch ahead (BuildArgs::ahead): a lattice is expected, the samples' box was the same in the last
-    // two completed builds of this size, the plan workspace's counters are zero.
-    static const bool no_ahead = getenv("PIGS_NO_AHEAD") != nullptr;
-    const bool ahead = do_samples && do_plan && plan_ws_clean && !coarse && !no_lookback && !no_ahead &&
-                       a.rf_hint != 0u && !a.no_lattice && box_ok && s.scan_blocks <= 1024u;
-    a.ahead = ahead; a.s_scan_in_scatter = ahead;
-    // Gaussians whose order in the caller's array is already spatial keep it (PlanParams::strips): one pass instead of
-    // count, scan and scatter
-    const bool strips = do_plan && build_lists && !defer_lists && !no_lookback &&
-                        plan_takes_strips(N, M, stream);
-    a.strips = strips;
-    // TRUSTED: point sets of this size have been the same compact lattice for TRUST_MIN_BUILDS verified builds and three
-    // copies in a row -- this build does not look again.  It launches what a build on a finished samples workspace
-    // launches, the Gaussians' pack and the lists; the pack's first workgroup writes the samples header the decision
-    // would have written, the list launch reads the points through it and holds every tile's real box against the
-    // remembered one (ListArgs::lattice_broken), and that word rides home with the plan's statistics every 8th build
-    // (phint_poll turns the memory around).  Results never depend on it: the lists come from the groups' real boxes.
-    const bool trusted = ahead && strips && trust && order == 0 && a.rf_hint >= 8u && (a.rf_hint & 7u) == 0u && M >= 64 && M % a.rf_hint == 0 &&
-                         ((M / a.rf_hint) & 7) == 0;
-    if (trusted) {
-        a.trusted = 1; a.ahead = 0; a.s_scan_in_scatter = 0;
-        hipLaunchKernelGGL(plan_count_kernel, dim3(gb), dim3(256), 0, stream, a);
-    } else if (ahead && strips) {
-        // nothing of the Gaussians is left for launches 2 and 3: the samples' fall-back moves into launch 2 whole
-        // (samples_sort_in_count; at most 256 workgroups: they meet at device-wide barriers) -- FOUR launches up to the forward
-        a.sort_in_count = 1; a.s_scan_in_scatter = 0;
-        a.s_blocks = (uint32_t)((M + 1023) / 1024);
-        const uint32_t swgs = (a.s_blocks + 7u) / 8u < 256u ? (a.s_blocks + 7u) / 8u : 256u;
-        hipLaunchKernelGGL(samples_bbox_kernel, dim3(a.bbox_blocks + gb), dim3(BBOX_THREADS), 0, stream, a);
-        hipLaunchKernelGGL(plan_count_kernel, dim3(swgs), dim3(256), 0, stream, a);
-    } else if (ahead) {
-        a.s_blocks = (uint32_t)((M + 1023) / 1024);
-        hipLaunchKernelGGL(samples_bbox_kernel, dim3(a.bbox_blocks + gb), dim3(BBOX_THREADS), 0, stream, a);
-        hipLaunchKernelGGL(plan_count_kernel, dim3(p.scan_blocks + (a.s_blocks + 7u) / 8u), dim3(256), 0, stream, a);
-        hipLaunchKernelGGL(plan_scatter_kernel, dim3(gb + (uint32_t)((M + 255) / 256)), dim3(256), 0, stream, a);
-    } else
-    if (do_samples) hipLaunchKernelGGL(samples_bbox_kernel, dim3(a.bbox_blocks), dim3(BBOX_THREADS), 0, stream, a);
-    else if (!plan_ws_clean) hipLaunchKernelGGL(plan_zero_kernel, dim3(64), dim3(256), 0, stream, a);
-    if (ahead) {
-        // (launched above)
-    } else {
-        // a lattice expected (the row length of the last build of this size): an eighth of the one-pass count's workgroups
-        // -- they leave at once when the points are index-tiled, and stride over the blocks when they are not
-        a.s_blocks = (uint32_t)((M + 1023) / 1024);
-        const uint32_t count_wgs = coarse ? s.h_wgs : (a.rf_hint && !a.no_lattice ? (a.s_blocks + 7u) / 8u : a.s_blocks);
-        hipLaunchKernelGGL(plan_count_kernel, dim3(gb + (do_samples ? count_wgs : 0u)), dim3(256), 0, stream, a);
-        const uint32_t scan_wgs = (do_plan && !strips ? p.scan_blocks : 0u) + (do_samples ? a.s_scan_blocks : 0u);
-        if (scan_wgs) hipLaunchKernelGGL(plan_scan_kernel, dim3(scan_wgs), dim3(256), 0, stream, a);
-        const bool staged = coarse && s.h_chunk <= SCATTER_STAGE_MAX;
-        const uint32_t scatter_wgs = (strips ? 0u : gb) + (do_samples ? (staged ? s.h_wgs : (uint32_t)((M + 255) / 256)) : 0u);
-        if (scatter_wgs)
-            hipLaunchKernelGGL(plan_scatter_kernel, dim3(scatter_wgs), dim3(256),
-                               staged ? s.h_chunk * sizeof(uint4) + 2 * SAMPLES_COARSE_BINS * sizeof(uint32_t) : 0, stream, a);
-        if (coarse) {
-            if (s.cells_per_bin * 16u <= SAMPLES_MAX_CELLS_PER_BIN)      // the LDS holds 16 sub-cell counters per cell
-                hipLaunchKernelGGL(samples_binsort_kernel<16>, dim3(SAMPLES_COARSE_BINS), dim3(1024),
-                                   s.cells_per_bin * 16u * sizeof(uint32_t), stream, a);
-            else
-                hipLaunchKernelGGL(samples_binsort_kernel<1>, dim3(SAMPLES_COARSE_BINS), dim3(1024),
-                                   s.cells_per_bin * sizeof(uint32_t), stream, a);
-        }
-    }
-    if (do_plan && build_lists && !defer_lists) {
-        ListArgs la = make_list_args(p, s, ws, sws, q_max, a.q_max);
-        if (trusted) {
+    // 2. what the memories say, 3. which launches
+    const BuildEnv env = build_env();
+    const MemoryAnswer mem = ask_memories(r, env, stream);
+    const BuildChoice b = choose_build(r, s, p, env, mem);
+    // 4. the kernels' arguments
+    BuildArgs a{};
+    a.do_samples = r.do_samples; a.do_plan = r.do_plan; a.no_lookback = r.no_lookback;
+    a.zero_gacc = !r.plan_ws_clean;
+    fill_samples_args(a, s, sws, samples, b.coarse);
+    if (r.do_plan) fill_plan_args(a, p, ws, r.q_max, b.q_max_b, means, conics, values);
+    a.no_lattice = b.no_lattice; a.rf_hint = b.rf_hint; a.bbox_blocks = b.bbox_blocks; a.s_blocks = b.s_blocks;
+    a.hint_axis = mem.axis;
+    memcpy(a.hint_box, mem.box, sizeof(a.hint_box));
+    a.fwd_only = b.fwd_only; a.ahead = b.ahead; a.s_scan_in_scatter = b.s_scan_in_scatter; a.sort_in_count = b.sort_in_count;
+    a.strips = b.strips; a.trusted = b.trusted;
+    const bool lists = r.do_plan && r.build_lists && !r.defer_lists;
+    ListArgs la{};
+    if (lists) {
+        la = make_list_args(p, s, ws, sws, r.q_max, a.q_max);
+        if (b.trusted) {      // the guard (plan_lists.h): every tile's real box against its share of the remembered one
             la.lattice_broken = &a.params->lattice_broken;
-            const float rf = (float)a.rf_hint, rs = (float)(M / a.rf_hint);
+            const float rf = (float)a.rf_hint, rs = (float)(r.M / a.rf_hint);
             la.guard_n[0] = a.hint_axis ? rs : rf; la.guard_n[1] = a.hint_axis ? rf : rs;      // points along x / along y
             la.guard_e[0] = 16.f * (a.hint_box[2] - a.hint_box[0]) * 1.001f;
             la.guard_e[1] = 16.f * (a.hint_box[3] - a.hint_box[1]) * 1.001f;
         }
-        launch_lists(s.ntiles, la, stream, strips, fwd_only);
+    }
+    // 5. the launches, then a note for the next build of these sizes
+    clear_hip_error();
+    for (int i = 0; i < b.n; ++i) {
+        const BuildLaunch& l = b.launches[i];
+        const dim3 grid(l.grid), block(l.block);
+        switch (l.kernel) {
+            case K_SAMPLES_BBOX: hipLaunchKernelGGL(samples_bbox_kernel, grid, block, l.lds, stream, a); break;
+            case K_PLAN_ZERO: hipLaunchKernelGGL(plan_zero_kernel, grid, block, l.lds, stream, a); break;
+            case K_PLAN_COUNT: hipLaunchKernelGGL(plan_count_kernel, grid, block, l.lds, stream, a); break;
+            case K_PLAN_SCAN: hipLaunchKernelGGL(plan_scan_kernel, grid, block, l.lds, stream, a); break;
+            case K_PLAN_SCATTER: hipLaunchKernelGGL(plan_scatter_kernel, grid, block, l.lds, stream, a); break;
+            case K_BINSORT_16: hipLaunchKernelGGL(samples_binsort_kernel<16>, grid, block, l.lds, stream, a); break;
+            case K_BINSORT_1: hipLaunchKernelGGL(samples_binsort_kernel<1>, grid, block, l.lds, stream, a); break;
+            case K_LISTS_SMALL:
+            case K_LISTS: launch_lists(l, la, stream, b.strips, b.fwd_only); break;
+        }
     }
     const int rc = launch_status();
-    if (do_plan) defer_set(ws, build_lists && defer_lists && rc == PIGS_OK, q_max, a.q_max);
-    if (do_plan && build_lists && !defer_lists && rc == PIGS_OK) plan_note_points(p, ws, stream, trusted);
-    if (trusted) {      // (the samples header holds only what this build put there: nothing to ask for)
-        if (rc == PIGS_OK) samples_note_trusted(s);
-    } else if (do_samples && rc == PIGS_OK && order == 0) samples_note_order(s, sws, stream);
+    if (r.do_plan) defer_set(ws, r.build_lists && r.defer_lists && rc == PIGS_OK, r.q_max, a.q_max);
+    if (rc != PIGS_OK) return rc;
+    if (lists) note_points(p, ws, stream, b.trusted);
+    // (the samples header of a trusted build holds only what the build put there: nothing to ask for, one more to count)
+    if (b.trusted || (r.do_samples && r.order == 0)) note_order(s, sws, stream, b.trusted);
     return rc;
 }
 
@@ -703,9 +436,11 @@ int aggregate_grid_build(void* ws, size_t ws_bytes, int64_t N, float q_grid, con
     if (!plan_supported(N, N, 1)) return PIGS_ERR_UNSUPPORTED;
     if (!ws || ws_bytes < aggregate_grid_bytes(N)) return PIGS_ERR_WORKSPACE;
     const size_t sb = align_up(make_samples_layout(N).total_bytes, 256);
+    BuildRequest r;
+    r.do_samples = r.do_plan = true; r.build_lists = false;
+    r.N = r.M = N; r.c = 1; r.q_max = r.q_max_b = q_grid;
     // values: any N readable floats (the records' value slot is never read by the neighbour lists)
-    return run_build(true, true, false, false, ws, sb, (char*)ws + sb, ws_bytes - sb, N, N, 1, q_grid, q_grid, means, conics,
-                     means, means, stream, false);
+    return run_build(r, ws, sb, (char*)ws + sb, ws_bytes - sb, means, conics, means, means, stream);
 }
 
 // info[0] = byte offset of PlanParams::level_mask inside the grid workspace, info[1] = levels of the grid
@@ -721,15 +456,24 @@ PlanView aggregate_grid_view(void* ws, int64_t N, float q_grid) {
 }
 
 int samples_build(void* sws, size_t sws_bytes, int64_t M, const void* samples, hipStream_t stream) {
-    return run_build(true, false, false, false, sws, sws_bytes, nullptr, 0, 0, M, 1, 1.f, 1.f, nullptr, nullptr, nullptr, samples, stream);
+    BuildRequest r;
+    r.do_samples = true; r.M = M;
+    return run_build(r, sws, sws_bytes, nullptr, 0, nullptr, nullptr, nullptr, samples, stream);
 }
 
 int plan_build(void* ws, size_t ws_bytes, void* sws, size_t sws_bytes, int flags, int64_t N, int64_t M, int c,
                float q_max, float q_max_backward, const void* means, const void* conics, const void* values, const void* samples,
                hipStream_t stream) {
-    return run_build((flags & 1) != 0, true, (flags & 2) != 0, (flags & 4) != 0, sws, sws_bytes, ws, ws_bytes, N, M, c, q_max, q_max_backward, means, conics, values,
-                     samples, stream, true, (flags & 8) ? 1 : (flags & 16) ? 2 : 0, (flags & PIGS_BUILD_DEFER_LISTS) != 0,
-                     (flags & PIGS_BUILD_FORWARD_ONLY) != 0);
+    BuildRequest r;
+    r.do_plan = true;
+    r.do_samples = (flags & PIGS_BUILD_SAMPLES) != 0;
+    r.plan_ws_clean = (flags & PIGS_BUILD_PLAN_WS_CLEAN) != 0;
+    r.no_lookback = (flags & PIGS_BUILD_DEBUG_NO_LOOKBACK) != 0;
+    r.order = (flags & PIGS_BUILD_POINTS_ORDERED) ? 1 : (flags & PIGS_BUILD_POINTS_UNORDERED) ? 2 : 0;
+    r.defer_lists = (flags & PIGS_BUILD_DEFER_LISTS) != 0;
+    r.fwd_only = (flags & PIGS_BUILD_FORWARD_ONLY) != 0;
+    r.N = N; r.M = M; r.c = c; r.q_max = q_max; r.q_max_b = q_max_backward;
+    return run_build(r, sws, sws_bytes, ws, ws_bytes, means, conics, values, samples, stream);
 }
 
 // the masks the fused first forward is compiled for (the rest: the list launch, then the forward launch)
@@ -777,7 +521,7 @@ static int plan_forward_c(const PlanView& pv_in, const SamplesView& sv, int mask
             }
         }
 #undef PIGS_FUSED
-        if (!done) launch_lists(sv.ntiles, la, stream);
+        if (!done) launch_lists(list_launch(sv.ntiles), la, stream);
     }
     if (block_missing(mask, a)) return PIGS_ERR_INVALID;
     // every compiled mask (the fused outputs are never fused with the list launch, the linear residual apart)
@@ -867,7 +611,7 @@ int plan_forward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, f
     if (first) la = make_list_args(p, s, ws, sws, d.q_f, d.q_wide);
     const int rc = a.c == 1 ? plan_forward_c<1>(pv, sv, cm, o, a, stream, first ? &la : nullptr)
                             : plan_forward_c<2>(pv, sv, cm, o, a, stream, first ? &la : nullptr);
-    if (first && rc == PIGS_OK) plan_note_points(p, ws, stream);
+    if (first && rc == PIGS_OK) note_points(p, ws, stream);
     return rc;
 }
 
@@ -883,10 +627,10 @@ int plan_backward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, 
         DeferredLists d{};
         if (defer_take(ws, d)) {
             clear_hip_error();
-            launch_lists(s.ntiles, make_list_args(p, s, ws, sws, d.q_f, d.q_wide), stream);
+            launch_lists(list_launch(s.ntiles), make_list_args(p, s, ws, sws, d.q_f, d.q_wide), stream);
             const int rc = launch_status();
             if (rc != PIGS_OK) return rc;
-            plan_note_points(p, ws, stream);
+            note_points(p, ws, stream);
         }
     }
     const float* g[4];

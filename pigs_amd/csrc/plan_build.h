@@ -137,9 +137,7 @@ __device__ __forceinline__ void wave_box_from_rows_dpp(float& x0, float& x1, flo
 // COPIED: the sampling kernels read the caller's array through the index arithmetic -- or the points go through
 // the sort.  The pass runs on the row length of the last build of this size (the library's memory, `rf_hint`)
 // while the search is still in flight, and is repeated only when the search finds another one.
-constexpr uint32_t BBOX_THREADS = 256;      // (1 024-thread workgroups -- 4 096 waves to launch -- cost small point sets ~3 us)
 constexpr uint32_t LAT_SEARCH0 = 2048, LAT_SEARCH1 = 16384;
-constexpr uint32_t BBOX_WIDE_POINTS = 1u << 19;
 __device__ __forceinline__ bool lattice_shape_ok(uint32_t rf, uint32_t n) {
     const uint32_t rs = rf ? n / rf : 0u;
     return rf >= 8u && (rf & 7u) == 0u && rs * rf == n && (rs & 7u) == 0u && n >= 64u;
@@ -861,7 +859,6 @@ __global__ __launch_bounds__(256) void plan_scan_kernel(BuildArgs a) {
 // by slot: consecutive threads write consecutive 16-byte records of a bin's run, where a direct scatter sends
 // every lane of a store to another line (16.7 -> 12.2 us at 1 M random points).  count(bin, w) is the difference
 // of neighbouring entries of the scanned matrix.
-constexpr uint32_t SCATTER_STAGE_MAX = 2048;       // points of a chunk the LDS stage holds (32 KB)
 __device__ __forceinline__ void samples_scatter_part(const BuildArgs& a, uint32_t w, uint4* stage, uint32_t* lscan, uint32_t* gbase) {
     const uint32_t tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;

@@ -17,10 +17,6 @@ namespace pigs {
 // four 16-point groups are tested against them and the accepted ones appended to the tile's list
 // and group lists; entries with an empty mask are dropped.
 // ------------------------------------------------------------------------------------------
-#ifndef PIGS_LISTS_TPW
-#define PIGS_LISTS_TPW 4
-#endif
-constexpr int LISTS_TPW = PIGS_LISTS_TPW;
 constexpr int SURV_CAP = 128;
 template <int TPW>
 struct ListsLds {

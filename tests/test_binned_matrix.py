@@ -28,7 +28,7 @@ SECOND_TRIP = {(1, 7), (2, 512)}
 
 # ---- plan.h
 POINTS_MODE_MIN_CELLS, POINTS_MODE_MIN_LIST, POINTS_MODE_BLOCK_CELLS, POINT_HELPER_BLOCKS = 16.0, 96, 64.0, 256
-LISTS_SMALL_TILES = 4096          # plan.hip: up to here a list wave builds one tile (its box is the "block" of the criteria)
+LISTS_SMALL_TILES = 4096          # build_choice.h: up to here a list wave builds one tile (its box is the "block" of the criteria)
 GRID_MARGIN = 1.1251              # gauss_grid: s0 = extent * 1.1251 / G0
 
 
@@ -139,7 +139,7 @@ def test_the_tables_describe_the_source():
     pair_math = source("pair_math.h")
     for name, value in NAMED.items():
         assert re.search(rf"constexpr int {name} = {value};", pair_math), name
-    assert f"constexpr uint32_t LISTS_SMALL_TILES = {LISTS_SMALL_TILES};" in plan
+    assert f"constexpr uint32_t LISTS_SMALL_TILES = {LISTS_SMALL_TILES};" in source("build_choice.h")
     # plan.h: the constants the scenes' comments rely on
     plan_h = source("plan.h")
     assert f"constexpr float POINTS_MODE_MIN_CELLS = {POINTS_MODE_MIN_CELLS:g}.f;" in plan_h

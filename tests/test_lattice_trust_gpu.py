@@ -1,4 +1,5 @@
-"""GPU: TRUSTED cold builds (include/pigs_amd.h, pigs_samples_trust_info; plan.hip, run_build).  Once point sets of a
+"""GPU: TRUSTED cold builds (include/pigs_amd.h, pigs_samples_trust_info; build_choice.h, choose_build: `trusted`,
+and OrderState::trusts; plan.hip, run_build).  Once point sets of a
 size have long been the same compact lattice, a cold build stops looking at the points in front of its list launch: the
 Gaussians' pack writes the samples header the decision launch would have written, the list launch reads the points
 through it and holds every tile's real box against the remembered one (plan_lists.h, the guard).  Results never depend
@@ -20,7 +21,7 @@ from pigs_amd import synthetic
 from test_lattice_gpu import grid, lattice_of
 
 pytestmark = pytest.mark.gpu
-TRUST_MIN_BUILDS = 64          # plan.hip
+TRUST_MIN_BUILDS = 64          # build_choice.h
 TOL = 1e-5
 ORDERS = (0, 1, 2)
 

@@ -2,7 +2,8 @@
 the one-pass build (points that arrive in runs sharing a cell) and the coarse-bin build (points in no
 order: torch.rand collocation points, /root/reference/main_pn.py:103; clamped normals,
 test_no_mlp.py:86).  Both must give the oracle's numbers on any input; the library's memory of how a
-point set of a given size last arrived only chooses between them."""
+point set of a given size last arrived only chooses between them (build_choice.h: OrderState, and `coarse` in
+choose_build; the choice itself is held on a CPU by tests/test_build_choice.py)."""
 import os
 
 import numpy as np

@@ -2,7 +2,8 @@
 PlanParams::strips): every 16 consecutive Gaussians are a strip with a bounding box (16 strips a super-strip), the tile lists come from the strip
 boxes -- no count, scan or scatter.  Results must be the oracle's whatever the order of the Gaussians (a lattice as the
 reference lays it out, /root/reference/model_pn.py:338-342; a shuffled one: every strip then reaches everywhere), and
-the library must take the strips only for Gaussians whose strips cover the domain a few times over."""
+the library must take the strips only for Gaussians whose strips cover the domain a few times over (build_choice.h:
+PointsState::takes_strips, and `strips` in choose_build)."""
 import os
 
 import numpy as np
