@@ -16,7 +16,7 @@ def full_conics(flat, d):
 
 
 def forward(means, conics_flat, values, samples, orders=(0, 1, 2), chunk=256):
-    """Returns {order: tensor} for orders within 0..2; dtype/device follow the inputs."""
+    """Returns {order: tensor} for orders within 0..3; dtype/device follow the inputs."""
     N, d = means.shape
     C = full_conics(conics_flat.reshape(N, -1), d)           # [N, d, d]
     values = values.reshape(N, -1)
@@ -34,4 +34,9 @@ def forward(means, conics_flat, values, samples, orders=(0, 1, 2), chunk=256):
         if 2 in outs:
             outer = p[..., :, None] * p[..., None, :] - C[None]
             outs[2].append(torch.einsum("mn,mnij,nc->mijc", dens, outer, values))
+        if 3 in outs:      # d_i d_j d_k exp(-q / 2) = (C_ij p_k + C_ik p_j + C_jk p_i - p_i p_j p_k) exp(-q / 2)
+            ppp = p[..., :, None, None] * p[..., None, :, None] * p[..., None, None, :]
+            cp = (C[None, :, :, :, None] * p[:, :, None, None, :] + C[None, :, :, None, :] * p[:, :, None, :, None]
+                  + C[None, :, None, :, :] * p[:, :, :, None, None])
+            outs[3].append(torch.einsum("mn,mnijk,nc->mijkc", dens, cp - ppp, values))
     return {o: torch.cat(v, 0) for o, v in outs.items()}

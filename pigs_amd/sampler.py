@@ -1201,10 +1201,12 @@ class GaussianSampler:
         ``r = a0 u + a1 . grad u + lap (u_xx + u_yy) - target`` as [M, c] in ONE launch (4 bytes per point and
         channel instead of the 28 of u, grad u and the Hessian), differentiable wrt means, values, conics (one
         launch) and ``target``.  ``a0``, ``lap``: floats; ``a1``: d floats (default zero); ``target``: [M, c]
-        (or [M] for c = 1) or None.  The reference's diffusion loss (model_pn.py:612-617, 834-849;
-        test_no_mlp.py:127-144: ``(u - u_prev) / dt - D lap u``) is
-        ``sampler.residual(a0=1 / dt, lap=-D, target=u_prev / dt).pow(2).mean()``.  Binned plans evaluate the
-        backward with the wide cut-off ``q_max_backward``.
+        (or [M] for c = 1) or None.  The reference's diffusion loss in the form of test_no_mlp.py:127-144,
+        ``(u - u_prev) / dt - D lap u``, is
+        ``sampler.residual(a0=1 / dt, lap=-D, target=u_prev / dt).pow(2).mean()``; the model's own form
+        (model_pn.py:612-617, 794-849: ``ut - dt * rhs``, the blend weighing the CURRENT level with ``time_samples``) is
+        in INTEGRATION.md 4, "compute_loss with the one-launch residuals", for every problem.  Binned plans evaluate
+        the backward with the wide cut-off ``q_max_backward``.
 
         THE GENERAL FORM (per-point coefficients and an advection term; still one launch each way):
         ``r = a0 u + a1 . grad u + lap (u_xx + u_yy) + advect (w . grad) u - target`` with
