@@ -3,6 +3,7 @@
 // list build of aggregate_neighbors (aggregate.hip).
 #pragma once
 #include "plan.h"
+#include "ellipse_rect.h"
 
 #ifndef PIGS_TRAV_STEPS
 #define PIGS_TRAV_STEPS 2     // candidate steps whose box records are in flight together (2, 4, 8 measured equal)
@@ -50,29 +51,14 @@ __device__ __forceinline__ void wave_lds_fence() {
 // edge(s) facing the centre; each facing edge is minimised in closed form.  Comparisons are
 // written so that NaN (degenerate conic) accepts.
 // ------------------------------------------------------------------------------------------
-struct Ellipse {
-    float x, y, a, b, c, nb_c, nb_a;      // centre, conic, -b/c, -b/a
-};
 // what depends on the Gaussian alone (two reciprocals), prepared once and reused for the tile's box
-// and its four group boxes
+// and its four group boxes (struct Ellipse and the test's arithmetic: ellipse_rect.h)
 __device__ __forceinline__ Ellipse ellipse_of(float4 A, float cc) {
     Ellipse e;
     e.x = A.x; e.y = A.y; e.a = A.z; e.b = A.w; e.c = cc;
     e.nb_c = -A.w * __builtin_amdgcn_rcpf(cc);
     e.nb_a = -A.w * __builtin_amdgcn_rcpf(A.z);
     return e;
-}
-// the minimum of q over the rectangle (NaN for a degenerate conic: every comparison `!(qmin > q_max)` accepts)
-__device__ __forceinline__ float ellipse_min_q_rect(const Ellipse& e, float x0, float y0, float x1, float y1) {
-    // clamp(v, lo, hi) with lo <= hi is the median of the three (one v_med3_f32; like the min / max
-    // pair it returns a bound when v is NaN)
-    const float l = x0 - e.x, r = x1 - e.x, bt = y0 - e.y, tp = y1 - e.y;
-    const float xe = __builtin_amdgcn_fmed3f(0.f, l, r), ye = __builtin_amdgcn_fmed3f(0.f, bt, tp);
-    const float ys = __builtin_amdgcn_fmed3f(e.nb_c * xe, bt, tp);
-    const float xs = __builtin_amdgcn_fmed3f(e.nb_a * ye, l, r);
-    const float q1 = e.a * xe * xe + (2.f * e.b * xe + e.c * ys) * ys;
-    const float q2 = e.c * ye * ye + (2.f * e.b * ye + e.a * xs) * xs;
-    return fminf(q1, q2);
 }
 __device__ __forceinline__ bool ellipse_reaches_rect(const Ellipse& e, float x0, float y0, float x1, float y1, float q_max) {
     return !(ellipse_min_q_rect(e, x0, y0, x1, y1) > q_max);

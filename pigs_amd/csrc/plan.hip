@@ -137,6 +137,12 @@ static int samples_order_setting() {      // PIGS_SAMPLES_ORDER
     const char* e = getenv("PIGS_SAMPLES_ORDER");
     return !e ? 0 : !strcmp(e, "ordered") ? 1 : !strcmp(e, "unordered") ? 2 : 0;
 }
+// PIGS_LISTS_PRODUCT=0: no block of a list launch takes the product path of the flush (plan_lists.h; tests and the A/B).
+// Read at every build like the others; it steers no launch choice, so it rides in ListArgs, not in BuildEnv.
+static uint32_t lists_product_setting() {
+    const char* e = getenv("PIGS_LISTS_PRODUCT");
+    return e && e[0] == '0' ? 0u : 1u;
+}
 static BuildEnv build_env() {
     static const char* const bbox = getenv("PIGS_BBOX_BLOCKS");      // the two A/B settings: once per process
     static const bool no_ahead = getenv("PIGS_NO_AHEAD") != nullptr;
@@ -336,6 +342,7 @@ static ListArgs make_list_args(const PlanLayout& p, const SamplesLayout& s, void
     la.points_wanted = &((PlanParams*)((char*)ws + p.off_params))->points_wanted;
     la.parea = (const float*)((char*)ws + p.off_parea);
     la.strip_cover = &((PlanParams*)((char*)ws + p.off_params))->strip_cover;
+    la.product = lists_product_setting();
     return la;
 }
 // the list launch (build_choice.h, list_launch); fwd_only: PIGS_BUILD_FORWARD_ONLY (build_block_lists<..., FWD_ONLY>)

@@ -502,7 +502,7 @@ __global__ __launch_bounds__(64 * PIGS_FWD_WG_WAVES, (fwd_waves<C, MASK>())) voi
 // hosts defer the lists for every plan all the same, because a cloud's first step is one of thousands.
 // ------------------------------------------------------------------------------------------
 template <int C, int MASK>
-__global__ __launch_bounds__(256) void plan_lists_forward_kernel(ListArgs a, float* __restrict__ o0, float* __restrict__ o1,
+__global__ __launch_bounds__(256, 5) void plan_lists_forward_kernel(ListArgs a, float* __restrict__ o0, float* __restrict__ o1,
                                                                  float* __restrict__ o2, float* __restrict__ o3, RzOf<float, MASK> rz) {
     __shared__ ListsLds<LISTS_TPW> lds_all[4];
     static_assert(sizeof(FwdLds) <= sizeof(ListsLds<LISTS_TPW>), "the forward's queues live in the list build's LDS");
@@ -512,7 +512,7 @@ __global__ __launch_bounds__(256) void plan_lists_forward_kernel(ListArgs a, flo
     const uint32_t tile0 = lists_tile0<LISTS_TPW>(wave);
     const uint32_t ntiles = a.sv.ntiles;
     if (tile0 >= ntiles) return;
-    build_block_lists<LISTS_TPW>(a, lds_all[wave], tile0, lane);
+    build_block_lists<LISTS_TPW, false, false, false>(a, lds_all[wave], tile0, lane);      // (general path only: plan_lists.h)
     // what this wave's lanes stored (headers, group lists) is read back by other lanes of it: the stores have
     // reached the L2 before the first load is issued
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");

@@ -6,6 +6,10 @@
 #pragma once
 #include "plan_build.h"
 
+#ifndef PIGS_LISTS_PRODUCT
+#define PIGS_LISTS_PRODUCT 1      // 0: no block takes the product path of the flush (as the environment word of the same name)
+#endif
+
 namespace pigs {
 
 // ------------------------------------------------------------------------------------------
@@ -16,6 +20,16 @@ namespace pigs {
 // LDS with what the ellipse test needs of them; every 128 survivors, and at the end, each tile's
 // four 16-point groups are tested against them and the accepted ones appended to the tile's list
 // and group lists; entries with an empty mask are dropped.
+//
+// PRODUCT BLOCKS.  On an index-tiled lattice a group is a 4 x 4 patch of the lattice, and the 4 TPW group boxes of a
+// block are the product of 2 sqrt(TPW) x-intervals and as many y-intervals.  ellipse_min_q_rect splits into terms of
+// one interval and terms of both (ellipse_rect.h): a block whose boxes ARE such a product -- decided from the boxes,
+// bit for bit, never from the samples' header -- tests every survivor against all its groups at once: the axis terms
+// of the 8 intervals, then 16 combinations; no per-tile filter, no `sel`, one read of the survivor.  Every other
+// block (points in no lattice, a rotated lattice, a ragged tile) takes the general path.  Both form bit-identical
+// minima for the same (ellipse, box); the product path only drops the tile pre-filter, so a (survivor, group) pair
+// whose group test passes while its tile's test fails -- the group box lies inside the tile's: rounding alone, at the
+// cut-off -- is listed there and not here.  PIGS_LISTS_PRODUCT=0 (-D or environment): the general path everywhere.
 // ------------------------------------------------------------------------------------------
 constexpr int SURV_CAP = 128;
 template <int TPW>
@@ -24,8 +38,10 @@ struct ListsLds {
     float4 sa[SURV_CAP];              // survivor: {mux, muy, a, b}
     float4 sb[SURV_CAP];              //           {c, -b/c, -b/a, sorted index (bits)}
     float4 gbox[TPW * 4];       // boxes of the groups: {x0, y0, x1, y1}
-    uint32_t sel[SURV_CAP];           // positions of the survivors that reach the tile in hand
+    float4 tbox[TPW];           // boxes of the tiles (written once, in the prologue)
+    uint32_t sel[SURV_CAP];           // general path: positions of the survivors that reach the tile in hand
 };
+static_assert(4 * sizeof(ListsLds<4>) <= 32768, "five workgroups of the list launch per CU");
 struct ListArgs {
     PlanView pv;
     SamplesView sv;
@@ -38,6 +54,7 @@ struct ListArgs {
     float q_f;            // the narrow cut-off (pv.q_max is the wide one)
     const float* parea;   // per strip: box area / domain area (written by the build's Gaussian pass)
     float* strip_cover;   //   their sum (PlanParams::strip_cover)
+    uint32_t product;     // blocks whose group boxes form a product may take the product path (PIGS_LISTS_PRODUCT != 0)
     // The guard of a TRUSTED build (plan.hip, run_build; null: none -- every other build).  Nobody looked at the points in
     // front of this launch: they are taken in index-tiled order because point sets of this size have long been the same
     // lattice.  The lists are right whatever the points are (they come from the groups' real boxes); what may have failed
@@ -58,14 +75,23 @@ struct ListArgs {
 // FWD_ONLY (PIGS_BUILD_FORWARD_ONLY; pv.q_max == q_f then): the forward reads the group lists alone, so the tile list
 // and its wide masks are not written, one cut-off is tested per group, and a tile whose group lists fit is LIST with a
 // count of zero (no tile list a backward could read; there is no TILE_MODE_GROUPS rebuild either).
-template <int TPW, bool STRIPS = false, bool FWD_ONLY = false>
+// PRODUCT = false: the product path is not compiled in (the fused list + forward launch, plan_forward.h: its wave holds
+// the forward's registers as well and the two paths together do not fit its 96).
+template <int TPW, bool STRIPS = false, bool FWD_ONLY = false, bool PRODUCT = true>
 __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TPW>& lds, uint32_t tile0, int lane) {
     const PlanView& pv = a.pv;
     const uint32_t ntiles = a.sv.ntiles;
-    const GaussGrid gg = pv.params->gg;
-    const uint32_t level_mask = pv.params->level_mask;
     constexpr bool strips = STRIPS;                       // candidates from strip boxes, not from grid cells (PlanParams::strips)
-    const uint32_t loff = pv.params->level_off[lane < PLAN_MAX_LEVELS ? lane : 0];   // lane = level: its first counter
+    // (the strips' walk reads nothing of the grid but the finest cell size)
+    GaussGrid gg{};
+    uint32_t level_mask = 0u, loff = 0u;
+    if constexpr (STRIPS) {
+        gg.inv_s0 = pv.params->gg.inv_s0;
+    } else {
+        gg = pv.params->gg;
+        level_mask = pv.params->level_mask;
+        loff = pv.params->level_off[lane < PLAN_MAX_LEVELS ? lane : 0];   // lane = level: its first counter
+    }
     const float INF = __builtin_huge_valf();
     SPoint sp[TPW];
     bool valid[TPW];
@@ -78,6 +104,8 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
         if (tile0 + (uint32_t)t < ntiles) sp[t] = tile_point(a.sv, po, tile0 + (uint32_t)t, (uint32_t)lane);     // wave-uniform
     }
     float bx0 = INF, bx1 = -INF, by0 = INF, by1 = -INF;
+    float gx0[TPW], gx1[TPW], gy0[TPW], gy1[TPW];         // every lane: the box of its own group, per tile
+    uint32_t has[TPW];                                    // per tile: the groups that hold a point (wave-uniform)
 #pragma unroll
     for (int t = 0; t < TPW; ++t) {
         float x0 = valid[t] ? sp[t].x : INF, x1 = valid[t] ? sp[t].x : -INF;
@@ -85,8 +113,46 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
         row_box_dpp(x0, x1, y0, y1);
         if ((lane & 15) == 0) lds.gbox[t * 4 + (lane >> 4)] = make_float4(x0, y0, x1, y1);
         bx0 = fminf(bx0, x0); bx1 = fmaxf(bx1, x1); by0 = fminf(by0, y0); by1 = fmaxf(by1, y1);
+        gx0[t] = x0; gx1[t] = x1; gy0[t] = y0; gy1[t] = y1;
+        // a group without a point (the ragged last tile) has an inverted box: never needed
+        const uint64_t hm = __ballot(x0 <= x1);
+        has[t] = (uint32_t)(hm & 1ull) | (uint32_t)(hm >> 15 & 2ull) | (uint32_t)(hm >> 30 & 4ull) | (uint32_t)(hm >> 45 & 8ull);
     }
     wave_box_from_rows_dpp(bx0, bx1, by0, by1);
+    // the tiles' boxes, once (lane = tile): the general flush, the guard and the `longest` check read them
+    wave_lds_fence();
+    if (lane < TPW) {
+        const float4 g0 = lds.gbox[lane * 4], g1 = lds.gbox[lane * 4 + 1], g2 = lds.gbox[lane * 4 + 2], g3 = lds.gbox[lane * 4 + 3];
+        lds.tbox[lane] = make_float4(fminf(fminf(g0.x, g1.x), fminf(g2.x, g3.x)), fminf(fminf(g0.y, g1.y), fminf(g2.y, g3.y)),
+                                     fmaxf(fmaxf(g0.z, g1.z), fmaxf(g2.z, g3.z)), fmaxf(fmaxf(g0.w, g1.w), fmaxf(g2.w, g3.w)));
+    }
+    wave_lds_fence();
+    // Do the group boxes form a product?  Group g of tile t is the 4 x 4 patch (g & 1, g >> 1) of the tile
+    // (lattice_index) and tiles t .. t + 3 of a block its 2 x 2 tile columns, lower tile first (lattice_tile_xy), so
+    // the group sits in column 2 (t >> 1) + (g & 1) and row 2 (t & 1) + (g >> 1) of the block's groups.  A product:
+    // every group holds a point, the groups of a column have bit-equal x0 and x1, those of a row bit-equal y0 and y1.
+    constexpr bool CAN_PRODUCT = PRODUCT && PIGS_LISTS_PRODUCT != 0 && (TPW == 1 || TPW == 4);
+    constexpr int NI = TPW == 4 ? 4 : 2;                  // intervals per axis
+    bool product = false;
+    if constexpr (CAN_PRODUCT) {
+        auto same = [](float u, float v) { return __builtin_bit_cast(uint32_t, u) == __builtin_bit_cast(uint32_t, v); };
+        bool ok = a.product != 0u;
+#pragma unroll
+        for (int t = 0; t < TPW; ++t) ok = ok && has[t] == 15u;
+        if (__builtin_amdgcn_readfirstlane((int)ok)) {      // (wave-uniform: random points leave here)
+            if constexpr (TPW == 4) {
+                ok = ok && same(gx0[0], gx0[1]) && same(gx1[0], gx1[1]) && same(gx0[2], gx0[3]) && same(gx1[2], gx1[3]);
+                ok = ok && same(gy0[0], gy0[2]) && same(gy1[0], gy1[2]) && same(gy0[1], gy0[3]) && same(gy1[1], gy1[3]);
+            }
+#pragma unroll
+            for (int h = 0; h < (TPW == 4 ? 2 : 1); ++h) {   // against the group above (lane ^ 32) and the one beside (lane ^ 16)
+                const int tc = 2 * h, tr = h;
+                ok = ok && same(gx0[tc], __shfl_xor(gx0[tc], 32)) && same(gx1[tc], __shfl_xor(gx1[tc], 32));
+                ok = ok && same(gy0[tr], __shfl_xor(gy0[tr], 16)) && same(gy1[tr], __shfl_xor(gy1[tr], 16));
+            }
+            product = __ballot(ok) == ~0ull;
+        }
+    }
 
     const uint32_t cap = pv.list_cap;
     // what a per-point walk would meet: 9 cells of every level at the level's mean occupancy (wave-uniform;
@@ -126,10 +192,37 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
         for (int g = 0; g < 4; ++g) ng[t][g] = 0;
     }
     int sn = 0;
-    // the tiles' tests on the survivors in LDS: per tile, (A) the survivors that reach the tile's
+    // one step's accepted survivors of tile t (this lane: sorted index j, wide mask gm, narrow mask gf; zero: none)
+    // appended to the tile's list and its four group lists
+    auto append = [&](int t, uint32_t j, uint32_t gm, uint32_t gf) __attribute__((always_inline)) {
+        uint32_t* tl = a.tlist + (size_t)(tile0 + (uint32_t)t) * cap;
+        uint32_t* gl = a.glist + (size_t)(tile0 + (uint32_t)t) * 4 * cap;
+        if constexpr (!FWD_ONLY) {
+            const uint64_t km = __ballot(gm != 0u);
+            const uint32_t cnt = (uint32_t)__builtin_popcountll(km);
+            if (n[t] + cnt <= cap) {
+                if (gm != 0u) tl[n[t] + (uint32_t)lanes_below(km)] = j | (gm << LIST_WIDE_SHIFT) | (gf << LIST_NARROW_SHIFT);
+            } else {
+                overflow[t] = true;
+            }
+            n[t] += cnt;
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const uint64_t mg = __ballot(gf >> g & 1u);
+            const uint32_t cg = (uint32_t)__builtin_popcountll(mg);
+            if (ng[t][g] + cg <= cap) {
+                if (gf >> g & 1u) gl[g * cap + ng[t][g] + (uint32_t)lanes_below(mg)] = j;
+            } else {
+                goverflow[t] = true;
+            }
+            ng[t][g] += cg;
+        }
+    };
+    // the tiles' tests on the survivors in LDS, general path: per tile, (A) the survivors that reach the tile's
     // box, compacted (their positions, one byte each would do: 128 survivors), then (B) the four
     // group tests on those: usually one step of 64 instead of two
-    auto flush = [&]() __attribute__((always_inline)) {
+    auto flush_general = [&]() __attribute__((always_inline)) {
         wave_lds_fence();
 #pragma unroll
         for (int t = 0; t < TPW; ++t) {
@@ -137,24 +230,19 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
             float4 gb[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) gb[g] = lds.gbox[t * 4 + g];
-            const float tx0 = fminf(fminf(gb[0].x, gb[1].x), fminf(gb[2].x, gb[3].x));
-            const float ty0 = fminf(fminf(gb[0].y, gb[1].y), fminf(gb[2].y, gb[3].y));
-            const float tx1 = fmaxf(fmaxf(gb[0].z, gb[1].z), fmaxf(gb[2].z, gb[3].z));
-            const float ty1 = fmaxf(fmaxf(gb[0].w, gb[1].w), fmaxf(gb[2].w, gb[3].w));
+            const float4 tb = lds.tbox[t];
             int sel = 0;
             for (int s0 = 0; s0 < sn; s0 += 64) {
                 const int k = s0 + lane < sn ? s0 + lane : 0;
                 const float4 A = lds.sa[k], B = lds.sb[k];
                 Ellipse e;
                 e.x = A.x; e.y = A.y; e.a = A.z; e.b = A.w; e.c = B.x; e.nb_c = B.y; e.nb_a = B.z;
-                const bool hit = s0 + lane < sn && ellipse_reaches_rect(e, tx0, ty0, tx1, ty1, pv.q_max);
+                const bool hit = s0 + lane < sn && ellipse_reaches_rect(e, tb.x, tb.y, tb.z, tb.w, pv.q_max);
                 const uint64_t hm = __ballot(hit);
                 if (hit) lds.sel[sel + lanes_below(hm)] = (uint32_t)k;
                 sel += __builtin_popcountll(hm);
             }
             wave_lds_fence();
-            uint32_t* tl = a.tlist + (size_t)(tile0 + (uint32_t)t) * cap;
-            uint32_t* gl = a.glist + (size_t)(tile0 + (uint32_t)t) * 4 * cap;
             for (int s0 = 0; s0 < sel; s0 += 64) {
                 const int k = (int)lds.sel[s0 + lane < sel ? s0 + lane : 0];
                 const float4 A = lds.sa[k], B = lds.sb[k];
@@ -164,39 +252,71 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
                 uint32_t gm = 0, gf = 0;       // wide (tile list, backward) and narrow (group lists, forward) masks
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    // a group without a point (the ragged last tile) has an inverted box: never needed
                     const float qmin = ellipse_min_q_rect(e, gb[g].x, gb[g].y, gb[g].z, gb[g].w);
-                    if (gb[g].x <= gb[g].z) {
-                        if (!FWD_ONLY && !(qmin > pv.q_max)) gm |= 1u << g;
-                        if (!(qmin > a.q_f)) gf |= 1u << g;
-                    }
+                    if (!FWD_ONLY && !(qmin > pv.q_max)) gm |= 1u << g;
+                    if (!(qmin > a.q_f)) gf |= 1u << g;
                 }
+                // a group without a point has an inverted box, never needed: the ragged last tile alone (wave-uniform)
+                if (has[t] != 15u) { gm &= has[t]; gf &= has[t]; }
                 if (s0 + lane >= sel) gm = gf = 0u;
-                if constexpr (!FWD_ONLY) {
-                    const uint64_t km = __ballot(gm != 0u);
-                    const uint32_t cnt = (uint32_t)__builtin_popcountll(km);
-                    if (n[t] + cnt <= cap) {
-                        if (gm != 0u) tl[n[t] + (uint32_t)lanes_below(km)] = j | (gm << LIST_WIDE_SHIFT) | (gf << LIST_NARROW_SHIFT);
-                    } else {
-                        overflow[t] = true;
-                    }
-                    n[t] += cnt;
-                }
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const uint64_t mg = __ballot(gf >> g & 1u);
-                    const uint32_t cg = (uint32_t)__builtin_popcountll(mg);
-                    if (ng[t][g] + cg <= cap) {
-                        if (gf >> g & 1u) gl[g * cap + ng[t][g] + (uint32_t)lanes_below(mg)] = j;
-                    } else {
-                        goverflow[t] = true;
-                    }
-                    ng[t][g] += cg;
-                }
+                append(t, j, gm, gf);
             }
             wave_lds_fence();
         }
         sn = 0;
+    };
+    // ... product path: lane = survivor, all 4 TPW groups of the block from the axis terms of its 2 NI intervals
+    // (ellipse_rect.h); bit 4 t + g of the masks = group g of tile t
+    auto flush_product = [&]() __attribute__((always_inline)) {
+        wave_lds_fence();
+        // the group in column i and row i of the block's groups holds x-interval i and y-interval i
+        auto diagonal = [](int i) { return TPW == 4 ? 12 * (i >> 1) + 3 * (i & 1) : 3 * i; };
+        for (int s0 = 0; s0 < sn; s0 += 64) {
+            const bool have = s0 + lane < sn;
+            const int k = have ? s0 + lane : 0;
+            const float4 A = lds.sa[k], B = lds.sb[k];
+            const uint32_t j = __builtin_bit_cast(uint32_t, B.w);
+            const float ea = A.z, ec = B.x, b2 = 2.f * A.w;
+            uint32_t gm = 0, gf = 0;
+            // Loops, not unrolled (rows and columns are wave-uniform): a fraction of the code and of the registers.  A
+            // full plan, whose wave holds more beside the flush, takes the rows two at a time -- the columns' terms
+            // are then formed once per pair, 28 instructions more per step, for 10 registers fewer.
+            constexpr int RP = FWD_ONLY ? NI : 2;           // rows per pass
+#pragma nounroll
+            for (int r0 = 0; r0 < NI; r0 += RP) {
+                AxisTerms Y[RP];
+#pragma unroll
+                for (int rr = 0; rr < RP; ++rr) {
+                    const float4 d = lds.gbox[diagonal(r0 + rr)];
+                    Y[rr] = axis_terms(A.y, ec, b2, B.z, d.y, d.w);
+                }
+#pragma nounroll
+                for (int c = 0; c < NI; ++c) {
+                    const float4 d = lds.gbox[diagonal(c)];
+                    const AxisTerms X = axis_terms(A.x, ea, b2, B.y, d.x, d.z);
+                    uint32_t wide = 0, narrow = 0;
+#pragma unroll
+                    for (int rr = 0; rr < RP; ++rr) {
+                        const float qmin = min_q_of_terms(X, Y[rr], ea, ec);
+                        const int bit = 4 * (rr >> 1) + 2 * (rr & 1);
+                        if (!FWD_ONLY && !(qmin > pv.q_max)) wide |= 1u << bit;
+                        if (!(qmin > a.q_f)) narrow |= 1u << bit;
+                    }
+                    // group (column c, row r): tile 2 (c >> 1) + (r >> 1), group (c & 1) + 2 (r & 1); r0 is even
+                    const int shift = 8 * (c >> 1) + (c & 1) + 4 * (r0 >> 1);
+                    gm |= wide << shift; gf |= narrow << shift;
+                }
+            }
+            if (!have) gm = gf = 0u;
+#pragma unroll
+            for (int t = 0; t < TPW; ++t) append(t, j, gm >> (4 * t) & 15u, gf >> (4 * t) & 15u);
+        }
+        wave_lds_fence();
+        sn = 0;
+    };
+    auto flush = [&]() __attribute__((always_inline)) {
+        if (product) flush_product();
+        else flush_general();
     };
     auto walk_rect = [&](float x0, float y0, float x1, float y1, bool walk, auto&& rows, auto&& batch) __attribute__((always_inline)) {
         if constexpr (STRIPS) traverse_strips(pv, x0, y0, x1, y1, lane, lds.trav, walk, rows, batch);
@@ -229,17 +349,13 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
     bool any_rare = false;
     bool rebuild[TPW];
     const bool guard = a.lattice_broken != nullptr;       // launch-uniform
-    if (guard) wave_lds_fence();                          // (the group boxes: no flush may have run)
 #pragma unroll
     for (int t = 0; t < TPW; ++t) {
         rebuild[t] = false;
         if (tile0 + (uint32_t)t >= ntiles) { overflow[t] = false; continue; }
         if (guard) {      // the trusted build's guard (ListArgs::lattice_broken); a comparison that NaN or inf fails: broken
-            float4 gb[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) gb[g] = lds.gbox[t * 4 + g];
-            const float wx = fmaxf(fmaxf(gb[0].z, gb[1].z), fmaxf(gb[2].z, gb[3].z)) - fminf(fminf(gb[0].x, gb[1].x), fminf(gb[2].x, gb[3].x));
-            const float wy = fmaxf(fmaxf(gb[0].w, gb[1].w), fmaxf(gb[2].w, gb[3].w)) - fminf(fminf(gb[0].y, gb[1].y), fminf(gb[2].y, gb[3].y));
+            const float4 tb = lds.tbox[t];
+            const float wx = tb.z - tb.x, wy = tb.w - tb.y;
             if (!(wx * a.guard_n[0] <= a.guard_e[0] && wy * a.guard_n[1] <= a.guard_e[1]) && lane == 0) *a.lattice_broken = 1u;
         }
         const bool tl_over = FWD_ONLY ? goverflow[t] : overflow[t];      // (no tile list: its group lists decide)
@@ -250,11 +366,8 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
         longest = ng[t][2] > longest ? ng[t][2] : longest;
         longest = ng[t][3] > longest ? ng[t][3] : longest;
         if (longest > POINTS_MODE_MIN_LIST) {      // (strips: the per-point walk needs the grid -- only noted)
-            float4 gb[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) gb[g] = lds.gbox[t * 4 + g];
-            const float wx = fmaxf(fmaxf(gb[0].z, gb[1].z), fmaxf(gb[2].z, gb[3].z)) - fminf(fminf(gb[0].x, gb[1].x), fminf(gb[2].x, gb[3].x));
-            const float wy = fmaxf(fmaxf(gb[0].w, gb[1].w), fmaxf(gb[2].w, gb[3].w)) - fminf(fminf(gb[0].y, gb[1].y), fminf(gb[2].y, gb[3].y));
+            const float4 tb = lds.tbox[t];
+            const float wx = tb.z - tb.x, wy = tb.w - tb.y;
             if (strips && wx * gg.inv_s0 * (wy * gg.inv_s0) > POINTS_MODE_MIN_CELLS) {
                 if (lane == 0) atomicAdd(a.points_wanted, 1u);
             }
@@ -297,10 +410,8 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
         float4 gb[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) gb[g] = lds.gbox[t * 4 + g];
-        const float tx0 = fminf(fminf(gb[0].x, gb[1].x), fminf(gb[2].x, gb[3].x));
-        const float ty0 = fminf(fminf(gb[0].y, gb[1].y), fminf(gb[2].y, gb[3].y));
-        const float tx1 = fmaxf(fmaxf(gb[0].z, gb[1].z), fmaxf(gb[2].z, gb[3].z));
-        const float ty1 = fmaxf(fmaxf(gb[0].w, gb[1].w), fmaxf(gb[2].w, gb[3].w));
+        const float4 tb = lds.tbox[t];
+        const float tx0 = tb.x, ty0 = tb.y, tx1 = tb.z, ty1 = tb.w;
         uint32_t* tl = a.tlist + (size_t)(tile0 + (uint32_t)t) * cap;
         if (mine_rebuild) {
             uint32_t* gl = a.glist + (size_t)(tile0 + (uint32_t)t) * 4 * cap;
@@ -393,7 +504,7 @@ __device__ __forceinline__ void lists_strip_cover(const ListArgs& a) {
 }
 
 template <int TPW, bool STRIPS, bool FWD_ONLY = false>
-__global__ __launch_bounds__(256) void plan_lists_kernel(ListArgs a) {
+__global__ __launch_bounds__(256, 5) void plan_lists_kernel(ListArgs a) {
     __shared__ ListsLds<TPW> lds_all[4];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
