@@ -54,6 +54,8 @@ struct BuildEnv {
     int gauss_strips = -1;       // PIGS_GAUSS_STRIPS=0 / 1: never / always
     int bbox_blocks = -1;        // PIGS_BBOX_BLOCKS (A/B: 256 | 512), read once per process
     bool no_ahead = false;       // PIGS_NO_AHEAD, read once per process
+    bool stats_home = true;      // PIGS_STATS_HOME=0: a plan's statistics travel by a copy of its header, not by the list
+                                 // launch's own stores (tests, A/B; no launch of the build's own depends on it)
 };
 
 // What the memories said of these sizes (all zero: nothing), resolved by the caller for "inside a capture".
@@ -133,7 +135,7 @@ inline BuildChoice choose_build(const BuildRequest& r, const SamplesLayout& s, c
     // copies in a row -- this build does not look again.  It launches what a build on a finished samples workspace
     // launches, the Gaussians' pack and the lists; the pack's first workgroup writes the samples header the decision
     // would have written, the list launch reads the points through it and holds every tile's real box against the
-    // remembered one (ListArgs::lattice_broken), and that word rides home with the plan's statistics every 8th build
+    // remembered one (ListArgs::lattice_broken), and that word goes home with the plan's statistics every 8th build
     // (plan.hip, points_landed turns the memory around).  Results never depend on it: the lists come from the groups'
     // real boxes.
     const uint32_t rf = b.rf_hint;
@@ -231,8 +233,9 @@ struct OrderState {
         if (mode == 0 || rf == 0u || !box_stable) return false;
         return mode == 1 || (same >= 2u && streak >= TRUST_MIN_BUILDS);
     }
-    // is the copy asked for behind build number `nth` (from 0)?  After the first two, every 16th (the copy is a ~4 us
-    // blit in the build's stream).  With a row length in the memory the build runs on expectations -- an eighth of the
+    // is the copy asked for behind build number `nth` (from 0)?  After the first two, every 16th (the samples' copy is
+    // a blit kernel of ~4 us in the build's stream: its order_stat words are sums that are final at the kernel's end
+    // only, so they cannot be stored home the way the plans' words are -- and a trusted build asks for none).  With a row length in the memory the build runs on expectations -- an eighth of the
     // count's workgroups, the Gaussians one launch ahead -- and a point set that stopped meeting them should not be met
     // 15 more times: every 8th build then, every 32nd once three copies in a row have said the same.
     bool copy_due(uint32_t nth) const { return nth < 2u || (nth & (rf ? (same >= 2u ? 31u : 7u) : 15u)) == 0u; }
@@ -241,14 +244,16 @@ struct OrderState {
 // ---- the plans' memory: does a plan of these sizes hold tiles in TILE_MODE_POINTS, do its Gaussians come in strips? ----
 // The fused first forward walks such tiles in their own list wave (right, and slow when there are hundreds: the thin
 // outskirts of a clustered cloud), the two-launch path spreads them over helper workgroups.  Which one a plan wants is
-// known on the device only, so the library remembers, per device and (N, M): behind the list build of the first two
-// plans of a size and of every 16th, five words from PlanParams::n_points on are copied to pinned memory on the build's
-// stream (nobody waits); a first forward takes the fused launch unless the last completed copy for its sizes showed
-// such tiles.  Never inside a capture.
+// known on the device only, so the library remembers, per device and (N, M): the list launch of the first two plans of
+// a size and of every 16th stores five words -- the ones from PlanParams::n_points on, each reduced to "zero or not"
+// but the cover -- into pinned memory that the device addresses, where they come into being, and an event follows the
+// launch (nobody waits, and no launch is added; PIGS_STATS_HOME=0: the five words are copied out of the header by a blit
+// behind the build instead); a first forward takes the fused launch unless the last completed picture for its sizes
+// showed such tiles.  Never inside a capture.  ("Copy" below: such a picture, whichever way it came.)
 constexpr uint32_t POINTS_WORDS = 5;        // {n_points, strip_cover, strips, points_wanted, lattice_broken}
 static_assert(offsetof(PlanParams, strip_cover) == offsetof(PlanParams, n_points) + 4 && offsetof(PlanParams, strips) == offsetof(PlanParams, n_points) + 8 &&
               offsetof(PlanParams, points_wanted) == offsetof(PlanParams, n_points) + 12 && offsetof(PlanParams, lattice_broken) == offsetof(PlanParams, n_points) + 16,
-              "one copy: n_points, strip_cover, strips, points_wanted, lattice_broken");
+              "one copy: n_points, strip_cover, strips, points_wanted, lattice_broken");      // (plan_lists.h, HOME_*: the same order)
 struct PointsState {
     bool has_points = false;
     float cover = -1.f;            // PlanParams::strip_cover of the last completed build (< 0: none yet)
@@ -264,7 +269,8 @@ struct PointsState {
     // time, TILE_MODE_POINTS: a plan that had such tiles keeps the cells.  Measured without: clamped normals
     // sigma = 0.15 over lattice Gaussians, warm step 111 -> 1 126 us.)
     bool takes_strips() const { return cover >= 0.f && cover <= STRIP_MAX_COVER && !has_points; }
-    // a copy has landed; true: a trusted build's guard said lattice_broken (the caller turns the samples' memory around)
+    // a copy has landed; true: a trusted build's guard said lattice_broken (the caller turns the samples' memory around).
+    // Words 0, 3 and 4 count as "zero or not": stored home by the list launch they are 0 or 1, copied they are counts.
     bool absorb(const uint32_t* w) {
         const bool took_before = takes_strips();
         has_points = w[0] != 0u || w[3] != 0u;

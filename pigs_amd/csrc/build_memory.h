@@ -1,8 +1,11 @@
 // Binned path, host side: the slot table behind the library's memories of the last builds (build_choice.h: OrderState
 // keyed by M, PointsState keyed by (N, M); instantiated in plan.hip, under its one mutex).  16 slots per table, least
-// recently used first to go; per slot one pinned buffer and one event.  A build asks for a few words of its workspace
-// header to be copied behind it on its own stream (request); a later call of the same (device, key) looks whether the
-// copy has landed (poll) and never waits.  Nothing here runs inside a stream capture: the callers see to that.
+// recently used first to go; per slot one pinned buffer, mapped into the device's address space, and one event.  A build
+// first reserves its slot (reserve), then sends a few words home behind itself on its own stream: either its last
+// kernel stores them into the slot's buffer where they come into being (home, then sent -- no launch of its own), or
+// they are copied out of its workspace header (request -- a blit kernel in the build's stream); a later call of the
+// same (device, key) looks whether they have landed (poll) and never waits.  Nothing here runs inside a stream capture:
+// the callers see to that.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -27,9 +30,11 @@ struct BuildMemory {
         int device = -1;
         Key key{};
         State st{};
-        bool pending = false;          // a copy is on its way
+        bool pending = false;          // words are on their way (or about to be: reserved)
+        bool recorded = false;         // ... and `ev` has been recorded behind them (poll looks at no other event)
         hipEvent_t ev = nullptr;
-        uint32_t* host = nullptr;      // pinned, WORDS words
+        uint32_t* host = nullptr;      // pinned and mapped, WORDS words; lives as long as the process
+        uint32_t* dev = nullptr;       // the same words as the slot's device addresses them
         uint64_t stamp = 0;
     };
     void (*landed)(Slot&);             // what a completed copy means (host[0 .. WORDS) -> st)
@@ -37,7 +42,7 @@ struct BuildMemory {
     uint64_t clock = 0;
 
     void poll(Slot& s) {
-        if (!s.pending) return;
+        if (!s.pending || !s.recorded) return;
         const hipError_t q = hipEventQuery(s.ev);
         (void)hipGetLastError();          // hipErrorNotReady is an answer, not a failure
         if (q != hipSuccess) return;
@@ -69,17 +74,34 @@ struct BuildMemory {
         if (lru->ev && lru->device != device) {      // an event belongs to the device it was created on
             (void)hipEventDestroy(lru->ev);
             lru->ev = nullptr;
+            lru->dev = nullptr;
         }
         if (!lru->ev && hipEventCreateWithFlags(&lru->ev, hipEventDisableTiming) != hipSuccess) { lru->ev = nullptr; (void)hipGetLastError(); return nullptr; }
-        if (!lru->host && hipHostMalloc((void**)&lru->host, WORDS * sizeof(uint32_t), hipHostMallocPortable) != hipSuccess) { lru->host = nullptr; (void)hipGetLastError(); return nullptr; }
-        lru->device = device; lru->key = key; lru->st = State{}; lru->pending = false; lru->stamp = ++clock;
+        if (!lru->host && hipHostMalloc((void**)&lru->host, WORDS * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) { lru->host = nullptr; (void)hipGetLastError(); return nullptr; }
+        if (!lru->dev && hipHostGetDevicePointer((void**)&lru->dev, lru->host, 0) != hipSuccess) { lru->dev = nullptr; (void)hipGetLastError(); return nullptr; }
+        lru->device = device; lru->key = key; lru->st = State{}; lru->pending = lru->recorded = false; lru->stamp = ++clock;
         return lru;
+    }
+    // The slot is this build's from here on: no other build sends words to it, nobody gives it away, and poll leaves it
+    // alone until request or sent has recorded the event (release: the build failed to launch).
+    void reserve(Slot& s) { s.pending = true; s.recorded = false; }
+    void release(Slot& s) { s.pending = false; s.recorded = false; }
+    // A reserved slot's words zeroed by the host (nothing on the device can be writing them: the slot was not pending)
+    // and its device address, for the kernel that stores the words that are not zero.
+    uint32_t* home(Slot& s) {
+        for (uint32_t k = 0; k < WORDS; ++k) s.host[k] = 0u;
+        return s.dev;
+    }
+    // ... behind that kernel's launch on `stream`
+    void sent(Slot& s, hipStream_t stream) {
+        s.recorded = hipEventRecord(s.ev, stream) == hipSuccess;
+        if (!s.recorded) s.pending = false;
+        (void)hipGetLastError();
     }
     // WORDS words from `src` (device memory) to the slot's pinned buffer, behind what `stream` holds
     void request(Slot& s, const void* src, hipStream_t stream) {
-        if (hipMemcpyAsync(s.host, src, WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess &&
-            hipEventRecord(s.ev, stream) == hipSuccess)
-            s.pending = true;
+        s.pending = s.recorded = hipMemcpyAsync(s.host, src, WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess &&
+                                 hipEventRecord(s.ev, stream) == hipSuccess;
         (void)hipGetLastError();
     }
 };

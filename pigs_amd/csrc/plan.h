@@ -201,9 +201,9 @@ struct PlanParams {
     // a block of tiles against super-strip boxes, then strip boxes, then the strips' records (grid_walk.h,
     // traverse_strips) instead of walking grid cells -- no count, no scan, no scatter.  Always correct (a strip box bounds its Gaussians'
     // ellipses whatever their order); fast when the strips cover the samples' domain only a few times over:
-    // strip_cover = sum of strip box areas / domain area, measured by every build (either kind) and remembered by the
-    // library, which decides the next build's kind from it.
-    float strip_cover;              // (adjacent to n_points: one copy for the library's memory)
+    // strip_cover = sum of strip box areas / domain area, measured by the builds (of either kind) whose statistics go
+    // home to the library's memory -- stale after every other build --, which decides the next build's kind from it.
+    float strip_cover;              // (adjacent to n_points: one copy for the library's memory under PIGS_STATS_HOME=0)
     uint32_t strips;                // this build kept the caller's order (lists from strip boxes)
     uint32_t points_wanted;         // ... and met this many blocks / tiles of far-apart points, which a build through the
                                     // cells would have left to the per-point walk (TILE_MODE_POINTS needs the grid): the

@@ -151,6 +151,7 @@ static BuildEnv build_env() {
     if (const char* e = getenv("PIGS_LATTICE_TRUST")) env.lattice_trust = e[0] == '0' ? 0 : e[0] == '1' ? 1 : -1;
     env.samples_order = samples_order_setting();
     if (const char* e = getenv("PIGS_GAUSS_STRIPS")) env.gauss_strips = e[0] == '1';
+    if (const char* e = getenv("PIGS_STATS_HOME")) env.stats_home = e[0] != '0';
     if (bbox) env.bbox_blocks = atoi(bbox) == 512 ? 512 : 256;
     env.no_ahead = no_ahead;
     return env;
@@ -218,16 +219,38 @@ static void note_order(const SamplesLayout& s, const void* sws, hipStream_t stre
     if (o->st.rf != 0u) ++o->st.streak;
     if (!o->pending && o->st.copy_due(nth)) g_order.request(*o, (const char*)sws + s.off_params, stream);
 }
-// behind a list build.  trusted: its guard's word is wanted home soon
-static void note_points(const PlanLayout& p, const void* ws, hipStream_t stream, bool trusted = false) {
+// In front of a build that ends in its list launch: count it and, when its statistics are due at home, reserve the slot
+// they go to (null: not due, or inside a capture).  trusted: its guard's word is wanted home soon.
+static PointsMemory::Slot* points_due(const PlanLayout& p, hipStream_t stream, bool trusted) {
     int dev = 0;
-    if (stream_capturing(stream) || !current_device(&dev)) return;
+    if (stream_capturing(stream) || !current_device(&dev)) return nullptr;
     std::lock_guard<std::mutex> lock(g_memory_mu);
     auto* h = g_points.find(dev, PointsKey{p.N, p.M}, true);
-    if (!h) return;
+    if (!h) return nullptr;
     const uint32_t nth = h->st.builds++;
-    if (!h->pending && h->st.copy_due(nth, trusted))
-        g_points.request(*h, &((const PlanParams*)((const char*)ws + p.off_params))->n_points, stream);
+    if (h->pending || !h->st.copy_due(nth, trusted)) return nullptr;
+    g_points.reserve(*h);
+    return h;
+}
+// ... the slot's words as the list launch addresses them, zeroed but for the one the host knows (ListArgs::home)
+static uint32_t* points_home(PointsMemory::Slot& h, bool strips) {
+    std::lock_guard<std::mutex> lock(g_memory_mu);
+    uint32_t* home = g_points.home(h);
+    h.host[HOME_STRIPS] = strips ? 1u : 0u;
+    return home;
+}
+// ... and behind the build's launches (ok: they were issued): the event behind the list launch's stores, or
+// (home == null, PIGS_STATS_HOME=0) the copy of the five words from PlanParams::n_points on and its event
+static void note_points(PointsMemory::Slot& h, bool ok, const uint32_t* home, const PlanLayout& p, const void* ws, hipStream_t stream) {
+    std::lock_guard<std::mutex> lock(g_memory_mu);
+    if (!ok) g_points.release(h);
+    else if (home) g_points.sent(h, stream);
+    else g_points.request(h, &((const PlanParams*)((const char*)ws + p.off_params))->n_points, stream);
+}
+
+// behind the list launch of a plan with deferred lists (the first sampling call's): count it and, when due, copy
+static void note_deferred_points(const PlanLayout& p, const void* ws, hipStream_t stream) {
+    if (PointsMemory::Slot* due = points_due(p, stream, false)) note_points(*due, true, nullptr, p, ws, stream);
 }
 
 // The sampling launches' question (staging, PlanView::stage): did the point set of this size arrive in no order?
@@ -340,7 +363,7 @@ static ListArgs make_list_args(const PlanLayout& p, const SamplesLayout& s, void
     la.ptiles = (uint32_t*)((char*)ws + p.off_ptiles);
     la.n_points = &((PlanParams*)((char*)ws + p.off_params))->n_points;
     la.points_wanted = &((PlanParams*)((char*)ws + p.off_params))->points_wanted;
-    la.parea = (const float*)((char*)ws + p.off_parea);
+    la.parea = (const float*)((char*)ws + p.off_parea);      // (run_build: null unless the build's statistics are wanted home)
     la.strip_cover = &((PlanParams*)((char*)ws + p.off_params))->strip_cover;
     la.product = lists_product_setting();
     return la;
@@ -393,9 +416,20 @@ static int run_build(const BuildRequest& r, void* sws, size_t sws_bytes, void* w
     a.fwd_only = b.fwd_only; a.ahead = b.ahead; a.s_scan_in_scatter = b.s_scan_in_scatter; a.sort_in_count = b.sort_in_count;
     a.strips = b.strips; a.trusted = b.trusted;
     const bool lists = r.do_plan && r.build_lists && !r.defer_lists;
+    // Are this build's statistics due at home (PointsState::copy_due)?  Then the pack leaves its strips' areas, the list
+    // launch sums them and stores every word that is not zero into the memory's slot itself (ListArgs::home).  With
+    // PIGS_STATS_HOME=0 every build measures, as every build did, and a due one is followed by a copy.
+    PointsMemory::Slot* due = lists ? points_due(p, stream, b.trusted) : nullptr;
+    // (Deferred lists are built by the first sampling call, which knows nothing of this one: they measure every time and
+    // keep the copy -- note_deferred_points.)
+    const bool deferred = r.do_plan && r.build_lists && r.defer_lists;
+    const bool measure = deferred || (lists && (due || !env.stats_home));
+    if (!measure) a.parea = nullptr;
     ListArgs la{};
     if (lists) {
         la = make_list_args(p, s, ws, sws, r.q_max, a.q_max);
+        if (!measure) la.parea = nullptr;
+        if (due && env.stats_home) la.home = points_home(*due, b.strips);
         if (b.trusted) {      // the guard (plan_lists.h): every tile's real box against its share of the remembered one
             la.lattice_broken = &a.params->lattice_broken;
             const float rf = (float)a.rf_hint, rs = (float)(r.M / a.rf_hint);
@@ -423,8 +457,8 @@ static int run_build(const BuildRequest& r, void* sws, size_t sws_bytes, void* w
     }
     const int rc = launch_status();
     if (r.do_plan) defer_set(ws, r.build_lists && r.defer_lists && rc == PIGS_OK, r.q_max, a.q_max);
+    if (due) note_points(*due, rc == PIGS_OK, la.home, p, ws, stream);
     if (rc != PIGS_OK) return rc;
-    if (lists) note_points(p, ws, stream, b.trusted);
     // (the samples header of a trusted build holds only what the build put there: nothing to ask for, one more to count)
     if (b.trusted || (r.do_samples && r.order == 0)) note_order(s, sws, stream, b.trusted);
     return rc;
@@ -618,7 +652,7 @@ int plan_forward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, f
     if (first) la = make_list_args(p, s, ws, sws, d.q_f, d.q_wide);
     const int rc = a.c == 1 ? plan_forward_c<1>(pv, sv, cm, o, a, stream, first ? &la : nullptr)
                             : plan_forward_c<2>(pv, sv, cm, o, a, stream, first ? &la : nullptr);
-    if (first && rc == PIGS_OK) note_points(p, ws, stream);
+    if (first && rc == PIGS_OK) note_deferred_points(p, ws, stream);
     return rc;
 }
 
@@ -637,7 +671,7 @@ int plan_backward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, 
             launch_lists(list_launch(s.ntiles), make_list_args(p, s, ws, sws, d.q_f, d.q_wide), stream);
             const int rc = launch_status();
             if (rc != PIGS_OK) return rc;
-            note_points(p, ws, stream);
+            note_deferred_points(p, ws, stream);
         }
     }
     const float* g[4];

@@ -75,7 +75,8 @@ struct BuildArgs {
                             // points that are no lattice are counted, scanned AND scattered by the samples' workgroups
                             // of launch 2, behind two device-wide barriers among them (samples_sort_in_count)
     // STRIPS (plan.h, PlanParams::strips): the Gaussians keep the caller's order -- gauss_pack_part instead of count,
-    // scan and scatter; `parea` is written by builds of either kind (the statistic the library decides from)
+    // scan and scatter; `parea` is written by builds of either kind (the statistic the library decides from) whose
+    // statistics are wanted home, null in every other build (plan.hip, run_build)
     int strips;
     int fwd_only;         // PIGS_BUILD_FORWARD_ONLY (PlanParams::fwd_only): q_max = q_f = q_b
     // TRUSTED build (plan.hip, run_build): point sets of this size have long been the same compact lattice, so nobody looks
@@ -385,9 +386,8 @@ __device__ __forceinline__ void samples_hist_part(const BuildArgs& a, uint32_t w
 
 // The Gaussians' half of the count: cell key (level by size, cell by centre) and rank of every Gaussian.  `box`: the
 // samples' bounding box the grid's domain is laid over -- of this build, or (BuildArgs::ahead) of the last one.
-struct GaussLoad { float m[2], c[3]; };
-// One Gaussian into its place (in cell order, or -- PlanParams::strips -- its own): records, the box the list build
-// tests first, the way back.
+struct GaussLoad { float m[2], c[3], v[2]; };      // (v: loaded by builds that keep the caller's order alone)
+// One Gaussian into its place in cell order: records, the box the walk through the cells tests first, the way back.
 __device__ __forceinline__ void gauss_scatter_one(const BuildArgs& a, uint32_t i, uint32_t pos) {
     float v[2] = {0.f, 0.f};
     for (int k = 0; k < a.c; ++k) v[k] = a.values[(size_t)i * a.c + k];
@@ -432,6 +432,9 @@ __device__ __forceinline__ void strip_box(const BuildArgs& a, uint32_t i, bool v
     if (first && i < a.N) {
         const uint32_t strip = i / STRIP;
         if (store) a.pbox[strip] = make_float4(x0, y0, x1, y1);
+    }
+    if (first && i < a.N && a.parea) {      // (launch-uniform: the build's statistics are wanted home)
+        const uint32_t strip = i / STRIP;
         // inside the domain only: what lies outside meets no tile
         const float dx = box[2] - box[0], dy = box[3] - box[1];
         const float w = fminf(x1, box[2]) - fmaxf(x0, box[0]), h = fminf(y1, box[3]) - fmaxf(y0, box[1]);
@@ -452,23 +455,38 @@ __device__ __forceinline__ void strip_box(const BuildArgs& a, uint32_t i, bool v
     }
 }
 // A build that keeps the caller's order (PlanParams::strips): records, boxes and the way back at position i itself, the
-// strip's box beside them -- the whole Gaussian half of a build in one pass, no atomics.
+// strip's box beside them -- the whole Gaussian half of a build in one pass, no atomics.  Everything comes from the
+// registers gauss_count_load filled (one round trip to memory, nothing is loaded again), and only what a plan of strips
+// reads is written: `gbox` belongs to the walk through the cells (grid_walk.h, traverse) and is left alone -- 16 B per
+// Gaussian that every launch boundary would write back.
 __device__ __forceinline__ void gauss_pack_part(const BuildArgs& a, uint32_t i, const float* box, const GaussLoad& ld) {
     const bool valid = i < a.N;
     float hx = 0.f, hy = 0.f;
     if (valid) {
-        gauss_scatter_one(a, i, i);
+        // {mux, muy, a, b}, {c, v0, v1, 0}
+        a.rec[2 * i] = make_float4(ld.m[0], ld.m[1], ld.c[0], ld.c[1]);
+        a.rec[2 * i + 1] = make_float4(ld.c[2], ld.v[0], ld.v[1], 0.f);
+        if (i == 0) {         // record N: all zero (gauss_scatter_one)
+            a.rec[2 * (size_t)a.N] = make_float4(0.f, 0.f, 0.f, 0.f);
+            a.rec[2 * (size_t)a.N + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        a.g2o[i] = i;
         const float k = a.q_max / (ld.c[0] * ld.c[2] - ld.c[1] * ld.c[1]);
-        hx = sqrtf(k * ld.c[2]) * 1.0001f; hy = sqrtf(k * ld.c[0]) * 1.0001f;      // (as gbox holds them)
+        hx = sqrtf(k * ld.c[2]) * 1.0001f; hy = sqrtf(k * ld.c[0]) * 1.0001f;      // (as gbox would hold them)
     }
     strip_box(a, i, valid, ld.m[0], ld.m[1], hx, hy, box, true);
 }
 __device__ __forceinline__ GaussLoad gauss_count_load(const BuildArgs& a, uint32_t bid) {      // (issued early: flies while the box is reduced)
-    GaussLoad ld = {{0.f, 0.f}, {0.f, 0.f, 0.f}};
+    GaussLoad ld = {{0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f}};
     const uint32_t i = bid * 256 + threadIdx.x;
     if (i < a.N) {
         ld.m[0] = a.means[2 * i]; ld.m[1] = a.means[2 * i + 1];
         ld.c[0] = a.conics[3 * i]; ld.c[1] = a.conics[3 * i + 1]; ld.c[2] = a.conics[3 * i + 2];
+        if (a.strips) {       // (launch-uniform) the pack forms the records from these registers
+#pragma unroll
+            for (int k = 0; k < 2; ++k)
+                if (k < a.c) ld.v[k] = a.values[(size_t)i * a.c + k];
+        }
     }
     return ld;
 }
@@ -617,7 +635,7 @@ __global__ __launch_bounds__(256) void plan_count_kernel(BuildArgs a) {
             pt[k] = i < a.M ? ((const float2*)a.samples)[i] : make_float2(0.f, 0.f);
         }
     };
-    GaussLoad gld = {{0.f, 0.f}, {0.f, 0.f, 0.f}};
+    GaussLoad gld = {{0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f}};
     if (gpart) gld = gauss_count_load(a, bid);
     else if (!a.coarse && lat_rf == 0u) load_points();
     float sbox[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};

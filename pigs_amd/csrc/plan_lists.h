@@ -52,8 +52,14 @@ struct ListArgs {
     uint32_t* n_points;   //   and its length (PlanParams::n_points, zeroed by the count kernel)
     uint32_t* points_wanted;   // PlanParams::points_wanted
     float q_f;            // the narrow cut-off (pv.q_max is the wide one)
-    const float* parea;   // per strip: box area / domain area (written by the build's Gaussian pass)
-    float* strip_cover;   //   their sum (PlanParams::strip_cover)
+    const float* parea;   // per strip: box area / domain area (written by the build's Gaussian pass; null: this build's
+    float* strip_cover;   //   statistics are not wanted home, nobody sums them) and their sum (PlanParams::strip_cover)
+    // Where this build's statistics come home: the device address of the five words of a slot of the plans' memory
+    // (build_choice.h, POINTS_WORDS; pinned host memory that the host zeroed before the launch), or null -- not due, a
+    // capture, or they travel by a copy of the workspace header (PIGS_STATS_HOME=0).  Every word is stored where it comes
+    // into being and only when it is not zero (stats_home): nothing waits for the end of the launch.  The workspace
+    // words stay the kernels' own working state.
+    uint32_t* home;
     uint32_t product;     // blocks whose group boxes form a product may take the product path (PIGS_LISTS_PRODUCT != 0)
     // The guard of a TRUSTED build (plan.hip, run_build; null: none -- every other build).  Nobody looked at the points in
     // front of this launch: they are taken in index-tiled order because point sets of this size have long been the same
@@ -67,6 +73,13 @@ struct ListArgs {
     uint32_t* lattice_broken;
     float guard_n[2], guard_e[2];
 };
+
+// one word of a build's statistics on its way home: a system-scope relaxed store (a plain vector store past the caches;
+// the host reads the word behind the event that follows the launch)
+__device__ __forceinline__ void stats_home(uint32_t* home, uint32_t word, uint32_t v) {
+    __hip_atomic_store(home + word, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+constexpr uint32_t HOME_N_POINTS = 0, HOME_STRIP_COVER = 1, HOME_STRIPS = 2, HOME_POINTS_WANTED = 3, HOME_LATTICE_BROKEN = 4;
 
 // the lists of the TPW tiles from tile0 (one wave).  TPW = 4 (a 4 x 4 block of sample cells: the traversal of the grid is
 // shared by four tiles) where the launch fills the chip; TPW = 1 for small point sets (LISTS_SMALL_TILES): the launch's
@@ -93,6 +106,20 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
         loff = pv.params->level_off[lane < PLAN_MAX_LEVELS ? lane : 0];   // lane = level: its first counter
     }
     const float INF = __builtin_huge_valf();
+    // lane 0: a tile for the queue of TILE_MODE_POINTS tiles / a block or tile of far-apart points met by a strips build.
+    // Whoever counts the first one sends the word home (a word at home says "any", not how many).
+    auto queue_points_tile = [&](uint32_t tile) {
+        const uint32_t k = atomicAdd(a.n_points, 1u);
+        a.ptiles[k] = tile;
+        if (k == 0u && a.home) stats_home(a.home, HOME_N_POINTS, 1u);
+    };
+    auto note_points_wanted = [&]() {
+        if (a.home) {
+            if (atomicAdd(a.points_wanted, 1u) == 0u) stats_home(a.home, HOME_POINTS_WANTED, 1u);
+        } else {
+            atomicAdd(a.points_wanted, 1u);
+        }
+    };
     SPoint sp[TPW];
     bool valid[TPW];
     const PointOrder po = point_order(a.sv);
@@ -172,14 +199,14 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
     // all: the traversal of such a box is the list build's own tail (thousands of candidates in one wave).
     if (strips && (bx1 - bx0) * gg.inv_s0 * ((by1 - by0) * gg.inv_s0) > POINTS_MODE_BLOCK_CELLS) {
         // far-apart points: the cells would have sent this block to the per-point walk -- say so (PlanParams::points_wanted)
-        if (lane == 0) atomicAdd(a.points_wanted, 1u);
+        if (lane == 0) note_points_wanted();
     }
     if (!strips && (bx1 - bx0) * gg.inv_s0 * ((by1 - by0) * gg.inv_s0) > POINTS_MODE_BLOCK_CELLS && walk_candidates() <= 4.f * (float)cap) {
         for (int t = 0; t < TPW; ++t) {
             if (tile0 + (uint32_t)t >= ntiles) break;
             if (lane < TILE_HDR_WORDS)
                 a.hdr[(size_t)(tile0 + (uint32_t)t) * TILE_HDR_WORDS + lane] = lane == 0 ? (TILE_MODE_POINTS << TILE_MODE_SHIFT) : 0u;
-            if (lane == 0) a.ptiles[atomicAdd(a.n_points, 1u)] = tile0 + (uint32_t)t;
+            if (lane == 0) queue_points_tile(tile0 + (uint32_t)t);
         }
         return;
     }
@@ -356,7 +383,10 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
         if (guard) {      // the trusted build's guard (ListArgs::lattice_broken); a comparison that NaN or inf fails: broken
             const float4 tb = lds.tbox[t];
             const float wx = tb.z - tb.x, wy = tb.w - tb.y;
-            if (!(wx * a.guard_n[0] <= a.guard_e[0] && wy * a.guard_n[1] <= a.guard_e[1]) && lane == 0) *a.lattice_broken = 1u;
+            if (!(wx * a.guard_n[0] <= a.guard_e[0] && wy * a.guard_n[1] <= a.guard_e[1]) && lane == 0) {
+                *a.lattice_broken = 1u;
+                if (a.home) stats_home(a.home, HOME_LATTICE_BROKEN, 1u);
+            }
         }
         const bool tl_over = FWD_ONLY ? goverflow[t] : overflow[t];      // (no tile list: its group lists decide)
         overflow[t] = tl_over && goverflow[t];            // from here on: the tile needs the ranges fallback
@@ -369,13 +399,13 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
             const float4 tb = lds.tbox[t];
             const float wx = tb.z - tb.x, wy = tb.w - tb.y;
             if (strips && wx * gg.inv_s0 * (wy * gg.inv_s0) > POINTS_MODE_MIN_CELLS) {
-                if (lane == 0) atomicAdd(a.points_wanted, 1u);
+                if (lane == 0) note_points_wanted();
             }
             if (!strips && wx * gg.inv_s0 * (wy * gg.inv_s0) > POINTS_MODE_MIN_CELLS && walk_candidates() <= 4.f * (float)(longest < cap ? longest : cap)) {
                 overflow[t] = false; rebuild[t] = false;
                 if (lane < 5)
                     a.hdr[(size_t)(tile0 + (uint32_t)t) * TILE_HDR_WORDS + lane] = lane == 0 ? (TILE_MODE_POINTS << TILE_MODE_SHIFT) : 0u;
-                if (lane == 0) a.ptiles[atomicAdd(a.n_points, 1u)] = tile0 + (uint32_t)t;
+                if (lane == 0) queue_points_tile(tile0 + (uint32_t)t);
                 continue;
             }
         }
@@ -454,7 +484,7 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
         if (!strips && (tx1 - tx0) * gg.inv_s0 * ((ty1 - ty0) * gg.inv_s0) > POINTS_MODE_MIN_CELLS && walk_candidates() <= 4.f * (float)cap) {
             if (lane < 5)
                 a.hdr[(size_t)(tile0 + (uint32_t)t) * TILE_HDR_WORDS + lane] = lane == 0 ? (TILE_MODE_POINTS << TILE_MODE_SHIFT) : 0u;
-            if (lane == 0) a.ptiles[atomicAdd(a.n_points, 1u)] = tile0 + (uint32_t)t;
+            if (lane == 0) queue_points_tile(tile0 + (uint32_t)t);
             continue;
         }
         uint32_t nr = 0;
@@ -488,11 +518,12 @@ template <int TPW>
 __device__ __forceinline__ uint32_t lists_tile0(int wave) {
     return (xcd_block_chunk<PIGS_XCD_CHUNK / TPW>(gridDim.x) * 4 + (uint32_t)wave) * TPW;
 }
-// the first workgroup of a list launch: the strips' cover of the domain (PlanParams::strip_cover), summed from what the
-// build's Gaussian pass left per strip
+// the first workgroup of a list launch whose statistics are wanted home (ListArgs::parea): the strips' cover of the
+// domain (PlanParams::strip_cover), summed from what the build's Gaussian pass left per strip.  Every other launch
+// leaves here at once and PlanParams::strip_cover as it was: only the way home reads it.
 __device__ __forceinline__ void lists_strip_cover(const ListArgs& a) {
     __shared__ float cover_sh[4];
-    if (blockIdx.x != 0) return;
+    if (blockIdx.x != 0 || a.parea == nullptr) return;      // (block-uniform)
     const uint32_t ns = (a.pv.N + STRIP - 1u) / STRIP;
     float sum = 0.f;
     for (uint32_t k = threadIdx.x; k < ns; k += 256u) sum += a.parea[k];
@@ -500,7 +531,12 @@ __device__ __forceinline__ void lists_strip_cover(const ListArgs& a) {
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
     if ((threadIdx.x & 63u) == 0u) cover_sh[threadIdx.x >> 6] = sum;
     __syncthreads();
-    if (threadIdx.x == 0) a.strip_cover[0] = cover_sh[0] + cover_sh[1] + cover_sh[2] + cover_sh[3];
+    if (threadIdx.x == 0) {
+        const float cover = cover_sh[0] + cover_sh[1] + cover_sh[2] + cover_sh[3];
+        a.strip_cover[0] = cover;
+        const uint32_t w = __builtin_bit_cast(uint32_t, cover);      // (0.0f is the zero word the host left there)
+        if (a.home && w != 0u) stats_home(a.home, HOME_STRIP_COVER, w);
+    }
 }
 
 template <int TPW, bool STRIPS, bool FWD_ONLY = false>
