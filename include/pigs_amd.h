@@ -866,6 +866,62 @@ int pigs_mlp_backward(int dtype, int64_t N, int L, const int* widths, const void
                       const void* const* biases, const void* g_y, void* scratch, size_t scratch_bytes, void* g_x,
                       void* const* g_weights, void* const* g_biases, void* stream);
 
+/* ---- The dynamics network's input transform (additive to ABI 10) -------------------------------
+ * InputTransform (model_pn.py:51-152) as DynamicsNetwork.forward uses it (:237-249): t_params, the input of
+ * input_projection.  d = 2, c = 1..4 channels, p = pde_size = 1..4, float32 only.  Row-major device arrays:
+ *   means [N][2], full_covariances [N][4], u [N][c], boundaries [N], sample_u [N][c], sample_ux [N][2c],
+ *   sample_uxx [N][2c], sample_pde [N][p];
+ *   params: a host array of 36 device pointers, net * 6 + (W1, b1, W2, b2, W3, b3); net 0 is latent_net (the Conv1d
+ *     weights [out][in][1] read as [out][in]: (7 + 6c + p) -> 16 -> 32 -> 16, tanh after every layer), nets 1..5 are
+ *     transform_net, transform_u_net, transform_ux_net, transform_uxx_net, transform_pde_net (16 -> 48 -> 32 -> k^2, tanh
+ *     between the layers, k = 2, c, 2c, 2c, p);
+ *   latent [16]; matrices [4 + 9 c^2 + p^2]: T [2][2], T_u [c][c], T_ux [2c][2c], T_uxx [2c][2c], T_pde [p][p], each
+ *     I + the net's output; t_params [N][5 + 6c + p].
+ *
+ * pigs_input_transform_matrices_forward, two launches (model_pn.py:104-119): the latent net over the concatenated row
+ *   (gathered from the eight arrays, no copy), one record of 16 sums per wave of live rows (at most 2 048 waves); then
+ *   one workgroup adds the records in a fixed order, divides by N, writes `latent` and runs the five nets.
+ * pigs_input_transform_apply_forward, one launch (model_pn.py:121-135, :137-152 and the cat of :241-249, :288-295):
+ *   t_params_n = (T Sigma_n, T_u u_n, boundaries_n, T_u sample_u_n, T_ux ux_n, T_uxx uxx_n, T_pde pde_n).  T means_n
+ *   is never used by the reference and is not computed.  boundaries may be NULL: zeros (:282).
+ * pigs_input_transform_apply_backward, one launch, two with g_matrices: from g_t_params to g_full_covariances [N][4] =
+ *   T^T g, g_u [N][c] = T_u^T g and g_matrices = sum_n g_n x_n^T (one record per wave, added in a fixed order).  A
+ *   NULL output is not written.
+ * pigs_input_transform_matrices_backward, one launch for the nets (recomputed from `latent`; their 30 gradients and
+ *   g_latent), and two more when a gradient through the latent net is wanted: g_means, g_full_covariances, g_u (the part
+ *   through the mean alone) and the six gradients of the latent net.  g_params is NULL or a host array of 36 device
+ *   pointers in the order of params; a NULL entry is not written.
+ * scratch: pigs_input_transform_scratch_bytes(N, c, p) bytes, 4-byte aligned; 0 for N < 1 or c, p outside 1..4.  It is
+ *   16 floats and min(ceil(N / 16), PIGS_MLP_MAX_RECORDS) records of the latent net's parameter count.  Not read by
+ *   the caller.
+ * Arguments are checked before any HIP call: a dtype other than PIGS_F32 or c, p outside 1..4 is PIGS_ERR_UNSUPPORTED;
+ *   N < 1, a null required array or entry, no gradient wanted, or a null, misaligned or short scratch where one is used
+ *   (always but in apply_forward and in apply_backward without g_matrices) is PIGS_ERR_INVALID.  No float atomics: every
+ *   output is a pure function of the inputs, bit for bit.  Nothing allocates, frees, synchronises or waits for another
+ *   workgroup.
+ */
+size_t pigs_input_transform_scratch_bytes(int64_t N, int c, int p);
+int pigs_input_transform_matrices_forward(int dtype, int64_t N, int c, int p, const void* means,
+                                          const void* full_covariances, const void* u, const void* boundaries,
+                                          const void* sample_u, const void* sample_ux, const void* sample_uxx,
+                                          const void* sample_pde, const void* const* params, void* scratch,
+                                          size_t scratch_bytes, void* latent, void* matrices, void* stream);
+int pigs_input_transform_matrices_backward(int dtype, int64_t N, int c, int p, const void* means,
+                                           const void* full_covariances, const void* u, const void* boundaries,
+                                           const void* sample_u, const void* sample_ux, const void* sample_uxx,
+                                           const void* sample_pde, const void* const* params, const void* latent,
+                                           const void* g_matrices, void* scratch, size_t scratch_bytes, void* g_means,
+                                           void* g_full_covariances, void* g_u, void* const* g_params, void* stream);
+int pigs_input_transform_apply_forward(int dtype, int64_t N, int c, int p, const void* matrices,
+                                       const void* full_covariances, const void* u, const void* boundaries,
+                                       const void* sample_u, const void* sample_ux, const void* sample_uxx,
+                                       const void* sample_pde, void* t_params, void* stream);
+int pigs_input_transform_apply_backward(int dtype, int64_t N, int c, int p, const void* matrices,
+                                        const void* full_covariances, const void* u, const void* sample_u,
+                                        const void* sample_ux, const void* sample_uxx, const void* sample_pde,
+                                        const void* g_t_params, void* scratch, size_t scratch_bytes,
+                                        void* g_full_covariances, void* g_u, void* g_matrices, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,11 @@ Public surface:
                             (pigs_amd.mlp; model_pn.py:154-174, 187-198, 203-226)
     FusedMLP                ``FusedMLP.from_sequential(seq)``: the same, as a module over an existing nn.Sequential
                             whose Parameters and state_dict keys it keeps
+    transform_matrices      the input transform's five matrices from the Gaussians (latent net, mean, five
+                            TransformNets) in two launches (pigs_amd.input_transform; model_pn.py:51-119)
+    apply_transforms        those matrices applied to the rows: ``t_params`` in one launch (model_pn.py:121-152, 237-249)
+    FusedInputTransform     ``FusedInputTransform.from_module(m)``: both, as a module over an existing InputTransform
+                            whose Parameters and state_dict keys it keeps
     build()                 compile the HIP library (hipcc, gfx950) and the native host extension in-tree
 """
 from .build import build_all as build  # noqa: F401  (libpigs_amd.so + the native host extension)
@@ -51,4 +56,7 @@ def __getattr__(name):
     if name in ("fused_mlp", "FusedMLP"):
         from . import mlp
         return getattr(mlp, name)
+    if name in ("transform_matrices", "apply_transforms", "FusedInputTransform"):
+        from . import input_transform
+        return getattr(input_transform, name)
     raise AttributeError(name)

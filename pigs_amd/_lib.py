@@ -164,6 +164,13 @@ SIGNATURES = {
     "pigs_mlp_scratch_bytes": (ctypes.c_size_t, [_i64, _i, _ip]),
     "pigs_mlp_forward": (_i, [_i, _i64, _i, _ip, _vp, _vpp, _vpp, _vp, _vp]),
     "pigs_mlp_backward": (_i, [_i, _i64, _i, _ip, _vp, _vpp, _vpp, _vp, _vp, ctypes.c_size_t, _vp, _vpp, _vpp, _vp]),
+    # the input transform (additive to ABI 10): dtype, N, c, p, the row arrays, ... ; params / g_params are 36 pointers
+    "pigs_input_transform_scratch_bytes": (ctypes.c_size_t, [_i64, _i, _i]),
+    "pigs_input_transform_matrices_forward": (_i, [_i, _i64, _i, _i] + [_vp] * 8 + [_vpp, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
+    "pigs_input_transform_matrices_backward": (_i, [_i, _i64, _i, _i] + [_vp] * 8 + [_vpp, _vp, _vp, _vp, ctypes.c_size_t]
+                                               + [_vp] * 3 + [_vpp, _vp]),
+    "pigs_input_transform_apply_forward": (_i, [_i, _i64, _i, _i] + [_vp] * 8 + [_vp, _vp]),
+    "pigs_input_transform_apply_backward": (_i, [_i, _i64, _i, _i] + [_vp] * 7 + [_vp, _vp, ctypes.c_size_t] + [_vp] * 3 + [_vp]),
 }
 
 _lib = None
