@@ -143,7 +143,7 @@ def test_replicated_is_identity_without_process_group():
 
 class _FlatGrads(torch.autograd.Function):
     """Stands in for the sampler's backward: the three gradients are views of ONE flat allocation
-    [means | values | conics] (pigs_amd/sampler.py::_gradient_views, csrc_host/pigs_host.cpp::gradient_views)."""
+    [means | values | conics] (pigs_amd/host_ctypes.py::_gradient_views, csrc_host/pigs_host.cpp::gradient_views)."""
 
     @staticmethod
     def forward(ctx, means, values, conics, w):

@@ -139,7 +139,7 @@ def test_backward_on_forward_only_workspace_writes_nan(hip_lib):
     """The C ABI: pigs_plan_backward / pigs_residual_backward on a workspace built with PIGS_BUILD_FORWARD_ONLY write NaN
     gradients (the plan's own flag, read on the device) -- never a gradient with terms missing.  The raw helper
     backward_raw runs such a plan's backward on a full plan of the same inputs and agrees with one."""
-    from pigs_amd import sampler as S
+    from pigs_amd import host_ctypes as S
     dev = torch.device("cuda")
     gs = synthetic.lattice_gaussians(32, 32, 0.7, seed=5)
     pts = synthetic.grid_samples(96, 96).float().to(dev)
@@ -218,7 +218,7 @@ def test_raw_backward_on_forward_only_plans_runs_full_on_both_hosts(hip_lib):
     a no_grad preprocess built: both run the backward on a full plan of the same inputs (built once, kept with the
     forward-only plan) and give a full plan's gradients, not NaN."""
     from diff_gaussian_sampling import GaussianSampler
-    from pigs_amd import sampler as S
+    from pigs_amd import host_ctypes as S
     from pigs_amd import _pigs_host
     dev = torch.device("cuda")
     gs = synthetic.lattice_gaussians(40, 40, 0.8, seed=7)

@@ -83,7 +83,7 @@ def test_residual_and_backward_as_first_calls(Sampler, hip_lib):
     """The C ABI directly: a residual forward as the first call (fused), and a BACKWARD as the first call on a plan
     with deferred lists (the list launch runs in front of it)."""
     import ctypes
-    from pigs_amd import sampler as S
+    from pigs_amd import host_ctypes as S
     t, pts, args = problem(1, seed=9)
     p64 = pts.cpu().double().numpy()
     s = Sampler(False, backend="binned", defer_lists=True)

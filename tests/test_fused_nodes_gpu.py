@@ -1,6 +1,6 @@
 """GPU: the five fused outputs -- residual() in its linear, general and coupled form, vorticity_terms() and
 vorticity_residual() -- share ONE autograd node and ONE call path per host (pigs_host.cpp FusedBackward / fused_apply,
-sampler.py _FusedFunction / _fused_call).  What that could break is state leaking from one operator's node into
+host_ctypes.py _FusedFunction / _fused_call).  What that could break is state leaking from one operator's node into
 another's: the wrong entry point, coefficient block, record (aux) or target edge.
 
 All five are created after one preprocess and differentiated in reverse order of creation with all five nodes alive;

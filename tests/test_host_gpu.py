@@ -1,5 +1,5 @@
 """The two host sides of GaussianSampler -- the native C++ torch extension (pigs_amd/_pigs_host.so, the
-default) and the ctypes host (pigs_amd/sampler.py) -- drive the same C ABI and must agree; and what a
+default) and the ctypes host (pigs_amd/host_ctypes.py) -- drive the same C ABI and must agree; and what a
 hipGraph capture may and may not share with eager calls (the sample-plan cache and the workspace
 pool stay out of a capture)."""
 import numpy as np
@@ -30,8 +30,9 @@ def case(n, res, kappa=0.8, seed=3, c=1, dev="cuda"):
 def test_native_extension_is_the_default_and_loaded(hip_lib):
     import sys
     from diff_gaussian_sampling import GaussianSampler
+    from pigs_amd import _pigs_host
     s = GaussianSampler(False)
-    assert s.host == "native" and s._core is not None
+    assert s.host == "native" and isinstance(s._core, _pigs_host.SamplerCore)
     assert "pigs_amd._pigs_host" in sys.modules
 
 

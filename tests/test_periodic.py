@@ -14,8 +14,7 @@ def test_constructor_validates_the_box(hip_lib, host):
     s = GaussianSampler(False, periodic=(-1, 1), host=host)
     assert s.periodic == (-1.0, 1.0)
     assert s.q_cut == max(s.q_max, s.q_max_backward, s.q_max_order3) == 44.0
-    if host == "native":
-        assert s._core.periodic == (-1.0, 1.0)
+    assert s._core.periodic == (-1.0, 1.0)
     assert GaussianSampler(False, host=host).periodic is None
     for bad in ((1, -1), (0.5, 0.5), (float("nan"), 1), (-1, float("inf")), (-1, 0, 1), (1,), 2.0, "ab", (None, 1)):
         with pytest.raises(ValueError):
@@ -87,13 +86,11 @@ def test_periodic_is_settable_and_reaches_both_hosts(hip_lib, host):
     s = GaussianSampler(False, host=host)
     s.periodic = (0, 3)
     assert s.periodic == (0.0, 3.0)
-    if host == "native":
-        assert s._core.periodic == (0.0, 3.0)
+    assert s._core.periodic == (0.0, 3.0)
     with pytest.raises(ValueError):
         s.periodic = (2, 1)
     assert s.periodic == (0.0, 3.0)
     s.periodic = None
     assert s.periodic is None
-    if host == "native":
-        assert s._core.periodic is None
+    assert s._core.periodic is None
     assert GaussianSampler(False, host=host, q_max_order3=50.0).q_cut == 50.0

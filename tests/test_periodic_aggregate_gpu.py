@@ -217,7 +217,7 @@ def test_grid_build_matches_the_plain_kernels_on_the_images(hip_lib):
     checker is out of reach; the comparison runs through the existing non-periodic kernels on the 9N image arrays
     (22 500 Gaussians, also sparse), arguments repeated, rows of block 0."""
     from diff_gaussian_sampling import GaussianSampler
-    from pigs_amd.sampler import periodic_images_raw
+    from pigs_amd.host_ctypes import periodic_images_raw
     n_side, L, K, F = 50, 4, 4, 3
     N = n_side * n_side
     m64, c64 = lattice(n_side, seed=7)

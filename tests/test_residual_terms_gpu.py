@@ -366,7 +366,7 @@ def test_floats_alone_stay_on_the_linear_kernel(hip_lib, backend):
     pigs_residual_forward through the C ABI on the same inputs (and plan)."""
     import ctypes
     from diff_gaussian_sampling import GaussianSampler
-    from pigs_amd import sampler as S
+    from pigs_amd import host_ctypes as S
     gs = synthetic.lattice_gaussians(20, 20, 1.1, seed=8)
     m, v, con = (gs[k].float().cuda().contiguous() for k in ("means", "values", "conics"))
     pts = (torch.rand((1500, 2), generator=torch.Generator().manual_seed(3)) * 2 - 1).cuda()

@@ -369,7 +369,7 @@ def test_backward_on_forward_only_workspace_writes_nan(hip_lib):
     pigs_residual_backward does (tests/test_forward_only_gpu.py) -- never a gradient with terms missing; the forward on it
     serves.  The raw helper runs such a plan's backward on a full plan of the same inputs and agrees with one."""
     import ctypes
-    from pigs_amd import sampler as S
+    from pigs_amd import host_ctypes as S
     t, pts, w = small_problem(M=3000, grad=False, n=32)
     m, v, c = (x.contiguous() for x in t)
     N, M = m.shape[0], pts.shape[0]

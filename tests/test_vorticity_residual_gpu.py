@@ -355,7 +355,7 @@ def test_differentiable_call_rebuilds_a_forward_only_plan(hip_lib, host):
 
 
 def test_no_grad_call_allocates_no_aux(hip_lib):
-    from pigs_amd import sampler as S
+    from pigs_amd import host_ctypes as S
     from diff_gaussian_sampling import GaussianSampler
     t, pts, w, tau, prev = small()
     seen = []
@@ -383,7 +383,7 @@ def test_backward_on_forward_only_workspace_writes_nan(hip_lib):
     """The C ABI: pigs_vorticity_residual_backward on a PIGS_BUILD_FORWARD_ONLY workspace writes NaN gradients, as every
     backward entry does; the forward on it serves."""
     from pigs_amd import _lib
-    from pigs_amd import sampler as S
+    from pigs_amd import host_ctypes as S
     t, pts, w, tau, prev = small(M=3000, grad=False, n=32)
     m, v, c = (x.contiguous() for x in t)
     N, M = m.shape[0], pts.shape[0]
