@@ -8,7 +8,7 @@ import os
 # torch must be imported before libpigs_amd.so is loaded: both need libamdhip64, and the library
 # must bind to the HIP runtime instance PyTorch brings along (loaded the other way round, the
 # process holds two runtimes and ours reports "no ROCm-capable device").
-import torch  # noqa: F401
+import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # PIGS_AMD_LIB selects another build of the same ABI (kernel experiments); default: in-tree library
@@ -23,6 +23,27 @@ _i64 = ctypes.c_int64
 _ip = ctypes.POINTER(ctypes.c_int)          # a host array of ints
 _vpp = ctypes.POINTER(ctypes.c_void_p)      # a host array of device pointers
 
+DTYPES = {torch.float32: PIGS_F32, torch.float64: PIGS_F64}
+
+
+def ptr(t):
+    """The device pointer of a tensor; null for None and for an empty tensor."""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else ctypes.c_void_p(0)
+
+
+def pointers(tensors):
+    """A host array of device pointers; null for None."""
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() if t is not None else None for t in tensors])
+
+
+_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+
+
+def stream(device):
+    # the current stream's handle: the raw getter skips building a torch.cuda.Stream object (5 us a call)
+    if _raw_stream is not None and device.index is not None:
+        return ctypes.c_void_p(_raw_stream(device.index))
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 class PigsResidualTerms(ctypes.Structure):

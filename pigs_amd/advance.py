@@ -30,26 +30,17 @@ Gradients may arrive at any subset of the nine outputs and leave towards means, 
 d = 2, c = 1..4, float32 / float64, contiguous GPU tensors, N >= 1; no CPU fallback.  Capturable into a hipGraph.
 """
 import collections
-import ctypes
 
 import torch
 
 from . import _lib
+from ._lib import DTYPES as _DTYPES, ptr as _ptr, stream as _stream
 
-_DTYPES = {torch.float32: 0, torch.float64: 1}
 ADVANCE_PENALTY_COLUMNS = ("dmeans", "dscaling", "dtransforms", "du")
 DELTA_COLUMNS = 5        # dmeans 2, dscaling 2, dtransforms 1; then du c
 
 Advanced = collections.namedtuple(
     "Advanced", "means u scaling transforms covariances conics full_covariances full_conics penalty")
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _check(means, u, scaling, transforms, deltas, boundary_mask, wrap):

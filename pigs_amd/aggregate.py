@@ -31,19 +31,11 @@ import ctypes
 import torch
 
 from . import _lib
+from ._lib import DTYPES as _DTYPES, ptr as _ptr, stream as _stream
 
-_DTYPES = {torch.float32: _lib.PIGS_F32, torch.float64: _lib.PIGS_F64}
 BRUTE_MAX = 2048     # pigs_amd/csrc/aggregate.hip AGG_BRUTE_MAX: up to here every pair is tested, cap = N
 LDS_MAX = 163840     # PIGS_AGGREGATE_LDS_MAX of include/pigs_amd.h: the LDS of a CU
 MAX_NEIGHBORS = {torch.float32: 8192, torch.float64: 4096}      # slab size when the counting pass cannot be read back (capture)
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else ctypes.c_void_p(0)
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 class NeighborLists:

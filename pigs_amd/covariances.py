@@ -8,17 +8,11 @@ with the same argument meaning: ``s`` [N,2] variances (> 0), ``t`` [N,1] raw cor
 (squashed by tanh).  One HIP launch forward and one backward (C ABI: pigs_build_covariances*)
 instead of the reference's chain of small torch kernels; d = 2, float32 / float64, GPU only.
 """
-import ctypes
 
 import torch
 
 from . import _lib
-
-_DTYPES = {torch.float32: 0, torch.float64: 1}
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+from ._lib import DTYPES as _DTYPES, ptr as _ptr, stream as _stream
 
 
 def _check(s, t):
@@ -45,7 +39,7 @@ class _BuildCovariances(torch.autograd.Function):
         con = torch.empty((N, 3), dtype=sc.dtype, device=sc.device)
         with torch.cuda.device(sc.device):
             rc = lib.pigs_build_covariances(_DTYPES[sc.dtype], N, _ptr(sc), _ptr(tc), _ptr(cov), _ptr(con),
-                                            ctypes.c_void_p(torch.cuda.current_stream(sc.device).cuda_stream))
+                                            _stream(sc.device))
         _lib.check(rc, "pigs_build_covariances")
         ctx.save_for_backward(sc, tc)
         ctx.t_shape = t.shape
@@ -67,7 +61,7 @@ class _BuildCovariances(torch.autograd.Function):
         with torch.cuda.device(sc.device):
             rc = lib.pigs_build_covariances_backward(
                 _DTYPES[sc.dtype], N, _ptr(sc), _ptr(tc), _ptr(g_cov), _ptr(g_con), _ptr(g_s), _ptr(g_t),
-                ctypes.c_void_p(torch.cuda.current_stream(sc.device).cuda_stream))
+                _stream(sc.device))
         _lib.check(rc, "pigs_build_covariances_backward")
         return g_s, g_t.reshape(ctx.t_shape)
 

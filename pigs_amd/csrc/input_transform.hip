@@ -385,100 +385,6 @@ __global__ __launch_bounds__(256) void it_matrices_backward_kernel(int64_t N, in
     }
 }
 
-// One layer of the latent net's backward on a wave's tile (the three products at the head of mlp.hip), its tile counts
-// NTO x NTI fixed at compile time so that the accumulators are the registers the net needs and no more; nti <= NTI is the
-// real count of the first layer's input tiles.  d: dZ_l on entry; on exit dZ_{l-1}, or dA_0 when `first`.
-template <int NTO, int NTI>
-__device__ __forceinline__ void it_backward_layer(f4 (&d)[MLP_TILES], f4 (&acc_w)[NTO][NTI], f4 (&acc_b)[NTO], bool want_w,
-                                                  bool want_b, bool want_da, bool first, const float* __restrict__ W, int nti,
-                                                  const float* __restrict__ a_l, float* __restrict__ dz_t, int own, int r,
-                                                  int g) {
-    const int S = 16 * nti + 4;
-    if (want_b) {
-#pragma unroll
-        for (int to = 0; to < NTO; ++to) acc_b[to] += d[to];
-    }
-    if (want_w) {                              // dW += dZ^T a: the row sits on the lane in both, dZ goes through LDS
-        mlp_wave_fence();
-#pragma unroll
-        for (int t = 0; t < NTO; ++t) *reinterpret_cast<f4*>(dz_t + own + 16 * t) = d[t];
-        mlp_wave_fence();
-        f4 at[NTI];
-#pragma unroll
-        for (int ti = 0; ti < NTI; ++ti)
-#pragma unroll
-            for (int s = 0; s < 4; ++s) at[ti][s] = ti < nti ? a_l[(4 * s + g) * MLP_ROW + 16 * ti + r] : 0.0f;
-#pragma unroll
-        for (int to = 0; to < NTO; ++to) {
-            f4 dt;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) dt[s] = dz_t[(4 * s + g) * MLP_ROW + 16 * to + r];
-#pragma unroll
-            for (int ti = 0; ti < NTI; ++ti)
-                if (ti < nti) {
-#pragma unroll
-                    for (int s = 0; s < 4; ++s)
-                        acc_w[to][ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(dt[s], at[ti][s], acc_w[to][ti], 0, 0, 0);
-                }
-        }
-    }
-    if (!want_da) return;
-    f4 da[NTI];                                // dA^T = W^T dZ^T: the image read down a column
-#pragma unroll
-    for (int ti = 0; ti < NTI; ++ti) {
-        f4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (ti < nti) {
-#pragma unroll
-            for (int to = 0; to < NTO; ++to)
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(W[(16 * to + 4 * g + s) * S + 16 * ti + r], d[to][s], acc, 0, 0, 0);
-        }
-        da[ti] = acc;
-    }
-#pragma unroll
-    for (int t = 0; t < MLP_TILES; ++t) d[t] = f4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int ti = 0; ti < NTI; ++ti) {
-        if (first) {
-            d[ti] = da[ti];
-        } else {
-            const f4 al = *reinterpret_cast<const f4*>(a_l + own + 16 * ti);
-#pragma unroll
-            for (int s = 0; s < 4; ++s) d[ti][s] = da[ti][s] * fmaf(-al[s], al[s], 1.0f);
-        }
-    }
-}
-
-// a layer's part of the wave's record: dW [out][in], then db [out]
-template <int NTO, int NTI>
-__device__ __forceinline__ void it_record_layer(float* __restrict__ rec, const f4 (&acc_w)[NTO][NTI], const f4 (&acc_b)[NTO],
-                                                bool want_w, bool want_b, int in, int outw, int r, int g) {
-    if (want_w) {
-#pragma unroll
-        for (int to = 0; to < NTO; ++to)
-#pragma unroll
-            for (int ti = 0; ti < NTI; ++ti)
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    const int o = 16 * to + 4 * g + s, i = 16 * ti + r;
-                    if (o < outw && i < in) rec[o * in + i] = acc_w[to][ti][s];
-                }
-    }
-    if (want_b) {
-#pragma unroll
-        for (int to = 0; to < NTO; ++to)
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                float v = acc_b[to][s];
-#pragma unroll
-                for (int m = 1; m < 16; m <<= 1) v += __shfl_xor(v, m);      // the 16 row lanes of this g, a fixed tree
-                const int o = 16 * to + 4 * g + s;
-                if (r == 0 && o < outw) rec[outw * in + o] = v;
-            }
-    }
-}
-
 // The latent net's backward.  It recomputes the activations (a_0, a_1, a_2 to this wave's LDS tiles, the output in
 // registers); every live row's dZ of the last layer is (g_latent / N) (1 - a_3^2), a dead row's is zero; dW and db stay in
 // registers, one record per wave (mlp.hip's finishing launch adds them); dA_0 goes to the means, covariance and u columns.
@@ -520,12 +426,12 @@ __global__ __launch_bounds__(64 * MLP_WAVES) void it_latent_backward_kernel(int6
         for (int t = 0; t < MLP_TILES; ++t) d[t] = f4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int s = 0; s < 4; ++s) d[0][s] = live ? gl[s] * fmaf(-a[0][s], a[0][s], 1.0f) : 0.0f;
-        it_backward_layer<1, 2>(d, w2, b2, out.g_W[2] != nullptr, out.g_b[2] != nullptr, true, false, it_lds + n.woff[2], 2,
-                                acts + 2 * TILE, dz_t, own, r, g);
-        it_backward_layer<2, 1>(d, w1, b1, out.g_W[1] != nullptr, out.g_b[1] != nullptr, true, false, it_lds + n.woff[1], 1,
-                                acts + TILE, dz_t, own, r, g);
-        it_backward_layer<1, MLP_TILES>(d, w0, b0, out.g_W[0] != nullptr, out.g_b[0] != nullptr, want_x, true,
-                                        it_lds + n.woff[0], nti0, acts, dz_t, own, r, g);
+        mlp_backward_layer<1, 2>(d, w2, b2, out.g_W[2] != nullptr, out.g_b[2] != nullptr, true, false, it_lds + n.woff[2], 1, 2,
+                                 acts + 2 * TILE, dz_t, own, r, g);
+        mlp_backward_layer<2, 1>(d, w1, b1, out.g_W[1] != nullptr, out.g_b[1] != nullptr, true, false, it_lds + n.woff[1], 2, 1,
+                                 acts + TILE, dz_t, own, r, g);
+        mlp_backward_layer<1, MLP_TILES>(d, w0, b0, out.g_W[0] != nullptr, out.g_b[0] != nullptr, want_x, true,
+                                         it_lds + n.woff[0], 1, nti0, acts, dz_t, own, r, g);
         if (want_x && live) {
 #pragma unroll
             for (int s = 0; s < 4; ++s) {      // columns 0 .. 5 + c < 16: feature tile 0 only
@@ -544,26 +450,22 @@ __global__ __launch_bounds__(64 * MLP_WAVES) void it_latent_backward_kernel(int6
     // this wave's record; a wave without a tile (only past the last tile's wave) writes none
     if (first >= tiles) return;
     float* __restrict__ rec = records + first * n.P;
-    it_record_layer<1, MLP_TILES>(rec + n.poff[0], w0, b0, out.g_W[0] != nullptr, out.g_b[0] != nullptr, n.w[0], IT_LATENT, r, g);
-    it_record_layer<2, 1>(rec + n.poff[1], w1, b1, out.g_W[1] != nullptr, out.g_b[1] != nullptr, IT_LATENT, IT_H2, r, g);
-    it_record_layer<1, 2>(rec + n.poff[2], w2, b2, out.g_W[2] != nullptr, out.g_b[2] != nullptr, IT_H2, IT_LATENT, r, g);
+    mlp_record_layer<1, MLP_TILES>(rec, n.poff[0], w0, b0, out.g_W[0] != nullptr, out.g_b[0] != nullptr, n.w[0], IT_LATENT, r, g);
+    mlp_record_layer<2, 1>(rec, n.poff[1], w1, b1, out.g_W[1] != nullptr, out.g_b[1] != nullptr, IT_LATENT, IT_H2, r, g);
+    mlp_record_layer<1, 2>(rec, n.poff[2], w2, b2, out.g_W[2] != nullptr, out.g_b[2] != nullptr, IT_H2, IT_LATENT, r, g);
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------
-static int64_t it_records(int64_t N) {
-    const int64_t tiles = (N + 15) / 16;
-    return tiles < PIGS_MLP_MAX_RECORDS ? tiles : PIGS_MLP_MAX_RECORDS;
-}
-
-static int it_latent_record_floats(int c, int p) {
-    return IT_LATENT * (it_x_width(c, p) + 1) + IT_H2 * (IT_LATENT + 1) + IT_LATENT * (IT_H2 + 1);
-}
+struct ItWidths {
+    int w[4];
+};
+static ItWidths it_latent_widths(int c, int p) { return {{it_x_width(c, p), IT_LATENT, IT_H2, IT_LATENT}}; }
 
 static bool it_sizes_supported(int dtype, int c, int p) { return dtype == PIGS_F32 && c >= 1 && c <= 4 && p >= 1 && p <= 4; }
 
 static size_t it_scratch_bytes(int64_t N, int c, int p) {
     if (N < 1 || c < 1 || c > 4 || p < 1 || p > 4) return 0;
-    return (size_t)(IT_HEAD + it_records(N) * it_latent_record_floats(c, p)) * sizeof(float);
+    return (size_t)(IT_HEAD + mlp_records(N) * mlp_record_floats(3, it_latent_widths(c, p).w)) * sizeof(float);
 }
 
 static bool it_scratch_ok(const void* scratch, size_t bytes, int64_t N, int c, int p) {
@@ -579,10 +481,9 @@ static ItRows it_rows(int c, int p, const void* const (&in)[8]) {
 }
 
 static MlpNet it_latent_net(int c, int p, const void* const* params, int* lds_floats) {
-    const int widths[4] = {it_x_width(c, p), IT_LATENT, IT_H2, IT_LATENT};
     const void* const W[3] = {params[0], params[2], params[4]};
     const void* const b[3] = {params[1], params[3], params[5]};
-    return mlp_describe(3, widths, W, b, lds_floats);
+    return mlp_describe(3, it_latent_widths(c, p).w, W, b, lds_floats);
 }
 
 static bool it_params_missing(const void* const* params) {
@@ -664,7 +565,7 @@ int pigs_input_transform_matrices_backward(int dtype, int64_t N, int c, int p, c
             grads.g_W[l] = out.p[2 * l];
             grads.g_b[l] = out.p[2 * l + 1];
         }
-        const int64_t tiles = (N + 15) / 16, records = it_records(N);
+        const int64_t tiles = (N + 15) / 16, records = mlp_records(N);
         const size_t lds = (size_t)(lds_floats + MLP_WAVES * 4 * 16 * MLP_ROW) * sizeof(float);      // images, 4 tiles a wave
         static_assert((848 + 672 + 592 + MLP_WAVES * 4 * 16 * MLP_ROW) * sizeof(float) <= 64 * 1024, "the default LDS limit");
         hipLaunchKernelGGL(it_latent_backward_kernel, dim3((unsigned)((records + MLP_WAVES - 1) / MLP_WAVES)),
@@ -703,7 +604,7 @@ int pigs_input_transform_apply_backward(int dtype, int64_t N, int c, int p, cons
     if (!g_full_covariances && !g_u && !g_matrices) return PIGS_ERR_INVALID;
     if (g_matrices && !it_scratch_ok(scratch, scratch_bytes, N, c, p)) return PIGS_ERR_INVALID;
     const void* const in[8] = {nullptr, full_covariances, u, nullptr, sample_u, sample_ux, sample_uxx, sample_pde};
-    const int64_t tiles = (N + 15) / 16, records = it_records(N);
+    const int64_t tiles = (N + 15) / 16, records = mlp_records(N);
     float* recs = g_matrices ? (float*)scratch + IT_HEAD : nullptr;
     clear_hip_error();
     hipLaunchKernelGGL(it_apply_backward_kernel, dim3((unsigned)((records + MLP_WAVES - 1) / MLP_WAVES)), dim3(64 * MLP_WAVES),

@@ -31,8 +31,8 @@
 // order.  No float atomics: the gradients are a pure function of the inputs.  Masked rows hold g_y = 0, hence dZ = 0 in
 // every layer.
 //
-// The net's description, the staging and the forward helpers (mlp_stage, mlp_layer, mlp_tanh, ...) live in mlp_chain.h:
-// input_transform.hip runs the same chain over gathered rows.
+// The net's description, the staging, the forward helpers (mlp_stage, mlp_layer, mlp_tanh, ...) and the backward's layer
+// (mlp_backward_layer, mlp_record_layer) live in mlp_chain.h: input_transform.hip runs the same chain over gathered rows.
 #include <hip/hip_runtime.h>
 
 #include "launch.h"
@@ -105,66 +105,11 @@ __global__ __launch_bounds__(64 * MLP_WAVES) void mlp_backward_kernel(int64_t N,
 #pragma unroll
         for (int l = PIGS_MLP_MAX_LAYERS - 1; l >= 0; --l) {
             if (l >= n.L) continue;
-            const int nti = mlp_tiles(n.w[l]), nto = mlp_tiles(n.w[l + 1]), S = 16 * nti + 4;
-            const float* __restrict__ a_l = acts + l * 16 * MLP_ROW;
-            if (out.g_b[l]) {
-#pragma unroll
-                for (int to = 0; to < MLP_TILES; ++to) acc_b[l][to] += d[to];
-            }
-            if (out.g_W[l]) {
-                mlp_wave_fence();
-#pragma unroll
-                for (int t = 0; t < MLP_TILES; ++t) *reinterpret_cast<f4*>(dz_t + own + 16 * t) = d[t];
-                mlp_wave_fence();
-                f4 at[MLP_TILES];
-#pragma unroll
-                for (int ti = 0; ti < MLP_TILES; ++ti)
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) at[ti][s] = ti < nti ? a_l[(4 * s + g) * MLP_ROW + 16 * ti + r] : 0.0f;
-#pragma unroll
-                for (int to = 0; to < MLP_TILES; ++to)
-                    if (to < nto) {
-                        f4 dt;
-#pragma unroll
-                        for (int s = 0; s < 4; ++s) dt[s] = dz_t[(4 * s + g) * MLP_ROW + 16 * to + r];
-#pragma unroll
-                        for (int ti = 0; ti < MLP_TILES; ++ti)
-                            if (ti < nti) {
-#pragma unroll
-                                for (int s = 0; s < 4; ++s)
-                                    acc_w[l][to][ti] =
-                                        __builtin_amdgcn_mfma_f32_16x16x4f32(dt[s], at[ti][s], acc_w[l][to][ti], 0, 0, 0);
-                            }
-                    }
-            }
-            if (l == 0 && !out.g_x) break;
-            const float* __restrict__ W = mlp_lds + n.woff[l];
-            f4 da[MLP_TILES];
-#pragma unroll
-            for (int ti = 0; ti < MLP_TILES; ++ti) {
-                f4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (ti < nti) {
-#pragma unroll
-                    for (int to = 0; to < MLP_TILES; ++to)
-                        if (to < nto) {
-#pragma unroll
-                            for (int s = 0; s < 4; ++s)
-                                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(W[(16 * to + 4 * g + s) * S + 16 * ti + r], d[to][s],
-                                                                           acc, 0, 0, 0);
-                        }
-                }
-                da[ti] = acc;
-            }
-            if (l == 0) {
-                mlp_store_rows(out.g_x, da, row, live, n.w[0], g);
-            } else {
-#pragma unroll
-                for (int t = 0; t < MLP_TILES; ++t) {
-                    const f4 al = *reinterpret_cast<const f4*>(a_l + own + 16 * t);
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) d[t][s] = da[t][s] * fmaf(-al[s], al[s], 1.0f);
-                }
-            }
+            const bool want_da = l > 0 || out.g_x;
+            mlp_backward_layer<MLP_TILES, MLP_TILES>(d, acc_w[l], acc_b[l], out.g_W[l] != nullptr, out.g_b[l] != nullptr,
+                                                     want_da, l == 0, mlp_lds + n.woff[l], mlp_tiles(n.w[l + 1]),
+                                                     mlp_tiles(n.w[l]), acts + l * 16 * MLP_ROW, dz_t, own, r, g);
+            if (l == 0 && want_da) mlp_store_rows(out.g_x, d, row, live, n.w[0], g);
         }
     }
 
@@ -174,30 +119,8 @@ __global__ __launch_bounds__(64 * MLP_WAVES) void mlp_backward_kernel(int64_t N,
 #pragma unroll
     for (int l = 0; l < PIGS_MLP_MAX_LAYERS; ++l) {
         if (l >= n.L) continue;
-        const int in = n.w[l], outw = n.w[l + 1];
-        if (out.g_W[l]) {
-#pragma unroll
-            for (int to = 0; to < MLP_TILES; ++to)
-#pragma unroll
-                for (int ti = 0; ti < MLP_TILES; ++ti)
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) {
-                        const int o = 16 * to + 4 * g + s, i = 16 * ti + r;
-                        if (o < outw && i < in) rec[n.poff[l] + o * in + i] = acc_w[l][to][ti][s];
-                    }
-        }
-        if (out.g_b[l]) {
-#pragma unroll
-            for (int to = 0; to < MLP_TILES; ++to)
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    float v = acc_b[l][to][s];
-#pragma unroll
-                    for (int m = 1; m < 16; m <<= 1) v += __shfl_xor(v, m);      // the 16 row lanes of this g, a fixed tree
-                    const int o = 16 * to + 4 * g + s;
-                    if (r == 0 && o < outw) rec[n.poff[l] + outw * in + o] = v;
-                }
-        }
+        mlp_record_layer<MLP_TILES, MLP_TILES>(rec, n.poff[l], acc_w[l], acc_b[l], out.g_W[l] != nullptr,
+                                               out.g_b[l] != nullptr, n.w[l], n.w[l + 1], r, g);
     }
 }
 
@@ -228,7 +151,7 @@ __global__ __launch_bounds__(256) void mlp_finish_kernel(MlpNet n, MlpGrads out,
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------
-static int64_t mlp_records(int64_t N) {
+int64_t mlp_records(int64_t N) {
     const int64_t tiles = (N + 15) / 16;
     return tiles < PIGS_MLP_MAX_RECORDS ? tiles : PIGS_MLP_MAX_RECORDS;
 }
@@ -240,7 +163,7 @@ static bool mlp_widths_ok(int L, const int* widths) {
     return true;
 }
 
-static int mlp_record_floats(int L, const int* widths) {
+int mlp_record_floats(int L, const int* widths) {
     int P = 0;
     for (int l = 0; l < L; ++l) P += widths[l + 1] * (widths[l] + 1);
     return P;

@@ -1,6 +1,8 @@
 // The register-resident tanh chain on v_mfma_f32_16x16x4_f32, shared by mlp.hip (one per-Gaussian net per launch) and
-// input_transform.hip (the latent net, whose rows are gathered from eight arrays and summed instead of stored).  The
-// operand layout and the padded LDS images are described at the head of mlp.hip.
+// input_transform.hip (the latent net, whose rows are gathered from eight arrays and summed instead of stored).  It holds
+// the backward as well: one layer's three products (mlp_backward_layer) and its part of a wave's record
+// (mlp_record_layer), which mlp.hip instantiates at the widest net and input_transform.hip at the latent net's tile
+// counts.  The operand layout and the padded LDS images are described at the head of mlp.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -58,7 +60,10 @@ inline MlpNet mlp_describe(int L, const int* widths, const void* const* weights,
     return n;
 }
 
-// mlp.hip: the launch that adds `records` records of n.P floats in a fixed order into out.g_W / out.g_b
+// mlp.hip: the backward's records (one per wave, at most PIGS_MLP_MAX_RECORDS) and the floats of one; the launch that
+// adds `records` records of n.P floats in a fixed order into out.g_W / out.g_b
+int64_t mlp_records(int64_t N);
+int mlp_record_floats(int L, const int* widths);
 void mlp_finish_launch(const MlpNet& n, const MlpGrads& out, int records, const float* scratch, hipStream_t stream);
 
 #if defined(__HIPCC__)
@@ -142,6 +147,110 @@ __device__ __forceinline__ void mlp_tanh(f4 (&a)[MLP_TILES], const f4 (&z)[MLP_T
     for (int t = 0; t < MLP_TILES; ++t)
 #pragma unroll
         for (int s = 0; s < 4; ++s) a[t][s] = tanhf(z[t][s]);
+}
+
+// One layer of the backward on a wave's tile (the three products at the head of mlp.hip).  NTO x NTI are the tile counts
+// of the accumulators, fixed at compile time so that a net of known widths holds the registers it needs and no more;
+// nto <= NTO and nti <= NTI are the layer's real counts.  d: dZ_l on entry; on exit dZ_{l-1}, or dA_0 when `first`.
+// a_l: the layer's input in this wave's LDS region as [row][feature]; dz_t: the tile dZ_l passes through; own: where this
+// lane's four features of feature tile 0 lie in a tile.
+template <int NTO, int NTI>
+__device__ __forceinline__ void mlp_backward_layer(f4 (&d)[MLP_TILES], f4 (&acc_w)[NTO][NTI], f4 (&acc_b)[NTO], bool want_w,
+                                                   bool want_b, bool want_da, bool first, const float* __restrict__ W, int nto,
+                                                   int nti, const float* __restrict__ a_l, float* __restrict__ dz_t, int own,
+                                                   int r, int g) {
+    const int S = 16 * nti + 4;
+    if (want_b) {
+#pragma unroll
+        for (int to = 0; to < NTO; ++to) acc_b[to] += d[to];
+    }
+    if (want_w) {                              // dW += dZ^T a: the row sits on the lane in both, dZ goes through LDS
+        mlp_wave_fence();
+#pragma unroll
+        for (int t = 0; t < NTO; ++t) *reinterpret_cast<f4*>(dz_t + own + 16 * t) = d[t];
+        mlp_wave_fence();
+        f4 at[NTI];
+#pragma unroll
+        for (int ti = 0; ti < NTI; ++ti)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) at[ti][s] = ti < nti ? a_l[(4 * s + g) * MLP_ROW + 16 * ti + r] : 0.0f;
+#pragma unroll
+        for (int to = 0; to < NTO; ++to)
+            if (to < nto) {
+                f4 dt;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) dt[s] = dz_t[(4 * s + g) * MLP_ROW + 16 * to + r];
+#pragma unroll
+                for (int ti = 0; ti < NTI; ++ti)
+                    if (ti < nti) {
+#pragma unroll
+                        for (int s = 0; s < 4; ++s)
+                            acc_w[to][ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(dt[s], at[ti][s], acc_w[to][ti], 0, 0, 0);
+                    }
+            }
+    }
+    if (!want_da) return;
+    f4 da[NTI];                                // dA^T = W^T dZ^T: the image read down a column
+#pragma unroll
+    for (int ti = 0; ti < NTI; ++ti) {
+        f4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (ti < nti) {
+#pragma unroll
+            for (int to = 0; to < NTO; ++to)
+                if (to < nto) {
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)
+                        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(W[(16 * to + 4 * g + s) * S + 16 * ti + r], d[to][s], acc, 0,
+                                                                   0, 0);
+                }
+        }
+        da[ti] = acc;
+    }
+#pragma unroll
+    for (int t = NTI; t < MLP_TILES; ++t) d[t] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int ti = 0; ti < NTI; ++ti) {
+        if (first) {
+            d[ti] = da[ti];
+        } else {
+            const f4 al = *reinterpret_cast<const f4*>(a_l + own + 16 * ti);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) d[ti][s] = da[ti][s] * fmaf(-al[s], al[s], 1.0f);
+        }
+    }
+}
+
+// A layer's part of the wave's record, which starts at rec[base]: dW [out][in], then db [out].  An index is the lane's
+// part (o, r), the same in every tile and layer, plus the tiles' part, which is uniform: mlp.hip's kernel writes its
+// record with every accumulator still live, and has no registers for a lane's index per tile.
+template <int NTO, int NTI>
+__device__ __forceinline__ void mlp_record_layer(float* __restrict__ rec, int base, const f4 (&acc_w)[NTO][NTI],
+                                                 const f4 (&acc_b)[NTO], bool want_w, bool want_b, int in, int outw, int r,
+                                                 int g) {
+    if (want_w) {
+#pragma unroll
+        for (int to = 0; to < NTO; ++to)
+#pragma unroll
+            for (int ti = 0; ti < NTI; ++ti)
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const int o = 4 * g + s;      // element [o][r] of tile (to, ti)
+                    if (o < outw - 16 * to && r < in - 16 * ti)
+                        rec[base + 16 * (to * in + ti) + o * in + r] = acc_w[to][ti][s];
+                }
+    }
+    if (want_b) {
+#pragma unroll
+        for (int to = 0; to < NTO; ++to)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                float v = acc_b[to][s];
+#pragma unroll
+                for (int m = 1; m < 16; m <<= 1) v += __shfl_xor(v, m);      // the 16 row lanes of this g, a fixed tree
+                const int o = 4 * g + s;
+                if (r == 0 && o < outw - 16 * to) rec[base + outw * in + 16 * to + o] = v;
+            }
+    }
 }
 
 #endif  // __HIPCC__

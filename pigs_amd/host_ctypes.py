@@ -8,9 +8,7 @@ import threading
 import torch
 
 from . import _lib, aggregate
-
-_DTYPES = {torch.float32: _lib.PIGS_F32, torch.float64: _lib.PIGS_F64}
-
+from ._lib import DTYPES as _DTYPES, ptr as _ptr, stream as _stream
 
 TRACE = 4       # order index of the Hessian's trace (mask bit 16); it travels in pointer slot 2
 # the columns of GaussianSampler.vorticity_terms(): the field, its divergence, the vorticity w = d_x u_y - d_y u_x,
@@ -22,20 +20,6 @@ VORTICITY_RESIDUAL_COLUMNS = ("div", "r")
 
 def _out_shape(order, M, d, c):
     return (M, c) if order == TRACE else (M,) + (d,) * order + (c,)
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else ctypes.c_void_p(0)
-
-
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-def _stream(device):
-    # the current stream's handle: the raw getter skips building a torch.cuda.Stream object (5 us a call)
-    if _raw_stream is not None and device.index is not None:
-        return ctypes.c_void_p(_raw_stream(device.index))
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 class _on_device:

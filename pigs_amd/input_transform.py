@@ -26,30 +26,18 @@ give the same bits on every call), capturable into a hipGraph; no CPU fallback.
     t_params = net(means, full_covariances, u, boundaries, sample_u, sample_ux, sample_uxx, sample_pde)
     more = net.transform_gaussians(full_covariances2, u2, sample_u2, sample_ux2, sample_uxx2, sample_pde2)
 """
-import ctypes
 import math
 
 import torch
 
 from . import _lib
+from ._lib import pointers as _pointers, ptr as _ptr, stream as _stream
 
 LATENT, HIDDEN1, HIDDEN2, LATENT_HIDDEN = 16, 48, 32, (16, 32, 16)
 NET_NAMES = ("latent_net", "transform_net", "transform_u_net", "transform_ux_net", "transform_uxx_net", "transform_pde_net")
 # the order of ``params``: per net of NET_NAMES, (weight, bias) of its three layers
 PARAM_ORDER = tuple(f"{net}.layers.{2 * l}.{kind}" for net in NET_NAMES for l in range(3) for kind in ("weight", "bias"))
 ROW_NAMES = ("means", "full_covariances", "u", "boundaries", "sample_u", "sample_ux", "sample_uxx", "sample_pde")
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _pointers(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() if t is not None else None for t in tensors])
 
 
 def in_dims(c, p):

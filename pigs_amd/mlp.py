@@ -26,21 +26,10 @@ import ctypes
 import torch
 
 from . import _lib
+from ._lib import pointers as _pointers, ptr as _ptr, stream as _stream
 
 MAX_LAYERS = 6
 MAX_WIDTH = 48
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _pointers(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() if t is not None else None for t in tensors])
 
 
 def _check(x, weights, biases):

@@ -39,20 +39,12 @@ import ctypes
 import torch
 
 from . import _lib
+from ._lib import DTYPES as _DTYPES, ptr as _ptr, stream as _stream
 
-_DTYPES = {torch.float32: 0, torch.float64: 1}
 MEANS_MAPS = {"tanh": 0, "identity": 1}
 GROUPS = ("means", "values", "scaling", "transform")
 
 Gaussians = collections.namedtuple("Gaussians", "means values covariances conics")
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _check(raw_means, values, raw_scaling, transform):

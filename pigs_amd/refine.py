@@ -26,26 +26,17 @@ The criteria that choose the ``split`` mask, on the device and without a host wa
     threshold_mask    score > mean + k std, the rule of test_no_mlp.py:203-205
 """
 import collections
-import ctypes
 
 import torch
 
 from . import _lib
+from ._lib import DTYPES as _DTYPES, ptr as _ptr, stream as _stream
 
-_DTYPES = {torch.float32: 0, torch.float64: 1}
 MODES = {"split": 0, "clone": 1}
 ROWS_PER_WORKGROUP = 1024      # PIGS_REFINE_ROWS: rows per workgroup of the index kernels
 SCAN_WIDTH = 256               # PIGS_REFINE_SCAN_WIDTH: workgroup totals per pass of the one-workgroup scan
 
 Refined = collections.namedtuple("Refined", "means scaling transforms values source child")
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _mode(mode):
