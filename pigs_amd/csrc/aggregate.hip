@@ -172,8 +172,7 @@ __global__ __launch_bounds__(256) void aggregate_cast_kernel(int64_t N, const T*
 
 // Few Gaussians (N <= AGG_BRUTE_MAX): every pair is tested, one wave per row, candidates 64 at a time, list
 // order ascending (deterministic); no grid, no workspace traffic.  At the model's N = 1 600 this is two
-// launches of ~13 us where the grid costs six.
-constexpr int64_t AGG_BRUTE_MAX = 2048;
+// launches of ~13 us where the grid costs six.  (AGG_BRUTE_MAX: aggregate_choice.h)
 // PER: with both centres in the box |delta| < L per axis and every half extent below L (the two preconditions of
 // pigs_aggregate_lists_periodic, include/pigs_amd.h; neither is checked), only the shifts k_x in {0, -sign dx},
 // k_y in {0, -sign dy} can reach: four tests a pair.  A lane's hits are a bit set over k; entries ascend in
@@ -324,7 +323,7 @@ __global__ __launch_bounds__(256) void aggregate_lists_kernel(PlanView pv, int64
 // launch is a single generation of waves and the three rounds of ~140 neighbours run side by side instead
 // of one after the other) and 1 for many (throughput: no idle waves).
 // ------------------------------------------------------------------------------------------
-constexpr int PART = 136;       // values of a wave's partial result: 128 components + scalars
+// (PART, the values of a wave's partial result: aggregate_choice.h)
 
 // phase 2 of every kernel: acc += scale(t) * X[t][idx] over the cnt parked rows; `scale_of(t)` returns the
 // two candidates (wave-uniform, read from lane t), `second` chooses per lane.  Four rows per iteration:
@@ -719,7 +718,7 @@ __global__ __launch_bounds__(256) void aggregate_zero_kernel(T* a, int64_t na, T
 //   queries, keys [N][H][K]; transforms [H][L][L]; distance_transforms [H][L][2E];
 //   out [N][H][L]; lse [N][H]; acc [N][H][L + 2E]; dacc [N][H][L + 2E]; D [N][H]
 // ------------------------------------------------------------------------------------------
-constexpr int HMAX = PIGS_AGGREGATE_HEADS_MAX;
+// (HMAX: aggregate_choice.h)
 #define PIGS_FOR_HEADS(h) _Pragma("unroll") for (int h = 0; h < HMAX; ++h) if (h < H)
 
 // phase 2 of the forward: a parked value is read once and feeds H accumulators; `scale_of(h, t)` returns head h's two
@@ -1210,13 +1209,13 @@ static size_t cast_bytes(int dtype, int64_t N) {       // float32 copies of cent
 }
 
 size_t aggregate_workspace_bytes(int dtype, int64_t N) {
-    if (N <= AGG_BRUTE_MAX) return 256;          // every pair is tested: no grid
+    if (aggregate_lists_all_pairs(N)) return 256;          // every pair is tested: no grid
     const size_t g = aggregate_grid_bytes(N);
     return g == 0 ? 0 : cast_bytes(dtype, N) + g;
 }
 
 int aggregate_grid_info(int dtype, int64_t N, int64_t* info) {
-    if (N <= AGG_BRUTE_MAX || aggregate_workspace_bytes(dtype, N) == 0) return PIGS_ERR_UNSUPPORTED;     // no grid
+    if (aggregate_lists_all_pairs(N) || aggregate_workspace_bytes(dtype, N) == 0) return PIGS_ERR_UNSUPPORTED;     // no grid
     aggregate_grid_levels(N, info);
     info[0] += (int64_t)cast_bytes(dtype, N);
     return PIGS_OK;
@@ -1232,7 +1231,7 @@ static int aggregate_lists_t(int dtype, int64_t N, int64_t cap, const void* mean
                              int32_t* col_counts, int32_t* col_lists, int32_t* overflow, double lo, double period,
                              hipStream_t stream) {
     const dim3 grid((unsigned)((N + 3) / 4)), block(256);
-    if (N <= AGG_BRUTE_MAX) {
+    if (aggregate_lists_all_pairs(N)) {
         clear_hip_error();
         hipLaunchKernelGGL((aggregate_lists_brute_kernel<T, false, PER>), grid, block, 0, stream, N, cap, (const T*)means,
                            (const T*)conics, (T)q_max, row_counts, row_lists, overflow, (T)period);
@@ -1283,12 +1282,11 @@ int aggregate_lists(int dtype, int64_t N, int64_t cap, const void* means, const 
 #undef PIGS_AGG_LISTS
 }
 
-// LDS of a sampling kernel: four wave regions of `region` values; beyond 64 KB the launch has to ask for it.
+// A sampling kernel's dynamic LDS (aggregate_choice.h): beyond AGG_LDS_DEFAULT the launch has to ask for it.
 // *rc keeps the first refusal (the C API admits no shape beyond AGG_LDS_MAX, so this is a runtime that grants less).
 template <typename Kernel>
-static size_t sampling_lds(Kernel kernel, size_t elem, size_t region, int* rc) {
-    const size_t bytes = elem * 4 * region;
-    if (bytes > 64 * 1024) {
+static size_t sampling_lds(Kernel kernel, size_t bytes, int* rc) {
+    if (bytes > AGG_LDS_DEFAULT) {
         const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
         if (e != hipSuccess && *rc == PIGS_OK) {
             (void)hipGetLastError();
@@ -1298,78 +1296,20 @@ static size_t sampling_lds(Kernel kernel, size_t elem, size_t region, int* rc) {
     }
     return bytes;
 }
-// A wave's region, in values: the forward parks [features_j ; 4F sin / cos] and merges H partials; the backward by rows
-// keeps H dacc blocks and parks [H K keys ; F]; the backward by columns parks H (L + K) values.
-static size_t rows_region(int stride) { return (size_t)(64 * stride > PART ? 64 * stride : PART); }
-static size_t forward_region(int H, int L, int F) {
-    const size_t r = rows_region((L + 4 * F) | 1);
-    return r > (size_t)H * PART ? r : (size_t)H * PART;
-}
-static size_t backward_rows_region(int H, int K, int F) { return (size_t)H * PART + rows_region((H * K + F) | 1); }
-static size_t backward_cols_region(int H, int L, int K) { return rows_region((H * (L + K)) | 1); }
-// the most dynamic LDS any of the three sampling kernels asks for at these sizes (a CU has AGG_LDS_MAX = 160 KB)
-size_t aggregate_lds_bytes(int dtype, int H, int L, int K, int F) {
-    const size_t a = forward_region(H, L, F), b = backward_rows_region(H, K, F), c = backward_cols_region(H, L, K);
-    return (dtype == PIGS_F64 ? 8 : 4) * 4 * (a > b ? (a > c ? a : c) : (b > c ? b : c));
-}
-// THE size rule of every sampling entry point, in one place: 1 <= H <= HMAX, at most 128 components per kernel (two per
-// lane) and every kernel's LDS within a CU's.  A shape is admitted when neither H nor a component count is out of
-// range and aggregate_lds_bytes <= AGG_LDS_MAX.  Anything beyond is refused, not attempted.
-static bool components_ok(int H, int L, int K, int F) {
-    return H >= 1 && H <= HMAX && L + 2 * (4 * F + 1) <= 128 && H * K + F <= 128 && H * (L + K) <= 128;
-}
-size_t aggregate_heads_lds_bytes(int dtype, int H, int L, int K, int F) {      // 0: H or a component count out of range
-    return components_ok(H, L, K, F) ? aggregate_lds_bytes(dtype, H, L, K, F) : 0;
-}
-bool aggregate_admitted(int dtype, int H, int L, int K, int F) {
-    return components_ok(H, L, K, F) && aggregate_lds_bytes(dtype, H, L, K, F) <= AGG_LDS_MAX;
-}
 
-// Waves per Gaussian, one head: a launch of few Gaussians is one generation of waves bound by a wave's serial life
-// (split every Gaussian's rounds over four waves); many Gaussians are a throughput problem (no idle waves)
-static int waves_per_gaussian(int64_t N) { return N <= 4096 ? 4 : N <= 8192 ? 2 : 1; }
-
-// Waves per Gaussian, H >= 2.  Up to AGG_BRUTE_MAX Gaussians (the model's sizes) a launch is bound by a wave's serial
-// life, and several heads ask for more LDS than one, so fewer of their workgroups are resident at once: the waves per
-// Gaussian are halved while the launch's workgroups exceed what the device holds (AGG_CUS compute units, per CU what
-// the LDS request admits, at most the eight workgroups of 32 waves).
-// What stands behind the rule is ONE sweep (profiles/aggregate_heads.txt "waves per Gaussian"):
-// the model's shape, H = 2, N = 1 600, 4 / 2 / 1 waves, float32 and float64.  There it picks 1 wave for all three
-// kernels in both dtypes; that is the best or within 1 us of it for the kernel by rows and for float64's forward and
-// rows, and it passes over the better 2-wave launch of float32's forward (25.5 against 27.9 us), float32's columns
-// (60.1 against 65.5) and float64's columns (117.7 against 123.9): 800 workgroups against 768 resident.  It is
-// applied unmeasured to H = 3, 4 and to other shapes.  Beyond AGG_BRUTE_MAX: the one-head rule, as measured there.
-// It stays keyed on H: applied to H = 1 it would halve the waves at the model's N = 1 600 (1 600 workgroups against
-// 768 resident).
-constexpr int AGG_CUS = 256;                     // compute units of an MI355X (the one device this library is built for)
-static int heads_waves_per_gaussian(int64_t N, size_t lds_bytes) {
-    int wpg = waves_per_gaussian(N);
-    if (N > AGG_BRUTE_MAX) return wpg;
-    size_t per_cu = AGG_LDS_MAX / (lds_bytes > 0 ? lds_bytes : 1);
-    per_cu = per_cu > 8 ? 8 : per_cu < 1 ? 1 : per_cu;      // 32 waves a CU: eight workgroups of four
-    const int64_t resident = (int64_t)AGG_CUS * (int64_t)per_cu;
-    while (wpg > 1 && (N * wpg + 3) / 4 > resident) wpg >>= 1;
-    return wpg;
-}
-
+// The launchers: every size, waves per Gaussian and grid is the choice's (aggregate_choice.h).
 template <typename T, bool PER>
 static int aggregate_forward_t(const AggregateArgs& a, hipStream_t stream) {
+    const AggregateLaunch f = choose_aggregate_forward(a.dtype, 1, a.N, a.L, a.K, a.F);
     int rc = PIGS_OK;
-    const size_t lds = sampling_lds(aggregate_forward_kernel<T, PER>, sizeof(T), forward_region(1, a.L, a.F), &rc);
+    const size_t lds = sampling_lds(aggregate_forward_kernel<T, PER>, f.lds, &rc);
     if (rc != PIGS_OK) return rc;
-    const int wpg = waves_per_gaussian(a.N), gpw = 4 / wpg;
     clear_hip_error();
-    hipLaunchKernelGGL((aggregate_forward_kernel<T, PER>), dim3((unsigned)((a.N + gpw - 1) / gpw)), dim3(256), lds, stream, a.N, a.L, a.K,
-                       a.F, a.cap, wpg, (const T*)a.means, (const T*)a.conics, a.row_counts, a.row_lists, (const T*)a.features,
+    hipLaunchKernelGGL((aggregate_forward_kernel<T, PER>), dim3(f.grid), dim3(256), lds, stream, a.N, a.L, a.K,
+                       a.F, a.cap, f.wpg, (const T*)a.means, (const T*)a.conics, a.row_counts, a.row_lists, (const T*)a.features,
                        (const T*)a.transform, (const T*)a.queries, (const T*)a.keys, (const T*)a.frequencies,
                        (const T*)a.distance_transform, (T*)a.out, (T*)a.lse, (T*)a.acc, (T)a.period);
     return launch_status();
-}
-
-size_t aggregate_backward_scratch_bytes(int dtype, int64_t N, int H, int L, int F) {
-    const size_t e = dtype == PIGS_F64 ? 8 : 4;
-    const int W = L + 2 * (4 * F + 1);
-    return align_up(e * (size_t)N * (size_t)(H * (W + 1) + F), 256);      // dacc [N][H][W], D [N][H], per-row d frequencies [N][F]
 }
 
 template <typename T, bool PER>
@@ -1378,31 +1318,27 @@ static int aggregate_backward_t(const AggregateArgs& a, hipStream_t stream) {
     T* dacc = (T*)a.scratch;
     T* D = dacc + (size_t)a.N * W;
     T* gfr = D + a.N;
+    const AggregateBackwardChoice b = choose_aggregate_backward(a.dtype, 1, a.N, a.L, a.K, a.F);
     int rc = PIGS_OK;
-    const size_t lds_r = sampling_lds(aggregate_backward_rows_kernel<T, PER>, sizeof(T), backward_rows_region(1, a.K, a.F), &rc);
-    const size_t lds_c = sampling_lds(aggregate_backward_cols_kernel<T, PER>, sizeof(T), backward_cols_region(1, a.L, a.K), &rc);
+    const size_t lds_r = sampling_lds(aggregate_backward_rows_kernel<T, PER>, b.rows.lds, &rc);
+    const size_t lds_c = sampling_lds(aggregate_backward_cols_kernel<T, PER>, b.cols.lds, &rc);
     if (rc != PIGS_OK) return rc;
-    const int wpg = waves_per_gaussian(a.N), gpw = 4 / wpg;
-    const dim3 grid((unsigned)((a.N + gpw - 1) / gpw)), block(256);
-    // the sums over N: one split per ~2048 Gaussians (a single split is a plain, deterministic sum)
-    int splits = (int)((a.N + 2047) / 2048);
-    splits = splits < 1 ? 1 : splits > 64 ? 64 : splits;
+    const dim3 block(256);
     clear_hip_error();
-    if (splits > 1) {
-        const int64_t mx = (int64_t)a.L * (2 * E > a.L ? 2 * E : a.L);
-        hipLaunchKernelGGL((aggregate_zero_kernel<T>), dim3((unsigned)((mx + 255) / 256)), dim3(256), 0, stream, (T*)a.g_transform,
+    if (b.splits > 1) {
+        hipLaunchKernelGGL((aggregate_zero_kernel<T>), dim3(b.zero_grid), dim3(256), 0, stream, (T*)a.g_transform,
                            (int64_t)a.L * a.L, (T*)a.g_distance_transform, (int64_t)a.L * 2 * E, (T*)a.g_frequencies, (int64_t)a.F);
     }
-    hipLaunchKernelGGL((aggregate_backward_rows_kernel<T, PER>), grid, block, lds_r, stream, a.N, a.L, a.K, a.F,
-                       a.cap, wpg, (const T*)a.means, (const T*)a.conics, a.row_counts, a.row_lists, (const T*)a.features,
+    hipLaunchKernelGGL((aggregate_backward_rows_kernel<T, PER>), dim3(b.rows.grid), block, lds_r, stream, a.N, a.L, a.K, a.F,
+                       a.cap, b.rows.wpg, (const T*)a.means, (const T*)a.conics, a.row_counts, a.row_lists, (const T*)a.features,
                        (const T*)a.transform, (const T*)a.queries, (const T*)a.keys, (const T*)a.frequencies,
                        (const T*)a.distance_transform, (const T*)a.lse, (const T*)a.acc, (const T*)a.gout, dacc, D,
                        (T*)a.g_queries, gfr, (T)a.period);
-    hipLaunchKernelGGL((aggregate_backward_cols_kernel<T, PER>), grid, block, lds_c, stream, a.N, a.L, a.K, a.F,
-                       a.cap, wpg, (const T*)a.means, (const T*)a.conics, a.col_counts, a.col_lists, (const T*)a.features,
+    hipLaunchKernelGGL((aggregate_backward_cols_kernel<T, PER>), dim3(b.cols.grid), block, lds_c, stream, a.N, a.L, a.K, a.F,
+                       a.cap, b.cols.wpg, (const T*)a.means, (const T*)a.conics, a.col_counts, a.col_lists, (const T*)a.features,
                        (const T*)a.queries, (const T*)a.keys, (const T*)a.frequencies, (const T*)a.lse, (const T*)dacc,
                        (const T*)D, (T*)a.g_features, (T*)a.g_keys, (T)a.period);
-    hipLaunchKernelGGL((aggregate_outer_kernel<T>), dim3((unsigned)((W + a.F) * splits)), dim3(256), 0, stream, a.N, a.L, a.F, splits,
+    hipLaunchKernelGGL((aggregate_outer_kernel<T>), dim3(b.outer_grid), dim3(256), 0, stream, a.N, a.L, a.F, b.splits,
                        (const T*)a.gout, (const T*)a.acc, (const T*)gfr, (T*)a.g_transform, (T*)a.g_distance_transform,
                        (T*)a.g_frequencies);
     return launch_status();
@@ -1411,13 +1347,13 @@ static int aggregate_backward_t(const AggregateArgs& a, hipStream_t stream) {
 // ---- the heads' launchers (2 <= a.H <= HMAX and an admitted shape: capi.hip checks; H = 1 goes to the ones above)
 template <typename T, bool PER>
 static int aggregate_heads_forward_t(const AggregateArgs& a, hipStream_t stream) {
+    const AggregateLaunch f = choose_aggregate_forward(a.dtype, a.H, a.N, a.L, a.K, a.F);
     int rc = PIGS_OK;
-    const size_t lds = sampling_lds(aggregate_heads_forward_kernel<T, PER>, sizeof(T), forward_region(a.H, a.L, a.F), &rc);
+    const size_t lds = sampling_lds(aggregate_heads_forward_kernel<T, PER>, f.lds, &rc);
     if (rc != PIGS_OK) return rc;
-    const int wpg = heads_waves_per_gaussian(a.N, lds), gpw = 4 / wpg;
     clear_hip_error();
-    hipLaunchKernelGGL((aggregate_heads_forward_kernel<T, PER>), dim3((unsigned)((a.N + gpw - 1) / gpw)), dim3(256), lds, stream, a.N,
-                       a.H, a.L, a.K, a.F, a.cap, wpg, (const T*)a.means, (const T*)a.conics, a.row_counts, a.row_lists,
+    hipLaunchKernelGGL((aggregate_heads_forward_kernel<T, PER>), dim3(f.grid), dim3(256), lds, stream, a.N,
+                       a.H, a.L, a.K, a.F, a.cap, f.wpg, (const T*)a.means, (const T*)a.conics, a.row_counts, a.row_lists,
                        (const T*)a.features, (const T*)a.transform, (const T*)a.queries, (const T*)a.keys, (const T*)a.frequencies,
                        (const T*)a.distance_transform, (T*)a.out, (T*)a.lse, (T*)a.acc, (T)a.period);
     return launch_status();
@@ -1429,32 +1365,29 @@ static int aggregate_heads_backward_t(const AggregateArgs& a, hipStream_t stream
     T* dacc = (T*)a.scratch;
     T* D = dacc + (size_t)a.N * H * W;
     T* gfr = D + (size_t)a.N * H;
+    const AggregateBackwardChoice b = choose_aggregate_backward(a.dtype, H, a.N, a.L, a.K, a.F);
     int rc = PIGS_OK;
-    const size_t lds_r = sampling_lds(aggregate_heads_backward_rows_kernel<T, PER>, sizeof(T), backward_rows_region(H, a.K, a.F), &rc);
-    const size_t lds_c = sampling_lds(aggregate_heads_backward_cols_kernel<T, PER>, sizeof(T), backward_cols_region(H, a.L, a.K), &rc);
+    const size_t lds_r = sampling_lds(aggregate_heads_backward_rows_kernel<T, PER>, b.rows.lds, &rc);
+    const size_t lds_c = sampling_lds(aggregate_heads_backward_cols_kernel<T, PER>, b.cols.lds, &rc);
     if (rc != PIGS_OK) return rc;
-    const int wpgr = heads_waves_per_gaussian(a.N, lds_r), wpgc = heads_waves_per_gaussian(a.N, lds_c);
-    const dim3 gridr((unsigned)((a.N + 4 / wpgr - 1) / (4 / wpgr))), gridc((unsigned)((a.N + 4 / wpgc - 1) / (4 / wpgc))), block(256);
-    int splits = (int)((a.N + 2047) / 2048);     // the rule of aggregate_backward_t
-    splits = splits < 1 ? 1 : splits > 64 ? 64 : splits;
+    const dim3 block(256);
     clear_hip_error();
-    if (splits > 1) {
-        const int64_t mx = (int64_t)H * a.L * (2 * E > a.L ? 2 * E : a.L);
-        hipLaunchKernelGGL((aggregate_zero_kernel<T>), dim3((unsigned)((mx + 255) / 256)), dim3(256), 0, stream, (T*)a.g_transform,
+    if (b.splits > 1) {
+        hipLaunchKernelGGL((aggregate_zero_kernel<T>), dim3(b.zero_grid), dim3(256), 0, stream, (T*)a.g_transform,
                            (int64_t)H * a.L * a.L, (T*)a.g_distance_transform, (int64_t)H * a.L * 2 * E, (T*)a.g_frequencies,
                            (int64_t)a.F);
     }
-    hipLaunchKernelGGL((aggregate_heads_backward_rows_kernel<T, PER>), gridr, block, lds_r, stream, a.N, H, a.L, a.K, a.F,
-                       a.cap, wpgr, (const T*)a.means, (const T*)a.conics, a.row_counts, a.row_lists, (const T*)a.features,
+    hipLaunchKernelGGL((aggregate_heads_backward_rows_kernel<T, PER>), dim3(b.rows.grid), block, lds_r, stream, a.N, H, a.L, a.K, a.F,
+                       a.cap, b.rows.wpg, (const T*)a.means, (const T*)a.conics, a.row_counts, a.row_lists, (const T*)a.features,
                        (const T*)a.transform, (const T*)a.queries, (const T*)a.keys, (const T*)a.frequencies,
                        (const T*)a.distance_transform, (const T*)a.lse, (const T*)a.acc, (const T*)a.gout, dacc, D,
                        (T*)a.g_queries, gfr, (T)a.period);
-    hipLaunchKernelGGL((aggregate_heads_backward_cols_kernel<T, PER>), gridc, block, lds_c, stream, a.N, H, a.L, a.K, a.F,
-                       a.cap, wpgc, (const T*)a.means, (const T*)a.conics, a.col_counts, a.col_lists, (const T*)a.features,
+    hipLaunchKernelGGL((aggregate_heads_backward_cols_kernel<T, PER>), dim3(b.cols.grid), block, lds_c, stream, a.N, H, a.L, a.K, a.F,
+                       a.cap, b.cols.wpg, (const T*)a.means, (const T*)a.conics, a.col_counts, a.col_lists, (const T*)a.features,
                        (const T*)a.queries, (const T*)a.keys, (const T*)a.frequencies, (const T*)a.lse, (const T*)dacc,
                        (const T*)D, (T*)a.g_features, (T*)a.g_keys, (T)a.period);
-    hipLaunchKernelGGL((aggregate_heads_outer_kernel<T>), dim3((unsigned)((H * W + a.F) * splits)), dim3(256), 0, stream, a.N, H, a.L,
-                       a.F, splits, (const T*)a.gout, (const T*)a.acc, (const T*)gfr, (T*)a.g_transform,
+    hipLaunchKernelGGL((aggregate_heads_outer_kernel<T>), dim3(b.outer_grid), dim3(256), 0, stream, a.N, H, a.L,
+                       a.F, b.splits, (const T*)a.gout, (const T*)a.acc, (const T*)gfr, (T*)a.g_transform,
                        (T*)a.g_distance_transform, (T*)a.g_frequencies);
     return launch_status();
 }

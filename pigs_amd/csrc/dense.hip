@@ -15,6 +15,7 @@
 //           share a Gaussian block (gridDim.y > 1) combine with float atomics.
 #include "pair_math.h"
 #include "launch.h"
+#include "dense_choice.h"
 
 namespace pigs {
 
@@ -230,9 +231,7 @@ __global__ __launch_bounds__(NW * 64) void dense_backward_kernel(
 // Forward: a workgroup of ROWS_WAVES waves takes 16 points; lane = 16 * row + i: point i of the workgroup, and
 // every (wave, row) pair one of 4 * ROWS_WAVES interleaved slices of the Gaussians (row-uniform loads: the 16
 // lanes of a row read the same record).  The four rows of a wave meet by two shuffles, the waves in LDS, in a
-// fixed order.  (8 waves: 256 VGPRs a wave -- the widest accumulator sets fit without spilling.)
-constexpr int ROWS_WAVES = 8;
-constexpr int ROWS_CHUNK_BYTES = 36 * 1024;      // Gaussian parameters staged per chunk (1 536 Gaussians of d = 2, c = 1, float32)
+// fixed order.  (ROWS_WAVES = 8 waves: 256 VGPRs a wave -- the widest accumulator sets fit without spilling.)
 template <typename T, int D, int C, int MASK>
 __global__ __launch_bounds__(64 * ROWS_WAVES) void dense_forward_rows_kernel(
     int64_t N, int64_t M, const T* __restrict__ means, const T* __restrict__ conics, const T* __restrict__ values,
@@ -257,7 +256,7 @@ __global__ __launch_bounds__(64 * ROWS_WAVES) void dense_forward_rows_kernel(
     // one coalesced round trip, then every (wave, row) slice walks ITS Gaussians of the chunk with row-uniform LDS
     // reads (fetched straight from global memory, a slice's 50 Gaussians at N = 1 600 were a chain of 25
     // dependent round trips: 12 us for 1.6 M pairs).
-    constexpr int CHUNK = ROWS_CHUNK_BYTES / (int)((D + NF + C) * sizeof(T));
+    constexpr int CHUNK = rows_chunk((int)sizeof(T), D, C);      // dense_choice.h, with ROWS_WAVES
     __shared__ T smu[CHUNK * D], scon[CHUNK * NF], sval[CHUNK * C];
     for (int64_t n0 = 0; n0 < N; n0 += CHUNK) {
         const int cnt = (int)(N - n0 < CHUNK ? N - n0 : CHUNK);
@@ -373,41 +372,35 @@ __global__ __launch_bounds__(256) void zero_grads_kernel(uint32_t* __restrict__ 
 // Host-side launchers
 // ------------------------------------------------------------------------------------------
 
-// tests/test_dense_matrix.py mirrors the selection of the two launchers below: a threshold changed here is changed there
+// Which variant a launch takes, its grid and its block are dense_choice.h's: the only statement of the selection, which
+// tests/test_dense_matrix.py reads through tests/launch_choice_main.cpp.  The two launchers ask, switch and launch.
 template <typename T, int D, int C, int MASK>
 static int launch_dense_forward(const SampleArgs& a, hipStream_t stream) {
-    const int64_t blocks = (a.M + 63) / 64;
-    if (blocks == 0 ) return PIGS_OK;
-    if (blocks > 0x7fffffffLL) return PIGS_ERR_INVALID;
+    static_assert(fwd_accumulators(D, C, MASK) == FwdLayout<D, C, MASK>::N, "dense_choice.h counts the accumulators of pair_math.h");
+    constexpr int E = (int)sizeof(T);
+    const DenseForwardChoice ch = choose_dense_forward(E, D, C, MASK, a.N, a.M);
+    if (ch.variant == DenseForward::NOTHING) return PIGS_OK;
+    if (ch.variant == DenseForward::INVALID) return PIGS_ERR_INVALID;
     clear_hip_error();
     const T* means = (const T*)a.means; const T* conics = (const T*)a.conics;
     const T* values = (const T*)a.values; const T* samples = (const T*)a.samples;
     T* o0 = (T*)a.out[0]; T* o1 = (T*)a.out[1]; T* o2 = (T*)a.out[2]; T* o3 = (T*)a.out[3];
     const RzOf<T, MASK> rz = rz_of<T, MASK>(a, false);
-    constexpr int NACC = FwdLayout<D, C, MASK>::N;
-    // few point blocks: spread the Gaussian loop over 16 waves per workgroup
-    // (a 1 024-thread workgroup leaves 128 VGPRs per wave: the wide accumulator sets -- several channels, third
-    // derivatives, float64 -- spilled there, so they keep the four-wave variant)
-    constexpr bool can16 = (15 * NACC * 64 * sizeof(T) <= 60 * 1024) && NACC * (sizeof(T) / 4) <= 7;
-    // few points (<= 256 of the 64-point blocks above): 16 points per workgroup, the Gaussians in 32 slices
-    constexpr bool can_rows = NACC * (sizeof(T) / 4) <= 28;      // beyond, the two records in flight spill even at 256 VGPRs
-    if constexpr (can_rows) {
-        if (blocks <= 256 && a.N >= 128) {
-            hipLaunchKernelGGL((dense_forward_rows_kernel<T, D, C, MASK>), dim3((unsigned)((a.M + 15) / 16)), dim3(64 * ROWS_WAVES), 0, stream,
-                               a.N, a.M, means, conics, values, samples, o0, o1, o2, o3, rz);
-            return launch_status();
-        }
-    }
-    if constexpr (can16) {
-      if (blocks < 1024 && a.N >= 64) {
-        hipLaunchKernelGGL((dense_forward_kernel<T, D, C, MASK, 16>), dim3((unsigned)blocks), dim3(1024), 0, stream,
-                           a.N, a.M, means, conics, values, samples, o0, o1, o2, o3, rz);
-        return launch_status();
-      }
-    }
-    {
-        hipLaunchKernelGGL((dense_forward_kernel<T, D, C, MASK, 4>), dim3((unsigned)blocks), dim3(256), 0, stream,
-                           a.N, a.M, means, conics, values, samples, o0, o1, o2, o3, rz);
+    const dim3 grid(ch.grid), block(ch.block);
+    switch (ch.variant) {      // a variant that an instantiation never takes is not compiled for it
+        case DenseForward::ROWS:
+            if constexpr (can_rows(E, D, C, MASK))
+                hipLaunchKernelGGL((dense_forward_rows_kernel<T, D, C, MASK>), grid, block, 0, stream, a.N, a.M, means, conics, values,
+                                   samples, o0, o1, o2, o3, rz);
+            break;
+        case DenseForward::W16:
+            if constexpr (can_w16(E, D, C, MASK))
+                hipLaunchKernelGGL((dense_forward_kernel<T, D, C, MASK, 16>), grid, block, 0, stream, a.N, a.M, means, conics, values,
+                                   samples, o0, o1, o2, o3, rz);
+            break;
+        default:
+            hipLaunchKernelGGL((dense_forward_kernel<T, D, C, MASK, 4>), grid, block, 0, stream, a.N, a.M, means, conics, values,
+                               samples, o0, o1, o2, o3, rz);
     }
     return launch_status();
 }
@@ -415,48 +408,35 @@ static int launch_dense_forward(const SampleArgs& a, hipStream_t stream) {
 template <typename T, int D, int C, int MASK>
 static int launch_dense_backward(const SampleArgs& a, hipStream_t stream) {
     constexpr int NF = Sym<D>::NF;
-    const int64_t gblocks = (a.N + 63) / 64;
-    if (gblocks == 0) return PIGS_OK;
-    if (gblocks > 0x7fffffffLL) return PIGS_ERR_INVALID;
+    const DenseBackwardChoice ch = choose_dense_backward(a.N, a.M);
+    if (ch.variant == DenseBackward::NOTHING) return PIGS_OK;
+    if (ch.variant == DenseBackward::INVALID) return PIGS_ERR_INVALID;
     clear_hip_error();
     T* gm = (T*)a.g_means; T* gc = (T*)a.g_conics; T* gv = (T*)a.g_values;
     // The gradient buffers are zeroed by a kernel of our own, one launch for all three:
     // hipMemsetAsync nodes replayed inside a hipGraph were seen (ROCm 7.2) to fill with a stale
     // 16-byte pattern now and then (tests/test_graph_gpu.py), and this is one launch, not three.
-    auto zero_grads = [&]() {
+    if (ch.zero) {
         const uint64_t wm = sizeof(T) / 4 * (uint64_t)a.N * D, wc = sizeof(T) / 4 * (uint64_t)a.N * NF,
                        wv = sizeof(T) / 4 * (uint64_t)a.N * C;
         const uint64_t blocks = (wm + wc + wv + 1023) / 1024;
-        hipLaunchKernelGGL(zero_grads_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, stream,
+        hipLaunchKernelGGL(zero_grads_kernel, dim3((unsigned)(blocks < ZERO_MAX_BLOCKS ? blocks : ZERO_MAX_BLOCKS)), dim3(256), 0, stream,
                            (uint32_t*)gm, wm, (uint32_t*)gc, wc, (uint32_t*)gv, wv);
-    };
-    if (a.M == 0) {
-        zero_grads();
-        return launch_status();
     }
-    // few points: 64-point slices staged in LDS, 256 Gaussians per workgroup (dense_backward_staged_kernel)
-    if (a.M <= 16384 && (a.M + 63) / 64 <= 65535) {
-        zero_grads();
-        const int64_t gx = (a.N + 255) / 256;
-        const int slice = gx * ((a.M + 63) / 64) < 512 ? 32 : 64;      // N = 1 600, 1 024 points: 112 workgroups of 64-point slices
-        hipLaunchKernelGGL((dense_backward_staged_kernel<T, D, C, MASK>), dim3((unsigned)gx, (unsigned)((a.M + slice - 1) / slice)),
-                           dim3(256), 0, stream, a.N, a.M, (const T*)a.means, (const T*)a.conics, (const T*)a.values,
-                           (const T*)a.samples, (const T*)a.gout[0], (const T*)a.gout[1], (const T*)a.gout[2], (const T*)a.gout[3],
-                           gm, gc, gv, rz_of<T, MASK>(a, true), slice);
-        return launch_status();
+    const dim3 grid(ch.gx, ch.gy), block(256);
+    switch (ch.variant) {
+        case DenseBackward::STAGED:
+            hipLaunchKernelGGL((dense_backward_staged_kernel<T, D, C, MASK>), grid, block, 0, stream, a.N, a.M, (const T*)a.means,
+                               (const T*)a.conics, (const T*)a.values, (const T*)a.samples, (const T*)a.gout[0], (const T*)a.gout[1],
+                               (const T*)a.gout[2], (const T*)a.gout[3], gm, gc, gv, rz_of<T, MASK>(a, true), ch.slice);
+            break;
+        case DenseBackward::SPLIT:
+            hipLaunchKernelGGL((dense_backward_kernel<T, D, C, MASK, 4>), grid, block, 0, stream, a.N, a.M, (const T*)a.means,
+                               (const T*)a.conics, (const T*)a.values, (const T*)a.samples, (const T*)a.gout[0], (const T*)a.gout[1],
+                               (const T*)a.gout[2], (const T*)a.gout[3], gm, gc, gv, rz_of<T, MASK>(a, true));
+            break;
+        default: break;      // ZERO_ONLY
     }
-    // split the point range over gridDim.y so that ~2048 workgroups exist; each wave should
-    // still see >= 64 points
-    int64_t ysplit = 2048 / gblocks;
-    const int64_t max_split = (a.M + 4 * 64 - 1) / (4 * 64);
-    if (ysplit > max_split) ysplit = max_split;
-    if (ysplit < 1) ysplit = 1;
-    if (ysplit > 65535) ysplit = 65535;
-    if (ysplit > 1) zero_grads();
-    hipLaunchKernelGGL((dense_backward_kernel<T, D, C, MASK, 4>), dim3((unsigned)gblocks, (unsigned)ysplit), dim3(256),
-                       0, stream, a.N, a.M, (const T*)a.means, (const T*)a.conics, (const T*)a.values,
-                       (const T*)a.samples, (const T*)a.gout[0], (const T*)a.gout[1], (const T*)a.gout[2],
-                       (const T*)a.gout[3], gm, gc, gv, rz_of<T, MASK>(a, true));
     return launch_status();
 }
 
@@ -470,21 +450,19 @@ static int dispatch_mask(bool backward, const SampleArgs& a, hipStream_t stream)
         return backward ? launch_dense_backward<T, D, C, MK>(a, stream)                      \
                         : launch_dense_forward<T, D, C, MK>(a, stream);
     switch (mask) {
-        PIGS_CASE(1) PIGS_CASE(2) PIGS_CASE(4) PIGS_CASE(8) PIGS_CASE(7) PIGS_CASE(15) PIGS_CASE(16) PIGS_CASE(19)
-        PIGS_CASE(32) PIGS_CASE(64)
+        PIGS_PLAIN_MASKS(PIGS_CASE)
         default: break;
     }
-    // the vorticity terms (ORDV) and residual (ORDN): a two-channel field in two dimensions, the only instantiations compiled
-    if constexpr (D == 2 && C == 2) {
+    // the lists and their conditions: instances.h
+    if constexpr (dense_vort_instance(D, C)) {
         switch (mask) {
-            PIGS_CASE(128) PIGS_CASE(512)
+            PIGS_DENSE_VORT_MASKS(PIGS_CASE)
             default: break;
         }
     }
-    // the coupled residual (ORDC) mixes channels: compiled for two and more
-    if constexpr (C >= 2) {
+    if constexpr (dense_coupled_instance(C)) {
         switch (mask) {
-            PIGS_CASE(256)
+            PIGS_DENSE_COUPLED_MASKS(PIGS_CASE)
             default: break;
         }
     }

@@ -4,6 +4,8 @@
 #include <stdint.h>
 
 #include "../../include/pigs_amd.h"
+#include "aggregate_choice.h"
+#include "instances.h"      // the order masks, covering_mask_of, the compiled instantiations
 
 namespace pigs {
 
@@ -148,11 +150,7 @@ struct AggregateArgs {
     void *g_features, *g_transform, *g_queries, *g_keys, *g_frequencies, *g_distance_transform;
 };
 size_t aggregate_workspace_bytes(int dtype, int64_t N);
-constexpr size_t AGG_LDS_MAX = 160 * 1024;       // LDS of a gfx950 CU: what one workgroup can ask for
-size_t aggregate_lds_bytes(int dtype, int H, int L, int K, int F);
-size_t aggregate_heads_lds_bytes(int dtype, int H, int L, int K, int F);      // the same, 0 where H or a component count is out of range
-bool aggregate_admitted(int dtype, int H, int L, int K, int F);               // the size rule (1 <= H <= 4)
-size_t aggregate_backward_scratch_bytes(int dtype, int64_t N, int H, int L, int F);
+// (the size rules -- AGG_LDS_MAX, aggregate_lds_bytes, aggregate_admitted, ... -- are aggregate_choice.h's inline functions)
 int aggregate_lists(int dtype, int64_t N, int64_t cap, const void* means, const void* conics, double q_max, void* workspace,
                     size_t workspace_bytes, int flags, int32_t* row_counts, int32_t* row_lists, int32_t* col_counts,
                     int32_t* col_lists, int32_t* overflow, hipStream_t stream, double lo = 0.0, double period = 0.0);
@@ -185,30 +183,6 @@ size_t samples_error_offset();
 size_t samples_lattice_offset();
 size_t plan_strips_offset();
 size_t plan_error_offset();
-
-// Order masks: bit k < 4 = derivative order k (pointer slot k); bit 4 (16) = the TRACE of the order-2
-// output (the Laplacian), which takes pointer slot 2 in place of the full Hessian, [M][c].
-// The fused outputs: one mask each, alone, the output in slot 0, reachable through their own entry points only.  The
-// kernels know them as ORDR, ORDG, ORDV, ORDC, ORDN (pair_math.h; dense.hip asserts that the two sets agree).
-constexpr int MASK_RESIDUAL = 32;             // the linear residual, [M][c] -- pigs_residual_*
-constexpr int MASK_TERMS = 64;                // the general residual, [M][c] -- pigs_residual_terms_*
-constexpr int MASK_VORTICITY = 128;           // the vorticity terms (d = 2, c = 2), [M][7] -- pigs_vorticity_*
-constexpr int MASK_COUPLED = 256;             // the coupled residual (c >= 2), [M][c] -- pigs_residual_coupled_*
-constexpr int MASK_VORT_RESIDUAL = 512;       // the vorticity residual (d = 2, c = 2), [M][2] -- pigs_vorticity_residual_*
-inline bool is_fused_output(int m) {
-    return m == MASK_RESIDUAL || m == MASK_TERMS || m == MASK_VORTICITY || m == MASK_COUPLED || m == MASK_VORT_RESIDUAL;
-}
-inline bool mask_valid(int m) { return m > 0 && m < 32 && !((m & 4) && (m & 16)); }
-inline bool mask_uses_slot(int m, int k) { return is_fused_output(m) ? k == 0 : (m >> k & 1) || (k == 2 && (m & 16)); }
-// Smallest compiled mask covering the request (compiled: single orders, 0..2, 0..3, the trace alone
-// and orders 0, 1 + trace); 0 = no compiled kernel (trace together with order 3).
-inline int covering_mask_of(int mask) {
-    if (is_fused_output(mask)) return mask;
-    if (mask & 16) return mask == 16 ? 16 : (mask & ~19) == 0 ? 19 : 0;
-    if (mask == 1 || mask == 2 || mask == 4 || mask == 8) return mask;
-    if ((mask & ~7) == 0) return 7;
-    return 15;
-}
 
 // The HIP "last error" is sticky per thread and the host process (PyTorch) makes its own HIP
 // calls: clear it before a launch, read it after.

@@ -472,6 +472,7 @@ struct PlanView {
 // box = {min x, min y, max x, max y}; min > max (+-inf) when there were no finite points.
 // The Gaussian grid spans the sample domain plus 1/16 of its extent on every side: centres
 // further out only matter through ellipses that reach back in, and clamp to the border cells.
+constexpr float GRID_MARGIN = 1.1251f;      // the Gaussian grid's side over the points' extent: 1/16 on every side, and a little
 __device__ inline GaussGrid gauss_grid(const float* box, int G0) {
     GaussGrid g;
     const float x0 = box[0], y0 = box[1], x1 = box[2], y1 = box[3];
@@ -480,7 +481,7 @@ __device__ inline GaussGrid gauss_grid(const float* box, int G0) {
     const float pad = ext * 0.0625f;
     g.ox = ((x1 >= x0) ? x0 : 0.f) - pad;
     g.oy = ((y1 >= y0) ? y0 : 0.f) - pad;
-    g.s0 = ext * 1.1251f / (float)G0;
+    g.s0 = ext * GRID_MARGIN / (float)G0;
     g.inv_s0 = 1.f / g.s0;
     return g;
 }

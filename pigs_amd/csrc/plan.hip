@@ -517,9 +517,6 @@ int plan_build(void* ws, size_t ws_bytes, void* sws, size_t sws_bytes, int flags
     return run_build(r, sws, sws_bytes, ws, ws_bytes, means, conics, values, samples, stream);
 }
 
-// the masks the fused first forward is compiled for (the rest: the list launch, then the forward launch)
-template <int C> static bool fused_first_compiled(int mask) { return C == 1 ? (mask == 1 || mask == 7 || mask == 19 || mask == 32) : mask == 7; }
-
 // a fused output whose coefficient block the caller left out (SampleArgs: terms, coupling, vort)
 static bool block_missing(int mask, const SampleArgs& a) {
     switch (mask) {
@@ -544,7 +541,7 @@ static int plan_forward_c(const PlanView& pv_in, const SamplesView& sv, int mask
     bool done = false;
     if (first) {
         // the plan's tile lists are still to be built (PIGS_BUILD_DEFER_LISTS): in this launch where a fused kernel
-        // is compiled for the mask, in a launch of their own in front of the forward otherwise
+        // is compiled for the mask (instances.h), in a launch of their own in front of the forward otherwise
         ListArgs la = *first;
         la.pv.stage = pv.stage;
         const dim3 lgrid((sv.ntiles + 4 * LISTS_TPW - 1) / (4 * LISTS_TPW));
@@ -554,18 +551,18 @@ static int plan_forward_c(const PlanView& pv_in, const SamplesView& sv, int mask
                            out[3], rz_of<float, MK>(a, false));                                                         \
         done = true;                                                                                                    \
         break;
-        if (fused_first_compiled<C>(mask) && !getenv("PIGS_NO_FUSED_FIRST") && !plan_expects_points(pv.N, sv.M, stream)) {
+        if (fused_first_compiled(C, mask) && !getenv("PIGS_NO_FUSED_FIRST") && !plan_expects_points(pv.N, sv.M, stream)) {
             if constexpr (C == 1) {
-                switch (mask) { PIGS_FUSED(1) PIGS_FUSED(7) PIGS_FUSED(19) PIGS_FUSED(32) }
+                switch (mask) { PIGS_FUSED_FIRST_C1_MASKS(PIGS_FUSED) }
             } else {
-                switch (mask) { PIGS_FUSED(7) }
+                switch (mask) { PIGS_FUSED_FIRST_C2_MASKS(PIGS_FUSED) }
             }
         }
 #undef PIGS_FUSED
         if (!done) launch_lists(list_launch(sv.ntiles), la, stream);
     }
     if (block_missing(mask, a)) return PIGS_ERR_INVALID;
-    // every compiled mask (the fused outputs are never fused with the list launch, the linear residual apart)
+    // every compiled mask: the lists of instances.h (the fused outputs are never fused with the list launch, the linear residual apart)
 #define PIGS_CASE(MK)                                                                                            \
     case MK:                                                                                                     \
         hipLaunchKernelGGL((tile_forward_kernel<C, MK>), grid, block, 0, stream, pv, sv, out[0], out[1], out[2], \
@@ -573,14 +570,13 @@ static int plan_forward_c(const PlanView& pv_in, const SamplesView& sv, int mask
         done = true;                                                                                             \
         break;
     if (!done) switch (mask) {
-        PIGS_CASE(1) PIGS_CASE(2) PIGS_CASE(4) PIGS_CASE(8) PIGS_CASE(7) PIGS_CASE(15) PIGS_CASE(16) PIGS_CASE(19)
-        PIGS_CASE(ORDR) PIGS_CASE(ORDG)
+        PIGS_PLAIN_MASKS(PIGS_CASE)
         default: break;
     }
     // the vorticity terms and residual and the coupled residual: two channels, the only instantiations compiled
     if constexpr (C == 2) {
         switch (mask) {
-            PIGS_CASE(ORDV) PIGS_CASE(ORDC) PIGS_CASE(ORDN)
+            PIGS_BINNED_C2_MASKS(PIGS_CASE)
             default: break;
         }
     }
@@ -617,13 +613,12 @@ static int plan_backward_c(const PlanView& pv_in, const SamplesView& sv, int mas
         done = true;                                                                                                 \
         break;
     switch (mask) {
-        PIGS_CASE(1) PIGS_CASE(2) PIGS_CASE(4) PIGS_CASE(8) PIGS_CASE(7) PIGS_CASE(15) PIGS_CASE(16) PIGS_CASE(19)
-        PIGS_CASE(ORDR) PIGS_CASE(ORDG)
+        PIGS_PLAIN_MASKS(PIGS_CASE)
         default: break;
     }
     if constexpr (C == 2) {      // as in plan_forward_c
         switch (mask) {
-            PIGS_CASE(ORDV) PIGS_CASE(ORDC) PIGS_CASE(ORDN)
+            PIGS_BINNED_C2_MASKS(PIGS_CASE)
             default: break;
         }
     }

@@ -1,63 +1,52 @@
-"""CPU: which launch variant the launchers of aggregate_neighbors_heads pick for a problem, mirrored in Python, with the
-table that says the GPU matrix (tests/test_aggregate_heads_matrix_gpu.py) reaches every one of them.
+"""CPU: the table that says the GPU matrix (tests/test_aggregate_heads_matrix_gpu.py) reaches every launch variant of
+the launchers of aggregate_neighbors_heads.
 
-The selection below restates, from pigs_amd/csrc/aggregate.hip: ``forward_region``, ``backward_rows_region``,
-``backward_cols_region``, ``components_ok``, ``aggregate_admitted``, ``heads_waves_per_gaussian`` (AGG_CUS compute units,
-at most eight workgroups a CU, AGG_BRUTE_MAX), the three heads kernels' ``WC``, ``hd0`` / ``hd1``, ``dens1`` and
-``c1 >= HL``, ``for_row``'s alignment test on the heads' row addresses, and the ``splits`` of the sums over N.  A
-threshold changed there is changed here, or the coverage test of this file no longer describes what the GPU matrix
-runs.  What the one-head mirror (tests/test_aggregate_matrix.py) already states is imported from it."""
+The regions, each kernel's LDS request, ``components_ok``, ``aggregate_admitted``, ``heads_waves_per_gaussian`` (with
+its compute units and workgroups per CU), the list build and the ``splits`` of the sums over N are asked of the
+launchers' own functions (pigs_amd/csrc/aggregate_choice.h) through the stand-alone program
+tests/launch_choice_main.cpp (tests/host_program.py); nothing here restates them.  What stays in Python describes the
+three heads kernels' insides, which no launcher computes -- ``WC`` (``widths``), ``hd0`` / ``hd1`` (``rows_head``,
+``cols_head``), ``dens1`` and ``c1 >= HL``, blocks that straddle lanes 63 | 64, ``for_row``'s alignment test on the
+heads' row addresses (``vector_rows``, ``dacc_rows``) -- and this file's own vocabulary: the tags, the expected tags
+and the coverage logic."""
 import ctypes
 import itertools
 
 import pytest
 
-from test_aggregate_matrix import AGG_BRUTE_MAX, KERNELS, LDS_DEFAULT, LDS_MAX, PART, SIZEOF, ceil_div, splits, waves_per_gaussian
-from test_aggregate_matrix import region as rows_region
+import host_program as hp
+from test_aggregate_matrix import KERNELS, SIZEOF, K_, ceil_div
 
-AGG_CUS = 256                # compute units of an MI355X
-WORKGROUPS_PER_CU = 8        # 32 waves a CU: eight workgroups of four
-HMAX = 4                     # PIGS_AGGREGATE_HEADS_MAX
+
+def choice(dtype, N, H, L, K, F):
+    return hp.aggregate(dtype, H, N, L, K, F)
 
 
 def regions(H, L, K, F):
     """A wave's region of the forward, the backward by rows and the backward by columns, in values."""
-    return {"forward": max(rows_region((L + 4 * F) | 1), H * PART),
-            "rows": H * PART + rows_region((H * K + F) | 1),
-            "cols": rows_region((H * (L + K)) | 1)}
+    return choice("float32", 1, H, L, K, F).regions
 
 
 def lds_bytes(dtype, H, L, K, F):
-    """sampling_lds: four wave regions."""
-    return {k: SIZEOF[dtype] * 4 * r for k, r in regions(H, L, K, F).items()}
+    return choice(dtype, 1, H, L, K, F).lds
 
 
 def components_ok(H, L, K, F):
-    return 1 <= H <= HMAX and L + 2 * (4 * F + 1) <= 128 and H * K + F <= 128 and H * (L + K) <= 128
+    return choice("float32", 1, H, L, K, F).components_ok
 
 
 def admitted(dtype, H, L, K, F):
     """aggregate_admitted (the entry points refuse L, K < 1 and F < 0 as invalid before it)."""
-    return L >= 1 and K >= 1 and F >= 0 and components_ok(H, L, K, F) and max(lds_bytes(dtype, H, L, K, F).values()) <= LDS_MAX
-
-
-def heads_waves_per_gaussian(N, lds):
-    wpg = waves_per_gaussian(N)
-    if N > AGG_BRUTE_MAX:
-        return wpg
-    resident = AGG_CUS * min(max(LDS_MAX // max(lds, 1), 1), WORKGROUPS_PER_CU)
-    while wpg > 1 and (N * wpg + 3) // 4 > resident:
-        wpg >>= 1
-    return wpg
+    return L >= 1 and K >= 1 and F >= 0 and choice(dtype, 1, H, L, K, F).admitted
 
 
 def waves(dtype, N, H, L, K, F):
     """Waves per Gaussian of the three kernels of one call."""
-    return {k: heads_waves_per_gaussian(N, b) for k, b in lds_bytes(dtype, H, L, K, F).items()}
+    return choice(dtype, N, H, L, K, F).waves
 
 
 def widths(H, L, K, F):
-    """WC of the three kernels: the components a wave's lanes share out, lane and lane + 64."""
+    """WC of the three kernels: the components a wave's lanes share out, lane and lane + 64 (inside the kernels)."""
     return {"forward": L + 8 * F, "rows": H * K + F, "cols": H * (L + K)}
 
 
@@ -98,16 +87,12 @@ def dacc_rows(dtype, H, L, F):
 @pytest.fixture(scope="module")
 def largest():
     """The most LDS an admitted shape of H >= 2 heads asks for, per dtype, with the shapes that ask for it."""
-    best = {t: (0, []) for t in SIZEOF}
-    for H in range(2, HMAX + 1):
-        for L, K, F in itertools.product(range(1, 64), range(1, 64), range(0, 16)):
-            if not components_ok(H, L, K, F):
-                continue
-            r = max(regions(H, L, K, F).values())
-            for t in SIZEOF:
-                b = SIZEOF[t] * 4 * r
-                if b <= LDS_MAX and b >= best[t][0]:
-                    best[t] = (b, (best[t][1] if b == best[t][0] else []) + [(H, L, K, F)])
+    shapes = [(H, L, K, F) for H in range(2, K_("HMAX") + 1) for L, K, F in itertools.product(range(1, 64), range(1, 64), range(0, 16))]
+    best = {}
+    for t in SIZEOF:
+        answers = hp.aggregate_many([(t, H, 1, L, K, F) for H, L, K, F in shapes])
+        top = max(a.lds_bytes for a in answers if a.admitted)
+        best[t] = (top, [s for s, a in zip(shapes, answers) if a.admitted and a.lds_bytes == top])
     return best
 
 
@@ -115,7 +100,7 @@ def sampling_tags(dtype, periodic, N, H, L, K, F, largest):
     """The edges of the launchers' selection that one aggregate_neighbors_heads call (forward and backward) sits on."""
     lds, wpg, wc = lds_bytes(dtype, H, L, K, F), waves(dtype, N, H, L, K, F), widths(H, L, K, F)
     HK, HL = H * K, H * L
-    grid = N > AGG_BRUTE_MAX
+    grid = hp.list_build(N) == "grid"
     tags = set()
     for k in KERNELS:
         if not grid:
@@ -124,7 +109,7 @@ def sampling_tags(dtype, periodic, N, H, L, K, F, largest):
                 tags.add(f"{k}: idle waves in the last workgroup at {wpg[k]} waves per Gaussian")
         second = wc[k] > 64
         tags.add(f"{k}: {'second component in ' + ('all' if wc[k] == 128 else 'part of the') + ' lanes' if second else 'one component'}")
-        tags.add(f"{k}: LDS {'above' if lds[k] > LDS_DEFAULT else 'within'} 64 KB")
+        tags.add(f"{k}: LDS {'above' if lds[k] > K_('AGG_LDS_DEFAULT') else 'within'} 64 KB")
         if second:          # the epilogue merges component lane + 64 of wpg partial results
             tags.add(f"{k}: second component at {wpg[k]} waves per Gaussian")
     if wpg["rows"] != wpg["cols"]:
@@ -139,7 +124,7 @@ def sampling_tags(dtype, periodic, N, H, L, K, F, largest):
         if H == 4:
             tags.add("grid lists: H = 4")
     if H >= 3:
-        tags.add("sums over N: one split with H >= 3" if splits(N) == 1 else "sums over N: atomic splits with H >= 3")
+        tags.add("sums over N: one split with H >= 3" if choice(dtype, N, H, L, K, F).splits == 1 else "sums over N: atomic splits with H >= 3")
     # forward: component c1 = lane + 64 reads the parked value c1 (features, sin / cos) below L + 4F, else c1 - 4F under
     # the density's weight (dens1)
     if wc["forward"] > 64:
@@ -170,7 +155,7 @@ def sampling_tags(dtype, periodic, N, H, L, K, F, largest):
         tags.add(f"H = {H} on a second-component case")
         if periodic:
             tags.add("periodic: a second component")
-    if regions(H, L, K, F)["forward"] == H * PART:
+    if regions(H, L, K, F)["forward"] == H * K_("PART"):
         tags.add("forward_region = H PART")
     if max(lds.values()) == largest[dtype][0]:
         tags.add("the most LDS an admitted shape of H >= 2 asks for")
@@ -195,9 +180,9 @@ def host_tags(dtype, N, H, L, K, F):
     tags = set()
     if len(set(wpg.values())) == 3:
         tags.add("both hosts: the three kernels at three different waves per Gaussian")
-    if max(lds.values()) > LDS_DEFAULT and dtype == "float64":
+    if max(lds.values()) > K_("AGG_LDS_DEFAULT") and dtype == "float64":
         tags.add("both hosts: float64 above 64 KB of LDS")
-    if splits(N) > 1:
+    if choice(dtype, N, H, L, K, F).splits > 1:
         tags.add("both hosts: grid lists and atomic splits")
     return tags
 
@@ -285,6 +270,9 @@ REFUSED = [("float64", 3, 16, 16, 2), ("float32", 2, 78, 50, 6), ("float64", 4, 
 
 # ------------------------------------------------------------------------------------------
 def test_mirror_tables(largest):
+    """The launchers' numbers, as the program answers them."""
+    heads_waves_per_gaussian, PART = hp.heads_waves, K_("PART")
+    assert (K_("AGG_CUS"), K_("AGG_WORKGROUPS_PER_CU"), K_("HMAX"), PART) == (256, 8, 4, 136)
     # the model's shape at the model's N: one wave per Gaussian in all three kernels, both dtypes
     assert lds_bytes("float32", 2, 16, 16, 6) == {"forward": 41984, "rows": 44288, "cols": 66560}
     assert lds_bytes("float64", 2, 16, 16, 6) == {"forward": 83968, "rows": 88576, "cols": 133120}
@@ -337,8 +325,8 @@ def test_the_gpu_matrix_reaches_every_heads_variant(largest):
     cases = all_cases(G)
     assert len({(name, t) for name, t, _ in cases}) == len(cases)
     for t, H, L, K, F, N in shapes_of(G):               # no test launches a shape that the size rule refuses
-        assert 2 <= H <= HMAX and admitted(t, H, L, K, F), (t, H, L, K, F)
-    assert all(N <= AGG_BRUTE_MAX for *_, N in G.SHAPE_CASES) and all(N > AGG_BRUTE_MAX for *_, N in G.VARIANT_CASES)
+        assert 2 <= H <= K_("HMAX") and admitted(t, H, L, K, F), (t, H, L, K, F)
+    assert all(hp.list_build(N) == "all-pairs" for *_, N in G.SHAPE_CASES) and all(hp.list_build(N) == "grid" for *_, N in G.VARIANT_CASES)
     for case in G.HOST_CASES:                           # a host case is a case of the matrix run through both hosts
         assert case in G.SHAPE_CASES + G.VARIANT_CASES
     gaps = missing(cases, largest)

@@ -4,7 +4,7 @@ sparse checker (oracle/aggregate_sparse.py) run once per head and stacked.
 tests/test_aggregate_heads_gpu.py leaves open the second component per lane of all three sampling kernels (its widths
 stay within 64), two of the three outcomes of ``heads_waves_per_gaussian`` at N <= 2 048, H = 3 and 4 beyond N = 25, the
 LDS requests above 64 KB in float32, F = 0 and the scalar rows of ``for_row``.  tests/test_aggregate_heads_matrix.py
-mirrors the launchers' selection and asserts, without a GPU, that the case lists below reach all of it.
+asks the launchers' own choice functions and asserts, without a GPU, that the case lists below reach all of it.
 
 Every case compares the output [N, H, L] and all six gradients.  The checker runs on the pair list read back from the
 lists the library built (so the cut-off band plays no part; the lists are tests/test_aggregate_matrix_gpu.py's
@@ -25,8 +25,8 @@ wave wherever N allows one.
 Bars: those of tests/test_aggregate_matrix_gpu.py -- float32 5e-5, float64 1e-10, the frequency gradient x 10, relative
 to the largest entry of the tensor; (e) at the 2e-5 of the test it complements.  No case needed another.
 
-Waves per Gaussian (forward / rows / columns) as the mirror predicts them -- ``WAVES`` below, which the mirror's
-coverage test holds against its own rule -- with (H, L, K, F) @ N:
+Waves per Gaussian (forward / rows / columns) as the launchers choose them -- ``WAVES`` below, which the CPU file's
+coverage test holds against the launchers' rule -- with (H, L, K, F) @ N:
     float32  (2, 40, 24, 5) @ 301: 4/4/2, @ 601: 2/2/1   (3, 20, 22, 4) @ 301: 4/4/2   (3, 21, 21, 4) @ 603: 4/2/1
              (4, 8, 24, 2) @ 301: 4/2/2, @ 601: 4/1/1    (2, 62, 2, 8) @ 301: 2/4/2, @ 601: 1/4/1
              (2, 1, 63, 2) @ 301: 4/2/2                  (4, 1, 29, 12) @ 301: 4/2/2

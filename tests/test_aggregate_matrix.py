@@ -1,60 +1,53 @@
-"""CPU: the sparse checker of the aggregation (oracle/aggregate_sparse.py) against the dense one, and which launch variant
-the aggregation's launchers pick for a problem, mirrored in Python, with the table that says the GPU matrix
-(tests/test_aggregate_matrix_gpu.py) reaches every one of them.
+"""CPU: the sparse checker of the aggregation (oracle/aggregate_sparse.py) against the dense one, and the table that says
+the GPU matrix (tests/test_aggregate_matrix_gpu.py) reaches every launch variant of the aggregation's launchers.
 
-The selection below restates ``aggregate_lists_t``, ``waves_per_gaussian``, ``aggregate_backward_t``, ``sampling_lds``,
-``for_row`` and the three kernels' ``WC > 64`` branches (pigs_amd/csrc/aggregate.hip) and ``aggregate_sizes_ok``
-(pigs_amd/csrc/capi.hip); a threshold changed there is changed here, or the coverage test of this file no longer
-describes what the GPU matrix runs."""
+Which list build a size takes, the waves per Gaussian, the splits of the sums over N, each kernel's LDS request and the
+size rule are asked of the launchers' own functions (pigs_amd/csrc/aggregate_choice.h) through the stand-alone program
+tests/launch_choice_main.cpp (tests/host_program.py); nothing here restates them.  What stays in Python describes the
+kernels' insides, which no launcher computes -- the ``WC > 64`` branches (``second_component``) and ``for_row``'s
+vector and scalar rows (``vector_rows``, ``dacc_rows``) -- and this file's own vocabulary: the tags, the tags that are
+expected, and the coverage logic."""
 import ctypes
 import itertools
 
 import pytest
 import torch
 
+import host_program as hp
 from oracle import aggregate_sparse as sparse
 from oracle import aggregate_torch as dense
 
 SIZEOF = {"float32": 4, "float64": 8}
-AGG_BRUTE_MAX = 2048         # aggregate_lists_t: up to here every pair is tested
-PART = 136                   # values of a wave's partial result
-LDS_DEFAULT = 64 * 1024      # sampling_lds: beyond, the launch asks for it (hipFuncSetAttribute)
-LDS_MAX = 160 * 1024         # AGG_LDS_MAX / PIGS_AGGREGATE_LDS_MAX: the LDS of a CU
-KERNELS = ("forward", "rows", "cols")
+KERNELS = hp.KERNELS
+
+
+def K_(name):
+    """a constant of aggregate_choice.h"""
+    return hp.constants()[name]
 
 
 def ceil_div(a, b):
     return -(-a // b)
 
 
-def waves_per_gaussian(N):
-    return 4 if N <= 4096 else 2 if N <= 8192 else 1
-
-
-def splits(N):
-    return min(max(ceil_div(N, 2048), 1), 64)
-
-
-def region(stride):
-    return max(64 * stride, PART)
+def choice(dtype, N, L, K, F, H=1):
+    """choose_aggregate_forward / _backward with the regions and the size rule: .lds, .waves and .grids per kernel"""
+    return hp.aggregate(dtype, H, N, L, K, F)
 
 
 def lds_bytes(dtype, L, K, F):
-    """Dynamic LDS of the forward, the backward by rows and the backward by columns."""
-    e = SIZEOF[dtype] * 4
-    return {"forward": e * region((L + 4 * F) | 1), "rows": e * (PART + region((K + F) | 1)), "cols": e * region((L + K) | 1)}
-
-
-def second_component(L, K, F):
-    """Which kernels run the acc1 / lane + 64 branches."""
-    return {"forward": L + 8 * F > 64, "rows": K + F > 64, "cols": L + K > 64}
+    """Dynamic LDS of the forward, the backward by rows and the backward by columns, as the launchers ask for it."""
+    return choice(dtype, 1, L, K, F).lds
 
 
 def admitted(dtype, L, K, F):
-    """aggregate_sizes_ok"""
-    if L < 1 or K < 1 or F < 0 or L + 2 * (4 * F + 1) > 128 or L + K > 128 or K + F > 128:
-        return False
-    return max(lds_bytes(dtype, L, K, F).values()) <= LDS_MAX
+    """aggregate_admitted, one head"""
+    return choice(dtype, 1, L, K, F).admitted
+
+
+def second_component(L, K, F):
+    """Which kernels run the acc1 / lane + 64 branches (inside the kernels: no launcher computes it)."""
+    return {"forward": L + 8 * F > 64, "rows": K + F > 64, "cols": L + K > 64}
 
 
 def vector_rows(dtype, n):
@@ -75,39 +68,36 @@ def dacc_rows(dtype, L, F):
 
 @pytest.fixture(scope="module")
 def largest():
-    """The most LDS an admitted shape of each dtype asks for."""
+    """The most LDS an admitted shape of each dtype asks for.  A kernel's request depends on two of the sizes: the
+    forward's on L and F, the backward by rows' on K and F, the backward by columns' on L + K."""
+    probes = {"forward": [(L, 1, F) for L in range(1, 127) for F in range(0, 16)],
+              "rows": [(1, K, F) for K in range(1, 128) for F in range(0, 16)],
+              "cols": [(n - 1, 1, 0) for n in range(2, 129)]}
     best = {}
     for dtype in SIZEOF:
-        strides = {k: set() for k in KERNELS}
-        for L, F in itertools.product(range(1, 127), range(0, 16)):
-            if L + 8 * F + 2 <= 128:
-                strides["forward"].add((L + 4 * F) | 1)
-        for K, F in itertools.product(range(1, 128), range(0, 16)):
-            if K + F <= 128:
-                strides["rows"].add((K + F) | 1)
-        strides["cols"] = {(n | 1) for n in range(2, 129)}
-        e = SIZEOF[dtype] * 4
-        sizes = [e * region(s) for s in strides["forward"] | strides["cols"]] + [e * (PART + region(s)) for s in strides["rows"]]
-        best[dtype] = max(b for b in sizes if b <= LDS_MAX)
+        sizes = [a.lds[k] for k, shapes in probes.items()
+                 for a in hp.aggregate_many([(dtype, 1, 1, L, K, F) for L, K, F in shapes]) if a.components_ok]
+        best[dtype] = max(b for b in sizes if b <= K_("AGG_LDS_MAX"))
     return best
 
 
 def sampling_tags(dtype, periodic, N, L, K, F, largest):
     """The edges of the launchers' selection that one aggregate_neighbors call (forward and backward) sits on."""
-    wpg = waves_per_gaussian(N)
-    tags = {f"waves per Gaussian: {wpg}, {'periodic' if periodic else 'plain'} lists of the "
-            f"{'all-pairs' if N <= AGG_BRUTE_MAX else 'grid'} build",
-            f"waves per Gaussian: {wpg}", "sums over N: one split" if splits(N) == 1 else "sums over N: atomic splits"}
+    ch = choice(dtype, N, L, K, F)
+    assert len(set(ch.waves.values())) == 1           # one head: the three kernels share the rule
+    wpg = ch.waves["forward"]
+    tags = {f"waves per Gaussian: {wpg}, {'periodic' if periodic else 'plain'} lists of the {hp.list_build(N)} build",
+            f"waves per Gaussian: {wpg}", "sums over N: one split" if ch.splits == 1 else "sums over N: atomic splits"}
     if N % (4 // wpg):
         tags.add(f"waves per Gaussian: {wpg}, idle waves in the last workgroup")
-    lds, second = lds_bytes(dtype, L, K, F), second_component(L, K, F)
+    lds, second = ch.lds, second_component(L, K, F)
     for k in KERNELS:
         tags.add(f"{k}: {'second component' if second[k] else 'one component'}")
         if second[k]:       # lanes with lane + 64 < WC carry one: all 64 at WC = 128, the first WC - 64 below
             wc = {"forward": L + 8 * F, "rows": K + F, "cols": L + K}[k]
             tags.add(f"{k}: second component {'in all lanes' if wc == 128 else 'in part of the lanes'}")
-        tags.add(f"{k}: LDS {'above' if lds[k] > LDS_DEFAULT else 'within'} 64 KB")
-        if second[k] and lds[k] <= LDS_DEFAULT:
+        tags.add(f"{k}: LDS {'above' if lds[k] > K_('AGG_LDS_DEFAULT') else 'within'} 64 KB")
+        if second[k] and lds[k] <= K_("AGG_LDS_DEFAULT"):
             tags.add("second component within the default LDS")
     tags.add("second component in: " + "+".join(k for k in KERNELS if second[k]))
     tags.add(f"for_row: rows of L {'vector' if vector_rows(dtype, L) else 'scalar'}, "
@@ -125,7 +115,7 @@ def sampling_tags(dtype, periodic, N, L, K, F, largest):
 
 
 def list_tags(gen, N, periodic):
-    return {f"lists: {'periodic ' if periodic else ''}{'all-pairs' if N <= AGG_BRUTE_MAX else 'grid'} build, {gen}"
+    return {f"lists: {'periodic ' if periodic else ''}{hp.list_build(N)} build, {gen}"
             + (f" N={N}" if gen == "spread" else "")}
 
 
@@ -189,8 +179,13 @@ def missing(cases, largest):
 
 # ------------------------------------------------------------------------------------------
 def test_mirror_tables(largest):
-    assert [waves_per_gaussian(N) for N in (1, 4096, 4097, 8192, 8193)] == [4, 4, 2, 2, 1]
+    """The launchers' numbers, as the program answers them."""
+    waves_per_gaussian = lambda N: set(choice("float32", N, 16, 16, 6).waves.values())
+    splits = lambda N: choice("float32", N, 16, 16, 6).splits
+    assert [waves_per_gaussian(N) for N in (1, 4096, 4097, 8192, 8193)] == [{4}, {4}, {2}, {2}, {1}]
     assert [splits(N) for N in (1, 2048, 2049, 4097, 8193, 1 << 20)] == [1, 1, 2, 3, 5, 64]
+    assert [hp.list_build(N) for N in (1, 2048, 2049)] == ["all-pairs", "all-pairs", "grid"]
+    assert (K_("PART"), K_("AGG_LDS_DEFAULT"), K_("AGG_LDS_MAX")) == (136, 64 * 1024, 160 * 1024)
     # the figures of the LDS limit: every float32 shape of the two-components rule fits, the largest (K + F = 128 in the
     # backward by rows, whose region carries dacc_i as well) at 134 272 B
     assert largest == {"float32": 134272, "float64": 162048}
@@ -234,14 +229,14 @@ def test_the_c_api_applies_the_lds_limit_before_any_hip_call(hip_lib):
     assert {admitted("float64", *s) for s in shapes} == {True, False}
     assert hip_lib.pigs_aggregate_lds_bytes(7, 4, 4, 1) == 0 and hip_lib.pigs_aggregate_lds_bytes(0, 0, 4, 1) == 0
     header = open(__import__("pigs_amd")._lib.HERE + "/../include/pigs_amd.h").read()
-    assert f"#define PIGS_AGGREGATE_LDS_MAX {LDS_MAX}" in header
+    assert f"#define PIGS_AGGREGATE_LDS_MAX {K_('AGG_LDS_MAX')}" in header
     # where the GPU tests read the grid's occupied levels: inside the workspace, and only where a grid is built
     info = (ctypes.c_int64 * 2)()
     for code, N in itertools.product((0, 1), (2049, 2500, 8193)):
         assert hip_lib.pigs_aggregate_grid_info(code, N, info) == 0
         assert 0 <= info[0] <= hip_lib.pigs_aggregate_workspace_bytes(code, N) - 4 and info[0] % 4 == 0
         assert info[1] == {2049: 6, 2500: 6, 8193: 7}[N]          # finest level of G0^2 cells, 4 G0^2 >= N; G0 = 2^(levels - 1)
-    assert hip_lib.pigs_aggregate_grid_info(0, AGG_BRUTE_MAX, info) == 2 and hip_lib.pigs_aggregate_grid_info(7, 4096, info) == 2
+    assert hip_lib.pigs_aggregate_grid_info(0, K_("AGG_BRUTE_MAX"), info) == 2 and hip_lib.pigs_aggregate_grid_info(7, 4096, info) == 2
 
 
 def test_the_gpu_matrix_reaches_every_launch_variant(largest):
@@ -252,7 +247,7 @@ def test_the_gpu_matrix_reaches_every_launch_variant(largest):
         assert admitted(t, L, K, F), (t, name)
     for t, *_, L, K, F in G.VARIANT_CASES + G.PERIODIC_NUMERIC:
         assert admitted(t, L, K, F)
-    assert G.SHAPE_N <= AGG_BRUTE_MAX and ceil_div(G.SHAPE_N, 64) == 5
+    assert hp.list_build(G.SHAPE_N) == "all-pairs" and ceil_div(G.SHAPE_N, 64) == 5
     gaps = missing(cases, largest)
     assert not gaps, gaps
     # nothing is expected that no case could reach, and every instance (name, dtype) is the only one at some edge of

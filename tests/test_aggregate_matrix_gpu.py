@@ -3,8 +3,8 @@ the three sampling kernels at every launch variant against the sparse float64 ch
 
 What tests/test_aggregate_gpu.py and tests/test_periodic_aggregate_gpu.py leave open is N > 2048 -- the grid walk that
 builds the lists, two and one waves per Gaussian, the split sums over N -- and the second component per lane of the
-three kernels; tests/test_aggregate_matrix.py mirrors the launchers' selection and asserts, without a GPU, that the case
-lists below reach all of it.
+three kernels; tests/test_aggregate_matrix.py asks the launchers' own choice functions and asserts, without a GPU, that
+the case lists below reach all of it.
 
 The cut-off band.  With u the unit roundoff of the kernel's dtype and S = |a dx^2| + |2 b dx dy| + |c dy^2|, a pair is
 sure in if q <= q_max - 8 u S, sure out if q > q_max + 8 u S and in the band otherwise (8 u S: a first-order bound of

@@ -1,23 +1,17 @@
 """CPU: the table that says the GPU matrix of the binned path (tests/test_binned_matrix_gpu.py) runs every instantiation
 of pigs_amd/csrc/plan.hip's sampling kernels -- tile_forward_kernel<C, MASK>, tile_backward_kernel<C, MASK> and the
-plan_lists_forward_kernel<C, MASK> of the fused first launch -- in every tile mode, and that the table describes the
-source.
+plan_lists_forward_kernel<C, MASK> of the fused first launch -- in every tile mode.
 
-Restated by hand: ``covering_mask_of`` (tests/test_dense_matrix.py covering_mask), the two ``PIGS_CASE`` tables of
-``plan_forward_c`` / ``plan_backward_c`` as INSTANCES, ``fused_first_compiled`` as FUSED_FIRST, the four tile modes, and
-``list_cap_for`` / the finest grid of ``make_plan_layout`` (pigs_amd/csrc/plan.h).  An instantiation added to plan.hip
-without a row here fails the source test; a scene dropped from the GPU module fails the coverage test."""
-import os
-import re
-
+Which (C, MASK) are compiled and which of them have a fused first launch is read from the lists that generate plan.hip's
+switches (pigs_amd/csrc/instances.h), and ``covering_mask_of``, ``list_cap_for``, the finest grid of ``make_plan_layout``
+and the constants of plan.h and build_choice.h from the library's own headers, all through the stand-alone program
+tests/launch_choice_main.cpp (tests/host_program.py): an instantiation added to instances.h without a scene in the
+matrix fails the coverage test, and so does a scene dropped from the GPU module.  What stays in Python describes the
+kernels' insides and this file's own bookkeeping, not a launcher's choice: the four tile modes, the sites of the
+stores per mode, and the coverage logic."""
+import host_program as hp
 from test_dense_matrix import masks_of
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PLAIN_MASKS = (1, 2, 4, 8, 7, 15, 16, 19, 32, 64)
-C2_MASKS = (128, 256, 512)                               # ORDV, ORDC, ORDN: two channels only
-NAMED = {"ORDR": 32, "ORDG": 64, "ORDV": 128, "ORDC": 256, "ORDN": 512}
-INSTANCES = {(1, m) for m in PLAIN_MASKS} | {(2, m) for m in PLAIN_MASKS + C2_MASKS}
-FUSED_FIRST = {(1, 1), (1, 7), (1, 19), (1, 32), (2, 7)}
 MODES = ("list", "groups", "ranges", "points")
 DIRECTIONS = ("forward", "backward")
 # every mode where the points are sorted into cells (plain stores, or the staging records), LIST also on an index-tiled
@@ -26,22 +20,24 @@ SITES = (("list", "lattice"), ("list", "sorted"), ("groups", "sorted"), ("ranges
 # the helper waves' second trip through their queue does not depend on the template: two instantiations stand for all
 SECOND_TRIP = {(1, 7), (2, 512)}
 
-# ---- plan.h
-POINTS_MODE_MIN_CELLS, POINTS_MODE_MIN_LIST, POINTS_MODE_BLOCK_CELLS, POINT_HELPER_BLOCKS = 16.0, 96, 64.0, 256
-LISTS_SMALL_TILES = 4096          # build_choice.h: up to here a list wave builds one tile (its box is the "block" of the criteria)
-GRID_MARGIN = 1.1251              # gauss_grid: s0 = extent * 1.1251 / G0
+
+def compiled():
+    """{(c, mask)} of tile_forward_kernel / tile_backward_kernel"""
+    return {(c, m) for c in (1, 2) for m in hp.instances("binned", c)}
 
 
-def list_cap_for(N):
-    return min(max((N + 15) // 16 * 16, 16), 512)
+def fused_first():
+    """{(c, mask)} of plan_lists_forward_kernel"""
+    return {(c, m) for c in (1, 2) for m in hp.instances("fused", c)}
 
 
-def finest_grid(N):
-    """make_plan_layout: G0, about 4 Gaussians per finest cell"""
-    g = 1
-    while g * g * 4 < N and g < 1024:
-        g <<= 1
-    return g
+def list_cap(N):
+    return hp.plan_sizes(N)[0]
+
+
+def finest(N):
+    """G0 of make_plan_layout: about 4 Gaussians per finest cell"""
+    return hp.plan_sizes(N)[1]
 
 
 def coverage(scenes, runs, kind_of):
@@ -61,7 +57,7 @@ def coverage(scenes, runs, kind_of):
 
 def missing(scenes, runs, kind_of):
     seen = coverage(scenes, runs, kind_of)
-    want = {(c, m, mode, order, dr) for c, m in INSTANCES for mode, order in SITES for dr in DIRECTIONS}
+    want = {(c, m, mode, order, dr) for c, m in compiled() for mode, order in SITES for dr in DIRECTIONS}
     want |= {(c, m, "points", "second trip", dr) for c, m in SECOND_TRIP for dr in DIRECTIONS}
     return sorted(want - seen)
 
@@ -72,7 +68,7 @@ def fused_missing(scenes, names, calls):
         if name in scenes:
             for c, first in calls:
                 seen.add((c, 32 if first == "linear residual" else masks_of(first)[0], scenes[name][0]))
-    return sorted({(c, m, mode) for c, m in FUSED_FIRST for mode in MODES} - seen)
+    return sorted({(c, m, mode) for c, m in fused_first() for mode in MODES} - seen)
 
 
 # ------------------------------------------------------------------------------------------
@@ -102,59 +98,23 @@ def test_every_fused_first_instantiation_runs_in_every_tile_mode():
         assert fused_missing(G.SCENES, G.FUSED_FIRST_SCENES, G.FUSED_FIRST_CALLS[:k] + G.FUSED_FIRST_CALLS[k + 1:]), k
 
 
-def source(name):
-    with open(os.path.join(ROOT, "pigs_amd", "csrc", name)) as f:
-        return f.read()
-
-
-def body_of(text, head):
-    """the text of the function whose definition starts with ``head``, up to the closing brace in column 0"""
-    start = text.index(head)
-    return text[start:text.index("\n}\n", start)]
-
-
-def invoked(text, macro):
-    """the arguments of the macro's invocations (its own #define apart), as masks"""
-    return [NAMED[a] if a in NAMED else int(a) for a in re.findall(macro + r"\((\w+)\)", text) if a != "MK"]
-
-
 def test_the_tables_describe_the_source():
-    assert len(INSTANCES) == 23 and len(FUSED_FIRST) == 5
-    plan = source("plan.hip")
-    for head in ("static int plan_forward_c(", "static int plan_backward_c("):
-        body = body_of(plan, head)
-        both, two = body.split("if constexpr (C == 2)")
-        assert "PIGS_CASE" in both and "PIGS_CASE" in two
-        got = {(c, m) for c in (1, 2) for m in invoked(both, "PIGS_CASE")} | {(2, m) for m in invoked(two, "PIGS_CASE")}
-        assert got == INSTANCES, (head, sorted(got ^ INSTANCES))
-        assert len(invoked(both, "PIGS_CASE")) == len(PLAIN_MASKS) and len(invoked(two, "PIGS_CASE")) == len(C2_MASKS)
-    fwd = body_of(plan, "static int plan_forward_c(")
-    one, two = fwd[fwd.index("if constexpr (C == 1)"):fwd.index("#undef PIGS_FUSED")].split("} else {")
-    got = {(1, m) for m in invoked(one, "PIGS_FUSED")} | {(2, m) for m in invoked(two, "PIGS_FUSED")}
-    assert got == FUSED_FIRST, sorted(got ^ FUSED_FIRST)
-    compiled = re.search(r"fused_first_compiled\(int mask\) \{ return C == 1 \? \((.*?)\) : (.*?); \}", plan)
-    masks = lambda expr: {int(m) for m in re.findall(r"mask == (\d+)", expr)}
-    assert {(1, m) for m in masks(compiled.group(1))} | {(2, m) for m in masks(compiled.group(2))} == FUSED_FIRST
-    assert "PIGS_FUSED" not in body_of(plan, "static int plan_backward_c(")
-    pair_math = source("pair_math.h")
-    for name, value in NAMED.items():
-        assert re.search(rf"constexpr int {name} = {value};", pair_math), name
-    assert f"constexpr uint32_t LISTS_SMALL_TILES = {LISTS_SMALL_TILES};" in source("build_choice.h")
+    """The instantiations and the constants, as the library's headers state them."""
+    K = hp.constants()
+    plain, two = hp.instances("binned", 1), hp.instances("binned", 2)
+    assert len(compiled()) == 23 and len(fused_first()) == 5
+    assert plain == (1, 2, 4, 8, 7, 15, 16, 19, 32, 64) and two == plain + (128, 256, 512)      # ten for both, three for two channels
+    assert plain == hp.instances("dense", 1, 1)
+    assert fused_first() == {(1, 1), (1, 7), (1, 19), (1, 32), (2, 7)} and fused_first() <= compiled()
+    assert {n: K[n] for n in ("ORDR", "ORDG", "ORDV", "ORDC", "ORDN")} == {"ORDR": 32, "ORDG": 64, "ORDV": 128, "ORDC": 256, "ORDN": 512}
+    assert K["LISTS_SMALL_TILES"] == 4096
     # plan.h: the constants the scenes' comments rely on
-    plan_h = source("plan.h")
-    assert f"constexpr float POINTS_MODE_MIN_CELLS = {POINTS_MODE_MIN_CELLS:g}.f;" in plan_h
-    assert f"constexpr uint32_t POINTS_MODE_MIN_LIST = {POINTS_MODE_MIN_LIST}u;" in plan_h
-    assert f"constexpr float POINTS_MODE_BLOCK_CELLS = {POINTS_MODE_BLOCK_CELLS:g}.f;" in plan_h
-    assert f"constexpr uint32_t POINT_HELPER_BLOCKS = {POINT_HELPER_BLOCKS}u;" in plan_h
-    assert ("constexpr uint32_t TILE_MODE_LIST = 0u, TILE_MODE_RANGES = 1u, TILE_MODE_GROUPS = 2u, TILE_MODE_POINTS = 3u;"
-            in plan_h)
-    cap = body_of(plan_h, "inline uint32_t list_cap_for(int64_t N)")
-    for line in ("int64_t cap = (N + 15) / 16 * 16;", "if (cap < 16) cap = 16;", "if (cap > 512) cap = 512;"):
-        assert line in cap, line
-    assert "while ((int64_t)g * g * 4 < N && g < 1024) g <<= 1;" in body_of(plan_h, "inline PlanLayout make_plan_layout(")
-    assert f"g.s0 = ext * {GRID_MARGIN}f / (float)G0;" in plan_h
-    assert [list_cap_for(n) for n in (1, 16, 17, 512, 513, 100000)] == [16, 16, 32, 512, 512, 512]
-    assert [finest_grid(n) for n in (1, 4, 5, 1024, 1025, 4096, 4097)] == [1, 1, 2, 16, 32, 32, 64]
+    assert (K["POINTS_MODE_MIN_CELLS"], K["POINTS_MODE_MIN_LIST"], K["POINTS_MODE_BLOCK_CELLS"], K["POINT_HELPER_BLOCKS"]) == (16, 96, 64, 256)
+    assert (K["TILE_MODE_LIST"], K["TILE_MODE_RANGES"], K["TILE_MODE_GROUPS"], K["TILE_MODE_POINTS"]) == (0, 1, 2, 3)
+    assert abs(K["GRID_MARGIN"] - 1.1251) < 1e-7            # gauss_grid: s0 = extent * GRID_MARGIN / G0, a float32
+    assert [list_cap(n) for n in (1, 16, 17, 512, 513, 100000)] == [16, 16, 32, 512, 512, 512]
+    assert [finest(n) for n in (1, 4, 5, 1024, 1025, 4096, 4097)] == [1, 1, 2, 16, 32, 32, 64]
+    assert finest(4 * 1024 * 1024 + 1) == 1024 and finest(1 << 30) == 1024       # the grid stops at 1 024 x 1 024
 
 
 def test_scene_arithmetic():
@@ -162,7 +122,10 @@ def test_scene_arithmetic():
     tile and quad, and the two criteria that send the P scenes' tiles to the per-point walk."""
     import test_binned_matrix_gpu as G
     S = G.SCENES
-    assert {n: (finest_grid(s[2]), list_cap_for(s[2])) for n, s in S.items()} == {
+    K = hp.constants()
+    LISTS_SMALL_TILES, GRID_MARGIN, POINT_HELPER_BLOCKS = K["LISTS_SMALL_TILES"], K["GRID_MARGIN"], K["POINT_HELPER_BLOCKS"]
+    POINTS_MODE_MIN_CELLS, POINTS_MODE_BLOCK_CELLS = K["POINTS_MODE_MIN_CELLS"], K["POINTS_MODE_BLOCK_CELLS"]
+    assert {n: (finest(s[2]), list_cap(s[2])) for n, s in S.items()} == {
         "L-lattice": (16, 512), "L-sorted": (16, 512), "R": (16, 512), "G": (32, 512), "P": (32, 512), "P-stride": (64, 512)}
     assert (S["L-lattice"][2], S["L-lattice"][3]) == (24 * 24, 64 * 64)
     assert S["R"][2] > 512                                      # a slab of 512 entries that 700 Gaussians can overflow
@@ -173,7 +136,7 @@ def test_scene_arithmetic():
         if "ragged quad" in claims:
             assert M % 4 != 0, name
         assert -(-M // 64) <= LISTS_SMALL_TILES
-    cells_of_domain = lambda N: (finest_grid(N) / GRID_MARGIN) ** 2      # finest cells under the points' box
+    cells_of_domain = lambda N: (finest(N) / GRID_MARGIN) ** 2      # finest cells under the points' box
     # P: uniform points, a tile's box is about 1 / tiles of the domain: more than POINTS_MODE_BLOCK_CELLS
     _, _, N, M, _, _ = S["P"]
     assert cells_of_domain(N) / -(-M // 64) > POINTS_MODE_BLOCK_CELLS

@@ -85,7 +85,7 @@ import numpy as np
 import pytest
 import torch
 
-import test_binned_matrix as mirror
+import host_program as hp
 from test_dense_matrix_gpu import Case, ORDER_SETS, Worst, A0, A1, AL, np64, out_shape
 
 pytestmark = pytest.mark.gpu
@@ -237,7 +237,7 @@ def assert_mode(cs, plan, hip_lib, s):
     elif cs.name == "L-sorted":
         assert counts[0] == tiles, what
         assert ng.max() > 64 and count.max() > 128, (what, int(ng.max()), int(count.max()))
-        assert ng.max() <= mirror.list_cap_for(cs.N) and count.max() <= mirror.list_cap_for(cs.N)
+        assert ng.max() <= hp.plan_sizes(cs.N)[0] and count.max() <= hp.plan_sizes(cs.N)[0]
         assert 1 <= cs.M % 64 <= 15 and ng[-1, 0] > 0 and not ng[-1, 1:].any(), (what, ng[-1].tolist())
     elif cs.name == "R":
         r = mode == 1
@@ -247,7 +247,7 @@ def assert_mode(cs, plan, hip_lib, s):
         assert not ((count[r] == 1) & (slabs[r, 1] == cs.N)).any(), "a tile fell back to the single range {0, N}"
     elif cs.name == "G":
         assert counts[2] > 0, what
-        assert ng[mode == 2].max() <= mirror.list_cap_for(cs.N)
+        assert ng[mode == 2].max() <= hp.plan_sizes(cs.N)[0]
     elif cs.name == "P":
         assert counts[3] == tiles and cs.M % 4 != 0, what
     else:

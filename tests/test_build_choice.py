@@ -5,14 +5,13 @@ through a small stand-alone program (tests/build_choice_main.cpp, host code only
 seven booleans, `order` and the memory's answers, each combination with several draws of the sizes and settings, and over
 the full cross of sizes and settings on the requests that reach the most paths."""
 import itertools
-import os
 import random
-import subprocess
 from collections import namedtuple
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_program
+
 BBOX, ZERO, COUNT, SCAN, SCATTER, BINSORT16, BINSORT1, LISTS_SMALL, LISTS = range(9)      # build_choice.h, BuildKernel
 RFS = (0, 8, 12, 128, 1024)
 # (2048^2: an eighth of the count's blocks is more than the 256 workgroups that may meet at a device-wide barrier)
@@ -28,18 +27,8 @@ Layout = namedtuple("Layout", "s_scan h_scan h_wgs h_chunk cells_per_bin ntiles 
 
 
 @pytest.fixture(scope="module")
-def program(tmp_path_factory):
-    hipcc = os.environ.get("HIPCC", "hipcc")      # as pigs_amd/build.py
-    exe = str(tmp_path_factory.mktemp("build_choice") / "build_choice_main")
-    subprocess.run([hipcc, "-x", "hip", "--cuda-host-only", "-O1", "-std=c++17", "-Wall", "-o", exe,
-                    os.path.join(ROOT, "tests", "build_choice_main.cpp")], check=True)
-
-    def run(lines):
-        out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, check=True).stdout
-        out = out.splitlines()
-        assert len(out) == len(lines)
-        return out
-    return run
+def program():
+    return lambda lines: host_program.ask("build_choice_main", lines)
 
 
 @pytest.fixture(scope="module")

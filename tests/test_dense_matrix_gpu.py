@@ -1,8 +1,8 @@
 """GPU: every instantiation of the dense kernels (pigs_amd/csrc/dense.hip: 2 dtypes x 2 dimensions x 4 channel counts x
 10 covering masks) through every launch variant it can take, against the float64 oracle.
 
-The shapes S1..S7 are the smallest that put a launch on an edge of its selection (tests/test_dense_matrix.py mirrors the
-selection and asserts, without a GPU, that the case list below covers the table); STORE_N x STORE_M is the smallest
+The shapes S1..S7 are the smallest that put a launch on an edge of its selection (tests/test_dense_matrix.py asks the
+launchers' own choice functions and asserts, without a GPU, that the case list below covers the table); STORE_N x STORE_M is the smallest
 problem whose backward stores its sums directly (gridDim.y == 1) instead of adding them into zeroed buffers.
 
 Expectations: oracle/c_oracle.py in float64 on the inputs as the kernel saw them (rounded to the test's dtype).  The
@@ -36,8 +36,6 @@ import numpy as np
 import pytest
 import torch
 
-import test_dense_matrix as mirror
-
 pytestmark = pytest.mark.gpu
 
 # ---- the case list: plain data (tests/test_dense_matrix.py reads it without a GPU)
@@ -48,8 +46,11 @@ SHAPES = (("S1", None, 81),         # N = rows chunk + 33: a second LDS chunk of
           ("S5", 300, 16350),       # 256 blocks: the last that take rows; staged backward of 64-point slices at its threshold
           ("S6", 130, 16445),       # 257 blocks: w16 / w4; split backward, 65 slices of 253 points
           ("S7", 70, 65473))        # 1 024 blocks: w4 also where w16 exists; split backward, 256 slices
-CASES = [(t, d, c, name, N if N is not None else mirror.rows_chunk(t, d, c) + 33, M)
-         for t, d, c in mirror.INSTANCES for name, N, M in SHAPES]
+INSTANCES = [(t, d, c) for t in ("float32", "float64") for d in (1, 2) for c in (1, 2, 3, 4)]
+# S1's N, the instantiation's rows chunk + 33 (tests/test_dense_matrix.py holds each to the library's chunk)
+S1_N = {("float32", 1): (3105, 2337, 1876, 1569), ("float32", 2): (1569, 1349, 1185, 1057),
+        ("float64", 1): (1569, 1185, 954, 801), ("float64", 2): (801, 691, 609, 545)}       # c = 1 .. 4
+CASES = [(t, d, c, name, N if N is not None else S1_N[t, d][c - 1], M) for t, d, c in INSTANCES for name, N, M in SHAPES]
 # (orders of one sample() call, the outputs its loss reads: None = all of them)
 ORDER_SETS = [((0,), None), ((1,), None), ((2,), None), ((3,), None), (("lap",), None), ((0, 1, 2), None),
               ((0, 1, 2, 3), None), ((0, 1, "lap"), None),
@@ -193,6 +194,7 @@ class Case:
 
 
 def run_matrix_case(dtype, d, c, name, N, M):
+    import test_dense_matrix as table        # the variants' names: asked of the launchers' choice functions
     import test_residual_terms_gpu as R
     cs = Case(dtype, d, c, N, M, (dtype, d, c, name))
     oracle, rng, args = cs.oracle, cs.rng, cs.args
@@ -200,14 +202,14 @@ def run_matrix_case(dtype, d, c, name, N, M):
     exp["lap"] = sum(exp[2][:, i, i] for i in range(d))
     r = {o: cs.draw(out_shape(o, M, d, c)) for o in (0, 1, 2, 3, "lap")}
     pieces = {o: cs.piece(o, r[o][1]) for o in r}
-    bvar = mirror.backward_variant(N, M)
+    bvar = table.choice(dtype, d, c, 1, N, M).backward
     s = cs.sampler()
 
     # ---- sample(): every covering mask alone, requests with holes, a backward with holes the forward did not have
     for orders, reads in ORDER_SETS:
         reads = orders if reads is None else reads
-        fmask, _ = mirror.masks_of(orders, reads)
-        fvar = mirror.forward_variant(dtype, d, c, fmask, N, M)
+        fmask, _ = table.masks_of(orders, reads)
+        fvar = table.choice(dtype, d, c, fmask, N, M).forward
         s.preprocess(cs.t[0], cs.t[1], None, cs.t[2], cs.t[3])          # forget the outputs of the previous set
         outs = s.sample(orders)
         for o, out in zip(orders, outs):
@@ -232,7 +234,7 @@ def run_matrix_case(dtype, d, c, name, N, M):
             (64, "fields", Fn, lambda t_: R.call(s, Fn, B, t_)),
             (64, "fields + advection", Fa, lambda t_: R.call(s, Fa, B, t_))):
         F64 = tuple(None if a is None else np64(a) for a in F)
-        fvar = mirror.forward_variant(dtype, d, c, mask, N, M)
+        fvar = table.choice(dtype, d, c, mask, N, M).forward
         want_r = R.compose(exp, F64, B64, tgt64, d)
         t_ = tgt.clone().requires_grad_(True)
         res = call(t_)
@@ -279,9 +281,10 @@ def test_direct_store_backward(hip_lib, dtype, d, c, what):
     sums without atomics, into buffers nobody zeroed.  The oracle takes 512 points for the outputs and 512 Gaussians
     (the first and the last workgroup and a random rest; a Gaussian's gradient needs no other Gaussian) against all
     points for the gradients; every entry must be finite."""
+    import test_dense_matrix as table
     import test_residual_terms_gpu as R
     N, M = STORE_N, STORE_M
-    assert mirror.backward_variant(N, M) == "split_store"
+    assert table.choice(dtype, d, c, 1, N, M).backward == "split_store"
     cs = Case(dtype, d, c, N, M, (dtype, d, c, what, "store"))
     oracle, rng, args = cs.oracle, cs.rng, cs.args
     psel = np.unique(np.concatenate((np.arange(64), np.arange(M - 64, M), rng.choice(M, 384, replace=False))))
@@ -298,7 +301,7 @@ def test_direct_store_backward(hip_lib, dtype, d, c, what):
         res = R.call(s, F, B, tgt)
         want = R.compose(exp, tuple(np64(a)[psel] for a in F), B64, tgt64[psel], d)
         cs.w.require(bool(torch.isfinite(res).all()), "output not finite")
-        cs.check_output(mirror.forward_variant(dtype, d, c, 64, N, M), "output", res[psel], want,
+        cs.check_output(table.choice(dtype, d, c, 64, N, M).forward, "output", res[psel], want,
                         scale=float(res.detach().abs().max()))
         dirty_the_allocator(cs)
         got = torch.autograd.grad((res * w).sum(), (cs.t[0], cs.t[1], cs.t[2]))
@@ -308,7 +311,7 @@ def test_direct_store_backward(hip_lib, dtype, d, c, what):
         R.check_against_own_composition(s, (cs.t[0], cs.t[1], cs.t[2]), F, B, tgt, d, w)
         cs.w.report()
         return
-    fmask, _ = mirror.masks_of(what)
+    fmask, _ = table.masks_of(what)
     exp = oracle.forward(*args[:3], args[3][psel], orders=tuple(o for o in what if o != "lap") + ((2,) if "lap" in what else ()))
     if "lap" in what:
         exp["lap"] = sum(exp[2][:, i, i] for i in range(d))
@@ -316,7 +319,7 @@ def test_direct_store_backward(hip_lib, dtype, d, c, what):
     r = {o: cs.draw(out_shape(o, M, d, c)) for o in what}
     for o, out in zip(what, outs):
         cs.w.require(bool(torch.isfinite(out).all()), (o, "output not finite"))
-        cs.check_output(mirror.forward_variant(dtype, d, c, fmask, N, M), ("output", o), out[psel], exp[o],
+        cs.check_output(table.choice(dtype, d, c, fmask, N, M).forward, ("output", o), out[psel], exp[o],
                         scale=float(out.detach().abs().max()))
     loss = sum((out * r[o][0]).sum() for o, out in zip(what, outs))
     dirty_the_allocator(cs)

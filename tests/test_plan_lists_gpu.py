@@ -79,7 +79,7 @@ import torch
 import test_binned_matrix_gpu as BM
 from oracle import dense_numpy, plan_lists as PL
 from test_binned_matrix_gpu import SCENES, assert_mode, geometry, headers, round32, seed_of
-from test_dense_matrix import covering_mask
+from host_program import covering as covering_mask      # covering_mask_of, asked of the library's own function
 from test_dense_matrix_gpu import A0, A1, AL, Worst, np64
 from test_plan_lists import STRIPS_CASES, strips_geometry
 

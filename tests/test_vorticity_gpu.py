@@ -26,7 +26,6 @@ from conftest import grads_within_accumulation_bound
 from oracle import c_oracle
 from pigs_amd import synthetic
 from test_binned_gpu import TOL, dev32
-from test_dense_matrix import backward_variant, forward_variant
 from test_periodic_gpu import check_grads as check_periodic_grads
 from test_periodic_gpu import periodic_forward
 from test_vorticity import column_scales, combine, expand
@@ -91,21 +90,22 @@ def check_f32_grads(got, args, gout64):
 # 1. dense, every launch variant the mask can take
 # ------------------------------------------------------------------------------------------
 NACC = 7
-# forward_variant / backward_variant mirror the launchers' selection by accumulator count: d = 2, c = 7, mask 1 is the
-# entry of tests/test_dense_matrix.py's table with FwdLayout::N == 7
+# the launchers' selection goes by accumulator count: d = 2, c = 7, mask 1 is the instantiation that
+# tests/host_program.py can ask about with FwdLayout::N == 7
 DENSE_SHAPES = [(33, 81), (161, 81), (100, 19201), (1300, 16400), (1300, 5501)]
 DENSE_CASES = [(torch.float32, N, M) for N, M in DENSE_SHAPES] + [(torch.float64, N, M) for N, M in DENSE_SHAPES[:3]]
 
 
 def variants_of(dtype, N, M):
-    name = "float32" if dtype == torch.float32 else "float64"
-    return forward_variant(name, 2, NACC, 1, N, M), backward_variant(N, M)
+    import host_program as hp
+    ch = hp.dense("float32" if dtype == torch.float32 else "float64", 2, NACC, 1, N, M)
+    return ch.forward, ch.backward
 
 
 def test_the_dense_cases_reach_every_variant():
-    """A changed threshold in dense.hip (mirrored in tests/test_dense_matrix.py) shows up here, not as a silent hole."""
-    from test_dense_matrix import nacc
-    assert nacc(2, NACC, 1) == NACC
+    """A changed threshold in dense_choice.h shows up here, not as a silent hole."""
+    import host_program as hp
+    assert hp.dense("float32", 2, NACC, 1, 1, 1).accumulators == NACC
     assert all(N % 64 and M % 64 for N, M in DENSE_SHAPES)
     f32 = [variants_of(torch.float32, N, M) for t, N, M in DENSE_CASES if t == torch.float32]
     f64 = [variants_of(torch.float64, N, M) for t, N, M in DENSE_CASES if t == torch.float64]
@@ -287,7 +287,7 @@ def test_hosts_agree_bitwise(hip_lib, dtype):
     the points with ONE slice, so every gradient entry is a single atomic add to zero and has no order to depend on.)"""
     from diff_gaussian_sampling import GaussianSampler
     means, values, con, pts, gout = dense_inputs(200, 32, 5)
-    assert backward_variant(200, 32) == "staged32"
+    assert variants_of(dtype, 200, 32)[1] == "staged32"
     res = {}
     for host in HOSTS:
         t = leaves_of(means, values, con, dtype)

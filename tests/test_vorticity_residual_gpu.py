@@ -26,7 +26,6 @@ from conftest import grads_within_accumulation_bound
 from oracle import c_oracle
 from pigs_amd import synthetic
 from test_binned_gpu import TOL, dev32
-from test_dense_matrix import backward_variant
 from test_periodic_gpu import check_grads as check_periodic_grads
 from test_periodic_gpu import periodic_forward
 from test_vorticity import combine, expand
@@ -286,7 +285,8 @@ def test_hosts_agree_bitwise(hip_lib, dtype):
     """Same C ABI, same launches: bit-identical outputs and gradients (N = 200, M = 32: staged32, one slice)."""
     from diff_gaussian_sampling import GaussianSampler
     means, values, con, pts, g7 = dense_inputs(200, 32, 5)
-    assert backward_variant(200, 32) == "staged32"
+    import host_program as hp
+    assert hp.dense("float32", 2, 2, 512, 200, 32).backward == "staged32"
     prev, tau, gout = dev(g7[::-1].copy(), dtype), dev(np.abs(g7[:, 0]), dtype), dev(g7[:, 1:3], dtype)
     res = {}
     for host in HOSTS:
