@@ -190,7 +190,8 @@ def test_quantile_formula_at_an_integer_position():
 
 @pytest.mark.parametrize("c", [1, 2])
 def test_oracle_is_the_reference_lines_restated(c):
-    """model_pn.py:733, :745, :750-754 with torch on the CPU, float64"""
+    """model_pn.py:733, :745, :750-754 with torch on the CPU, float64 (the oracle is held to the three fields and the split
+    of a recorded forward of the reference in tests/test_model_split.py)"""
     n = 1600
     su, pu, D = random_fields(n, c, 11 + c)
     boundary = np.random.default_rng(3).random((n, 1)) < 0.8

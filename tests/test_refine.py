@@ -80,7 +80,8 @@ def refine_oracle(means, scaling, transforms, values, keep, split, mode="split",
 
 def reference_split_restated(means, scaling, transforms, values, keep, split):
     """model_pn.py:703-714 (prune by one mask) and :586-601 (Model.split) in float64 torch on the CPU:
-    torch.linalg.eig, the eigenpair of largest |eigenvalue|, children at -/+ eigenvalue * eigenvector, u / 2."""
+    torch.linalg.eig, the eigenpair of largest |eigenvalue|, children at -/+ eigenvalue * eigenvector, u / 2.
+    Itself held to a recorded forward of the reference in tests/test_model_split.py."""
     m, s, t, u = (torch.as_tensor(np.asarray(a, np.float64)) for a in (means, scaling, transforms, values))
     kept = torch.as_tensor(keep)
     m, s, t, u = m[kept], s[kept], t[kept], u[kept]
