@@ -866,6 +866,43 @@ int pigs_mlp_backward(int dtype, int64_t N, int L, const int* widths, const void
                       const void* const* biases, const void* g_y, void* scratch, size_t scratch_bytes, void* g_x,
                       void* const* g_weights, void* const* g_biases, void* stream);
 
+/* ---- A bank of tanh networks of one shape over one input, per launch (additive to ABI 10) ------
+ * The query_transform / key_transform nets of all attention heads (model_pn.py:203-226, used at :259-261) have one shape
+ * and read the same features.  A bank is B such nets, 1 <= B <= PIGS_MLP_BANK_MAX_NETS, each a net of the pigs_mlp_*
+ * block in every respect (the same L, the same widths w_0 .. w_L, float32), all applied to the same x [N][w_0].  With a
+ * group count G that divides B,
+ *   y [G][N][B / G][w_L]:   y[b / (B / G)][row][b % (B / G)][:] = net_b(x[row])
+ * G = 1 gives [1][N][B][w_L]; B = 4, G = 2 with the nets in the order (q0, q1, k0, k1) gives y[0] = queries [N][H][K]
+ * and y[1] = keys [N][H][K] of pigs_aggregate_heads_forward, contiguous, without a stack or a copy.
+ * `widths` is a host array of L + 1 ints, the same for every net; `weights`, `biases`, `g_weights`, `g_biases` are host
+ * arrays of B L device pointers, net b's layer l at index b L + l.  The host arrays are read during the call and not kept.
+ *
+ * pigs_mlp_bank_forward, one launch.  A workgroup belongs to one net: it stages that net's weights in LDS (the LDS need
+ *   is that of one net: every net pigs_mlp_forward takes is taken for every B) and runs pigs_mlp_forward's chain; only
+ *   the store differs.  y of net b has the bits of pigs_mlp_forward(x, net b).
+ * pigs_mlp_bank_backward, at most two launches.  From g_y (the layout of y) to g_x [N][w_0] = sum_b g_x^(b), added in the
+ *   order b = 0, 1, .., B - 1, and every g_weights / g_biases entry; a NULL g_x, a NULL array or a NULL entry is not
+ *   written.  Launch 1 is pigs_mlp_backward's first launch per net, at most PIGS_MLP_MAX_RECORDS waves and records PER
+ *   NET; net 0 writes its part of g_x into g_x, net b > 0 into the scratch.  Launch 2 adds every net's records in the order
+ *   of pigs_mlp_backward and adds the parts into g_x element by element; it is left out when B = 1 and only g_x is wanted.
+ *   A net with no gradient wanted is not run when g_x is not wanted either.  No float atomics: every output is a pure
+ *   function of the inputs, bit for bit.
+ * scratch: pigs_mlp_bank_scratch_bytes(N, B, L, widths) bytes = B pigs_mlp_scratch_bytes(N, L, widths) for the records,
+ *   then (B - 1) N w_0 floats for the parts of g_x; 4-byte aligned; 0 for N <= 0 or an unsupported bank.  Needed with a
+ *   weight or bias gradient wanted, and with g_x wanted when B > 1.  Not read by the caller.
+ * Arguments are checked before any HIP call: a dtype other than PIGS_F32, L or a width out of range, or B outside
+ *   1..PIGS_MLP_BANK_MAX_NETS is PIGS_ERR_UNSUPPORTED; G < 1 or G not dividing B, N <= 0, a null required array (widths,
+ *   x, weights, biases and their entries, y or g_y; the backward with no gradient wanted), or a null, misaligned or short
+ *   scratch when it is needed is PIGS_ERR_INVALID.  Nothing allocates, frees, synchronises or waits for another workgroup.
+ */
+#define PIGS_MLP_BANK_MAX_NETS 8
+size_t pigs_mlp_bank_scratch_bytes(int64_t N, int B, int L, const int* widths);
+int pigs_mlp_bank_forward(int dtype, int64_t N, int B, int G, int L, const int* widths, const void* x,
+                          const void* const* weights, const void* const* biases, void* y, void* stream);
+int pigs_mlp_bank_backward(int dtype, int64_t N, int B, int G, int L, const int* widths, const void* x,
+                           const void* const* weights, const void* const* biases, const void* g_y, void* scratch,
+                           size_t scratch_bytes, void* g_x, void* const* g_weights, void* const* g_biases, void* stream);
+
 /* ---- The dynamics network's input transform (additive to ABI 10) -------------------------------
  * InputTransform (model_pn.py:51-152) as DynamicsNetwork.forward uses it (:237-249): t_params, the input of
  * input_projection.  d = 2, c = 1..4 channels, p = pde_size = 1..4, float32 only.  Row-major device arrays:

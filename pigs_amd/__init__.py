@@ -23,7 +23,11 @@ Public surface:
                             (pigs_amd.mlp; model_pn.py:154-174, 187-198, 203-226)
     FusedMLP                ``FusedMLP.from_sequential(seq)``: the same, as a module over an existing nn.Sequential
                             whose Parameters and state_dict keys it keeps
-    transform_matrices      the input transform's five matrices from the Gaussians (latent net, mean, five
+    fused_mlp_bank          up to 8 such nets of one shape over one input in one launch forward and at most two
+                            backward; the model's query / key nets of all heads leave ``queries`` and ``keys`` in the
+                            layout of ``aggregate_neighbors_heads`` (pigs_amd.mlp; model_pn.py:259-261)
+    FusedMLPBank            ``FusedMLPBank(nets, groups)``: the same as a non-owning callable over existing nets
+    transform_matrices     the input transform's five matrices from the Gaussians (latent net, mean, five
                             TransformNets) in two launches (pigs_amd.input_transform; model_pn.py:51-119)
     apply_transforms        those matrices applied to the rows: ``t_params`` in one launch (model_pn.py:121-152, 237-249)
     FusedInputTransform     ``FusedInputTransform.from_module(m)``: both, as a module over an existing InputTransform
@@ -53,7 +57,7 @@ def __getattr__(name):
     if name in ("advance_gaussians", "ADVANCE_PENALTY_COLUMNS"):
         from . import advance
         return getattr(advance, name)
-    if name in ("fused_mlp", "FusedMLP"):
+    if name in ("fused_mlp", "FusedMLP", "fused_mlp_bank", "FusedMLPBank"):
         from . import mlp
         return getattr(mlp, name)
     if name in ("transform_matrices", "apply_transforms", "FusedInputTransform"):

@@ -185,6 +185,11 @@ SIGNATURES = {
     "pigs_mlp_scratch_bytes": (ctypes.c_size_t, [_i64, _i, _ip]),
     "pigs_mlp_forward": (_i, [_i, _i64, _i, _ip, _vp, _vpp, _vpp, _vp, _vp]),
     "pigs_mlp_backward": (_i, [_i, _i64, _i, _ip, _vp, _vpp, _vpp, _vp, _vp, ctypes.c_size_t, _vp, _vpp, _vpp, _vp]),
+    # a bank of B nets of one shape over one x (additive to ABI 10): + B, G; the pointer arrays hold B * L entries
+    "pigs_mlp_bank_scratch_bytes": (ctypes.c_size_t, [_i64, _i, _i, _ip]),
+    "pigs_mlp_bank_forward": (_i, [_i, _i64, _i, _i, _i, _ip, _vp, _vpp, _vpp, _vp, _vp]),
+    "pigs_mlp_bank_backward": (_i, [_i, _i64, _i, _i, _i, _ip, _vp, _vpp, _vpp, _vp, _vp, ctypes.c_size_t, _vp, _vpp, _vpp,
+                                    _vp]),
     # the input transform (additive to ABI 10): dtype, N, c, p, the row arrays, ... ; params / g_params are 36 pointers
     "pigs_input_transform_scratch_bytes": (ctypes.c_size_t, [_i64, _i, _i]),
     "pigs_input_transform_matrices_forward": (_i, [_i, _i64, _i, _i] + [_vp] * 8 + [_vpp, _vp, ctypes.c_size_t, _vp, _vp, _vp]),

@@ -771,4 +771,44 @@ int pigs_mlp_backward(int dtype, int64_t N, int L, const int* widths, const void
     return mlp_backward(s, (hipStream_t)stream);
 }
 
+size_t pigs_mlp_bank_scratch_bytes(int64_t N, int B, int L, const int* widths) {
+    return mlp_bank_scratch_bytes(N, B, L, widths);
+}
+
+static int mlp_bank_sizes_ok(int dtype, int64_t N, int B, int G, int L, const int* widths) {
+    if (dtype != PIGS_F32) return PIGS_ERR_UNSUPPORTED;
+    if (B < 1 || B > PIGS_MLP_BANK_MAX_NETS) return PIGS_ERR_UNSUPPORTED;
+    const int rc = mlp_sizes_ok(dtype, N, L, widths);
+    if (rc != PIGS_OK) return rc;
+    return G < 1 || B % G ? PIGS_ERR_INVALID : PIGS_OK;
+}
+
+int pigs_mlp_bank_forward(int dtype, int64_t N, int B, int G, int L, const int* widths, const void* x,
+                          const void* const* weights, const void* const* biases, void* y, void* stream) {
+    const int rc = mlp_bank_sizes_ok(dtype, N, B, G, L, widths);
+    if (rc != PIGS_OK) return rc;
+    if (mlp_net_missing(B * L, x, weights, biases) || !y) return PIGS_ERR_INVALID;
+    MlpBankStep s{};
+    s.N = N; s.B = B; s.G = G; s.L = L; s.widths = widths; s.x = x; s.weights = weights; s.biases = biases; s.y = y;
+    return mlp_bank_forward(s, (hipStream_t)stream);
+}
+
+int pigs_mlp_bank_backward(int dtype, int64_t N, int B, int G, int L, const int* widths, const void* x,
+                           const void* const* weights, const void* const* biases, const void* g_y, void* scratch,
+                           size_t scratch_bytes, void* g_x, void* const* g_weights, void* const* g_biases, void* stream) {
+    const int rc = mlp_bank_sizes_ok(dtype, N, B, G, L, widths);
+    if (rc != PIGS_OK) return rc;
+    if (mlp_net_missing(B * L, x, weights, biases) || !g_y) return PIGS_ERR_INVALID;
+    bool params = false;
+    for (int k = 0; k < B * L; ++k) params = params || (g_weights && g_weights[k]) || (g_biases && g_biases[k]);
+    if (!g_x && !params) return PIGS_ERR_INVALID;
+    if ((params || (g_x && B > 1)) &&
+        (!scratch || ((uintptr_t)scratch & 3u) || scratch_bytes < mlp_bank_scratch_bytes(N, B, L, widths)))
+        return PIGS_ERR_INVALID;
+    MlpBankStep s{};
+    s.N = N; s.B = B; s.G = G; s.L = L; s.widths = widths; s.x = x; s.weights = weights; s.biases = biases; s.g_y = g_y;
+    s.scratch = scratch; s.g_x = g_x; s.g_weights = g_weights; s.g_biases = g_biases;
+    return mlp_bank_backward(s, (hipStream_t)stream);
+}
+
 }  // extern "C"

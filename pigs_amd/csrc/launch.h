@@ -129,6 +129,25 @@ size_t mlp_scratch_bytes(int64_t N, int L, const int* widths);
 int mlp_forward(const MlpStep& s, hipStream_t stream);
 int mlp_backward(const MlpStep& s, hipStream_t stream);
 
+// mlp_bank.hip: B nets of one shape over one x; y and g_y are [G][N][B / G][widths[L]]
+struct MlpBankStep {
+    int64_t N;
+    int B, G, L;
+    const int* widths;                  // [L + 1], host: the same for every net
+    const void* x;                      // [N][widths[0]]
+    const void* const* weights;         // [B * L] device pointers, host array, net b's layer l at b * L + l
+    const void* const* biases;
+    void* y;                            // forward
+    const void* g_y;                    // backward: the incoming gradient
+    void* scratch;                      // backward: the waves' records of every net, then the nets' parts of g_x
+    void* g_x;                          // backward: null = not wanted
+    void* const* g_weights;             // backward: null, or [B * L] with null entries = not wanted
+    void* const* g_biases;
+};
+size_t mlp_bank_scratch_bytes(int64_t N, int B, int L, const int* widths);
+int mlp_bank_forward(const MlpBankStep& s, hipStream_t stream);
+int mlp_bank_backward(const MlpBankStep& s, hipStream_t stream);
+
 // periodic.hip: images (fold = false; a = means, conics, values; o = image arrays) or the fold of their gradients
 // (fold = true; a = image gradients, null = zero; o = gradients)
 int periodic_dispatch(bool fold, int dtype, int c, int64_t N, double lo, double period, double q_cut, const void* a0,

@@ -31,8 +31,11 @@
 // order.  No float atomics: the gradients are a pure function of the inputs.  Masked rows hold g_y = 0, hence dZ = 0 in
 // every layer.
 //
-// The net's description, the staging, the forward helpers (mlp_stage, mlp_layer, mlp_tanh, ...) and the backward's layer
-// (mlp_backward_layer, mlp_record_layer) live in mlp_chain.h: input_transform.hip runs the same chain over gathered rows.
+// The net's description, the staging, the forward helpers (mlp_stage, mlp_layer, mlp_tanh, ...), the backward's layer
+// (mlp_backward_layer, mlp_record_layer) and the bodies of the forward and the finishing kernel live in mlp_chain.h:
+// input_transform.hip runs the same chain over gathered rows, mlp_bank.hip the same bodies for several nets of one shape
+// in one launch.  The backward kernel's body stands here AND in mlp_chain.h (mlp_backward_tiles<MLP_TILES>, for the
+// bank): called as a function it no longer fits this kernel's registers; a change to one is a change to both.
 #include <hip/hip_runtime.h>
 
 #include "launch.h"
@@ -48,20 +51,7 @@ __global__ __launch_bounds__(64 * MLP_WAVES) void mlp_forward_kernel(int64_t N, 
                                                                      const float* __restrict__ x, float* __restrict__ y) {
     extern __shared__ float mlp_lds[];
     mlp_stage(n, mlp_lds);
-    const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
-    const int64_t stride = (int64_t)gridDim.x * MLP_WAVES;
-    for (int64_t tile = (int64_t)blockIdx.x * MLP_WAVES + (threadIdx.x >> 6); tile < tiles; tile += stride) {
-        const int64_t row = tile * 16 + r;
-        const bool live = row < N;
-        f4 a[MLP_TILES], z[MLP_TILES];
-        mlp_load_rows(a, x, row, live, n.w[0], g);
-        for (int l = 0; l < n.L; ++l) {
-            const int nti = mlp_tiles(n.w[l]), nto = mlp_tiles(n.w[l + 1]);
-            mlp_layer(z, a, mlp_lds + n.woff[l], mlp_lds + n.boff[l], 16 * nti + 4, nti, nto, r, g);
-            if (l + 1 < n.L) mlp_tanh(a, z);
-        }
-        mlp_store_rows(y, z, row, live, n.w[n.L], g);
-    }
+    mlp_forward_tiles(N, tiles, n, mlp_lds, x, y, n.w[n.L]);
 }
 
 __global__ __launch_bounds__(64 * MLP_WAVES) void mlp_backward_kernel(int64_t N, int64_t tiles, MlpNet n, MlpGrads out,
@@ -91,7 +81,7 @@ __global__ __launch_bounds__(64 * MLP_WAVES) void mlp_backward_kernel(int64_t N,
         const bool live = row < N;
         f4 a[MLP_TILES], d[MLP_TILES];
         mlp_wave_fence();                      // the previous tile's reads of this region are done
-        mlp_load_rows(a, x, row, live, n.w[0], g);
+        mlp_load_rows(a, x, row, live, n.w[0], n.w[0], g);
         for (int l = 0; l < n.L; ++l) {        // a_l to LDS, then a_{l+1}; y itself is not needed
 #pragma unroll
             for (int t = 0; t < MLP_TILES; ++t) *reinterpret_cast<f4*>(acts + l * 16 * MLP_ROW + own + 16 * t) = a[t];
@@ -101,7 +91,7 @@ __global__ __launch_bounds__(64 * MLP_WAVES) void mlp_backward_kernel(int64_t N,
                 mlp_tanh(a, d);
             }
         }
-        mlp_load_rows(d, g_y, row, live, n.w[n.L], g);      // dZ of the last layer
+        mlp_load_rows(d, g_y, row, live, n.w[n.L], n.w[n.L], g);      // dZ of the last layer
 #pragma unroll
         for (int l = PIGS_MLP_MAX_LAYERS - 1; l >= 0; --l) {
             if (l >= n.L) continue;
@@ -109,7 +99,7 @@ __global__ __launch_bounds__(64 * MLP_WAVES) void mlp_backward_kernel(int64_t N,
             mlp_backward_layer<MLP_TILES, MLP_TILES>(d, acc_w[l], acc_b[l], out.g_W[l] != nullptr, out.g_b[l] != nullptr,
                                                      want_da, l == 0, mlp_lds + n.woff[l], mlp_tiles(n.w[l + 1]),
                                                      mlp_tiles(n.w[l]), acts + l * 16 * MLP_ROW, dz_t, own, r, g);
-            if (l == 0 && want_da) mlp_store_rows(out.g_x, d, row, live, n.w[0], g);
+            if (l == 0 && want_da) mlp_store_rows(out.g_x, d, row, live, n.w[0], n.w[0], g);
         }
     }
 
@@ -124,30 +114,10 @@ __global__ __launch_bounds__(64 * MLP_WAVES) void mlp_backward_kernel(int64_t N,
     }
 }
 
-// Four lanes per parameter (lane = 16 part + e): lane `part` adds records part, part + 4, ... in that order, then the four
-// partial sums are added as (p0 + p1) + (p2 + p3).  A fixed order, and four times as many loads in flight as one thread
-// per parameter (measured, delta_net at N = 1 600, 100 records: 24.4 us with one thread per parameter).
+// the records added in a fixed order into g_W / g_b (mlp_finish_block, mlp_chain.h)
 __global__ __launch_bounds__(256) void mlp_finish_kernel(MlpNet n, MlpGrads out, int records,
                                                          const float* __restrict__ scratch) {
-    const int lane = threadIdx.x & 63, part = lane >> 4;
-    const int e = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + (lane & 15);
-    const bool live = e < n.P;
-    float sum = 0.0f;
-    if (live) {
-#pragma unroll 8
-        for (int rcd = part; rcd < records; rcd += 4) sum += scratch[(int64_t)rcd * n.P + e];
-    }
-    sum += __shfl_xor(sum, 16);
-    sum += __shfl_xor(sum, 32);
-    if (!live || part) return;
-    for (int l = 0; l < n.L; ++l) {
-        const int k = e - n.poff[l], nw = n.w[l] * n.w[l + 1];
-        if (k >= 0 && k < nw) {
-            if (out.g_W[l]) out.g_W[l][k] = sum;
-        } else if (k >= nw && k < nw + n.w[l + 1]) {
-            if (out.g_b[l]) out.g_b[l][k - nw] = sum;
-        }
-    }
+    mlp_finish_block(n, out, records, scratch, blockIdx.x);
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
-// The register-resident tanh chain on v_mfma_f32_16x16x4_f32, shared by mlp.hip (one per-Gaussian net per launch) and
-// input_transform.hip (the latent net, whose rows are gathered from eight arrays and summed instead of stored).  It holds
+// The register-resident tanh chain on v_mfma_f32_16x16x4_f32, shared by mlp.hip (one per-Gaussian net per launch),
+// mlp_bank.hip (several nets of one shape over one input per launch) and input_transform.hip (the latent net, whose rows
+// are gathered from eight arrays and summed instead of stored).  It holds
 // the backward as well: one layer's three products (mlp_backward_layer) and its part of a wave's record
 // (mlp_record_layer), which mlp.hip instantiates at the widest net and input_transform.hip at the latent net's tile
 // counts.  The operand layout and the padded LDS images are described at the head of mlp.hip.
@@ -79,11 +80,13 @@ __device__ __forceinline__ void mlp_wave_fence() {
 // element 0 and is replaced by zero), so that the loads of an unrolled body are issued together.  (Measured and dropped:
 // ONE loop over the floats of all images with the layer found per element -- delta_net's forward at N = 1 600 took 18.4
 // us against 16.5 us with a loop per layer.)
-__device__ __forceinline__ void mlp_stage(const MlpNet& n, float* __restrict__ lds) {
+// (Ws, bs: the L weight and bias arrays -- n's own, or those of one net of a bank of n's shape, mlp_bank.hip)
+__device__ __forceinline__ void mlp_stage(const MlpNet& n, const float* const* Ws, const float* const* bs,
+                                          float* __restrict__ lds) {
     for (int l = 0; l < n.L; ++l) {
         const int in = n.w[l], out = n.w[l + 1], nti = mlp_tiles(in), op = 16 * mlp_tiles(out), S = 16 * nti + 4;
-        const float* __restrict__ W = n.W[l];
-        const float* __restrict__ b = n.b[l];
+        const float* __restrict__ W = Ws[l];
+        const float* __restrict__ b = bs[l];
         float* __restrict__ dst = lds + n.woff[l];
 #pragma unroll 4
         for (int idx = threadIdx.x; idx < op * nti * 16; idx += 64 * MLP_WAVES) {
@@ -98,27 +101,29 @@ __device__ __forceinline__ void mlp_stage(const MlpNet& n, float* __restrict__ l
     __syncthreads();
 }
 
-// a tile of 16 rows of a [N][width] array in the accumulator layout: lane (r, g) holds features 16 t + 4 g + 0..3 of
-// row r; rows past N and features past the width are zeros
+__device__ __forceinline__ void mlp_stage(const MlpNet& n, float* __restrict__ lds) { mlp_stage(n, n.W, n.b, lds); }
+
+// a tile of 16 rows of `width` floats, `stride` floats apart ([N][width]: stride = width), in the accumulator layout:
+// lane (r, g) holds features 16 t + 4 g + 0..3 of row r; rows past N and features past the width are zeros
 __device__ __forceinline__ void mlp_load_rows(f4 (&a)[MLP_TILES], const float* __restrict__ src, int64_t row, bool live,
-                                              int width, int g) {
+                                              int width, int stride, int g) {
 #pragma unroll
     for (int t = 0; t < MLP_TILES; ++t)
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             const int k = 16 * t + 4 * g + s;
-            a[t][s] = (live && k < width) ? src[row * width + k] : 0.0f;
+            a[t][s] = (live && k < width) ? src[row * stride + k] : 0.0f;
         }
 }
 
 __device__ __forceinline__ void mlp_store_rows(float* __restrict__ dst, const f4 (&a)[MLP_TILES], int64_t row, bool live,
-                                               int width, int g) {
+                                               int width, int stride, int g) {
 #pragma unroll
     for (int t = 0; t < MLP_TILES; ++t)
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             const int k = 16 * t + 4 * g + s;
-            if (live && k < width) dst[row * width + k] = a[t][s];
+            if (live && k < width) dst[row * stride + k] = a[t][s];
         }
 }
 
@@ -250,6 +255,118 @@ __device__ __forceinline__ void mlp_record_layer(float* __restrict__ rec, int ba
                 const int o = 4 * g + s;
                 if (r == 0 && o < outw - 16 * to) rec[base + outw * in + 16 * to + o] = v;
             }
+    }
+}
+
+// ---- the bodies of mlp.hip's three kernels, shared with mlp_bank.hip (one net of a bank per workgroup) ------------
+// The forward of the staged net over this workgroup's tiles: tile = blockIdx.x * MLP_WAVES + wave, + the grid's waves,
+// ...  Rows of y lie y_stride floats apart (one net: w_L).
+__device__ __forceinline__ void mlp_forward_tiles(int64_t N, int64_t tiles, const MlpNet& n, const float* __restrict__ lds,
+                                                  const float* __restrict__ x, float* __restrict__ y, int y_stride) {
+    const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
+    const int64_t stride = (int64_t)gridDim.x * MLP_WAVES;
+    for (int64_t tile = (int64_t)blockIdx.x * MLP_WAVES + (threadIdx.x >> 6); tile < tiles; tile += stride) {
+        const int64_t row = tile * 16 + r;
+        const bool live = row < N;
+        f4 a[MLP_TILES], z[MLP_TILES];
+        mlp_load_rows(a, x, row, live, n.w[0], n.w[0], g);
+        for (int l = 0; l < n.L; ++l) {
+            const int nti = mlp_tiles(n.w[l]), nto = mlp_tiles(n.w[l + 1]);
+            mlp_layer(z, a, lds + n.woff[l], lds + n.boff[l], 16 * nti + 4, nti, nto, r, g);
+            if (l + 1 < n.L) mlp_tanh(a, z);
+        }
+        mlp_store_rows(y, z, row, live, n.w[n.L], y_stride, g);
+    }
+}
+
+// The backward of the staged net over this wave's tiles (the same walk), and the wave's record at records[first * n.P].
+// Rows of g_y lie gy_stride floats apart; out.g_x is [N][w_0].  T: the 16-feature tiles of the net's widest layer, or
+// more -- the accumulators a wave holds are PIGS_MLP_MAX_LAYERS x T x T tiles of dW.  This is the text of mlp.hip's
+// mlp_backward_kernel at T = MLP_TILES, which keeps its own copy: called from there, the register allocator no longer
+// fits that kernel into its registers (512 VGPRs and 32 spilled, against 488 and none).
+template <int T>
+__device__ __forceinline__ void mlp_backward_tiles(int64_t N, int64_t tiles, const MlpNet& n, const MlpGrads& out,
+                                                   float* __restrict__ lds, const float* __restrict__ x,
+                                                   const float* __restrict__ g_y, int gy_stride,
+                                                   float* __restrict__ records) {
+    const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4, wave = threadIdx.x >> 6;
+    float* __restrict__ acts = lds + n.wave_off + wave * (n.L + 1) * 16 * MLP_ROW;      // a_l: tile l; dZ: tile L
+    float* __restrict__ dz_t = acts + n.L * 16 * MLP_ROW;
+    const int own = r * MLP_ROW + 4 * g;       // where this lane's four features of feature tile 0 lie in a tile
+
+    f4 acc_w[PIGS_MLP_MAX_LAYERS][T][T], acc_b[PIGS_MLP_MAX_LAYERS][T];
+#pragma unroll
+    for (int l = 0; l < PIGS_MLP_MAX_LAYERS; ++l)
+#pragma unroll
+        for (int to = 0; to < T; ++to) {
+            acc_b[l][to] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int ti = 0; ti < T; ++ti) acc_w[l][to][ti] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+        }
+
+    const int64_t first = (int64_t)blockIdx.x * MLP_WAVES + wave, stride = (int64_t)gridDim.x * MLP_WAVES;
+    for (int64_t tile = first; tile < tiles; tile += stride) {
+        const int64_t row = tile * 16 + r;
+        const bool live = row < N;
+        f4 a[MLP_TILES], d[MLP_TILES];
+        mlp_wave_fence();                      // the previous tile's reads of this region are done
+        mlp_load_rows(a, x, row, live, n.w[0], n.w[0], g);
+        for (int l = 0; l < n.L; ++l) {        // a_l to LDS, then a_{l+1}; y itself is not needed
+#pragma unroll
+            for (int t = 0; t < MLP_TILES; ++t) *reinterpret_cast<f4*>(acts + l * 16 * MLP_ROW + own + 16 * t) = a[t];
+            if (l + 1 < n.L) {
+                const int nti = mlp_tiles(n.w[l]), nto = mlp_tiles(n.w[l + 1]);
+                mlp_layer(d, a, lds + n.woff[l], lds + n.boff[l], 16 * nti + 4, nti, nto, r, g);
+                mlp_tanh(a, d);
+            }
+        }
+        mlp_load_rows(d, g_y, row, live, n.w[n.L], gy_stride, g);      // dZ of the last layer
+#pragma unroll
+        for (int l = PIGS_MLP_MAX_LAYERS - 1; l >= 0; --l) {
+            if (l >= n.L) continue;
+            const bool want_da = l > 0 || out.g_x;
+            mlp_backward_layer<T, T>(d, acc_w[l], acc_b[l], out.g_W[l] != nullptr, out.g_b[l] != nullptr,
+                                                     want_da, l == 0, lds + n.woff[l], mlp_tiles(n.w[l + 1]),
+                                                     mlp_tiles(n.w[l]), acts + l * 16 * MLP_ROW, dz_t, own, r, g);
+            if (l == 0 && want_da) mlp_store_rows(out.g_x, d, row, live, n.w[0], n.w[0], g);
+        }
+    }
+
+    // this wave's record; a wave without a tile (only past the last tile's wave) writes none
+    if (first >= tiles) return;
+    float* __restrict__ rec = records + first * n.P;
+#pragma unroll
+    for (int l = 0; l < PIGS_MLP_MAX_LAYERS; ++l) {
+        if (l >= n.L) continue;
+        mlp_record_layer<T, T>(rec, n.poff[l], acc_w[l], acc_b[l], out.g_W[l] != nullptr,
+                                               out.g_b[l] != nullptr, n.w[l], n.w[l + 1], r, g);
+    }
+}
+
+// Parameter e of the net from `records` records of n.P floats, by four lanes (lane = 16 part + e's low bits): lane `part`
+// adds records part, part + 4, ... in that order, then the four partial sums are added as (p0 + p1) + (p2 + p3).  A
+// fixed order, and four times as many loads in flight as one thread per parameter (measured, delta_net at N = 1 600, 100
+// records: 24.4 us with one thread per parameter).  `block`: which 64 parameters this workgroup of 256 adds.
+__device__ __forceinline__ void mlp_finish_block(const MlpNet& n, const MlpGrads& out, int records,
+                                                 const float* __restrict__ scratch, int block) {
+    const int lane = threadIdx.x & 63, part = lane >> 4;
+    const int e = (block * 4 + (threadIdx.x >> 6)) * 16 + (lane & 15);
+    const bool live = e < n.P;
+    float sum = 0.0f;
+    if (live) {
+#pragma unroll 8
+        for (int rcd = part; rcd < records; rcd += 4) sum += scratch[(int64_t)rcd * n.P + e];
+    }
+    sum += __shfl_xor(sum, 16);
+    sum += __shfl_xor(sum, 32);
+    if (!live || part) return;
+    for (int l = 0; l < n.L; ++l) {
+        const int k = e - n.poff[l], nw = n.w[l] * n.w[l + 1];
+        if (k >= 0 && k < nw) {
+            if (out.g_W[l]) out.g_W[l][k] = sum;
+        } else if (k >= nw && k < nw + n.w[l + 1]) {
+            if (out.g_b[l]) out.g_b[l][k - nw] = sum;
+        }
     }
 }
 
