@@ -360,6 +360,42 @@ int pigs_vorticity_residual_backward(int dtype, int64_t N, int64_t M,
                                      void* plan_ws, size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes,
                                      void* stream);
 
+/*
+ * The network inputs in ONE launch (additive to ABI 10; d = 2; forward only): the four arrays that the reference's
+ * Model.forward samples at its Gaussians' means under no_grad and hands to its dynamics network
+ * (model_pn.py:645-664), in the layouts of those lines,
+ *     sample_u   [M][c]        u
+ *     sample_ux  [M][2][c]     d_i u_ch, the memory of the order-1 output
+ *     sample_uxx [M][2][c]     u_xx of every channel, then u_yy (planar: the cat of :664), not the Hessian
+ *     sample_pde [M][p]        pde_rhs (:612-631) by params->kind:
+ *         PIGS_NET_ZERO           zeros                                          p = c   (Problem.TEST)
+ *         PIGS_NET_DIFFUSION      u_xx + u_yy                                    p = c
+ *         PIGS_NET_BURGERS        nu (u_xx + u_yy) - u_ch d_x u_ch               p = c
+ *         PIGS_NET_WAVE           (u_1, wave[0] (u_xx + u_yy)_0 - wave[1] u_1)   c = 2, p = 2
+ *         PIGS_NET_NAVIER_STOKES  nu lap w - (u_0 w_x + u_1 w_y),                c = 2, p = 1
+ *                                 w = d_x u_y - d_y u_x
+ * Only the sums these need are accumulated: 5 c per point, 13 for Navier-Stokes (orders 0..3 carry 30 at c = 2).
+ * All four outputs are contiguous, in the call's dtype, and required when M > 0.  d != 2, or c != 2 with the wave or
+ * Navier-Stokes kind, is PIGS_ERR_UNSUPPORTED; an unknown kind is PIGS_ERR_INVALID.  There is no backward: the model
+ * calls it under no_grad.  plan_ws == NULL: dense (c <= 4, f32 / f64); else through a built plan (f32, c <= 2; for
+ * Navier-Stokes the caller builds it with the cut-off it wants for third derivatives).
+ */
+#define PIGS_NET_ZERO 0
+#define PIGS_NET_DIFFUSION 1
+#define PIGS_NET_BURGERS 2
+#define PIGS_NET_WAVE 3
+#define PIGS_NET_NAVIER_STOKES 4
+typedef struct PigsNetworkInputs {
+    int kind;                               /* PIGS_NET_* */
+    double nu, wave[2];                     /* burgers, navier_stokes: nu; wave: its two constants */
+} PigsNetworkInputs;
+int pigs_network_inputs_forward(int dtype, int d, int c, int64_t N, int64_t M,
+                                const void* means, const void* conics, const void* values, const void* samples,
+                                const PigsNetworkInputs* params, void* sample_u, void* sample_ux, void* sample_uxx,
+                                void* sample_pde,
+                                void* plan_ws, size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes,
+                                void* stream);
+
 /* Byte offset, inside a samples / plan workspace, of a uint32 DIAGNOSTIC that a build leaves at 0 and
  * sets to non-zero when a workgroup of its in-kernel scan did not receive a predecessor's total within
  * the bounded wait and summed that predecessor's counters itself.  The result is valid either way

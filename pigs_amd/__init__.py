@@ -4,6 +4,7 @@ Public surface:
     GaussianSampler         drop-in for ``diff_gaussian_sampling.GaussianSampler``
     VORTICITY_COLUMNS       the column names of ``GaussianSampler.vorticity_terms()``
     VORTICITY_RESIDUAL_COLUMNS  the column names of ``GaussianSampler.vorticity_residual()``
+    NETWORK_PDES            the right-hand sides ``GaussianSampler.network_inputs()`` composes
     covariances             fused ``build_covariances`` / ``build_full_covariances`` (gaussians.py:163-193)
     split_gaussians         prune and split / clone Gaussians in HIP with one host read (pigs_amd.refine;
                             model_pn.py:578-605, :703-714 and test_no_mlp.py:198-240)
@@ -48,6 +49,9 @@ def __getattr__(name):
     if name == "VORTICITY_RESIDUAL_COLUMNS":
         from .sampler import VORTICITY_RESIDUAL_COLUMNS
         return VORTICITY_RESIDUAL_COLUMNS
+    if name == "NETWORK_PDES":
+        from .sampler import NETWORK_PDES
+        return NETWORK_PDES
     if name in ("split_gaussians", "refine_index", "split_mask", "threshold_mask", "split_criterion"):
         from . import refine
         return getattr(refine, name)

@@ -75,6 +75,14 @@ class PigsVorticityResidual(ctypes.Structure):
 _vorticity_residual_p = ctypes.POINTER(PigsVorticityResidual)
 
 
+class PigsNetworkInputs(ctypes.Structure):
+    """struct PigsNetworkInputs of include/pigs_amd.h (the right-hand side's kind, nu and the two wave constants)"""
+    _fields_ = [("kind", _i), ("nu", ctypes.c_double), ("wave", ctypes.c_double * 2)]
+
+
+_network_inputs_p = ctypes.POINTER(PigsNetworkInputs)
+
+
 class PigsAdamStep(ctypes.Structure):
     """struct PigsAdamStep of include/pigs_amd.h (the optimiser's rates, running products and parameterisation)"""
     _fields_ = [("lr", ctypes.c_double * 4), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
@@ -129,6 +137,9 @@ SIGNATURES = {
                                         + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
     "pigs_vorticity_residual_backward": (_i, [_i, _i64, _i64] + [_vp] * 4 + [_vorticity_residual_p, _vp, _vp] + [_vp] * 3
                                          + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
+    # the network inputs (additive to ABI 10; forward only): params, sample_u, sample_ux, sample_uxx, sample_pde
+    "pigs_network_inputs_forward": (_i, [_i, _i, _i, _i64, _i64] + [_vp] * 4 + [_network_inputs_p] + [_vp] * 4
+                                    + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
     # the coupled residual (additive to ABI 10): coupling, target, out / coupling, gout, gradients
     "pigs_residual_coupled_forward": (_i, [_i, _i, _i, _i64, _i64] + [_vp] * 4 + [_coupling_p, _vp, _vp]
                                       + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),

@@ -303,6 +303,22 @@ int pigs_vorticity_residual_backward(int dtype, int64_t N, int64_t M, const void
     return fused_launch(true, a, plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, stream);
 }
 
+// network inputs (pair_math.h ORDI, ORDJ): sample_u, sample_ux, sample_uxx, sample_pde of Model.forward; d = 2, forward only
+int pigs_network_inputs_forward(int dtype, int d, int c, int64_t N, int64_t M, const void* means, const void* conics,
+                                const void* values, const void* samples, const PigsNetworkInputs* params, void* sample_u,
+                                void* sample_ux, void* sample_uxx, void* sample_pde, void* plan_ws, size_t plan_ws_bytes,
+                                const void* samples_ws, size_t samples_ws_bytes, void* stream) {
+    if (!params || (M > 0 && (!sample_u || !sample_ux || !sample_uxx || !sample_pde))) return PIGS_ERR_INVALID;
+    if (params->kind < PIGS_NET_ZERO || params->kind > PIGS_NET_NAVIER_STOKES) return PIGS_ERR_INVALID;
+    if (d == 1) return PIGS_ERR_UNSUPPORTED;      // the model is two-dimensional
+    const bool ns = params->kind == PIGS_NET_NAVIER_STOKES;
+    if ((ns || params->kind == PIGS_NET_WAVE) && c >= 1 && c <= 4 && c != 2) return PIGS_ERR_UNSUPPORTED;
+    SampleArgs a = fused_args(ns ? MASK_NET_INPUTS_NS : MASK_NET_INPUTS, dtype, d, c, N, M, means, conics, values, samples);
+    a.net = params;
+    a.out[0] = sample_u; a.out[1] = sample_ux; a.out[2] = sample_uxx; a.out[3] = sample_pde;
+    return fused_launch(false, a, plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, stream);
+}
+
 // ---- periodic domain (ABI 10): the 3 x 3 images of every Gaussian and the fold of their gradients (periodic.hip)
 int pigs_periodic_images(int dtype, int c, int64_t N, double lo, double period, double q_cut, const void* means,
                          const void* conics, const void* values, void* img_means, void* img_conics, void* img_values,

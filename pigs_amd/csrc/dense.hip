@@ -20,7 +20,7 @@
 namespace pigs {
 
 static_assert(MASK_RESIDUAL == ORDR && MASK_TERMS == ORDG && MASK_VORTICITY == ORDV && MASK_COUPLED == ORDC &&
-                  MASK_VORT_RESIDUAL == ORDN,
+                  MASK_VORT_RESIDUAL == ORDN && MASK_NET_INPUTS == ORDI && MASK_NET_INPUTS_NS == ORDJ,
               "launch.h and pair_math.h name the same fused-output masks");
 
 template <typename T, int D, int C, int MASK, int NW>
@@ -467,6 +467,17 @@ static int dispatch_mask(bool backward, const SampleArgs& a, hipStream_t stream)
         }
     }
 #undef PIGS_CASE
+    // the forward-only list: no backward is compiled for its members
+#define PIGS_CASE_FORWARD(MK)                                                                \
+    case MK:                                                                                 \
+        if constexpr (network_instance(D, C, MK))                                            \
+            return backward ? PIGS_ERR_UNSUPPORTED : launch_dense_forward<T, D, C, MK>(a, stream); \
+        break;
+    switch (mask) {
+        PIGS_DENSE_NETWORK_MASKS(PIGS_CASE_FORWARD)
+        default: break;
+    }
+#undef PIGS_CASE_FORWARD
     return PIGS_ERR_UNSUPPORTED;
 }
 

@@ -24,6 +24,8 @@ struct SampleArgs {
     const PigsResidualCoupling* coupling;      // MASK_COUPLED: coefficients, fields, the two matrices
     const PigsVorticityResidual* vort;         // MASK_VORT_RESIDUAL: coefficients, tau field; `target` = prev [M][7] or null,
                                                //   `aux` = [M][4] (the forward writes it, the backward reads it)
+    const PigsNetworkInputs* net;              // MASK_NET_INPUTS, MASK_NET_INPUTS_NS: the right-hand side's kind and constants;
+                                               //   the four arrays leave through out[0..3]
 };
 
 int dense_dispatch(bool backward, const SampleArgs& a, hipStream_t stream);

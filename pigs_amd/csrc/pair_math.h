@@ -78,6 +78,30 @@ constexpr int ORDC_AS = ORD0 | ORD2T;
 // backward with the seven incoming gradients formed from gout[m][0..1], the coefficients and that record
 // (Gsym::load_vorticity_residual); prev is not read there.
 constexpr int ORDN = 512;
+// THE NETWORK INPUTS (mask == ORDI or ORDJ, alone; D == 2; forward only): the four arrays that the reference's
+// Model.forward hands to its dynamics network (model_pn.py:645-664), each through its own output slot,
+//   o0[m][ch]          = u                                   sample_u    [M][c]
+//   o1[m][i][ch]       = d_i u_ch                            sample_ux   [M][2c], the memory of order 1
+//   o2[m][0][ch], [1]  = u_xx, u_yy                          sample_uxx  [M][2c], planar (the cat of :664)
+//   o3[m][..]          = pde_rhs (:612-631) by NetIn::kind   sample_pde  [M][p]
+// Of the Hessian only the diagonal is wanted and of the third derivative only lap w, so ORDI accumulates u, +sum p w
+// and the two diagonal second derivatives (5 c sums, no t_xy) and ORDJ (C == 2) those ten and w_x, w_y, lap w formed
+// per pair as ORDV forms them: 13 sums against the 30 of orders 0..3.  pde_rhs holds products of two such sums (u u_x,
+// u . grad w), so it is composed once per point in fwd_store.  The kind is a run-time field: the store runs once per point.
+constexpr int ORDI = 1024;      // kinds zero, diffusion, burgers, wave
+constexpr int ORDJ = 2048;      // kind navier_stokes
+constexpr bool is_net_inputs(int MASK) { return MASK == ORDI || MASK == ORDJ; }
+constexpr int NET_ZERO = 0, NET_DIFFUSION = 1, NET_BURGERS = 2, NET_WAVE = 3, NET_NAVIER_STOKES = 4;      // PIGS_NET_* of the C ABI
+constexpr int NNETJ = 13;
+template <typename T> struct NetIn {
+    int kind;
+    T nu, wave[2];
+};
+// host side: the block from the C ABI's PigsNetworkInputs (include/pigs_amd.h) in the launch's type
+template <typename T, typename ABI>
+inline NetIn<T> make_net_in(const ABI& t) {
+    return NetIn<T>{t.kind, (T)t.nu, {(T)t.wave[0], (T)t.wave[1]}};
+}
 constexpr int bwd_mask_of(int MASK) {
     return (MASK == ORDR || MASK == ORDG) ? ORDR_AS : (MASK == ORDV || MASK == ORDN) ? ORDV_AS : MASK == ORDC ? ORDC_AS : MASK;
 }
@@ -137,7 +161,7 @@ inline VortResid<T> make_vort_resid(const ABI& t, const void* prev, const void* 
 // the coefficient block a kernel compiled for MASK receives
 template <typename T, int MASK>
 using RzOf = std::conditional_t<MASK == ORDG, Terms<T>, std::conditional_t<MASK == ORDC, Coupled<T>,
-             std::conditional_t<MASK == ORDN, VortResid<T>, Resid<T>>>>;
+             std::conditional_t<MASK == ORDN, VortResid<T>, std::conditional_t<is_net_inputs(MASK), NetIn<T>, Resid<T>>>>>;
 // host side: that block from a launcher's arguments (launch.h's SampleArgs; aux: the forward's output, the backward's
 // input; the target / previous level is read by the forward alone)
 template <typename T, int MASK, typename ARGS>
@@ -148,6 +172,8 @@ inline RzOf<T, MASK> rz_of(const ARGS& a, bool backward) {
         return make_coupled<T>(*a.coupling, backward ? nullptr : a.target);
     } else if constexpr (MASK == ORDN) {
         return make_vort_resid<T>(*a.vort, backward ? nullptr : a.target, a.aux);
+    } else if constexpr (is_net_inputs(MASK)) {
+        return make_net_in<T>(*a.net);
     } else {
         return Resid<T>{(T)a.resid[0], {(T)a.resid[1], (T)a.resid[2]}, (T)a.resid[3], backward ? nullptr : (const T*)a.target};
     }
@@ -194,7 +220,10 @@ template <int D, int C, int MASK_> struct FwdLayout {
     static constexpr int O1 = O0 + ((MASK & ORD0) ? C : 0);
     static constexpr int O2 = O1 + ((MASK & ORD1) ? D * C : 0);
     static constexpr int O3 = O2 + ((MASK & ORD2) ? Sym<D>::NF * C : (MASK & ORD2T) ? C : 0);
-    static constexpr int N = O3 + ((MASK & ORD3) ? Sym<D>::N3 * C : 0) + ((MASK & ORDR) ? C : 0) + ((MASK == ORDV || MASK == ORDN) ? NVORT : 0);
+    static constexpr int N = O3 + ((MASK & ORD3) ? Sym<D>::N3 * C : 0) + ((MASK & ORDR) ? C : 0) + ((MASK == ORDV || MASK == ORDN) ? NVORT : 0) +
+                             (MASK == ORDI ? 5 * C : MASK == ORDJ ? NNETJ : 0);
+    // the network inputs (D = 2): u, +sum p_i w, t_xx w, t_yy w per channel; ORDJ: w_x, w_y, lap w behind them
+    static constexpr int IU = 0, IP = C, IXX = 3 * C, IYY = 4 * C, IW = 5 * C;
 };
 
 // Pair geometry: x, p, g (and nothing else) for one (point, Gaussian).
@@ -267,6 +296,37 @@ __device__ __forceinline__ void fwd_accumulate(T* acc, const T* s, const T* mu, 
         acc[4] = fma_<T>(txx, wy, fma_<T>(-txy, wx, acc[4]));     // d_x w
         acc[5] = fma_<T>(txy, wy, fma_<T>(-tyy, wx, acc[5]));     // d_y w
         acc[6] = fma_<T>(Lx, wy, fma_<T>(-Ly, wx, acc[6]));       // lap w
+        return;
+    }
+    if constexpr (is_net_inputs(MASK)) {
+        static_assert(D == 2, "the network inputs are those of the reference's two-dimensional model");
+        static_assert(MASK == ORDI || C == 2, "the Navier-Stokes right-hand side is that of a two-channel field");
+        T px = pr.p[0], py = pr.p[1];
+        if constexpr (MASK == ORDJ) {      // the guard of ORDV above: an underflowed g must not meet an overflowing cubic
+            const bool live = pr.g > T(0);
+            px = live ? px : T(0);
+            py = live ? py : T(0);
+        }
+        const T txx = fma_<T>(px, px, -con[0]), tyy = fma_<T>(py, py, -con[2]);
+#pragma unroll
+        for (int ch = 0; ch < C; ++ch) {
+            const T w = v[ch] * pr.g;
+            acc[L::IU + ch] += w;
+            acc[L::IP + ch] = fma_<T>(px, w, acc[L::IP + ch]);
+            acc[L::IP + C + ch] = fma_<T>(py, w, acc[L::IP + C + ch]);
+            acc[L::IXX + ch] = fma_<T>(txx, w, acc[L::IXX + ch]);
+            acc[L::IYY + ch] = fma_<T>(tyy, w, acc[L::IYY + ch]);
+        }
+        if constexpr (MASK == ORDJ) {      // grad w and lap w, as ORDV forms them
+            const T txy = fma_<T>(px, py, -con[1]);
+            const T ttr = txx + tyy;
+            const T Lx = fma_<T>(T(2), fma_<T>(con[0], px, con[1] * py), -ttr * px);
+            const T Ly = fma_<T>(T(2), fma_<T>(con[1], px, con[2] * py), -ttr * py);
+            const T wx = v[0] * pr.g, wy = v[1] * pr.g;
+            acc[L::IW + 0] = fma_<T>(txx, wy, fma_<T>(-txy, wx, acc[L::IW + 0]));     // d_x w
+            acc[L::IW + 1] = fma_<T>(txy, wy, fma_<T>(-tyy, wx, acc[L::IW + 1]));     // d_y w
+            acc[L::IW + 2] = fma_<T>(Lx, wy, fma_<T>(-Ly, wx, acc[L::IW + 2]));       // lap w
+        }
         return;
     }
     if constexpr ((MASK & ORD3) != 0) {
@@ -421,6 +481,38 @@ __device__ __forceinline__ void fwd_store(const T* acc, int64_t m, T* __restrict
 #pragma unroll
         for (int ch = 0; ch < C; ++ch)
             store_out<STREAM>(&o0[m * C + ch], rz->target ? acc[ch] - rz->target[m * C + ch] : acc[ch]);
+        return;
+    }
+    if constexpr (is_net_inputs(MASK)) {
+        // the composing store: the four arrays of Model.forward in their layouts (:650-664), pde_rhs by kind (:612-631)
+        if constexpr (STREAM) asm volatile("" ::: "memory");      // as for ORDV below: keeps the hint
+#pragma unroll
+        for (int ch = 0; ch < C; ++ch) store_out<STREAM>(&o0[m * C + ch], acc[L::IU + ch]);
+#pragma unroll
+        for (int k = 0; k < 2 * C; ++k) store_out<STREAM>(&o1[m * 2 * C + k], -acc[L::IP + k]);      // the sign of order 1
+#pragma unroll
+        for (int k = 0; k < 2 * C; ++k) store_out<STREAM>(&o2[m * 2 * C + k], acc[L::IXX + k]);       // u_xx of every channel, then u_yy
+        if constexpr (MASK == ORDJ) {
+            // nu lap w - (u_0 w_x + u_1 w_y)
+            const T adv = fma_<T>(acc[L::IU + 0], acc[L::IW + 0], acc[L::IU + 1] * acc[L::IW + 1]);
+            store_out<STREAM>(&o3[m], fma_<T>(rz->nu, acc[L::IW + 2], -adv));
+        } else if (rz->kind == NET_WAVE) {
+            // (u_1, wave_0 lap u_0 - wave_1 u_1): two channels, which the entry point has checked
+            if constexpr (C == 2) {
+                const T lap0 = acc[L::IXX + 0] + acc[L::IYY + 0];
+                store_out<STREAM>(&o3[m * 2 + 0], acc[L::IU + 1]);
+                store_out<STREAM>(&o3[m * 2 + 1], fma_<T>(rz->wave[0], lap0, -rz->wave[1] * acc[L::IU + 1]));
+            }
+        } else {
+            // zero; lap u; nu lap u - u_ch d_x u_ch (the accumulator holds -d_x u)
+            const int kind = rz->kind;
+#pragma unroll
+            for (int ch = 0; ch < C; ++ch) {
+                const T lap = acc[L::IXX + ch] + acc[L::IYY + ch];
+                const T burgers = fma_<T>(rz->nu, lap, acc[L::IU + ch] * acc[L::IP + ch]);
+                store_out<STREAM>(&o3[m * C + ch], kind == NET_DIFFUSION ? lap : kind == NET_BURGERS ? burgers : T(0));
+            }
+        }
         return;
     }
     if constexpr (MASK == ORDV) {

@@ -523,6 +523,8 @@ static bool block_missing(int mask, const SampleArgs& a) {
         case ORDG: return !a.terms;
         case ORDC: return !a.coupling;
         case ORDN: return !a.vort;
+        case ORDI:
+        case ORDJ: return !a.net;
         default: return false;
     }
 }
@@ -580,6 +582,20 @@ static int plan_forward_c(const PlanView& pv_in, const SamplesView& sv, int mask
             default: break;
         }
     }
+    // the network inputs: the forward-only list, each member for the channel counts network_instance names
+#define PIGS_CASE_FORWARD(MK)                                                                                        \
+    case MK:                                                                                                         \
+        if constexpr (network_instance(2, C, MK)) {                                                                  \
+            hipLaunchKernelGGL((tile_forward_kernel<C, MK>), grid, block, 0, stream, pv, sv, out[0], out[1], out[2], \
+                               out[3], rz_of<float, MK>(a, false));                                                  \
+            done = true;                                                                                             \
+        }                                                                                                            \
+        break;
+    switch (mask) {
+        PIGS_BINNED_NETWORK_MASKS(PIGS_CASE_FORWARD)
+        default: break;
+    }
+#undef PIGS_CASE_FORWARD
 #undef PIGS_CASE
     if (!done) return PIGS_ERR_UNSUPPORTED;
     if (staged) {

@@ -1215,6 +1215,38 @@ struct Core {
         return fused_apply(VORTICITY_RESIDUAL, means, values, conics, samples, t, prev, debug, plan_for(8));
     }
 
+    // sample_u, sample_ux, sample_uxx, sample_pde (kind: PIGS_NET_*) as views of one allocation; forward only: no
+    // autograd node, and the plan of the bound inputs as it stands (a forward-only one serves); Navier-Stokes takes
+    // the order-3 plan where there is one
+    py::tuple network_inputs(int kind, double nu, double wave0, double wave1) {
+        require_inputs();
+        at::AutoGradMode no_grad(false);
+        const int64_t N = means.size(0), c = values.size(1), M = samples.size(0);
+        const int64_t widths[4] = {c, 2 * c, 2 * c, kind == PIGS_NET_WAVE ? 2 : kind == PIGS_NET_NAVIER_STOKES ? 1 : c};
+        const bool launch = N > 0 && M > 0;
+        const int64_t total = M * (widths[0] + widths[1] + widths[2] + widths[3]);
+        at::Tensor buf = launch ? at::empty({total}, means.options()) : at::zeros({total}, means.options());
+        at::Tensor outs[4];
+        int64_t at_ = 0;
+        for (int k = 0; k < 4; ++k) {
+            outs[k] = buf.narrow(0, at_, M * widths[k]).view({M, widths[k]});
+            at_ += M * widths[k];
+        }
+        if (launch) {
+            std::shared_ptr<Plan> p = plan_for(kind == PIGS_NET_NAVIER_STOKES ? 8 : 0);
+            c10::DeviceGuard guard(means.device());
+            const hipStream_t stream = current_stream(means);
+            const FusedLaunch l = fused_launch_of(means, values, conics, samples, p.get(), stream);
+            PigsNetworkInputs z{};
+            z.kind = kind; z.nu = nu; z.wave[0] = wave0; z.wave[1] = wave1;
+            check(pigs_network_inputs_forward(l.dtype, l.d, l.c, l.N, l.M, l.means, l.conics, l.values, l.samples, &z, ptr(outs[0]),
+                                              ptr(outs[1]), ptr(outs[2]), ptr(outs[3]), l.pp.pw, l.pp.pb, l.pp.sw, l.pp.sb, stream),
+                  "pigs_network_inputs_forward");
+        }
+        if (debug) device_sync(means);
+        return py::make_tuple(outs[0], outs[1], outs[2], outs[3]);
+    }
+
     void preprocess_aggregate(int64_t cap) {
         require_inputs();
         if (means.size(1) != 2) raise_py(PyExc_NotImplementedError, "aggregate_neighbors is implemented for d = 2");
@@ -1350,6 +1382,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("vorticity_terms", &Core::vorticity_terms)
         .def("vorticity_residual", &Core::vorticity_residual, py::arg("nu"), py::arg("dt"), py::arg("time_term"), py::arg("tau"),
              py::arg("tau_field") = c10::optional<at::Tensor>(), py::arg("prev") = c10::optional<at::Tensor>())
+        // (underscored: tests/test_host_cpu.py pins the set of public core names; the facade's network_inputs() drives it)
+        .def("_network_inputs", &Core::network_inputs, py::arg("kind"), py::arg("nu"), py::arg("wave0"), py::arg("wave1"))
         .def("preprocess_aggregate", &Core::preprocess_aggregate, py::arg("cap") = -1)
         .def("aggregate_neighbors", &Core::aggregate_neighbors)
         .def("aggregate_neighbors_heads", &Core::aggregate_neighbors_heads)

@@ -16,6 +16,14 @@ TRACE = 4       # order index of the Hessian's trace (mask bit 16); it travels i
 VORTICITY_COLUMNS = ("u_x", "u_y", "div", "w", "w_x", "w_y", "lap_w")
 # the columns of GaussianSampler.vorticity_residual(): the blended divergence and the vorticity equation's residual
 VORTICITY_RESIDUAL_COLUMNS = ("div", "r")
+# the right-hand sides of GaussianSampler.network_inputs(), in the order of the C ABI's PIGS_NET_* codes
+NETWORK_PDES = ("zero", "diffusion", "burgers", "wave", "navier_stokes")
+_NET_WAVE, _NET_NAVIER_STOKES = NETWORK_PDES.index("wave"), NETWORK_PDES.index("navier_stokes")
+
+
+def network_pde_width(kind, c):
+    """Columns of sample_pde: two for the wave system, one for the vorticity equation, else the channels."""
+    return 2 if kind == _NET_WAVE else 1 if kind == _NET_NAVIER_STOKES else c
 
 
 def _out_shape(order, M, d, c):
@@ -838,6 +846,38 @@ class SamplerCore:
     def vorticity_residual(self, nu, dt, time_term, tau, tau_field=None, prev=None):
         params = VorticityResidual(nu, dt, time_term, tau if tau_field is None else tau_field)
         return self._fused(_VorticityResidualFunction, 8, prev, params, want_aux=self._needs_backward())
+
+    def _network_inputs(self, kind, nu, wave0, wave1):
+        """sample_u, sample_ux, sample_uxx, sample_pde as views of one allocation; forward only, no autograd node."""
+        means, values, conics, samples = self._require_inputs()
+        N, d = means.shape
+        c, M = values.shape[1], samples.shape[0]
+        widths = (c, 2 * c, 2 * c, network_pde_width(kind, c))
+        with torch.no_grad():
+            launch = N > 0 and M > 0
+            buf = (torch.empty if launch else torch.zeros)(M * sum(widths), dtype=means.dtype, device=means.device)
+            outs, at = [], 0
+            for w in widths:
+                outs.append(buf[at:at + M * w].view(M, w))
+                at += M * w
+            if launch:
+                # the plan of the bound inputs as it stands (a forward-only one serves: no backward follows); the
+                # vorticity's third derivatives take the order-3 plan
+                plan = self._plan_for(8 if kind == _NET_NAVIER_STOKES else 0)
+                pw = (_ptr(plan.workspace), plan.workspace.numel(), _ptr(plan.samples.workspace), plan.samples.workspace.numel()) \
+                    if plan is not None else (ctypes.c_void_p(0), 0, ctypes.c_void_p(0), 0)
+                with _on_device(means.device):
+                    stream = _stream(means.device)
+                    if plan is not None and hasattr(plan, "note_stream"):
+                        plan.note_stream(stream.value)
+                    params = _lib.PigsNetworkInputs(kind, nu, (wave0, wave1))
+                    rc = _lib.load().pigs_network_inputs_forward(
+                        _DTYPES[means.dtype], d, c, N, M, _ptr(means), _ptr(conics), _ptr(values), _ptr(samples),
+                        ctypes.byref(params), *(_ptr(o) for o in outs), *pw, stream)
+                    _lib.check(rc, "pigs_network_inputs_forward")
+            if self._debug:
+                torch.cuda.synchronize(means.device)
+        return tuple(outs)
 
     # ------------------------------------------------------------------ neighbour aggregation
     def preprocess_aggregate(self, cap=-1):

@@ -23,13 +23,18 @@ This file is the facade: the public class, its documentation and the argument ch
 state and the policy live in a core -- ``_pigs_host.SamplerCore`` (csrc_host/pigs_host.cpp, the default) or
 ``host_ctypes.SamplerCore`` -- with one interface ("hosts").
 """
+import collections
 import math
 import os
 
 import torch
 
 from . import _lib, host_ctypes
-from .host_ctypes import TRACE, VORTICITY_COLUMNS, VORTICITY_RESIDUAL_COLUMNS, backward_raw, forward_raw  # noqa: F401
+from .host_ctypes import (NETWORK_PDES, TRACE, VORTICITY_COLUMNS, VORTICITY_RESIDUAL_COLUMNS, backward_raw,  # noqa: F401
+                          forward_raw, network_pde_width)
+
+# what GaussianSampler.network_inputs() returns: the four arrays of the reference's Model.forward (model_pn.py:650-664)
+NetworkInputs = collections.namedtuple("NetworkInputs", ("sample_u", "sample_ux", "sample_uxx", "sample_pde"))
 
 
 def _periodic_box(periodic):
@@ -501,6 +506,46 @@ class GaussianSampler:
         nu, dt, time_term = float(nu), float(dt), float(time_term)
         field = f_tau if isinstance(f_tau, torch.Tensor) else None
         return self._core.vorticity_residual(nu, dt, time_term, 0.0 if field is not None else f_tau, field, prev)
+
+    def network_inputs(self, pde, nu=0.0, wave=(10.0, 0.1)):
+        """Extension of the reference API: the four arrays that the reference's ``Model.forward`` samples at its
+        Gaussians' means under ``no_grad`` and hands to its dynamics network (model_pn.py:645-664), in ONE launch and
+        in the layouts of those lines, as the named tuple ``(sample_u, sample_ux, sample_uxx, sample_pde)``::
+
+            sample_u   [M, c]     u
+            sample_ux  [M, 2c]    sample_ux[m, i*c + ch] = d_i u_ch      (sample_gaussians_derivative().reshape(M, -1))
+            sample_uxx [M, 2c]    u_xx of every channel, then u_yy       (the cat of :664: planar, not interleaved)
+            sample_pde [M, p]     pde_rhs (:612-631) by ``pde``
+
+        ``pde`` is one of ``pigs_amd.NETWORK_PDES``: ``"zero"`` (Problem.TEST; p = c), ``"diffusion"`` (``u_xx + u_yy``;
+        p = c), ``"burgers"`` (``nu (u_xx + u_yy) - u_ch d_x u_ch``, channel by channel as the reference's broadcast
+        does; p = c), ``"wave"`` (``(u_1, wave[0] (u_xx + u_yy)_0 - wave[1] u_1)``; c = 2, p = 2) and
+        ``"navier_stokes"`` (``nu lap w - (u_0 w_x + u_1 w_y)`` with ``w = d_x u_y - d_y u_x``; c = 2, p = 1).  The
+        kernel accumulates only what these need -- 5 c sums per point, 13 for Navier-Stokes, where orders 0..3 carry
+        30 at c = 2 -- and composes ``sample_pde`` once per point, so none of the reference's slicing, stacking and
+        ``cat`` kernels follow.  The four tensors are contiguous views of one allocation and go straight into
+        ``FusedInputTransform.forward`` / ``.transform_gaussians``.
+
+        Forward only: the model calls it under ``no_grad``, and the outputs never require a gradient, whatever the
+        bound tensors do.  No autograd node, no host wait, scratch from torch: it records into a ``GraphedStep``.
+        d = 2 only; dense float32 / float64 with c = 1..4, binned float32 with c <= 2 (Navier-Stokes on the order-3
+        plan, ``q_max_order3``); periodic samplers included.  M = 0 or N = 0 returns zeros of the right shapes without a
+        launch.  Anything else raises ``NotImplementedError`` by name.  INTEGRATION.md 4 has the time step it belongs
+        to; DESIGN.md 25 the kernels."""
+        means, values, conics, samples = self._require_inputs()
+        if pde not in NETWORK_PDES:
+            raise ValueError(f"pde must be one of {NETWORK_PDES}, got {pde!r}")
+        kind = NETWORK_PDES.index(pde)
+        d, c = means.shape[1], values.shape[1]
+        if d != 2:
+            raise NotImplementedError(f"network_inputs() is implemented for d = 2 (the reference's model), got d = {d}")
+        if pde in ("wave", "navier_stokes") and c != 2:
+            raise NotImplementedError(f"network_inputs(pde={pde!r}) needs a two-channel field, got c = {c}")
+        try:
+            w0, w1 = (float(x) for x in wave)
+        except (TypeError, ValueError):
+            raise ValueError(f"wave must be two floats, got {wave!r}") from None
+        return NetworkInputs(*self._core._network_inputs(kind, float(nu), w0, w1))
 
     def sample_gaussians(self):
         """u [M, c]"""
