@@ -939,6 +939,52 @@ int pigs_mlp_bank_backward(int dtype, int64_t N, int B, int G, int L, const int*
                            const void* const* weights, const void* const* biases, const void* g_y, void* scratch,
                            size_t scratch_bytes, void* g_x, void* const* g_weights, void* const* g_biases, void* stream);
 
+/* ---- A tanh network over a row that lies in several arrays, with block means (additive to ABI 10) -
+ * delta_net reads the features and the heads' neighbour features side by side (model_pn.py:265-268, a cat), and
+ * magnitude_loss (:892-901) is the mean square of each head's block of that joined row.  Here the net of the pigs_mlp_*
+ * block in every respect (L, widths, weights, biases, float32) takes its input row as P arrays, 1 <= P <=
+ * PIGS_MLP_JOINED_MAX_PARTS:
+ *   x[row] = (parts[0][row], .., parts[P-1][row]),  parts[p] [N][part_widths[p]] row-major,  sum_p part_widths[p] = widths[0]
+ *   y [N][w_L] = the net of x, with the bits of pigs_mlp_forward on the joined array.
+ * `blocks` is NULL (no block means) or a host array of P ints: blocks[p] = 0 takes none of part p, blocks[p] >= 1 must
+ * divide part_widths[p] and cuts part p's columns into blocks[p] equal blocks; sum_p blocks[p] <=
+ * PIGS_MLP_JOINED_MAX_BLOCKS.  With a block wanted,
+ *   m [sum_p blocks[p]] (float32), in the order of the parts:  m[j] = mean over the N rows and block j's columns of x^2.
+ * `part_widths`, `parts`, `blocks`, `g_parts` are host arrays, read during the call and not kept.
+ *
+ * pigs_mlp_joined_forward.  Without block means: one launch, no scratch, `m` not touched.  With them: the same launch,
+ *   in which every wave also writes one record of column sums of x^2 to `scratch`, and a one-workgroup launch that adds
+ *   the records in double in a fixed order, divides by N part_widths[p] / blocks[p] (formed in double) and rounds once.
+ * pigs_mlp_joined_backward, the launches of pigs_mlp_backward (one, and a second one when any weight or bias gradient is
+ *   wanted).  From g_y [N][w_L] and g_m [sum_p blocks[p]], either of which may be NULL (= zero) but not both, to
+ *   g_parts[p] [N][part_widths[p]], g_weights[l] and g_biases[l]; a NULL array or a NULL entry is not written.
+ *     g_parts[p][row][k] = dA_0[row][K_p + k] + (g_m[block of k] * 2 / (N part_widths[p] / blocks[p])) x[row][k]
+ *   (K_p = part p's first column; the second term only for a part with blocks, and only with g_m).  The factor 2 / (N ..)
+ *   is formed in double and rounded once.  Every g_weights / g_biases has the bits of pigs_mlp_backward on the joined
+ *   array; without g_m every g_parts[p] has the bits of its columns of pigs_mlp_backward's g_x.  No float atomics.
+ * scratch: pigs_mlp_joined_scratch_bytes(N, L, widths, P, blocks, backward) bytes, 4-byte aligned.  backward = 0: the
+ *   forward's, min(ceil(N / 16), 2048) records of widths[0] floats with a block wanted, else 0.  backward != 0:
+ *   pigs_mlp_scratch_bytes(N, L, widths), needed only with a weight or bias gradient wanted.  0 for N <= 0 or an
+ *   unsupported net.  Not read by the caller.
+ * Arguments are checked before any HIP call and before any pointer is dereferenced: a dtype other than PIGS_F32, L, P, a
+ *   width or a part's width out of range, or more than PIGS_MLP_JOINED_MAX_BLOCKS blocks is PIGS_ERR_UNSUPPORTED; N <= 0,
+ *   part widths that do not add up to widths[0], a negative blocks[p] or one that does not divide part_widths[p], a null
+ *   required array or entry (widths, part_widths, parts, weights, biases and their entries, y; m with a block wanted; g_y
+ *   and g_m both; g_m without a block), a backward with no gradient wanted, or a null, misaligned or short scratch when it
+ *   is needed is PIGS_ERR_INVALID.  Nothing allocates, frees, synchronises or waits for another workgroup.
+ */
+#define PIGS_MLP_JOINED_MAX_PARTS 4
+#define PIGS_MLP_JOINED_MAX_BLOCKS 8
+size_t pigs_mlp_joined_scratch_bytes(int64_t N, int L, const int* widths, int P, const int* blocks, int backward);
+int pigs_mlp_joined_forward(int dtype, int64_t N, int L, const int* widths, int P, const int* part_widths,
+                            const void* const* parts, const int* blocks, const void* const* weights,
+                            const void* const* biases, void* scratch, size_t scratch_bytes, void* y, void* m, void* stream);
+int pigs_mlp_joined_backward(int dtype, int64_t N, int L, const int* widths, int P, const int* part_widths,
+                             const void* const* parts, const int* blocks, const void* const* weights,
+                             const void* const* biases, const void* g_y, const void* g_m, void* scratch,
+                             size_t scratch_bytes, void* const* g_parts, void* const* g_weights, void* const* g_biases,
+                             void* stream);
+
 /* ---- The dynamics network's input transform (additive to ABI 10) -------------------------------
  * InputTransform (model_pn.py:51-152) as DynamicsNetwork.forward uses it (:237-249): t_params, the input of
  * input_projection.  d = 2, c = 1..4 channels, p = pde_size = 1..4, float32 only.  Row-major device arrays:

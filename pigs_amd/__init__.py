@@ -28,6 +28,9 @@ Public surface:
                             backward; the model's query / key nets of all heads leave ``queries`` and ``keys`` in the
                             layout of ``aggregate_neighbors_heads`` (pigs_amd.mlp; model_pn.py:259-261)
     FusedMLPBank            ``FusedMLPBank(nets, groups)``: the same as a non-owning callable over existing nets
+    fused_mlp_joined        such a net on a row that lies in up to 4 arrays, without the cat, and optionally the block means
+                            of squares of those arrays: delta_net on (features, heads) and magnitude_loss's head
+                            magnitudes; ``FusedMLP.joined`` is the same over a module (model_pn.py:265-268, 892-901)
     transform_matrices     the input transform's five matrices from the Gaussians (latent net, mean, five
                             TransformNets) in two launches (pigs_amd.input_transform; model_pn.py:51-119)
     apply_transforms        those matrices applied to the rows: ``t_params`` in one launch (model_pn.py:121-152, 237-249)
@@ -61,7 +64,7 @@ def __getattr__(name):
     if name in ("advance_gaussians", "ADVANCE_PENALTY_COLUMNS"):
         from . import advance
         return getattr(advance, name)
-    if name in ("fused_mlp", "FusedMLP", "fused_mlp_bank", "FusedMLPBank"):
+    if name in ("fused_mlp", "FusedMLP", "fused_mlp_bank", "FusedMLPBank", "fused_mlp_joined"):
         from . import mlp
         return getattr(mlp, name)
     if name in ("transform_matrices", "apply_transforms", "FusedInputTransform"):

@@ -201,6 +201,12 @@ SIGNATURES = {
     "pigs_mlp_bank_forward": (_i, [_i, _i64, _i, _i, _i, _ip, _vp, _vpp, _vpp, _vp, _vp]),
     "pigs_mlp_bank_backward": (_i, [_i, _i64, _i, _i, _i, _ip, _vp, _vpp, _vpp, _vp, _vp, ctypes.c_size_t, _vp, _vpp, _vpp,
                                     _vp]),
+    # one net over a row in P arrays, with block means (additive to ABI 10): widths, P, part_widths, parts, blocks, weights,
+    # biases, scratch, y, m / ..., g_y, g_m, scratch, g_parts, the parameter gradients
+    "pigs_mlp_joined_scratch_bytes": (ctypes.c_size_t, [_i64, _i, _ip, _i, _ip, _i]),
+    "pigs_mlp_joined_forward": (_i, [_i, _i64, _i, _ip, _i, _ip, _vpp, _ip, _vpp, _vpp, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
+    "pigs_mlp_joined_backward": (_i, [_i, _i64, _i, _ip, _i, _ip, _vpp, _ip, _vpp, _vpp, _vp, _vp, _vp, ctypes.c_size_t, _vpp,
+                                      _vpp, _vpp, _vp]),
     # the input transform (additive to ABI 10): dtype, N, c, p, the row arrays, ... ; params / g_params are 36 pointers
     "pigs_input_transform_scratch_bytes": (ctypes.c_size_t, [_i64, _i, _i]),
     "pigs_input_transform_matrices_forward": (_i, [_i, _i64, _i, _i] + [_vp] * 8 + [_vpp, _vp, ctypes.c_size_t, _vp, _vp, _vp]),

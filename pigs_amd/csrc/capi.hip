@@ -827,4 +827,84 @@ int pigs_mlp_bank_backward(int dtype, int64_t N, int B, int G, int L, const int*
     return mlp_bank_backward(s, (hipStream_t)stream);
 }
 
+size_t pigs_mlp_joined_scratch_bytes(int64_t N, int L, const int* widths, int P, const int* blocks, int backward) {
+    if (P < 1 || P > PIGS_MLP_JOINED_MAX_PARTS) return 0;
+    return mlp_joined_scratch_bytes(N, L, widths, P, blocks, backward);
+}
+
+// the sizes of a joined call; *block_count: the sum of blocks
+static int mlp_joined_sizes_ok(int dtype, int64_t N, int L, const int* widths, int P, const int* part_widths,
+                               const int* blocks, int* block_count) {
+    if (dtype != PIGS_F32) return PIGS_ERR_UNSUPPORTED;
+    if (P < 1 || P > PIGS_MLP_JOINED_MAX_PARTS) return PIGS_ERR_UNSUPPORTED;
+    if (L < 1 || L > PIGS_MLP_MAX_LAYERS) return PIGS_ERR_UNSUPPORTED;
+    if (!widths || !part_widths) return PIGS_ERR_INVALID;
+    for (int l = 0; l <= L; ++l)
+        if (widths[l] < 1 || widths[l] > PIGS_MLP_MAX_WIDTH) return PIGS_ERR_UNSUPPORTED;
+    int sum = 0, count = 0;
+    for (int p = 0; p < P; ++p) {
+        if (part_widths[p] < 1 || part_widths[p] > PIGS_MLP_MAX_WIDTH) return PIGS_ERR_UNSUPPORTED;
+        sum += part_widths[p];
+    }
+    for (int p = 0; blocks && p < P; ++p) {
+        if (blocks[p] < 0) return PIGS_ERR_INVALID;
+        if (blocks[p] > PIGS_MLP_JOINED_MAX_BLOCKS - count) return PIGS_ERR_UNSUPPORTED;
+        count += blocks[p];
+    }
+    if (N <= 0 || sum != widths[0]) return PIGS_ERR_INVALID;
+    for (int p = 0; blocks && p < P; ++p)
+        if (blocks[p] && part_widths[p] % blocks[p]) return PIGS_ERR_INVALID;
+    *block_count = count;
+    return PIGS_OK;
+}
+
+static bool mlp_joined_missing(int L, int P, const void* const* parts, const void* const* weights,
+                               const void* const* biases) {
+    if (!parts) return true;
+    for (int p = 0; p < P; ++p)
+        if (!parts[p]) return true;
+    return mlp_net_missing(L, parts, weights, biases);
+}
+
+static bool mlp_scratch_short(const void* scratch, size_t have, size_t need) {
+    return need && (!scratch || ((uintptr_t)scratch & 3u) || have < need);
+}
+
+int pigs_mlp_joined_forward(int dtype, int64_t N, int L, const int* widths, int P, const int* part_widths,
+                            const void* const* parts, const int* blocks, const void* const* weights,
+                            const void* const* biases, void* scratch, size_t scratch_bytes, void* y, void* m, void* stream) {
+    int count = 0;
+    const int rc = mlp_joined_sizes_ok(dtype, N, L, widths, P, part_widths, blocks, &count);
+    if (rc != PIGS_OK) return rc;
+    if (mlp_joined_missing(L, P, parts, weights, biases) || !y || (count && !m)) return PIGS_ERR_INVALID;
+    if (mlp_scratch_short(scratch, scratch_bytes, mlp_joined_scratch_bytes(N, L, widths, P, blocks, 0))) return PIGS_ERR_INVALID;
+    MlpJoinedStep s{};
+    s.N = N; s.L = L; s.P = P; s.widths = widths; s.part_widths = part_widths; s.parts = parts;
+    s.blocks = count ? blocks : nullptr; s.weights = weights; s.biases = biases; s.y = y; s.m = m; s.scratch = scratch;
+    return mlp_joined_forward(s, (hipStream_t)stream);
+}
+
+int pigs_mlp_joined_backward(int dtype, int64_t N, int L, const int* widths, int P, const int* part_widths,
+                             const void* const* parts, const int* blocks, const void* const* weights,
+                             const void* const* biases, const void* g_y, const void* g_m, void* scratch,
+                             size_t scratch_bytes, void* const* g_parts, void* const* g_weights, void* const* g_biases,
+                             void* stream) {
+    int count = 0;
+    const int rc = mlp_joined_sizes_ok(dtype, N, L, widths, P, part_widths, blocks, &count);
+    if (rc != PIGS_OK) return rc;
+    if (mlp_joined_missing(L, P, parts, weights, biases)) return PIGS_ERR_INVALID;
+    if ((!g_y && !g_m) || (g_m && !count)) return PIGS_ERR_INVALID;
+    bool params = false, wanted = false;
+    for (int l = 0; l < L; ++l) params = params || (g_weights && g_weights[l]) || (g_biases && g_biases[l]);
+    for (int p = 0; p < P; ++p) wanted = wanted || (g_parts && g_parts[p]);
+    if (!wanted && !params) return PIGS_ERR_INVALID;
+    if (params && mlp_scratch_short(scratch, scratch_bytes, mlp_joined_scratch_bytes(N, L, widths, P, blocks, 1)))
+        return PIGS_ERR_INVALID;
+    MlpJoinedStep s{};
+    s.N = N; s.L = L; s.P = P; s.widths = widths; s.part_widths = part_widths; s.parts = parts;
+    s.blocks = count ? blocks : nullptr; s.weights = weights; s.biases = biases; s.g_y = g_y; s.g_m = g_m;
+    s.scratch = scratch; s.g_parts = g_parts; s.g_weights = g_weights; s.g_biases = g_biases;
+    return mlp_joined_backward(s, (hipStream_t)stream);
+}
+
 }  // extern "C"

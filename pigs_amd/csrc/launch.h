@@ -150,6 +150,29 @@ size_t mlp_bank_scratch_bytes(int64_t N, int B, int L, const int* widths);
 int mlp_bank_forward(const MlpBankStep& s, hipStream_t stream);
 int mlp_bank_backward(const MlpBankStep& s, hipStream_t stream);
 
+// mlp_joined.hip: one net whose input row is P arrays side by side; optionally the block means of squares of the parts
+struct MlpJoinedStep {
+    int64_t N;
+    int L, P;
+    const int* widths;                  // [L + 1], host; widths[0] = the sum of part_widths
+    const int* part_widths;             // [P], host
+    const void* const* parts;           // [P] device pointers, host array: part p [N][part_widths[p]]
+    const int* blocks;                  // null = no block means, or [P]: part p's columns in blocks[p] equal blocks
+    const void* const* weights;         // [L]
+    const void* const* biases;
+    void* y;                            // forward: [N][widths[L]]
+    void* m;                            // forward: [sum of blocks], with block means only
+    const void* g_y;                    // backward: null = zero
+    const void* g_m;                    // backward: null = zero
+    void* scratch;                      // forward: the waves' column sums; backward: the waves' records
+    void* const* g_parts;               // backward: null, or [P] with null entries = not wanted
+    void* const* g_weights;
+    void* const* g_biases;
+};
+size_t mlp_joined_scratch_bytes(int64_t N, int L, const int* widths, int P, const int* blocks, int backward);
+int mlp_joined_forward(const MlpJoinedStep& s, hipStream_t stream);
+int mlp_joined_backward(const MlpJoinedStep& s, hipStream_t stream);
+
 // periodic.hip: images (fold = false; a = means, conics, values; o = image arrays) or the fold of their gradients
 // (fold = true; a = image gradients, null = zero; o = gradients)
 int periodic_dispatch(bool fold, int dtype, int c, int64_t N, double lo, double period, double q_cut, const void* a0,

@@ -34,8 +34,9 @@
 // The net's description, the staging, the forward helpers (mlp_stage, mlp_layer, mlp_tanh, ...), the backward's layer
 // (mlp_backward_layer, mlp_record_layer) and the bodies of the forward and the finishing kernel live in mlp_chain.h:
 // input_transform.hip runs the same chain over gathered rows, mlp_bank.hip the same bodies for several nets of one shape
-// in one launch.  The backward kernel's body stands here AND in mlp_chain.h (mlp_backward_tiles<MLP_TILES>, for the
-// bank): called as a function it no longer fits this kernel's registers; a change to one is a change to both.
+// in one launch.  The backward kernel's body is the text of mlp_backward_body.h, included here, in mlp_chain.h
+// (mlp_backward_tiles<T>, for the bank) and in mlp_joined.hip: called as a function it no longer fits this kernel's
+// registers.
 #include <hip/hip_runtime.h>
 
 #include "launch.h"
@@ -60,58 +61,21 @@ __global__ __launch_bounds__(64 * MLP_WAVES) void mlp_backward_kernel(int64_t N,
                                                                       float* __restrict__ scratch) {
     extern __shared__ float mlp_lds[];
     mlp_stage(n, mlp_lds);
-    const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4, wave = threadIdx.x >> 6;
-    float* __restrict__ acts = mlp_lds + n.wave_off + wave * (n.L + 1) * 16 * MLP_ROW;      // a_l: tile l; dZ: tile L
-    float* __restrict__ dz_t = acts + n.L * 16 * MLP_ROW;
-    const int own = r * MLP_ROW + 4 * g;       // where this lane's four features of feature tile 0 lie in a tile
-
-    f4 acc_w[PIGS_MLP_MAX_LAYERS][MLP_TILES][MLP_TILES], acc_b[PIGS_MLP_MAX_LAYERS][MLP_TILES];
-#pragma unroll
-    for (int l = 0; l < PIGS_MLP_MAX_LAYERS; ++l)
-#pragma unroll
-        for (int to = 0; to < MLP_TILES; ++to) {
-            acc_b[l][to] = f4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int ti = 0; ti < MLP_TILES; ++ti) acc_w[l][to][ti] = f4{0.0f, 0.0f, 0.0f, 0.0f};
-        }
-
-    const int64_t first = (int64_t)blockIdx.x * MLP_WAVES + wave, stride = (int64_t)gridDim.x * MLP_WAVES;
-    for (int64_t tile = first; tile < tiles; tile += stride) {
-        const int64_t row = tile * 16 + r;
-        const bool live = row < N;
-        f4 a[MLP_TILES], d[MLP_TILES];
-        mlp_wave_fence();                      // the previous tile's reads of this region are done
-        mlp_load_rows(a, x, row, live, n.w[0], n.w[0], g);
-        for (int l = 0; l < n.L; ++l) {        // a_l to LDS, then a_{l+1}; y itself is not needed
-#pragma unroll
-            for (int t = 0; t < MLP_TILES; ++t) *reinterpret_cast<f4*>(acts + l * 16 * MLP_ROW + own + 16 * t) = a[t];
-            if (l + 1 < n.L) {
-                const int nti = mlp_tiles(n.w[l]), nto = mlp_tiles(n.w[l + 1]);
-                mlp_layer(d, a, mlp_lds + n.woff[l], mlp_lds + n.boff[l], 16 * nti + 4, nti, nto, r, g);
-                mlp_tanh(a, d);
-            }
-        }
-        mlp_load_rows(d, g_y, row, live, n.w[n.L], n.w[n.L], g);      // dZ of the last layer
-#pragma unroll
-        for (int l = PIGS_MLP_MAX_LAYERS - 1; l >= 0; --l) {
-            if (l >= n.L) continue;
-            const bool want_da = l > 0 || out.g_x;
-            mlp_backward_layer<MLP_TILES, MLP_TILES>(d, acc_w[l], acc_b[l], out.g_W[l] != nullptr, out.g_b[l] != nullptr,
-                                                     want_da, l == 0, mlp_lds + n.woff[l], mlp_tiles(n.w[l + 1]),
-                                                     mlp_tiles(n.w[l]), acts + l * 16 * MLP_ROW, dz_t, own, r, g);
-            if (l == 0 && want_da) mlp_store_rows(out.g_x, d, row, live, n.w[0], n.w[0], g);
-        }
-    }
-
-    // this wave's record; a wave without a tile (only past the last tile's wave) writes none
-    if (first >= tiles) return;
-    float* __restrict__ rec = scratch + first * n.P;
-#pragma unroll
-    for (int l = 0; l < PIGS_MLP_MAX_LAYERS; ++l) {
-        if (l >= n.L) continue;
-        mlp_record_layer<MLP_TILES, MLP_TILES>(rec, n.poff[l], acc_w[l], acc_b[l], out.g_W[l] != nullptr,
-                                               out.g_b[l] != nullptr, n.w[l], n.w[l + 1], r, g);
-    }
+#define MLP_BODY_T MLP_TILES
+#define MLP_BODY_LDS mlp_lds
+#define MLP_BODY_LOAD_X(a, row, live, g) mlp_load_rows(a, x, row, live, n.w[0], n.w[0], g)
+#define MLP_BODY_LOAD_GY(d, row, live, g) mlp_load_rows(d, g_y, row, live, n.w[n.L], n.w[n.L], g)
+#define MLP_BODY_WANT_DA0 out.g_x
+#define MLP_BODY_STORE_DA0(d, row, live, g) mlp_store_rows(out.g_x, d, row, live, n.w[0], n.w[0], g)
+#define MLP_BODY_RECORDS scratch
+#include "mlp_backward_body.h"
+#undef MLP_BODY_T
+#undef MLP_BODY_LDS
+#undef MLP_BODY_LOAD_X
+#undef MLP_BODY_LOAD_GY
+#undef MLP_BODY_WANT_DA0
+#undef MLP_BODY_STORE_DA0
+#undef MLP_BODY_RECORDS
 }
 
 // the records added in a fixed order into g_W / g_b (mlp_finish_block, mlp_chain.h)

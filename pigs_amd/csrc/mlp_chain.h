@@ -1,5 +1,6 @@
 // The register-resident tanh chain on v_mfma_f32_16x16x4_f32, shared by mlp.hip (one per-Gaussian net per launch),
-// mlp_bank.hip (several nets of one shape over one input per launch) and input_transform.hip (the latent net, whose rows
+// mlp_bank.hip (several nets of one shape over one input per launch), mlp_joined.hip (one net whose input row lies in
+// several arrays) and input_transform.hip (the latent net, whose rows
 // are gathered from eight arrays and summed instead of stored).  It holds
 // the backward as well: one layer's three products (mlp_backward_layer) and its part of a wave's record
 // (mlp_record_layer), which mlp.hip instantiates at the widest net and input_transform.hip at the latent net's tile
@@ -33,6 +34,25 @@ struct MlpGrads {
     float* g_x;                                // null = not wanted
     float* g_W[PIGS_MLP_MAX_LAYERS];
     float* g_b[PIGS_MLP_MAX_LAYERS];
+};
+
+// a row that is up to MLP_PARTS arrays side by side (mlp_joined.hip; mlp_load_parts below).  The host also says whether
+// every 16-column tile's columns lie in ONE part, and which: the kernels then take each tile as mlp_load_rows would, from
+// an address that is a kernel argument of its own.  (Found in the kernel by compares, the part became an index into the
+// kernel's argument arrays: two dependent scalar loads per tile, waited for at one wave per SIMD.)
+constexpr int MLP_PARTS = PIGS_MLP_JOINED_MAX_PARTS;
+struct MlpJoin {
+    int start[MLP_PARTS];                      // part p's first column in the row; INT_MAX for a part that is not there
+    int width[MLP_PARTS];                      //   and its columns (0)
+    int tiles_whole;                           // every 16-column tile lies in one part (or past the row's end)
+    int tile_start[MLP_TILES];                 //   then: the first column of tile t's part
+    int tile_width[MLP_TILES];                 //   and that part's columns
+};
+
+template <class T>
+struct MlpPartPointers {
+    T* part[MLP_PARTS];                        // null: a part that is not there, or not wanted
+    T* tile[MLP_TILES];                        // with tiles_whole: the part of tile t
 };
 
 __host__ __device__ constexpr int mlp_tiles(int width) { return (width + 15) >> 4; }
@@ -124,6 +144,86 @@ __device__ __forceinline__ void mlp_store_rows(float* __restrict__ dst, const f4
         for (int s = 0; s < 4; ++s) {
             const int k = 16 * t + 4 * g + s;
             if (live && k < width) dst[row * stride + k] = a[t][s];
+        }
+}
+
+// The same two for a row that is MLP_PARTS arrays side by side (mlp_joined.hip): part p is [N][width[p]] and holds
+// columns start[p] .. start[p] + width[p] - 1 of the row.  Where every 16-column tile lies in ONE part (the model's
+// (16, 32)), a row is loaded and stored as mlp_load_rows / mlp_store_rows would, each tile from its own pointer, all loads
+// of a row in one basic block so that they are in flight together.  Otherwise every element chooses its part by compares
+// against the parts' bounds: a lane's four columns may lie in two parts.  There a lane forms its row's address in each
+// part once (the column's start taken off), and a column costs the selects and one add.  (Its four addresses are scalars,
+// not an array: an array is kept in scratch memory and indexed.)
+static_assert(MLP_PARTS == 4, "mlp_part_of names every part");
+template <class T>
+__device__ __forceinline__ T* mlp_part_of(int k, const MlpJoin& j, T* at0, T* at1, T* at2, T* at3) {
+    T* p = at0;
+    p = k >= j.start[1] ? at1 : p;
+    p = k >= j.start[2] ? at2 : p;
+    p = k >= j.start[3] ? at3 : p;
+    return p;
+}
+
+// where column 0 of the row would lie if a part of `width` columns from column `start` on ran on from it: the
+// result[k] is column k of the row; null stays null
+template <class T>
+__device__ __forceinline__ T* mlp_part_row(T* base, int width, int start, int64_t row) {
+    return base ? base + (row * width - start) : nullptr;
+}
+
+__device__ __forceinline__ void mlp_load_parts(f4 (&a)[MLP_TILES], const MlpJoin& j, const MlpPartPointers<const float>& x,
+                                               int64_t row, bool live, int width, int g) {
+    if (j.tiles_whole) {
+#pragma unroll
+        for (int t = 0; t < MLP_TILES; ++t) {
+            const float* const at = mlp_part_row(x.tile[t], j.tile_width[t], j.tile_start[t], row);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const int k = 16 * t + 4 * g + s;
+                a[t][s] = (live && k < width) ? at[k] : 0.0f;
+            }
+        }
+        return;
+    }
+    const float* const at0 = mlp_part_row(x.part[0], j.width[0], 0, row);
+    const float* const at1 = mlp_part_row(x.part[1], j.width[1], j.start[1], row);
+    const float* const at2 = mlp_part_row(x.part[2], j.width[2], j.start[2], row);
+    const float* const at3 = mlp_part_row(x.part[3], j.width[3], j.start[3], row);
+#pragma unroll
+    for (int t = 0; t < MLP_TILES; ++t)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int k = 16 * t + 4 * g + s;
+            a[t][s] = (live && k < width) ? mlp_part_of(k, j, at0, at1, at2, at3)[k] : 0.0f;
+        }
+}
+
+// a null pointer: that part is not written
+__device__ __forceinline__ void mlp_store_parts(const MlpPartPointers<float>& dst, const MlpJoin& j, const f4 (&a)[MLP_TILES],
+                                                int64_t row, bool live, int width, int g) {
+    if (j.tiles_whole) {
+#pragma unroll
+        for (int t = 0; t < MLP_TILES; ++t) {
+            float* const at = mlp_part_row(dst.tile[t], j.tile_width[t], j.tile_start[t], row);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const int k = 16 * t + 4 * g + s;
+                if (live && k < width && at) at[k] = a[t][s];
+            }
+        }
+        return;
+    }
+    float* const at0 = mlp_part_row(dst.part[0], j.width[0], 0, row);
+    float* const at1 = mlp_part_row(dst.part[1], j.width[1], j.start[1], row);
+    float* const at2 = mlp_part_row(dst.part[2], j.width[2], j.start[2], row);
+    float* const at3 = mlp_part_row(dst.part[3], j.width[3], j.start[3], row);
+#pragma unroll
+    for (int t = 0; t < MLP_TILES; ++t)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int k = 16 * t + 4 * g + s;
+            float* const p = mlp_part_of(k, j, at0, at1, at2, at3);
+            if (live && k < width && p) p[k] = a[t][s];
         }
 }
 
@@ -260,16 +360,19 @@ __device__ __forceinline__ void mlp_record_layer(float* __restrict__ rec, int ba
 
 // ---- the bodies of mlp.hip's three kernels, shared with mlp_bank.hip (one net of a bank per workgroup) ------------
 // The forward of the staged net over this workgroup's tiles: tile = blockIdx.x * MLP_WAVES + wave, + the grid's waves,
-// ...  Rows of y lie y_stride floats apart (one net: w_L).
+// ...  Rows of y lie y_stride floats apart (one net: w_L).  load(a, row, live, g) brings a_0 in mlp_load_rows's layout;
+// seen(a) is called with it once per tile (mlp_joined.hip adds its squares there).
+template <class Load, class Seen>
 __device__ __forceinline__ void mlp_forward_tiles(int64_t N, int64_t tiles, const MlpNet& n, const float* __restrict__ lds,
-                                                  const float* __restrict__ x, float* __restrict__ y, int y_stride) {
+                                                  Load load, Seen seen, float* __restrict__ y, int y_stride) {
     const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
     const int64_t stride = (int64_t)gridDim.x * MLP_WAVES;
     for (int64_t tile = (int64_t)blockIdx.x * MLP_WAVES + (threadIdx.x >> 6); tile < tiles; tile += stride) {
         const int64_t row = tile * 16 + r;
         const bool live = row < N;
         f4 a[MLP_TILES], z[MLP_TILES];
-        mlp_load_rows(a, x, row, live, n.w[0], n.w[0], g);
+        load(a, row, live, g);
+        seen(a);
         for (int l = 0; l < n.L; ++l) {
             const int nti = mlp_tiles(n.w[l]), nto = mlp_tiles(n.w[l + 1]);
             mlp_layer(z, a, lds + n.woff[l], lds + n.boff[l], 16 * nti + 4, nti, nto, r, g);
@@ -279,68 +382,40 @@ __device__ __forceinline__ void mlp_forward_tiles(int64_t N, int64_t tiles, cons
     }
 }
 
+// the same with x one array [N][w_0]
+__device__ __forceinline__ void mlp_forward_tiles(int64_t N, int64_t tiles, const MlpNet& n, const float* __restrict__ lds,
+                                                  const float* __restrict__ x, float* __restrict__ y, int y_stride) {
+    mlp_forward_tiles(
+        N, tiles, n, lds,
+        [&](f4 (&a)[MLP_TILES], int64_t row, bool live, int g) { mlp_load_rows(a, x, row, live, n.w[0], n.w[0], g); },
+        [](const f4 (&)[MLP_TILES]) {}, y, y_stride);
+}
+
 // The backward of the staged net over this wave's tiles (the same walk), and the wave's record at records[first * n.P].
 // Rows of g_y lie gy_stride floats apart; out.g_x is [N][w_0].  T: the 16-feature tiles of the net's widest layer, or
-// more -- the accumulators a wave holds are PIGS_MLP_MAX_LAYERS x T x T tiles of dW.  This is the text of mlp.hip's
-// mlp_backward_kernel at T = MLP_TILES, which keeps its own copy: called from there, the register allocator no longer
-// fits that kernel into its registers (512 VGPRs and 32 spilled, against 488 and none).
+// more -- the accumulators a wave holds are PIGS_MLP_MAX_LAYERS x T x T tiles of dW.  The body is the text of
+// mlp_backward_body.h, which mlp.hip's mlp_backward_kernel includes as well: calling this function from there, the
+// register allocator no longer fits that kernel into its registers (512 VGPRs and 32 spilled, against 488 and none).
 template <int T>
 __device__ __forceinline__ void mlp_backward_tiles(int64_t N, int64_t tiles, const MlpNet& n, const MlpGrads& out,
                                                    float* __restrict__ lds, const float* __restrict__ x,
                                                    const float* __restrict__ g_y, int gy_stride,
                                                    float* __restrict__ records) {
-    const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4, wave = threadIdx.x >> 6;
-    float* __restrict__ acts = lds + n.wave_off + wave * (n.L + 1) * 16 * MLP_ROW;      // a_l: tile l; dZ: tile L
-    float* __restrict__ dz_t = acts + n.L * 16 * MLP_ROW;
-    const int own = r * MLP_ROW + 4 * g;       // where this lane's four features of feature tile 0 lie in a tile
-
-    f4 acc_w[PIGS_MLP_MAX_LAYERS][T][T], acc_b[PIGS_MLP_MAX_LAYERS][T];
-#pragma unroll
-    for (int l = 0; l < PIGS_MLP_MAX_LAYERS; ++l)
-#pragma unroll
-        for (int to = 0; to < T; ++to) {
-            acc_b[l][to] = f4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int ti = 0; ti < T; ++ti) acc_w[l][to][ti] = f4{0.0f, 0.0f, 0.0f, 0.0f};
-        }
-
-    const int64_t first = (int64_t)blockIdx.x * MLP_WAVES + wave, stride = (int64_t)gridDim.x * MLP_WAVES;
-    for (int64_t tile = first; tile < tiles; tile += stride) {
-        const int64_t row = tile * 16 + r;
-        const bool live = row < N;
-        f4 a[MLP_TILES], d[MLP_TILES];
-        mlp_wave_fence();                      // the previous tile's reads of this region are done
-        mlp_load_rows(a, x, row, live, n.w[0], n.w[0], g);
-        for (int l = 0; l < n.L; ++l) {        // a_l to LDS, then a_{l+1}; y itself is not needed
-#pragma unroll
-            for (int t = 0; t < MLP_TILES; ++t) *reinterpret_cast<f4*>(acts + l * 16 * MLP_ROW + own + 16 * t) = a[t];
-            if (l + 1 < n.L) {
-                const int nti = mlp_tiles(n.w[l]), nto = mlp_tiles(n.w[l + 1]);
-                mlp_layer(d, a, lds + n.woff[l], lds + n.boff[l], 16 * nti + 4, nti, nto, r, g);
-                mlp_tanh(a, d);
-            }
-        }
-        mlp_load_rows(d, g_y, row, live, n.w[n.L], gy_stride, g);      // dZ of the last layer
-#pragma unroll
-        for (int l = PIGS_MLP_MAX_LAYERS - 1; l >= 0; --l) {
-            if (l >= n.L) continue;
-            const bool want_da = l > 0 || out.g_x;
-            mlp_backward_layer<T, T>(d, acc_w[l], acc_b[l], out.g_W[l] != nullptr, out.g_b[l] != nullptr,
-                                                     want_da, l == 0, lds + n.woff[l], mlp_tiles(n.w[l + 1]),
-                                                     mlp_tiles(n.w[l]), acts + l * 16 * MLP_ROW, dz_t, own, r, g);
-            if (l == 0 && want_da) mlp_store_rows(out.g_x, d, row, live, n.w[0], n.w[0], g);
-        }
-    }
-
-    // this wave's record; a wave without a tile (only past the last tile's wave) writes none
-    if (first >= tiles) return;
-    float* __restrict__ rec = records + first * n.P;
-#pragma unroll
-    for (int l = 0; l < PIGS_MLP_MAX_LAYERS; ++l) {
-        if (l >= n.L) continue;
-        mlp_record_layer<T, T>(rec, n.poff[l], acc_w[l], acc_b[l], out.g_W[l] != nullptr,
-                                               out.g_b[l] != nullptr, n.w[l], n.w[l + 1], r, g);
-    }
+#define MLP_BODY_T T
+#define MLP_BODY_LDS lds
+#define MLP_BODY_LOAD_X(a, row, live, g) mlp_load_rows(a, x, row, live, n.w[0], n.w[0], g)
+#define MLP_BODY_LOAD_GY(d, row, live, g) mlp_load_rows(d, g_y, row, live, n.w[n.L], gy_stride, g)
+#define MLP_BODY_WANT_DA0 out.g_x
+#define MLP_BODY_STORE_DA0(d, row, live, g) mlp_store_rows(out.g_x, d, row, live, n.w[0], n.w[0], g)
+#define MLP_BODY_RECORDS records
+#include "mlp_backward_body.h"
+#undef MLP_BODY_T
+#undef MLP_BODY_LDS
+#undef MLP_BODY_LOAD_X
+#undef MLP_BODY_LOAD_GY
+#undef MLP_BODY_WANT_DA0
+#undef MLP_BODY_STORE_DA0
+#undef MLP_BODY_RECORDS
 }
 
 // Parameter e of the net from `records` records of n.P floats, by four lanes (lane = 16 part + e's low bits): lane `part`

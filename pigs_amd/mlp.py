@@ -31,6 +31,13 @@ bit: ``qk[0]`` and ``qk[1]`` are the contiguous ``queries`` / ``keys`` [N, H, K]
 gradient of ``x`` is the nets' gradients added in the order of the nets.
 
     bank = FusedMLPBank([*query_transform, *key_transform], groups=2)      # non-owning: registers no parameter
+
+A row that lies in several arrays (C ABI: pigs_mlp_joined_forward / pigs_mlp_joined_backward): delta_net reads the features
+and the heads' neighbour features side by side (:265-268, a cat), and magnitude_loss (:892-901) is the mean square of each
+head's block of that row.  Without the cat, its backward's split, or any reduction launch:
+
+    deltas, mags = delta_net.joined((features, nf), block_means=(0, H))      # FusedMLP.joined -> fused_mlp_joined
+    magnitude_loss = ((mags - 1) ** 2).mean()
 """
 import ctypes
 
@@ -42,12 +49,15 @@ from ._lib import pointers as _pointers, ptr as _ptr, stream as _stream
 MAX_LAYERS = 6
 MAX_WIDTH = 48
 MAX_NETS = 8
+MAX_PARTS = 4
+MAX_BLOCKS = 8
 
 
-def _check(x, weights, biases):
-    """the refusals, with the exception types of advance._check; returns the widths"""
+def _check(x, weights, biases, joined=None):
+    """the refusals, with the exception types of advance._check; returns the widths.  ``joined``: (N, w_0, [(name,
+    part)]) when the row lies in several arrays (``_check_joined``, which has looked at their shapes; ``x`` is None)"""
     weights, biases = tuple(weights), tuple(biases)
-    if not isinstance(x, torch.Tensor):
+    if joined is None and not isinstance(x, torch.Tensor):
         raise TypeError("x must be a torch.Tensor")
     L = len(weights)
     if len(biases) != L:
@@ -58,9 +68,12 @@ def _check(x, weights, biases):
         for n, a in ((f"weights[{l}]", weights[l]), (f"biases[{l}]", biases[l])):
             if not isinstance(a, torch.Tensor):
                 raise TypeError(f"{n} must be a torch.Tensor" + (" (a net without biases is not built)" if a is None else ""))
-    if x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[0] != 1):
+    if joined is not None:
+        N, widths, inputs = joined[0], [joined[1]], list(joined[2])
+    elif x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[0] != 1):
         raise ValueError(f"x must be [N, w] or [1, N, w], got {tuple(x.shape)}")
-    N, widths = x.shape[-2], [x.shape[-1]]
+    else:
+        N, widths, inputs = x.shape[-2], [x.shape[-1]], [("x", x)]
     if N < 1:
         raise ValueError("no rows: N must be at least 1")
     for l in range(L):
@@ -72,15 +85,16 @@ def _check(x, weights, biases):
     for l, w in enumerate(widths):
         if not 1 <= w <= MAX_WIDTH:
             raise NotImplementedError(f"width {w} (w_{l}): every width must be in 1..{MAX_WIDTH}")
-    arrays = [("x", x)] + [(f"weights[{l}]", weights[l]) for l in range(L)] + [(f"biases[{l}]", biases[l]) for l in range(L)]
+    arrays = inputs + [(f"weights[{l}]", weights[l]) for l in range(L)] + [(f"biases[{l}]", biases[l]) for l in range(L)]
     if any(a.dtype != torch.float32 for _, a in arrays):
         raise TypeError(f"dtypes {sorted({str(a.dtype) for _, a in arrays})}: float32 only")
     for n, a in arrays:
         if not a.is_contiguous():
             raise ValueError(f"{n} must be contiguous")
+    first, x = arrays[0]
     for n, a in arrays:
         if not a.is_cuda or a.device != x.device:
-            raise RuntimeError(f"{n} is on {a.device}" + (f", x on {x.device}" if a is not x else "")
+            raise RuntimeError(f"{n} is on {a.device}" + (f", {first} on {x.device}" if a is not x else "")
                                + ": the network runs on one GPU (no CPU fallback)")
     return widths
 
@@ -181,6 +195,146 @@ class FusedMLP(torch.nn.Sequential):
     def forward(self, x):
         linears = [self[k] for k in self._linears]
         return fused_mlp(x, [m.weight for m in linears], [m.bias for m in linears])
+
+    def joined(self, parts, block_means=None):
+        """``fused_mlp_joined`` with this net's ``nn.Linear`` children as they are now (read at every call, as ``forward``
+        does): the net on a row that lies in several arrays, and optionally the block means of its squares."""
+        linears = [self[k] for k in self._linears]
+        return fused_mlp_joined(parts, [m.weight for m in linears], [m.bias for m in linears], block_means)
+
+
+def _check_joined(parts, weights, biases, block_means):
+    """the joined call's refusals, with ``_check``'s exception types, naming the part: the parts among themselves first,
+    then ``_check`` with the parts in the place of x.  Returns N, where each part's rows begin (1 for [1, N, ...]), the
+    parts' widths and the blocks (a tuple of P ints, or None for none)."""
+    parts = tuple(parts)
+    P = len(parts)
+    if not 1 <= P <= MAX_PARTS:
+        raise NotImplementedError(f"{P} parts: 1..{MAX_PARTS} per call")
+    for p, t in enumerate(parts):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"parts[{p}] must be a torch.Tensor")
+        if t.dim() < 2:
+            raise ValueError(f"parts[{p}] must be [N, ...] or [1, N, ...] with at least one column, got {tuple(t.shape)}")
+    # [1, n, ...] reads as one row or as n rows behind a leading 1: a part that reads one way only says which N it is
+    sure = [t.shape[0] for t in parts if t.shape[0] != 1 or t.dim() == 2]
+    N = sure[0] if sure else parts[0].shape[1]
+    leads, part_widths = [], []
+    for p, t in enumerate(parts):
+        lead = 1 if t.dim() >= 3 and t.shape[0] == 1 and t.shape[1] == N else 0
+        if t.shape[lead] != N:
+            raise ValueError(f"parts[{p}] {tuple(t.shape)} has {t.shape[lead]} rows, the others {N}")
+        w = 1
+        for n in t.shape[lead + 1:]:
+            w *= n
+        if not 1 <= w <= MAX_WIDTH:
+            raise NotImplementedError(f"parts[{p}] {tuple(t.shape)} is {w} columns wide: 1..{MAX_WIDTH}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"parts[{p}] is {t.dtype}: float32 only")
+        leads.append(lead)
+        part_widths.append(w)
+    weights = tuple(weights)
+    if weights and isinstance(weights[0], torch.Tensor) and weights[0].dim() == 2 and weights[0].shape[1] != sum(part_widths):
+        raise ValueError(f"the parts' widths {part_widths} add up to {sum(part_widths)}, weights[0] is "
+                         f"{tuple(weights[0].shape)}")
+    blocks = None
+    if block_means is not None:
+        blocks = tuple(block_means)
+        if len(blocks) != P:
+            raise ValueError(f"block_means has {len(blocks)} entries for {P} parts")
+        for p, b in enumerate(blocks):
+            if not isinstance(b, int) or isinstance(b, bool) or b < 0:
+                raise ValueError(f"block_means[{p}] = {b!r} must be an int >= 0")
+            if b and part_widths[p] % b:
+                raise ValueError(f"block_means[{p}] = {b} does not divide parts[{p}]'s {part_widths[p]} columns")
+        if sum(blocks) > MAX_BLOCKS:
+            raise NotImplementedError(f"{sum(blocks)} blocks: at most {MAX_BLOCKS} per call")
+    _check(None, weights, biases, joined=(N, sum(part_widths), [(f"parts[{p}]", t) for p, t in enumerate(parts)]))
+    return N, leads, part_widths, blocks
+
+
+class _FusedMLPJoined(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, P, blocks, *tensors):
+        lib = _lib.load()
+        parts, params = tensors[:P], tensors[P:]
+        L = len(params) // 2
+        weights, biases = params[:L], params[L:]
+        x0 = parts[0]
+        N = x0.shape[0]
+        part_widths = (ctypes.c_int * P)(*[t.shape[1] for t in parts])
+        widths = (ctypes.c_int * (L + 1))(sum(part_widths), *[w.shape[0] for w in weights])
+        count = sum(blocks) if blocks else 0
+        cblocks = (ctypes.c_int * P)(*blocks) if count else None
+        y = torch.empty((N, widths[L]), dtype=x0.dtype, device=x0.device)
+        m = torch.empty((count,), dtype=x0.dtype, device=x0.device) if count else None
+        nbytes = lib.pigs_mlp_joined_scratch_bytes(N, L, widths, P, cblocks, 0) if count else 0
+        scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=x0.device) if nbytes else None
+        with torch.cuda.device(x0.device):
+            rc = lib.pigs_mlp_joined_forward(_lib.PIGS_F32, N, L, widths, P, part_widths, _pointers(parts), cblocks,
+                                             _pointers(weights), _pointers(biases), _ptr(scratch), nbytes, _ptr(y), _ptr(m),
+                                             _stream(x0.device))
+        _lib.check(rc, "pigs_mlp_joined_forward")
+        ctx.save_for_backward(*tensors)
+        ctx.joined = (P, L, count, widths, part_widths, cblocks)
+        ctx.set_materialize_grads(False)          # an output that is not used arrives as None, and stays a null pointer
+        return (y, m) if count else y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_y, g_m=None):
+        tensors = ctx.saved_tensors
+        P, L, count, widths, part_widths, cblocks = ctx.joined
+        needs = ctx.needs_input_grad[2:]
+        if not any(needs) or (g_y is None and g_m is None):
+            return (None,) * (2 + len(needs))
+        lib = _lib.load()
+        parts, weights, biases = tensors[:P], tensors[P:P + L], tensors[P + L:]
+        N = parts[0].shape[0]
+        g_y = g_y.contiguous() if g_y is not None else None
+        g_m = g_m.contiguous() if g_m is not None else None
+        grads = [torch.empty_like(t) if need else None for t, need in zip(tensors, needs)]
+        nbytes = lib.pigs_mlp_joined_scratch_bytes(N, L, widths, P, cblocks, 1) if any(needs[P:]) else 0
+        scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=parts[0].device) if nbytes else None
+        with torch.cuda.device(parts[0].device):
+            rc = lib.pigs_mlp_joined_backward(_lib.PIGS_F32, N, L, widths, P, part_widths, _pointers(parts), cblocks,
+                                              _pointers(weights), _pointers(biases), _ptr(g_y), _ptr(g_m), _ptr(scratch),
+                                              nbytes, _pointers(grads[:P]), _pointers(grads[P:P + L]),
+                                              _pointers(grads[P + L:]), _stream(parts[0].device))
+        _lib.check(rc, "pigs_mlp_joined_backward")
+        return (None, None, *grads)
+
+
+def fused_mlp_joined(parts, weights, biases, block_means=None):
+    """``fused_mlp`` on a row that lies in several arrays, without the cat; optionally the block means of squares.
+
+        y = fused_mlp_joined(parts, weights, biases)
+        y, m = fused_mlp_joined(parts, weights, biases, block_means=(b_0, .., b_{P-1}))
+
+    ``parts``: 1..4 contiguous float32 GPU tensors [N, ...] or [1, N, ...] with one N; a part's trailing dimensions are
+    its columns (w_p >= 1 of them), so the heads' [N, H, L] goes in as it is.  The parts' widths add up to w_0 <= 48.
+    ``y`` is ``fused_mlp(torch.cat(flat parts, -1), weights, biases)`` bit for bit, with the leading shape of part 0.
+    ``block_means``: None, or one int per part: 0 takes nothing of that part; b >= 1 must divide w_p and cuts the part's
+    columns into b equal blocks; at most 8 blocks in all.  ``m`` is float32 [sum b_p], in the order of the parts:
+    ``m[j]`` = the mean over the N rows and the block's w_p / b_p columns of x**2.  Without block means one launch and no
+    scratch; with them the same launch and a one-workgroup finish.  The backward is ``fused_mlp``'s launches and gives one
+    gradient per part, in the part's own shape, only where asked:
+
+        g_part_p[row, k] = dA_0[row, K_p + k] + g_m[block of k] * 2 x[row, k] / (N w_p / b_p)
+
+    with the parameter gradients bit for bit ``fused_mlp``'s on the cat, and without ``m`` in the loss every g_part the
+    bits of its slice of ``fused_mlp``'s g_x.  Once-differentiable, no float atomics, capturable (GraphedStep).  The
+    model's call (model_pn.py:265-268, :892-901): ``deltas, mags = delta_net.joined((features, nf), block_means=(0, H))``,
+    ``magnitude_loss = ((mags - 1) ** 2).mean()``."""
+    parts, weights, biases = tuple(parts), tuple(weights), tuple(biases)
+    N, leads, part_widths, blocks = _check_joined(parts, weights, biases, block_means)
+    rows = [t.reshape(N, w) for t, w in zip(parts, part_widths)]          # views: a gradient keeps its part's shape
+    out = _FusedMLPJoined.apply(len(parts), blocks if blocks and sum(blocks) else None, *rows, *weights, *biases)
+    y, m = out if isinstance(out, tuple) else (out, None)
+    y = y.reshape(*parts[0].shape[:leads[0] + 1], y.shape[-1])
+    if blocks is None:
+        return y
+    return y, (m if m is not None else y.new_zeros((0,)))
 
 
 def _check_bank(x, weights, biases, groups):
