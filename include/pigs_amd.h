@@ -808,6 +808,57 @@ int pigs_optim_step(int dtype, int c, int64_t N, const PigsAdamStep* hyper, void
                     const void* g_conics, void* means, void* covariances, void* conics, void* stream);
 
 /*
+ * The optimiser's gradient statistics and its d = 1 form (additive to ABI 10: the number does not change; PigsAdamStep,
+ * pigs_optim_materialize and pigs_optim_step are as they were).
+ *
+ * Statistics.  The densification of the MLP-free loops thresholds sums of the RAW parameters' gradients, which with
+ * pigs_optim_step exist only in the kernel's registers.  With G_m = dL/d raw_means and G_s = dL/d raw_scaling after the
+ * chain rule, exactly as Adam consumes them, a step with a PigsGradStats does, per Gaussian and for a group whose
+ * gradient is present (means: g_means; scaling: g_covariances or g_conics):
+ *      last_mean_grad  = G_m,  mean_grad  += G_m,  mean_grad_norm  += || mean_grad ||_2     (the sum AFTER adding)
+ *      last_scale_grad = G_s,  scale_grad += G_s,  scale_grad_norm += || scale_grad ||_2
+ *   in the same launch; this replaces test_no_mlp.py:149-155 and test_no_mlp_1d.py:156-162 (mean_grad += raw_means.grad,
+ *   mean_grad_norm += torch.norm(mean_grad, dim=-1), the same pair for the scaling) and the reads of raw_means.grad /
+ *   scaling.grad in test_initialize.py:156-158 and test_initialize_1d.py:68-71.  The arrays have the parameters' dtype:
+ *   mean_grad, scale_grad, last_* [N][d], the two norms [N] (d = 1: the norm is |x|).  An absent group's arrays are not
+ *   touched.  Parameters, moments and outputs are bit for bit those of a step without statistics.
+ *   device_counts: NULL, or 2 doubles on the device (steps counted for means, scaling; the counter of :155 / :162); it
+ *   needs hyper->device_state, and the ONE-thread launch that advances the products adds 1 to the count of each present
+ *   group.  Without a device state the caller counts.
+ * pigs_optim_step_stats: pigs_optim_step's arguments, then the statistics (not NULL).  One launch, two with a device state.
+ *
+ * d = 1 (test_no_mlp_1d.py:109-111, 189-190; test_initialize_1d.py:54-56, 75-76): parameters raw_means [N], values [N][c],
+ *   raw_scaling [N]; three groups in slots 0..2 of PigsAdamStep's arrays and of the device state (slot 3 is not used).
+ *   means = tanh(raw_means) * scale or raw_means (with the wrap), s = exp(raw_scaling), covariances = s, conics = 1 / s.
+ *   Chain rule: d raw_means = g_means * scale * sech^2(raw_means); d raw_scaling = g_covariances * s - g_conics / s (one of
+ *   the two NULL counts as zero, both NULL skip the group).  Adam, the wrap, the null-gradient rule, the running products
+ *   and the outputs of the UPDATED parameters as for d = 2.
+ * pigs_optim1d_materialize writes means, covariances, conics [N] each: one launch.
+ * pigs_optim1d_step: one launch (two with a device state); stats is NULL or as above.
+ *
+ * Refusals, before any HIP call, as for pigs_optim_step; in addition a NULL statistics array, device_counts without
+ * hyper->device_state or off 8 bytes, a NULL stats for pigs_optim_step_stats, or (d = 2) a mean_grad / scale_grad /
+ * last_* array not aligned to a row is PIGS_ERR_INVALID.
+ */
+typedef struct PigsGradStats {
+    void *mean_grad, *mean_grad_norm, *scale_grad, *scale_grad_norm, *last_mean_grad, *last_scale_grad;
+    double* device_counts;            /* [2] on the device (means, scaling), or NULL */
+} PigsGradStats;
+int pigs_optim_step_stats(int dtype, int c, int64_t N, const PigsAdamStep* hyper, void* raw_means, void* values,
+                          void* raw_scaling, void* transform, void* exp_avg_means, void* exp_avg_values,
+                          void* exp_avg_scaling, void* exp_avg_transform, void* exp_avg_sq_means, void* exp_avg_sq_values,
+                          void* exp_avg_sq_scaling, void* exp_avg_sq_transform, const void* g_means, const void* g_values,
+                          const void* g_covariances, const void* g_conics, void* means, void* covariances, void* conics,
+                          const PigsGradStats* stats, void* stream);
+int pigs_optim1d_materialize(int dtype, int means_map, int64_t N, double scale, const void* raw_means,
+                             const void* raw_scaling, void* means, void* covariances, void* conics, void* stream);
+int pigs_optim1d_step(int dtype, int c, int64_t N, const PigsAdamStep* hyper, void* raw_means, void* values,
+                      void* raw_scaling, void* exp_avg_means, void* exp_avg_values, void* exp_avg_scaling,
+                      void* exp_avg_sq_means, void* exp_avg_sq_values, void* exp_avg_sq_scaling, const void* g_means,
+                      const void* g_values, const void* g_covariances, const void* g_conics, void* means, void* covariances,
+                      void* conics, const PigsGradStats* stats, void* stream);
+
+/*
  * The model's state update: the dynamics network's deltas applied to the Gaussians, the next covariances and the
  * conservation penalty (additive to ABI 10: the number does not change).  d = 2, c = 1..4, float32 / float64.
  * Replaces, per time step of the loop with the network (main_pn.py:171-232 driving model_pn.Model):

@@ -14,7 +14,9 @@ Public surface:
     split_mask              the quantile rule alone (:733-754), from the three sampled fields
     threshold_mask          score > mean + k std, the rule of test_no_mlp.py:203-205
     GaussianAdam            the Gaussians' parameterisation, its backward and Adam in one launch per step
-                            (pigs_amd.optim; test_no_mlp.py:99-104, 146, 185-186, test_initialize.py:172-180)
+                            (pigs_amd.optim; test_no_mlp.py:99-104, 146, 185-186, test_initialize.py:172-180); with
+                            ``grad_stats=True`` also the densification's gradient sums (test_no_mlp.py:149-155)
+    GaussianAdam1D          the same for d = 1 (test_no_mlp_1d.py:109-111, 156-162, 189-190)
     advance_gaussians       the dynamics network's deltas applied to the Gaussians, the next covariances and the
                             conservation penalty in two launches, one for the backward (pigs_amd.advance;
                             model_pn.py:270-273, 677-698, 878-882)
@@ -58,9 +60,9 @@ def __getattr__(name):
     if name in ("split_gaussians", "refine_index", "split_mask", "threshold_mask", "split_criterion"):
         from . import refine
         return getattr(refine, name)
-    if name == "GaussianAdam":
-        from .optim import GaussianAdam
-        return GaussianAdam
+    if name in ("GaussianAdam", "GaussianAdam1D"):
+        from . import optim
+        return getattr(optim, name)
     if name in ("advance_gaussians", "ADVANCE_PENALTY_COLUMNS"):
         from . import advance
         return getattr(advance, name)

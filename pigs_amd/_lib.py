@@ -93,6 +93,15 @@ class PigsAdamStep(ctypes.Structure):
 
 _adam_p = ctypes.POINTER(PigsAdamStep)
 
+
+class PigsGradStats(ctypes.Structure):
+    """struct PigsGradStats of include/pigs_amd.h (the optimiser's six statistic arrays and its device counts)"""
+    _fields_ = [("mean_grad", _vp), ("mean_grad_norm", _vp), ("scale_grad", _vp), ("scale_grad_norm", _vp),
+                ("last_mean_grad", _vp), ("last_scale_grad", _vp), ("device_counts", _vp)]
+
+
+_stats_p = ctypes.POINTER(PigsGradStats)
+
 # name -> (restype, argtypes); must list every symbol include/pigs_amd.h declares
 SIGNATURES = {
     "pigs_abi_version": (_i, []),
@@ -186,6 +195,10 @@ SIGNATURES = {
     # the optimiser (additive to ABI 10): parameters, outputs / hyper, parameters, moments, gradients, outputs
     "pigs_optim_materialize": (_i, [_i, _i, _i64, ctypes.c_double] + [_vp] * 3 + [_vp] * 3 + [_vp]),
     "pigs_optim_step": (_i, [_i, _i, _i64, _adam_p] + [_vp] * 4 + [_vp] * 8 + [_vp] * 4 + [_vp] * 3 + [_vp]),
+    # its gradient statistics and its d = 1 form (additive to ABI 10): + stats / three groups, stats or NULL
+    "pigs_optim_step_stats": (_i, [_i, _i, _i64, _adam_p] + [_vp] * 4 + [_vp] * 8 + [_vp] * 4 + [_vp] * 3 + [_stats_p, _vp]),
+    "pigs_optim1d_materialize": (_i, [_i, _i, _i64, ctypes.c_double] + [_vp] * 2 + [_vp] * 3 + [_vp]),
+    "pigs_optim1d_step": (_i, [_i, _i, _i64, _adam_p] + [_vp] * 3 + [_vp] * 6 + [_vp] * 4 + [_vp] * 3 + [_stats_p, _vp]),
     # the model's state update (additive to ABI 10): wrap, state, deltas, mask, scratch, the nine outputs /
     # saved arrays, mask, scratch, the nine incoming gradients, the five gradients
     "pigs_advance_scratch_bytes": (ctypes.c_size_t, [_i64]),

@@ -652,16 +652,30 @@ int pigs_optim_materialize(int dtype, int means_map, int64_t N, double scale, co
                              covariances, conics, (hipStream_t)stream);
 }
 
-int pigs_optim_step(int dtype, int c, int64_t N, const PigsAdamStep* hyper, void* raw_means, void* values,
-                    void* raw_scaling, void* transform, void* exp_avg_means, void* exp_avg_values, void* exp_avg_scaling,
-                    void* exp_avg_transform, void* exp_avg_sq_means, void* exp_avg_sq_values, void* exp_avg_sq_scaling,
-                    void* exp_avg_sq_transform, const void* g_means, const void* g_values, const void* g_covariances,
-                    const void* g_conics, void* means, void* covariances, void* conics, void* stream) {
+// the statistics' arrays: all six, the [N][2] ones aligned to a row when d = 2; device counts only with a device state
+static int optim_stats_ok(const PigsGradStats* s, const PigsAdamStep* hyper, int dtype, bool rows_of_two) {
+    if (!s->mean_grad || !s->mean_grad_norm || !s->scale_grad || !s->scale_grad_norm || !s->last_mean_grad ||
+        !s->last_scale_grad)
+        return PIGS_ERR_INVALID;
+    if (s->device_counts && !hyper->device_state) return PIGS_ERR_INVALID;
+    if (((uintptr_t)s->device_counts & 7u) != 0) return PIGS_ERR_INVALID;
+    if (rows_of_two && (refine_misaligned(s->mean_grad, dtype) || refine_misaligned(s->scale_grad, dtype) ||
+                        refine_misaligned(s->last_mean_grad, dtype) || refine_misaligned(s->last_scale_grad, dtype)))
+        return PIGS_ERR_INVALID;
+    return PIGS_OK;
+}
+
+static int optim_step_checked(int dtype, int c, int64_t N, const PigsAdamStep* hyper, void* raw_means, void* values,
+                              void* raw_scaling, void* transform, void* exp_avg_means, void* exp_avg_values,
+                              void* exp_avg_scaling, void* exp_avg_transform, void* exp_avg_sq_means, void* exp_avg_sq_values,
+                              void* exp_avg_sq_scaling, void* exp_avg_sq_transform, const void* g_means, const void* g_values,
+                              const void* g_covariances, const void* g_conics, void* means, void* covariances, void* conics,
+                              const PigsGradStats* stats, void* stream) {
     if (!hyper) return PIGS_ERR_INVALID;
     const int rc = optim_sizes_ok(dtype, hyper->means_map, c, N);
     if (rc != PIGS_OK) return rc;
     OptimStep o{};
-    o.dtype = dtype; o.c = c; o.N = N; o.hyper = hyper;
+    o.dtype = dtype; o.c = c; o.N = N; o.hyper = hyper; o.stats = stats;
     o.params[0] = raw_means; o.params[1] = values; o.params[2] = raw_scaling; o.params[3] = transform;
     o.exp_avg[0] = exp_avg_means; o.exp_avg[1] = exp_avg_values; o.exp_avg[2] = exp_avg_scaling;
     o.exp_avg[3] = exp_avg_transform;
@@ -678,7 +692,70 @@ int pigs_optim_step(int dtype, int c, int64_t N, const PigsAdamStep* hyper, void
             refine_misaligned(o.exp_avg_sq[g], dtype))
             return PIGS_ERR_INVALID;
     if (refine_misaligned(g_means, dtype) || refine_misaligned(means, dtype)) return PIGS_ERR_INVALID;
+    if (stats) {
+        const int ok = optim_stats_ok(stats, hyper, dtype, true);
+        if (ok != PIGS_OK) return ok;
+    }
     return optim_step(o, (hipStream_t)stream);
+}
+
+int pigs_optim_step(int dtype, int c, int64_t N, const PigsAdamStep* hyper, void* raw_means, void* values,
+                    void* raw_scaling, void* transform, void* exp_avg_means, void* exp_avg_values, void* exp_avg_scaling,
+                    void* exp_avg_transform, void* exp_avg_sq_means, void* exp_avg_sq_values, void* exp_avg_sq_scaling,
+                    void* exp_avg_sq_transform, const void* g_means, const void* g_values, const void* g_covariances,
+                    const void* g_conics, void* means, void* covariances, void* conics, void* stream) {
+    return optim_step_checked(dtype, c, N, hyper, raw_means, values, raw_scaling, transform, exp_avg_means, exp_avg_values,
+                              exp_avg_scaling, exp_avg_transform, exp_avg_sq_means, exp_avg_sq_values, exp_avg_sq_scaling,
+                              exp_avg_sq_transform, g_means, g_values, g_covariances, g_conics, means, covariances, conics,
+                              nullptr, stream);
+}
+
+int pigs_optim_step_stats(int dtype, int c, int64_t N, const PigsAdamStep* hyper, void* raw_means, void* values,
+                          void* raw_scaling, void* transform, void* exp_avg_means, void* exp_avg_values,
+                          void* exp_avg_scaling, void* exp_avg_transform, void* exp_avg_sq_means, void* exp_avg_sq_values,
+                          void* exp_avg_sq_scaling, void* exp_avg_sq_transform, const void* g_means, const void* g_values,
+                          const void* g_covariances, const void* g_conics, void* means, void* covariances, void* conics,
+                          const PigsGradStats* stats, void* stream) {
+    if (!stats) return PIGS_ERR_INVALID;
+    return optim_step_checked(dtype, c, N, hyper, raw_means, values, raw_scaling, transform, exp_avg_means, exp_avg_values,
+                              exp_avg_scaling, exp_avg_transform, exp_avg_sq_means, exp_avg_sq_values, exp_avg_sq_scaling,
+                              exp_avg_sq_transform, g_means, g_values, g_covariances, g_conics, means, covariances, conics,
+                              stats, stream);
+}
+
+int pigs_optim1d_materialize(int dtype, int means_map, int64_t N, double scale, const void* raw_means,
+                             const void* raw_scaling, void* means, void* covariances, void* conics, void* stream) {
+    const int rc = optim_sizes_ok(dtype, means_map, 1, N);
+    if (rc != PIGS_OK) return rc;
+    if (!raw_means || !raw_scaling || !means || !covariances || !conics) return PIGS_ERR_INVALID;
+    return optim1d_materialize(dtype, N, means_map == PIGS_OPTIM_MEANS_TANH, scale, raw_means, raw_scaling, means,
+                               covariances, conics, (hipStream_t)stream);
+}
+
+int pigs_optim1d_step(int dtype, int c, int64_t N, const PigsAdamStep* hyper, void* raw_means, void* values,
+                      void* raw_scaling, void* exp_avg_means, void* exp_avg_values, void* exp_avg_scaling,
+                      void* exp_avg_sq_means, void* exp_avg_sq_values, void* exp_avg_sq_scaling, const void* g_means,
+                      const void* g_values, const void* g_covariances, const void* g_conics, void* means, void* covariances,
+                      void* conics, const PigsGradStats* stats, void* stream) {
+    if (!hyper) return PIGS_ERR_INVALID;
+    const int rc = optim_sizes_ok(dtype, hyper->means_map, c, N);
+    if (rc != PIGS_OK) return rc;
+    OptimStep o{};
+    o.dtype = dtype; o.c = c; o.N = N; o.hyper = hyper; o.stats = stats;
+    o.params[0] = raw_means; o.params[1] = values; o.params[2] = raw_scaling;
+    o.exp_avg[0] = exp_avg_means; o.exp_avg[1] = exp_avg_values; o.exp_avg[2] = exp_avg_scaling;
+    o.exp_avg_sq[0] = exp_avg_sq_means; o.exp_avg_sq[1] = exp_avg_sq_values; o.exp_avg_sq[2] = exp_avg_sq_scaling;
+    o.grads[0] = g_means; o.grads[1] = g_values; o.grads[2] = g_covariances; o.grads[3] = g_conics;
+    o.out[0] = means; o.out[1] = covariances; o.out[2] = conics;
+    for (int g = 0; g < 3; ++g)
+        if (!o.params[g] || !o.exp_avg[g] || !o.exp_avg_sq[g]) return PIGS_ERR_INVALID;
+    if (!means || !covariances || !conics) return PIGS_ERR_INVALID;
+    if (!g_means && !g_values && !g_covariances && !g_conics) return PIGS_ERR_INVALID;
+    if (stats) {
+        const int ok = optim_stats_ok(stats, hyper, dtype, false);
+        if (ok != PIGS_OK) return ok;
+    }
+    return optim1d_step(o, (hipStream_t)stream);
 }
 
 size_t pigs_advance_scratch_bytes(int64_t N) { return advance_scratch_bytes(N); }

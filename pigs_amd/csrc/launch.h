@@ -90,10 +90,15 @@ struct OptimStep {
     void *params[4], *exp_avg[4], *exp_avg_sq[4];      // raw_means, values, raw_scaling, transform
     const void* grads[4];                              // d means, d values, d covariances, d conics (null = none)
     void* out[3];                                      // the next step's means, covariances, conics
+    const PigsGradStats* stats;                        // or null: no gradient statistics
 };
 int optim_materialize(int dtype, int64_t N, bool tanh_map, double scale, const void* raw_means, const void* raw_scaling,
                       const void* transform, void* o_means, void* o_cov, void* o_conic, hipStream_t stream);
 int optim_step(const OptimStep& o, hipStream_t stream);
+// d = 1: slots 0..2 of the arrays are raw_means, values, raw_scaling; slot 3 is not read
+int optim1d_materialize(int dtype, int64_t N, bool tanh_map, double scale, const void* raw_means, const void* raw_scaling,
+                        void* o_means, void* o_cov, void* o_conic, hipStream_t stream);
+int optim1d_step(const OptimStep& o, hipStream_t stream);
 
 // advance.hip
 struct AdvanceStep {

@@ -31,7 +31,25 @@ the device, written in place between replays); the two modes give bit-identical 
 means, covariances and conics live in three static buffers (a graph replay must read what the replay before it wrote)
 and ``gaussians()`` returns fresh leaves over them; otherwise every step writes fresh tensors.
 
-d = 2, c = 1..4, float32 / float64, GPU tensors only, no CPU fallback.  weight_decay, amsgrad and maximize are not built.
+``grad_stats=True`` keeps, in the same launch (C ABI: pigs_optim_step_stats), what the reference's densification reads
+from ``raw_means.grad`` and ``scaling.grad`` (test_no_mlp.py:149-155, 203-205; test_no_mlp_1d.py:156-162, 215-222), which
+here exist only in the kernel's registers.  With G the gradient of a raw parameter as Adam consumes it, per step and for
+a group whose gradient is present:  last = G,  sum += G,  norm += ||sum||_2 per row (of the sum AFTER adding):
+
+    opt.grad_stats           GradStats(mean_grad, mean_grad_norm, scale_grad, scale_grad_norm, last_mean_grad,
+                             last_scale_grad): live buffers in the parameters' dtype, updated in place by step()
+    opt.grad_counts          {"means": n, "scaling": n}: steps accumulated (capturable mode: a device read)
+    opt.reset_grad_stats()   zero the sums and the counts, in place (the reference starts after its warm-up, :149)
+    opt.refine(source, child, shift_means=None)   the statistics restart as zeros of the new row count (:249-252);
+                             ``shift_means [N_old, d]``: a row with child >= 0 gets raw_means[source] + shift_means[source],
+                             the ``+ split_dir`` of test_no_mlp_1d.py:219-222
+
+``GaussianAdam1D(raw_means [N,1], values [N,c], raw_scaling [N,1], ...)`` is the same for d = 1 (test_no_mlp_1d.py:109-111,
+test_initialize_1d.py:54-56; C ABI: pigs_optim1d_materialize, pigs_optim1d_step): three groups (means, values, scaling),
+s = exp(raw_scaling), covariances = s, conics = 1 / s, all leaves [N,1].
+
+GaussianAdam: d = 2; GaussianAdam1D: d = 1.  c = 1..4, float32 / float64, GPU tensors only, no CPU fallback.
+weight_decay, amsgrad and maximize are not built.
 """
 import collections
 import ctypes
@@ -44,7 +62,12 @@ from ._lib import DTYPES as _DTYPES, ptr as _ptr, stream as _stream
 MEANS_MAPS = {"tanh": 0, "identity": 1}
 GROUPS = ("means", "values", "scaling", "transform")
 
+GROUPS_1D = ("means", "values", "scaling")
+STAT_GROUPS = ("means", "scaling")
+
 Gaussians = collections.namedtuple("Gaussians", "means values covariances conics")
+GradStats = collections.namedtuple("GradStats", "mean_grad mean_grad_norm scale_grad scale_grad_norm last_mean_grad "
+                                                "last_scale_grad")
 
 
 def _check(raw_means, values, raw_scaling, transform):
@@ -81,7 +104,35 @@ def _check(raw_means, values, raw_scaling, transform):
             raise ValueError(f"{n} must be aligned to a row ({2 * a.element_size()} bytes): it is updated in place")
 
 
-def _rates(lr):
+def _check_1d(raw_means, values, raw_scaling):
+    names = ("raw_means", "values", "raw_scaling")
+    arrays = (raw_means, values, raw_scaling)
+    for n, a in zip(names, arrays):
+        if not isinstance(a, torch.Tensor):
+            raise TypeError(f"{n} must be a torch.Tensor")
+    for n, a in ((names[0], raw_means), (names[2], raw_scaling)):
+        if a.dim() != 2 or a.shape[1] != 1:
+            raise NotImplementedError(f"{n} must be [N, 1] (d = 1; GaussianAdam is d = 2), got {tuple(a.shape)}")
+    N = raw_means.shape[0]
+    if N < 1:
+        raise ValueError("no Gaussians: N must be at least 1")
+    if values.dim() != 2 or not 1 <= values.shape[1] <= 4:
+        raise NotImplementedError(f"values must be [N, c] with c = 1..4, got {tuple(values.shape)}")
+    for n, a in zip(names[1:], arrays[1:]):
+        if a.shape[0] != N:
+            raise ValueError(f"{n} holds {a.shape[0]} rows, raw_means {N}")
+    if raw_means.dtype not in _DTYPES or any(a.dtype != raw_means.dtype for a in arrays):
+        raise TypeError(f"dtypes {[str(a.dtype) for a in arrays]}: float32 or float64, all alike")
+    for n, a in zip(names, arrays):
+        if not a.is_cuda or a.device != raw_means.device:
+            raise RuntimeError(f"{n} is on {a.device}" + (f", raw_means on {raw_means.device}" if a is not raw_means else "")
+                               + ": the optimiser runs on one GPU (no CPU fallback)")
+    for n, a in zip(names, arrays):
+        if not a.is_contiguous():
+            raise ValueError(f"{n} must be contiguous: it is updated in place")
+
+
+def _rates(lr, GROUPS=GROUPS):
     if isinstance(lr, dict):
         if set(lr) != set(GROUPS):
             raise ValueError(f"lr as a dict needs exactly the keys {GROUPS}, got {sorted(lr)}")
@@ -94,24 +145,39 @@ def _rates(lr):
     return out
 
 
-def follow_maps(param, exp_avg, exp_avg_sq, source, child):
+def follow_maps(param, exp_avg, exp_avg_sq, source, child, shift=None):
     """One group through ``pigs_amd.refine``'s maps (test_no_mlp.py:218-240): the parameter and its two moments
-    ``index_select``-ed by ``source``, the moments of the rows with ``child >= 0`` zeroed.  Torch ops, any device."""
+    ``index_select``-ed by ``source``, the moments of the rows with ``child >= 0`` zeroed.  With ``shift`` (of the old
+    parameter's shape) a row with ``child >= 0`` is ``param[source] + shift[source]`` (test_no_mlp_1d.py:219-222).
+    Torch ops, any device."""
     with torch.no_grad():
         fresh = (child >= 0).reshape((-1,) + (1,) * (param.dim() - 1))
         moments = []
         for m in (exp_avg, exp_avg_sq):
             carried = m.index_select(0, source)
             moments.append(torch.where(fresh, torch.zeros_like(carried), carried))
-        return param.detach().index_select(0, source), moments[0], moments[1]
+        new = param.detach().index_select(0, source)
+        if shift is not None:
+            new = torch.where(fresh, new + shift.detach().index_select(0, source), new)
+        return new, moments[0], moments[1]
 
 
 class GaussianAdam:
     """Adam over (raw_means [N,2], values [N,c], raw_scaling [N,2], transform [N,1] or [N]); see the module text.
     The four tensors (plain or nn.Parameter) are updated in place."""
 
+    GROUPS = GROUPS
+    _WIDTHS = (2, 3, 3)               # means, covariances, conics
+    _ROWS_OF_TWO = True
+
     def __init__(self, raw_means, values, raw_scaling, transform, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, *,
-                 means_map="tanh", scale=1.0, wrap=None, capturable=False, weight_decay=0, amsgrad=False, maximize=False):
+                 means_map="tanh", scale=1.0, wrap=None, capturable=False, grad_stats=False, weight_decay=0, amsgrad=False,
+                 maximize=False):
+        self._setup((raw_means, values, raw_scaling, transform), lr, betas, eps, means_map, scale, wrap, capturable,
+                    grad_stats, weight_decay, amsgrad, maximize)
+
+    def _setup(self, params, lr, betas, eps, means_map, scale, wrap, capturable, grad_stats, weight_decay, amsgrad, maximize):
+        GROUPS = self.GROUPS
         if weight_decay != 0 or amsgrad or maximize:
             raise NotImplementedError("weight_decay, amsgrad and maximize are not built")
         if means_map not in MEANS_MAPS:
@@ -128,73 +194,132 @@ class GaussianAdam:
             raise ValueError(f"betas = {betas}: each in [0, 1)")
         if not float(eps) >= 0.0:
             raise ValueError(f"eps = {eps}: not negative")
-        rates = _rates(lr)
-        _check(raw_means, values, raw_scaling, transform)
+        rates = _rates(lr, GROUPS)
+        self._check_params(*params)
         _lib.load()
-        self.raw_means, self.values, self.raw_scaling, self.transform = raw_means, values, raw_scaling, transform
+        self._set_params(params)
         self.means_map, self.scale, self.wrap = means_map, float(scale), wrap
         self.betas, self.eps, self.capturable = (beta1, beta2), float(eps), bool(capturable)
         self._lr = rates
-        self.device, self.dtype = raw_means.device, raw_means.dtype
-        self.lr_tensor = self.state_tensor = None
+        self.device, self.dtype = self.raw_means.device, self.raw_means.dtype
+        self.lr_tensor = self.state_tensor = self.counts_tensor = None
         if self.capturable:
-            self.lr_tensor = torch.tensor([self._lr[g] for g in GROUPS], dtype=torch.float64, device=self.device)
+            self.lr_tensor = torch.tensor(self._four(self._lr, 0.0), dtype=torch.float64, device=self.device)
             # beta1^t [4], beta2^t [4], step counts [4]
             self.state_tensor = torch.tensor([1.0] * 8 + [0.0] * 4, dtype=torch.float64, device=self.device)
         self._steps = {g: 0 for g in GROUPS}
         self._pow1 = {g: 1.0 for g in GROUPS}
         self._pow2 = {g: 1.0 for g in GROUPS}
         self._zero_moments()
+        self._stats = None        # GradStats, with grad_stats=True
+        self._stat_counts = {g: 0 for g in STAT_GROUPS}
+        if grad_stats:
+            self._stats = self._zero_stats()
+            if self.capturable:   # steps accumulated for means, scaling: advanced by the one-thread launch
+                self.counts_tensor = torch.zeros(2, dtype=torch.float64, device=self.device)
         self._static = None       # capturable: the three buffers every step writes
         self._next = None         # (means, covariances, conics) of the current parameters, or None: materialise
         self._leaves = None       # what gaussians() handed out and step() reads the gradients of
 
+    _check_params = staticmethod(_check)
+
+    def _four(self, per_group, pad):
+        """a per-group dict as the four slots of the C ABI's arrays (d = 1 leaves the last one unused)"""
+        return [per_group[g] for g in self.GROUPS] + [pad] * (4 - len(self.GROUPS))
+
     # ---- state ------------------------------------------------------------------------------------------------
+    def _set_params(self, params):
+        self.raw_means, self.values, self.raw_scaling, self.transform = params
+
     def _params(self):
         return (self.raw_means, self.values, self.raw_scaling, self.transform)
 
     def _zero_moments(self):
-        self.exp_avg = {g: torch.zeros_like(p, requires_grad=False) for g, p in zip(GROUPS, self._params())}
-        self.exp_avg_sq = {g: torch.zeros_like(p, requires_grad=False) for g, p in zip(GROUPS, self._params())}
+        self.exp_avg = {g: torch.zeros_like(p, requires_grad=False) for g, p in zip(self.GROUPS, self._params())}
+        self.exp_avg_sq = {g: torch.zeros_like(p, requires_grad=False) for g, p in zip(self.GROUPS, self._params())}
+
+    def _zero_stats(self):
+        N, d = self.raw_means.shape
+        rows = lambda: torch.zeros((N, d), dtype=self.dtype, device=self.device)
+        norm = lambda: torch.zeros(N, dtype=self.dtype, device=self.device)
+        return GradStats(rows(), norm(), rows(), norm(), rows(), rows())
 
     @property
     def lr(self):
-        """The four rates, a dict over GROUPS; assign a float or a dict.  Host mode reads it at every step (entries may
+        """The rates, a dict over the groups; assign a float or a dict.  Host mode reads it at every step (entries may
         be changed in place); the capturable mode reads ``lr_tensor``, which an assignment rewrites."""
         return self._lr
 
     @lr.setter
     def lr(self, lr):
-        self._lr = _rates(lr)
+        self._lr = _rates(lr, self.GROUPS)
         if self.capturable:
-            self.lr_tensor.copy_(torch.tensor([self._lr[g] for g in GROUPS], dtype=torch.float64))
+            self.lr_tensor.copy_(torch.tensor(self._four(self._lr, 0.0), dtype=torch.float64))
 
     @property
     def steps(self):
         """Steps taken per group (a group whose gradient was None did not step).  Capturable mode: a device read."""
         if self.capturable:
             counts = self.state_tensor[8:].tolist()
-            return {g: int(n) for g, n in zip(GROUPS, counts)}
+            return {g: int(n) for g, n in zip(self.GROUPS, counts)}
         return dict(self._steps)
 
+    def _need_stats(self):
+        if self._stats is None:
+            raise RuntimeError("this optimiser keeps no gradient statistics: construct it with grad_stats=True")
+
+    @property
+    def grad_stats(self):
+        """GradStats(mean_grad, mean_grad_norm, scale_grad, scale_grad_norm, last_mean_grad, last_scale_grad): the live
+        buffers ``step()`` updates in place (replaced by ``refine`` alone)."""
+        self._need_stats()
+        return self._stats
+
+    @property
+    def grad_counts(self):
+        """Steps accumulated since the last reset, {"means": n, "scaling": n}.  Capturable mode: a device read."""
+        self._need_stats()
+        if self.capturable:
+            return {g: int(n) for g, n in zip(STAT_GROUPS, self.counts_tensor.tolist())}
+        return dict(self._stat_counts)
+
+    def reset_grad_stats(self):
+        """Zero the sums, the last gradients and the counts, in place (capturable: launches that a graph may hold)."""
+        self._need_stats()
+        for t in self._stats:
+            t.zero_()
+        self._stat_counts = {g: 0 for g in STAT_GROUPS}
+        if self.capturable:
+            self.counts_tensor.zero_()
+
     def state_dict(self):
-        """This class's own layout: counts and running products per group, clones of the eight moments, the rates."""
+        """This class's own layout: counts and running products per group, clones of the moments, the rates; with
+        ``grad_stats`` the statistics and their counts under "grad_stats"."""
+        GROUPS = self.GROUPS
         if self.capturable:
             host = self.state_tensor.tolist()
             pow1, pow2 = dict(zip(GROUPS, host[:4])), dict(zip(GROUPS, host[4:8]))
             lr = dict(zip(GROUPS, self.lr_tensor.tolist()))
         else:
             pow1, pow2, lr = dict(self._pow1), dict(self._pow2), dict(self._lr)
-        return {"step": self.steps, "beta1_pow": pow1, "beta2_pow": pow2, "lr": lr, "betas": self.betas, "eps": self.eps,
-                "exp_avg": {g: t.clone() for g, t in self.exp_avg.items()},
-                "exp_avg_sq": {g: t.clone() for g, t in self.exp_avg_sq.items()}}
+        out = {"step": self.steps, "beta1_pow": pow1, "beta2_pow": pow2, "lr": lr, "betas": self.betas, "eps": self.eps,
+               "exp_avg": {g: t.clone() for g, t in self.exp_avg.items()},
+               "exp_avg_sq": {g: t.clone() for g, t in self.exp_avg_sq.items()}}
+        if self._stats is not None:
+            out["grad_stats"] = dict({k: t.clone() for k, t in self._stats._asdict().items()}, counts=self.grad_counts)
+        return out
 
     def load_state_dict(self, state):
+        GROUPS = self.GROUPS
         for key in ("exp_avg", "exp_avg_sq"):
             for g, p in zip(GROUPS, self._params()):
                 t = state[key][g]
                 if t.shape != p.shape:
                     raise ValueError(f"{key}[{g!r}] is {tuple(t.shape)}, the parameter {tuple(p.shape)}")
+        if self._stats is not None and "grad_stats" in state:
+            for k, mine in self._stats._asdict().items():
+                if state["grad_stats"][k].shape != mine.shape:
+                    raise ValueError(f"grad_stats[{k!r}] is {tuple(state['grad_stats'][k].shape)}, here {tuple(mine.shape)}")
         self.exp_avg = {g: state["exp_avg"][g].to(device=self.device, dtype=self.dtype, copy=True).contiguous()
                            for g in GROUPS}
         self.exp_avg_sq = {g: state["exp_avg_sq"][g].to(device=self.device, dtype=self.dtype, copy=True).contiguous()
@@ -204,9 +329,18 @@ class GaussianAdam:
         self._pow1 = {g: float(state["beta1_pow"][g]) for g in GROUPS}
         self._pow2 = {g: float(state["beta2_pow"][g]) for g in GROUPS}
         if self.capturable:
-            host = [self._pow1[g] for g in GROUPS] + [self._pow2[g] for g in GROUPS] + [float(self._steps[g]) for g in GROUPS]
+            host = self._four(self._pow1, 1.0) + self._four(self._pow2, 1.0) + self._four(self._steps, 0.0)
             self.state_tensor.copy_(torch.tensor(host, dtype=torch.float64))
         self.lr = state["lr"]
+        if self._stats is not None:
+            self.reset_grad_stats()               # a dict without the key: zeros
+            if "grad_stats" in state:
+                for k, mine in self._stats._asdict().items():
+                    mine.copy_(state["grad_stats"][k])
+                self._stat_counts = {g: int(state["grad_stats"]["counts"][g]) for g in STAT_GROUPS}
+                if self.capturable:
+                    self.counts_tensor.copy_(torch.tensor([float(self._stat_counts[g]) for g in STAT_GROUPS],
+                                                          dtype=torch.float64))
         self._next = self._leaves = None          # the parameters may have been reloaded too: materialise again
 
     # ---- the Gaussians ----------------------------------------------------------------------------------------
@@ -214,25 +348,28 @@ class GaussianAdam:
         N = self.raw_means.shape[0]
         if self.capturable:
             if self._static is None or self._static[0].shape[0] != N:
-                self._static = tuple(torch.empty((N, w), dtype=self.dtype, device=self.device) for w in (2, 3, 3))
+                self._static = tuple(torch.empty((N, w), dtype=self.dtype, device=self.device) for w in self._WIDTHS)
             return self._static
-        return tuple(torch.empty((N, w), dtype=self.dtype, device=self.device) for w in (2, 3, 3))
+        return tuple(torch.empty((N, w), dtype=self.dtype, device=self.device) for w in self._WIDTHS)
+
+    def _call_materialize(self, lib, outs):
+        rc = lib.pigs_optim_materialize(_DTYPES[self.dtype], MEANS_MAPS[self.means_map], self.raw_means.shape[0],
+                                        self.scale, _ptr(self.raw_means), _ptr(self.raw_scaling), _ptr(self.transform),
+                                        *[_ptr(o) for o in outs], _stream(self.device))
+        _lib.check(rc, "pigs_optim_materialize")
 
     def _materialize(self):
         lib = _lib.load()
         outs = self._outputs()
         with torch.cuda.device(self.device):
-            rc = lib.pigs_optim_materialize(_DTYPES[self.dtype], MEANS_MAPS[self.means_map], self.raw_means.shape[0],
-                                            self.scale, _ptr(self.raw_means), _ptr(self.raw_scaling), _ptr(self.transform),
-                                            *[_ptr(o) for o in outs], _stream(self.device))
-        _lib.check(rc, "pigs_optim_materialize")
+            self._call_materialize(lib, outs)
         for o in outs:
             torch.autograd.graph.increment_version(o)
         return outs
 
     def gaussians(self):
-        """(means [N,2], values [N,c], covariances [N,3], conics [N,3]): leaves that require grad.  ``values`` shares
-        the parameter's storage.  Launches nothing after a ``step()``; the same leaves until the next ``step()``."""
+        """(means [N,d], values [N,c], covariances, conics ([N,3]; d = 1: [N,1])): leaves that require grad.  ``values``
+        shares the parameter's storage.  Launches nothing after a ``step()``; the same leaves until the next ``step()``."""
         if self._leaves is not None:
             return self._leaves
         if self._next is None:
@@ -253,17 +390,36 @@ class GaussianAdam:
             g = g.clone()
         return g
 
+    def _stats_struct(self):
+        s = _lib.PigsGradStats()
+        for k, t in self._stats._asdict().items():
+            setattr(s, k, t.data_ptr())
+        if self.capturable:
+            s.device_counts = self.counts_tensor.data_ptr()
+        return s
+
+    def _call_step(self, lib, h, grads, outs):
+        args = (_DTYPES[self.dtype], self.values.shape[1], self.raw_means.shape[0], ctypes.byref(h),
+                *[_ptr(p) for p in self._params()], *[_ptr(self.exp_avg[g]) for g in GROUPS],
+                *[_ptr(self.exp_avg_sq[g]) for g in GROUPS], *[_ptr(g) for g in grads], *[_ptr(o) for o in outs])
+        if self._stats is None:
+            _lib.check(lib.pigs_optim_step(*args, _stream(self.device)), "pigs_optim_step")
+        else:
+            s = self._stats_struct()
+            _lib.check(lib.pigs_optim_step_stats(*args, ctypes.byref(s), _stream(self.device)), "pigs_optim_step_stats")
+
     def step(self):
-        """One launch (two with ``capturable=True``): chain rule, Adam, wrap, the next step's Gaussians."""
+        """One launch (two with ``capturable=True``): chain rule, Adam, wrap, the statistics, the next step's Gaussians."""
         if self._leaves is None:
             raise RuntimeError("step() without gaussians(): the gradients are read from the leaves it returns")
+        GROUPS = self.GROUPS
         leaves = self._leaves
-        grads = (self._grad(leaves.means, True), self._grad(leaves.values), self._grad(leaves.covariances),
+        grads = (self._grad(leaves.means, self._ROWS_OF_TWO), self._grad(leaves.values), self._grad(leaves.covariances),
                  self._grad(leaves.conics))
         if all(g is None for g in grads):
             return                # as torch.optim.Adam with no gradient anywhere: nothing moves, nothing is launched
         present = (grads[0] is not None, grads[1] is not None, grads[2] is not None or grads[3] is not None)
-        present = dict(zip(GROUPS, present + (present[2],)))
+        present = dict(zip(GROUPS, present + (present[2],)))      # the transform (d = 2) goes with the scaling
         lib = _lib.load()
         h = _lib.PigsAdamStep()
         h.beta1, h.beta2, h.eps, h.scale = self.betas[0], self.betas[1], self.eps, self.scale
@@ -279,18 +435,24 @@ class GaussianAdam:
                     self._pow1[g] *= self.betas[0]
                     self._pow2[g] *= self.betas[1]
                 h.lr[k], h.beta1_pow[k], h.beta2_pow[k] = self._lr[g], self._pow1[g], self._pow2[g]
+            if self._stats is not None:
+                for g in STAT_GROUPS:
+                    self._stat_counts[g] += int(present[g])
         outs = self._outputs()
         params = self._params()
         with torch.cuda.device(self.device):
-            rc = lib.pigs_optim_step(_DTYPES[self.dtype], self.values.shape[1], self.raw_means.shape[0], ctypes.byref(h),
-                                     *[_ptr(p) for p in params], *[_ptr(self.exp_avg[g]) for g in GROUPS],
-                                     *[_ptr(self.exp_avg_sq[g]) for g in GROUPS], *[_ptr(g) for g in grads],
-                                     *[_ptr(o) for o in outs], _stream(self.device))
-        _lib.check(rc, "pigs_optim_step")
+            self._call_step(lib, h, grads, outs)
         # the writes went through raw pointers: a stale autograd node must complain as it would after torch.optim
         for g, p in zip(GROUPS, params):
             if present[g]:
                 torch.autograd.graph.increment_version(p)
+        if self._stats is not None:
+            st = self._stats
+            for g, arrays in zip(STAT_GROUPS, ((st.mean_grad, st.mean_grad_norm, st.last_mean_grad),
+                                               (st.scale_grad, st.scale_grad_norm, st.last_scale_grad))):
+                if present[g]:
+                    for t in arrays:
+                        torch.autograd.graph.increment_version(t)
         if self.capturable:
             for o in outs:
                 torch.autograd.graph.increment_version(o)
@@ -299,11 +461,14 @@ class GaussianAdam:
         self._next, self._leaves = outs, None
 
     # ---- refinement -------------------------------------------------------------------------------------------
-    def refine(self, source, child):
-        """Make the four parameters and the eight moments follow ``pigs_amd.refine``'s maps: ``index_select`` by
-        ``source``, the moments of the rows with ``child >= 0`` zeroed (test_no_mlp.py:218-240).  The parameters are
-        replaced (their row count changes) and returned, (raw_means, values, raw_scaling, transform), nn.Parameters
-        where they were; the Gaussians are materialised again at the next ``gaussians()``.  Torch ops, not capturable."""
+    def refine(self, source, child, shift_means=None):
+        """Make the parameters and their moments follow ``pigs_amd.refine``'s maps: ``index_select`` by ``source``, the
+        moments of the rows with ``child >= 0`` zeroed (test_no_mlp.py:218-240).  With ``shift_means [N_old, d]`` a row
+        with ``child >= 0`` gets ``raw_means[source] + shift_means[source]`` (the ``+ split_dir`` of
+        test_no_mlp_1d.py:219-222, test_initialize_1d.py:108-111).  The parameters are replaced (their row count changes)
+        and returned in the constructor's order, nn.Parameters where they were; the statistics restart as zeros of the
+        new row count with counts 0 (test_no_mlp.py:249-252); the Gaussians are materialised again at the next
+        ``gaussians()``.  Torch ops, not capturable."""
         if not (isinstance(source, torch.Tensor) and isinstance(child, torch.Tensor)):
             raise TypeError("source and child must be torch.Tensors (pigs_amd.refine_index)")
         if source.dim() != 1 or child.shape != source.shape:
@@ -312,10 +477,59 @@ class GaussianAdam:
             raise RuntimeError(f"source is on {source.device}, child on {child.device}, the parameters on {self.device}")
         if source.shape[0] < 1:
             raise ValueError("refine would leave no Gaussians")
+        if shift_means is not None:
+            if not isinstance(shift_means, torch.Tensor) or shift_means.shape != self.raw_means.shape:
+                raise ValueError(f"shift_means must be a tensor of raw_means' shape {tuple(self.raw_means.shape)}")
+            if shift_means.device != self.device or shift_means.dtype != self.dtype:
+                raise TypeError(f"shift_means is {shift_means.dtype} on {shift_means.device}, the parameters "
+                                f"{self.dtype} on {self.device}")
         new = []
-        for g, p in zip(GROUPS, self._params()):
-            q, self.exp_avg[g], self.exp_avg_sq[g] = follow_maps(p, self.exp_avg[g], self.exp_avg_sq[g], source, child)
+        for g, p in zip(self.GROUPS, self._params()):
+            q, self.exp_avg[g], self.exp_avg_sq[g] = follow_maps(p, self.exp_avg[g], self.exp_avg_sq[g], source, child,
+                                                                 shift_means if g == "means" else None)
             new.append(torch.nn.Parameter(q, requires_grad=p.requires_grad) if isinstance(p, torch.nn.Parameter) else q)
-        self.raw_means, self.values, self.raw_scaling, self.transform = new
+        self._set_params(new)
+        if self._stats is not None:
+            self._stats = self._zero_stats()
+            self._stat_counts = {g: 0 for g in STAT_GROUPS}
+            if self.capturable:
+                self.counts_tensor.zero_()
         self._next = self._leaves = None
         return tuple(new)
+
+
+class GaussianAdam1D(GaussianAdam):
+    """Adam over (raw_means [N,1], values [N,c], raw_scaling [N,1]): GaussianAdam for d = 1, three groups; see the module
+    text.  ``gaussians()`` returns means, covariances and conics as [N,1] leaves (reshape to [N,1,1] as the reference does
+    at test_no_mlp_1d.py:74 if wanted)."""
+
+    GROUPS = GROUPS_1D
+    _WIDTHS = (1, 1, 1)
+    _ROWS_OF_TWO = False
+    _check_params = staticmethod(_check_1d)
+
+    def __init__(self, raw_means, values, raw_scaling, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, *, means_map="tanh",
+                 scale=1.0, wrap=None, capturable=False, grad_stats=False, weight_decay=0, amsgrad=False, maximize=False):
+        self._setup((raw_means, values, raw_scaling), lr, betas, eps, means_map, scale, wrap, capturable, grad_stats,
+                    weight_decay, amsgrad, maximize)
+
+    def _set_params(self, params):
+        self.raw_means, self.values, self.raw_scaling = params
+
+    def _params(self):
+        return (self.raw_means, self.values, self.raw_scaling)
+
+    def _call_materialize(self, lib, outs):
+        rc = lib.pigs_optim1d_materialize(_DTYPES[self.dtype], MEANS_MAPS[self.means_map], self.raw_means.shape[0],
+                                          self.scale, _ptr(self.raw_means), _ptr(self.raw_scaling),
+                                          *[_ptr(o) for o in outs], _stream(self.device))
+        _lib.check(rc, "pigs_optim1d_materialize")
+
+    def _call_step(self, lib, h, grads, outs):
+        s = self._stats_struct() if self._stats is not None else None
+        rc = lib.pigs_optim1d_step(_DTYPES[self.dtype], self.values.shape[1], self.raw_means.shape[0], ctypes.byref(h),
+                                   *[_ptr(p) for p in self._params()], *[_ptr(self.exp_avg[g]) for g in GROUPS_1D],
+                                   *[_ptr(self.exp_avg_sq[g]) for g in GROUPS_1D], *[_ptr(g) for g in grads],
+                                   *[_ptr(o) for o in outs], ctypes.byref(s) if s is not None else None,
+                                   _stream(self.device))
+        _lib.check(rc, "pigs_optim1d_step")
