@@ -444,6 +444,13 @@ size_t pigs_plan_strips_offset(void);
  * Returns PIGS_ERR_UNSUPPORTED for sizes the binned path does not take (N >= 2^24 among them). */
 int pigs_plan_layout_info(int64_t N, int64_t M, int c, int64_t info[6]);
 
+/* ... and where the Gaussians' half of a plan sits (additive to ABI 10; tools and tests): info[0] = byte offset of the
+ * records in the plan's order (float4[2 N + 2]: {mux, muy, a, b}, {c, v0, v1, 0}; record N is all zero), info[1] = byte
+ * offset of the strip boxes (float4[ceil(N / 16)]: {min x, min y, max x, max y}), info[2] = byte offset of the
+ * super-strip boxes (float4[ceil(N / 256)]); both kinds of boxes are written by builds that keep the caller's order
+ * alone (pigs_plan_strips_offset).  info[3] = 0. */
+int pigs_plan_records_info(int64_t N, int64_t M, int c, int64_t info[4]);
+
 /* The same for a samples workspace (additive to ABI 10): where the points sit in the order the sampling kernels take
  * them.  info[0] = tiles (64 consecutive sorted points each, four groups of 16), info[1] = byte offset of the sorted
  * points, info[2] = bytes per sorted point ({float x, y; uint32 m}: the coordinates and the point's index in the

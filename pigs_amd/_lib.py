@@ -115,6 +115,7 @@ SIGNATURES = {
     "pigs_plan_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i]),
     "pigs_plan_layout_info": (_i, [_i64, _i64, _i, ctypes.POINTER(_i64)]),
     "pigs_samples_layout_info": (_i, [_i64, ctypes.POINTER(_i64)]),             # additive to ABI 10
+    "pigs_plan_records_info": (_i, [_i64, _i64, _i, ctypes.POINTER(_i64)]),     # additive to ABI 10
     "pigs_samples_error_offset": (ctypes.c_size_t, []),
     "pigs_plan_error_offset": (ctypes.c_size_t, []),
     "pigs_samples_lattice_offset": (ctypes.c_size_t, []),

@@ -98,6 +98,11 @@ int pigs_plan_layout_info(int64_t N, int64_t M, int c, int64_t info[6]) {
     return plan_layout_info(N, M, c, info);
 }
 
+int pigs_plan_records_info(int64_t N, int64_t M, int c, int64_t info[4]) {
+    if (!info) return PIGS_ERR_INVALID;
+    return plan_records_info(N, M, c, info);
+}
+
 int pigs_samples_layout_info(int64_t M, int64_t info[4]) {
     if (!info) return PIGS_ERR_INVALID;
     return samples_layout_info(M, info);

@@ -221,6 +221,7 @@ int plan_forward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, f
 int plan_backward(void* ws, size_t ws_bytes, const void* sws, size_t sws_bytes, float q_max, const SampleArgs& a,
                   hipStream_t stream);
 int plan_layout_info(int64_t N, int64_t M, int c, int64_t* info);
+int plan_records_info(int64_t N, int64_t M, int c, int64_t* info);
 int samples_layout_info(int64_t M, int64_t* info);
 // the Gaussian grid alone (aggregate.hip): plan.hip
 size_t aggregate_grid_bytes(int64_t N);

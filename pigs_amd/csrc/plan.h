@@ -467,6 +467,23 @@ struct PlanView {
     float4* stage;
 };
 
+// The list launch's store of what the NEXT launch reads (tile headers, tile lists, group lists).  through: the word is
+// written through to memory as it is issued and the line stays in the L2 that took it -- `sc0 sc1` on a plain vector
+// store, never `nt` (which gives the line up: the reader would miss) -- so the launch's end finds no dirty lines of
+// these arrays to write back; !through: the plain cacheable store.  Same address, same value either way.  A
+// system-scope relaxed atomic store, `global_store_dword ... sc0 sc1` in the ISA (as stats_home, plan_lists.h).  The
+// caller is the only writer of the address within its launch and nothing in the launch reads it back.
+// PIGS_STORE_THROUGH (plan.hip) chooses; the argument is a compile-time constant where it is called.  Array and index
+// apart, as the plain `a[i] = v` has them: handed a finished pointer, the list launch formed every address in 64-bit
+// scalar adds and spilled more scalar registers for it (+345 instructions in plan_lists_kernel<4, true, true>).
+// (A float4 form, one `global_store_dwordx4 ... sc0 sc1` by inline assembly, served the strips pack: slower by the bench
+// line, taken out with it -- DESIGN.md section 3.3.)
+template <typename I>
+__device__ __forceinline__ void store_through(uint32_t* a, I i, uint32_t v, bool through) {
+    if (through) __hip_atomic_store(&a[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    else a[i] = v;
+}
+
 // ---- grid geometry derived (identically by every thread) from the sample bounding box ----
 
 // box = {min x, min y, max x, max y}; min > max (+-inf) when there were no finite points.

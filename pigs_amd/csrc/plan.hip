@@ -85,6 +85,13 @@ int plan_layout_info(int64_t N, int64_t M, int c, int64_t* info) {
     return PIGS_OK;
 }
 
+int plan_records_info(int64_t N, int64_t M, int c, int64_t* info) {
+    if (!plan_supported(N, M, c)) return PIGS_ERR_UNSUPPORTED;
+    const PlanLayout p = make_plan_layout(N, M, c);
+    info[0] = (int64_t)p.off_rec; info[1] = (int64_t)p.off_pbox; info[2] = (int64_t)p.off_sbox; info[3] = 0;
+    return PIGS_OK;
+}
+
 int samples_layout_info(int64_t M, int64_t* info) {
     if (!samples_supported(M)) return PIGS_ERR_UNSUPPORTED;
     const SamplesLayout s = make_samples_layout(M);
@@ -141,6 +148,14 @@ static int samples_order_setting() {      // PIGS_SAMPLES_ORDER
 // Read at every build like the others; it steers no launch choice, so it rides in ListArgs, not in BuildEnv.
 static uint32_t lists_product_setting() {
     const char* e = getenv("PIGS_LISTS_PRODUCT");
+    return e && e[0] == '0' ? 0u : 1u;
+}
+// PIGS_STORE_THROUGH=0: no list launch sends its headers and lists by write-through stores (plan.h, store_through;
+// launch_lists says which do; the A/B and tests/test_store_through_gpu.py).  Read at every build like the others; it steers no
+// launch choice, only the instantiation of the list kernel, so it rides in ListArgs, not in BuildEnv.  (The strips pack
+// had such stores too, `=pack`: slower by the bench line, taken out -- DESIGN.md section 3.3.)
+static uint32_t store_through_setting() {
+    const char* e = getenv("PIGS_STORE_THROUGH");
     return e && e[0] == '0' ? 0u : 1u;
 }
 static BuildEnv build_env() {
@@ -366,16 +381,23 @@ static ListArgs make_list_args(const PlanLayout& p, const SamplesLayout& s, void
     la.parea = (const float*)((char*)ws + p.off_parea);      // (run_build: null unless the build's statistics are wanted home)
     la.strip_cover = &((PlanParams*)((char*)ws + p.off_params))->strip_cover;
     la.product = lists_product_setting();
+    la.through = store_through_setting();
     return la;
 }
 // the list launch (build_choice.h, list_launch); fwd_only: PIGS_BUILD_FORWARD_ONLY (build_block_lists<..., FWD_ONLY>)
+// ... and la.through: headers and lists leave by write-through stores (plan.h, store_through) -- in the launch that was
+// measured to gain by them, the forward-only build of more than LISTS_SMALL_TILES tiles (the cold step's).  Full plans
+// and small point sets keep plain stores: one `--full` line each of parent and branch showed the training step and the
+// c2 step no better or worse with them, and nothing there was measured twice.
 static void launch_lists(const BuildLaunch& l, const ListArgs& la, hipStream_t stream, bool strips = false, bool fwd_only = false) {
     const bool small = l.kernel == K_LISTS_SMALL;
     const dim3 grid(l.grid), block(l.block);
     if (fwd_only) {
         if (small && strips) hipLaunchKernelGGL((plan_lists_kernel<1, true, true>), grid, block, 0, stream, la);
         else if (small) hipLaunchKernelGGL((plan_lists_kernel<1, false, true>), grid, block, 0, stream, la);
+        else if (strips && la.through) hipLaunchKernelGGL((plan_lists_kernel<LISTS_TPW, true, true, true>), grid, block, 0, stream, la);
         else if (strips) hipLaunchKernelGGL((plan_lists_kernel<LISTS_TPW, true, true>), grid, block, 0, stream, la);
+        else if (la.through) hipLaunchKernelGGL((plan_lists_kernel<LISTS_TPW, false, true, true>), grid, block, 0, stream, la);
         else hipLaunchKernelGGL((plan_lists_kernel<LISTS_TPW, false, true>), grid, block, 0, stream, la);
         return;
     }

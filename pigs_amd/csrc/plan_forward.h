@@ -512,7 +512,7 @@ __global__ __launch_bounds__(256, 5) void plan_lists_forward_kernel(ListArgs a, 
     const uint32_t tile0 = lists_tile0<LISTS_TPW>(wave);
     const uint32_t ntiles = a.sv.ntiles;
     if (tile0 >= ntiles) return;
-    build_block_lists<LISTS_TPW, false, false, false>(a, lds_all[wave], tile0, lane);      // (general path only: plan_lists.h)
+    build_block_lists<LISTS_TPW, false, false, false>(a, lds_all[wave], tile0, lane);      // (general path, plain stores: plan_lists.h)
     // what this wave's lanes stored (headers, group lists) is read back by other lanes of it: the stores have
     // reached the L2 before the first load is issued
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");

@@ -61,6 +61,8 @@ struct ListArgs {
     // words stay the kernels' own working state.
     uint32_t* home;
     uint32_t product;     // blocks whose group boxes form a product may take the product path (PIGS_LISTS_PRODUCT != 0)
+    uint32_t through;     // headers and lists leave by write-through stores (plan.h, store_through; PIGS_STORE_THROUGH):
+                          // read by the host alone, which launches plan_lists_kernel<..., THROUGH> by it
     // The guard of a TRUSTED build (plan.hip, run_build; null: none -- every other build).  Nobody looked at the points in
     // front of this launch: they are taken in index-tiled order because point sets of this size have long been the same
     // lattice.  The lists are right whatever the points are (they come from the groups' real boxes); what may have failed
@@ -90,7 +92,13 @@ constexpr uint32_t HOME_N_POINTS = 0, HOME_STRIP_COVER = 1, HOME_STRIPS = 2, HOM
 // count of zero (no tile list a backward could read; there is no TILE_MODE_GROUPS rebuild either).
 // PRODUCT = false: the product path is not compiled in (the fused list + forward launch, plan_forward.h: its wave holds
 // the forward's registers as well and the two paths together do not fit its 96).
-template <int TPW, bool STRIPS = false, bool FWD_ONLY = false, bool PRODUCT = true>
+// THROUGH: headers and lists leave by write-through stores (plan.h, store_through).  A template argument, not a word
+// of ListArgs read in the kernel: built that way first -- a launch-uniform branch around each store, every address
+// handed over as a finished pointer -- the launch was 0.3-0.7 us SLOWER than the parent's with the new stores and
+// 1.8 us slower with the plain ones.  The plain instantiations are the parent's code,
+// instruction for instruction.  The fused launch keeps plain stores: its waves read their own headers and lists back
+// behind a workgroup-scope release.
+template <int TPW, bool STRIPS = false, bool FWD_ONLY = false, bool PRODUCT = true, bool THROUGH = false>
 __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TPW>& lds, uint32_t tile0, int lane) {
     const PlanView& pv = a.pv;
     const uint32_t ntiles = a.sv.ntiles;
@@ -106,6 +114,7 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
         loff = pv.params->level_off[lane < PLAN_MAX_LEVELS ? lane : 0];   // lane = level: its first counter
     }
     const float INF = __builtin_huge_valf();
+    constexpr bool through = THROUGH;
     // lane 0: a tile for the queue of TILE_MODE_POINTS tiles / a block or tile of far-apart points met by a strips build.
     // Whoever counts the first one sends the word home (a word at home says "any", not how many).
     auto queue_points_tile = [&](uint32_t tile) {
@@ -205,7 +214,7 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
         for (int t = 0; t < TPW; ++t) {
             if (tile0 + (uint32_t)t >= ntiles) break;
             if (lane < TILE_HDR_WORDS)
-                a.hdr[(size_t)(tile0 + (uint32_t)t) * TILE_HDR_WORDS + lane] = lane == 0 ? (TILE_MODE_POINTS << TILE_MODE_SHIFT) : 0u;
+                store_through(a.hdr, (size_t)(tile0 + (uint32_t)t) * TILE_HDR_WORDS + lane, lane == 0 ? (TILE_MODE_POINTS << TILE_MODE_SHIFT) : 0u, through);
             if (lane == 0) queue_points_tile(tile0 + (uint32_t)t);
         }
         return;
@@ -228,7 +237,7 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
             const uint64_t km = __ballot(gm != 0u);
             const uint32_t cnt = (uint32_t)__builtin_popcountll(km);
             if (n[t] + cnt <= cap) {
-                if (gm != 0u) tl[n[t] + (uint32_t)lanes_below(km)] = j | (gm << LIST_WIDE_SHIFT) | (gf << LIST_NARROW_SHIFT);
+                if (gm != 0u) store_through(tl, n[t] + (uint32_t)lanes_below(km), j | (gm << LIST_WIDE_SHIFT) | (gf << LIST_NARROW_SHIFT), through);
             } else {
                 overflow[t] = true;
             }
@@ -239,7 +248,7 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
             const uint64_t mg = __ballot(gf >> g & 1u);
             const uint32_t cg = (uint32_t)__builtin_popcountll(mg);
             if (ng[t][g] + cg <= cap) {
-                if (gf >> g & 1u) gl[g * cap + ng[t][g] + (uint32_t)lanes_below(mg)] = j;
+                if (gf >> g & 1u) store_through(gl, g * cap + ng[t][g] + (uint32_t)lanes_below(mg), j, through);
             } else {
                 goverflow[t] = true;
             }
@@ -404,7 +413,7 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
             if (!strips && wx * gg.inv_s0 * (wy * gg.inv_s0) > POINTS_MODE_MIN_CELLS && walk_candidates() <= 4.f * (float)(longest < cap ? longest : cap)) {
                 overflow[t] = false; rebuild[t] = false;
                 if (lane < 5)
-                    a.hdr[(size_t)(tile0 + (uint32_t)t) * TILE_HDR_WORDS + lane] = lane == 0 ? (TILE_MODE_POINTS << TILE_MODE_SHIFT) : 0u;
+                    store_through(a.hdr, (size_t)(tile0 + (uint32_t)t) * TILE_HDR_WORDS + lane, lane == 0 ? (TILE_MODE_POINTS << TILE_MODE_SHIFT) : 0u, through);
                 if (lane == 0) queue_points_tile(tile0 + (uint32_t)t);
                 continue;
             }
@@ -417,7 +426,7 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
 #pragma unroll
             for (int g = 0; g < 4; ++g)
                 if (lane == 1 + g) w = ng[t][g];
-            if (lane < 5) a.hdr[(size_t)(tile0 + (uint32_t)t) * TILE_HDR_WORDS + lane] = w;      // words 5..7: the block's
+            if (lane < 5) store_through(a.hdr, (size_t)(tile0 + (uint32_t)t) * TILE_HDR_WORDS + lane, w, through);      // words 5..7: the block's
         }
     }
     if (!any_rare) return;
@@ -459,7 +468,7 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
                     const uint64_t mg = __ballot(hit);
                     const uint32_t cg = (uint32_t)__builtin_popcountll(mg);
                     if (ngw[g] + cg <= cap) {
-                        if (hit) gl[g * cap + ngw[g] + (uint32_t)lanes_below(mg)] = j;
+                        if (hit) store_through(gl, g * cap + ngw[g] + (uint32_t)lanes_below(mg), j, through);
                     } else {
                         gover = true;
                     }
@@ -473,7 +482,7 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
 #pragma unroll
                     for (int g = 0; g < 4; ++g)
                         if (lane == 1 + g) w = ngw[g];
-                    a.hdr[(size_t)(tile0 + (uint32_t)t) * TILE_HDR_WORDS + lane] = w;
+                    store_through(a.hdr, (size_t)(tile0 + (uint32_t)t) * TILE_HDR_WORDS + lane, w, through);
                 }
                 continue;
             }
@@ -483,7 +492,7 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
         // around its own point at sampling time (plan.h, TILE_MODE_POINTS)
         if (!strips && (tx1 - tx0) * gg.inv_s0 * ((ty1 - ty0) * gg.inv_s0) > POINTS_MODE_MIN_CELLS && walk_candidates() <= 4.f * (float)cap) {
             if (lane < 5)
-                a.hdr[(size_t)(tile0 + (uint32_t)t) * TILE_HDR_WORDS + lane] = lane == 0 ? (TILE_MODE_POINTS << TILE_MODE_SHIFT) : 0u;
+                store_through(a.hdr, (size_t)(tile0 + (uint32_t)t) * TILE_HDR_WORDS + lane, lane == 0 ? (TILE_MODE_POINTS << TILE_MODE_SHIFT) : 0u, through);
             if (lane == 0) queue_points_tile(tile0 + (uint32_t)t);
             continue;
         }
@@ -497,7 +506,7 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
             if (2 * (nr + cnt) <= cap) {
                 if (keep) {
                     const uint32_t p = 2 * (nr + (uint32_t)lanes_below(km));
-                    tl[p] = jb; tl[p + 1] = len;
+                    store_through(tl, p, jb, through); store_through(tl, p + 1, len, through);
                 }
             } else {
                 fits = false;
@@ -505,10 +514,10 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
             nr += cnt;
         },
                  [](const float4, const float4, uint64_t, uint32_t) {});
-        if (!fits && lane == 0) { tl[0] = 0; tl[1] = pv.N; }
+        if (!fits && lane == 0) { store_through(tl, 0, 0u, through); store_through(tl, 1, pv.N, through); }
         const uint32_t cnt = fits ? nr : 1u;
         if (lane < 5)
-            a.hdr[(size_t)(tile0 + (uint32_t)t) * TILE_HDR_WORDS + lane] = lane == 0 ? (cnt | (TILE_MODE_RANGES << TILE_MODE_SHIFT)) : 0u;
+            store_through(a.hdr, (size_t)(tile0 + (uint32_t)t) * TILE_HDR_WORDS + lane, lane == 0 ? (cnt | (TILE_MODE_RANGES << TILE_MODE_SHIFT)) : 0u, through);
     }
 }
 
@@ -539,7 +548,7 @@ __device__ __forceinline__ void lists_strip_cover(const ListArgs& a) {
     }
 }
 
-template <int TPW, bool STRIPS, bool FWD_ONLY = false>
+template <int TPW, bool STRIPS, bool FWD_ONLY = false, bool THROUGH = false>
 __global__ __launch_bounds__(256, 5) void plan_lists_kernel(ListArgs a) {
     __shared__ ListsLds<TPW> lds_all[4];
     const int lane = threadIdx.x & 63;
@@ -547,7 +556,7 @@ __global__ __launch_bounds__(256, 5) void plan_lists_kernel(ListArgs a) {
     lists_strip_cover(a);
     const uint32_t tile0 = lists_tile0<TPW>(wave);
     if (tile0 >= a.sv.ntiles) return;
-    build_block_lists<TPW, STRIPS, FWD_ONLY>(a, lds_all[wave], tile0, lane);
+    build_block_lists<TPW, STRIPS, FWD_ONLY, true, THROUGH>(a, lds_all[wave], tile0, lane);
 }
 
 }  // namespace pigs
