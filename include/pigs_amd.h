@@ -866,6 +866,61 @@ int pigs_optim1d_step(int dtype, int c, int64_t N, const PigsAdamStep* hyper, vo
                       void* conics, const PigsGradStats* stats, void* stream);
 
 /*
+ * The optimiser of the loop with the network: Adam over up to 128 small tensors in two launches, and the loss-weighted
+ * rate of that loop on the device (additive to ABI 10: the number does not change).  float32 / float64, all tensors
+ * alike.  Replaces, per time step of main_pn.py:171-232, torch.optim.Adam(model.parameters()).step() (:59, :222; the
+ * reference's DynamicsNetwork is 90 trainable tensors of some 30 000 elements), the rate g["lr"] = g["prev_lr"] *
+ * loss_weight (:217-218) and loss_weight *= exp(-epsilon * current_loss.item()) (:225), whose device read it removes
+ * together with those of total_loss (:227) and all_sufficient (:228).
+ *
+ * The state, pigs_network_adam_state_doubles(S) = 4 + 5 S doubles on the device, aligned to 8 bytes:
+ *   [0] rate_scale (initially 1)   [1] loss_sum   [2] loss_max   [3] loss_count        (initially 0)
+ *   then five arrays of S: steps (0), beta1_pow (1), beta2_pow (1), step_size, bc2_sqrt (the last two are written before
+ *   they are read).
+ * The moments, exp_avg and exp_avg_sq: ONE flat array each, in the parameters' dtype, aligned to 16 bytes.  Tensor s
+ * owns counts[s] elements from offset seg[s], seg[0] = 0, seg[s + 1] = seg[s] + counts[s] rounded up to a multiple of 4
+ * (the padding is never read or written); the arrays hold seg[S] elements.
+ *
+ * pigs_network_adam_step, two launches on `stream`; a tensor takes part when grads[s] is not NULL:
+ *   1. one wave, lanes over the tensors.  Per present tensor, in double:
+ *        steps[s] += 1,  beta1_pow[s] *= beta1,  beta2_pow[s] *= beta2,
+ *        step_size[s] = rate / (1 - beta1_pow[s]),  bc2_sqrt[s] = sqrt(1 - beta2_pow[s]),
+ *      rate = lr * rate_scale, lr = *dev_lr when dev_lr is not NULL.  Then, when `loss` is not NULL (one float32 or
+ *      float64 on the device, loss_dtype PIGS_F32 / PIGS_F64), one lane does, in double,
+ *        rate_scale *= exp(-decay * loss),  loss_sum += loss,  loss_max = loss if loss > loss_max or loss is NaN,
+ *        loss_count += 1:
+ *      the step uses the rate from BEFORE the decay, the order of main_pn.py:217-225.  A non-finite loss has no special
+ *      case: IEEE arithmetic gives what the reference's line gives (a NaN loss makes rate_scale, loss_sum and loss_max
+ *      NaN, and they stay so until they are reset).
+ *   2. workgroups of 256 threads over chunks of 1 024 elements of the present tensors (an absent tensor has none):
+ *        m <- beta1 m + (1 - beta1) g,  v <- beta2 v + (1 - beta2) g^2,  p <- p - step_size m / (sqrt(v) / bc2_sqrt + eps)
+ *      with the multiply-adds as explicit fma, in place on params[s] and the two flat arrays.  A tensor whose parameter and
+ *      gradient are both aligned to 16 bytes is read and written 16 bytes at a time with a scalar tail, any other one
+ *      element at a time; both ways give the same bits, and the bits do not depend on where the chunks fall.
+ *   An absent tensor keeps its parameter, its moments, its step count and its running products, as torch.optim.Adam
+ *   leaves a parameter whose .grad is None.  Nothing waits for another workgroup, allocates, frees or synchronises; the
+ *   pointers travel in the launch's arguments, so a captured call replays with the addresses it was recorded with.
+ * Refusals, before any HIP call.  PIGS_ERR_UNSUPPORTED: a dtype (or, with a loss, a loss_dtype) other than PIGS_F32 /
+ *   PIGS_F64.  PIGS_ERR_INVALID: a NULL block; tensors < 1 or > PIGS_NETWORK_ADAM_MAX_TENSORS; a NULL parameter; a count
+ *   <= 0; 2^31 elements or more in all (counted with the padding); every gradient NULL; a parameter or gradient not
+ *   aligned to its element; a NULL state or one off 8 bytes; a NULL moment array or one off 16 bytes; a dev_lr off 8
+ *   bytes; a loss not aligned to its type.  pigs_network_adam_state_doubles returns 0 for a count outside 1..128.
+ */
+#define PIGS_NETWORK_ADAM_MAX_TENSORS 128
+typedef struct PigsNetworkAdam {
+    int tensors;                                            /* S */
+    int64_t counts[PIGS_NETWORK_ADAM_MAX_TENSORS];          /* elements per tensor */
+    void* params[PIGS_NETWORK_ADAM_MAX_TENSORS];
+    const void* grads[PIGS_NETWORK_ADAM_MAX_TENSORS];       /* NULL: the tensor sits this step out */
+    double lr, beta1, beta2, eps;
+    double decay;                                           /* read with a loss only */
+    const double* dev_lr;                                   /* one double on the device, or NULL */
+} PigsNetworkAdam;
+int pigs_network_adam_state_doubles(int tensors);
+int pigs_network_adam_step(int dtype, const PigsNetworkAdam* block, double* state, void* exp_avg, void* exp_avg_sq,
+                           const void* loss, int loss_dtype, void* stream);
+
+/*
  * The model's state update: the dynamics network's deltas applied to the Gaussians, the next covariances and the
  * conservation penalty (additive to ABI 10: the number does not change).  d = 2, c = 1..4, float32 / float64.
  * Replaces, per time step of the loop with the network (main_pn.py:171-232 driving model_pn.Model):

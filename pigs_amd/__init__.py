@@ -17,6 +17,9 @@ Public surface:
                             (pigs_amd.optim; test_no_mlp.py:99-104, 146, 185-186, test_initialize.py:172-180); with
                             ``grad_stats=True`` also the densification's gradient sums (test_no_mlp.py:149-155)
     GaussianAdam1D          the same for d = 1 (test_no_mlp_1d.py:109-111, 156-162, 189-190)
+    NetworkAdam             a drop-in for ``torch.optim.Adam(model.parameters())`` in the loop with the network: Adam over
+                            up to 128 small tensors in two launches, the loss-weighted rate and the epoch's loss sums on
+                            the device (pigs_amd.network_adam; main_pn.py:59, 157, 217-228)
     advance_gaussians       the dynamics network's deltas applied to the Gaussians, the next covariances and the
                             conservation penalty in two launches, one for the backward (pigs_amd.advance;
                             model_pn.py:270-273, 677-698, 878-882)
@@ -63,6 +66,9 @@ def __getattr__(name):
     if name in ("GaussianAdam", "GaussianAdam1D"):
         from . import optim
         return getattr(optim, name)
+    if name == "NetworkAdam":
+        from .network_adam import NetworkAdam
+        return NetworkAdam
     if name in ("advance_gaussians", "ADVANCE_PENALTY_COLUMNS"):
         from . import advance
         return getattr(advance, name)

@@ -102,6 +102,18 @@ class PigsGradStats(ctypes.Structure):
 
 _stats_p = ctypes.POINTER(PigsGradStats)
 
+NETWORK_ADAM_MAX_TENSORS = 128
+
+
+class PigsNetworkAdam(ctypes.Structure):
+    """struct PigsNetworkAdam of include/pigs_amd.h (the network optimiser's tensor table, its rates and its decay)"""
+    _fields_ = [("tensors", _i), ("counts", _i64 * NETWORK_ADAM_MAX_TENSORS), ("params", _vp * NETWORK_ADAM_MAX_TENSORS),
+                ("grads", _vp * NETWORK_ADAM_MAX_TENSORS), ("lr", ctypes.c_double), ("beta1", ctypes.c_double),
+                ("beta2", ctypes.c_double), ("eps", ctypes.c_double), ("decay", ctypes.c_double), ("dev_lr", _vp)]
+
+
+_network_adam_p = ctypes.POINTER(PigsNetworkAdam)
+
 # name -> (restype, argtypes); must list every symbol include/pigs_amd.h declares
 SIGNATURES = {
     "pigs_abi_version": (_i, []),
@@ -200,6 +212,9 @@ SIGNATURES = {
     "pigs_optim_step_stats": (_i, [_i, _i, _i64, _adam_p] + [_vp] * 4 + [_vp] * 8 + [_vp] * 4 + [_vp] * 3 + [_stats_p, _vp]),
     "pigs_optim1d_materialize": (_i, [_i, _i, _i64, ctypes.c_double] + [_vp] * 2 + [_vp] * 3 + [_vp]),
     "pigs_optim1d_step": (_i, [_i, _i, _i64, _adam_p] + [_vp] * 3 + [_vp] * 6 + [_vp] * 4 + [_vp] * 3 + [_stats_p, _vp]),
+    # the network's optimiser (additive to ABI 10): block, state, the flat moments, loss, its dtype
+    "pigs_network_adam_state_doubles": (_i, [_i]),
+    "pigs_network_adam_step": (_i, [_i, _network_adam_p, _vp, _vp, _vp, _vp, _i, _vp]),
     # the model's state update (additive to ABI 10): wrap, state, deltas, mask, scratch, the nine outputs /
     # saved arrays, mask, scratch, the nine incoming gradients, the five gradients
     "pigs_advance_scratch_bytes": (ctypes.c_size_t, [_i64]),

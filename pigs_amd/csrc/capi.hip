@@ -763,6 +763,36 @@ int pigs_optim1d_step(int dtype, int c, int64_t N, const PigsAdamStep* hyper, vo
     return optim1d_step(o, (hipStream_t)stream);
 }
 
+int pigs_network_adam_state_doubles(int tensors) {
+    return tensors >= 1 && tensors <= NETWORK_ADAM_MAX ? network_adam_state_doubles(tensors) : 0;
+}
+
+int pigs_network_adam_step(int dtype, const PigsNetworkAdam* block, double* state, void* exp_avg, void* exp_avg_sq,
+                           const void* loss, int loss_dtype, void* stream) {
+    if (dtype != PIGS_F32 && dtype != PIGS_F64) return PIGS_ERR_UNSUPPORTED;
+    if (loss && loss_dtype != PIGS_F32 && loss_dtype != PIGS_F64) return PIGS_ERR_UNSUPPORTED;
+    if (!block || block->tensors < 1 || block->tensors > NETWORK_ADAM_MAX) return PIGS_ERR_INVALID;
+    const uintptr_t element = dtype == PIGS_F32 ? 3u : 7u;
+    int64_t end = 0;                                  // the moments' elements, every segment starting at a multiple of 4
+    bool any = false;
+    for (int s = 0; s < block->tensors; ++s) {
+        if (!block->params[s] || block->counts[s] <= 0) return PIGS_ERR_INVALID;
+        if (block->counts[s] > 0x7fffffffLL) return PIGS_ERR_INVALID;
+        end = ((end + 3) & ~(int64_t)3) + block->counts[s];
+        if (end > 0x7fffffffLL) return PIGS_ERR_INVALID;
+        if (((uintptr_t)block->params[s] & element) || ((uintptr_t)block->grads[s] & element)) return PIGS_ERR_INVALID;
+        any = any || block->grads[s];
+    }
+    if (!any) return PIGS_ERR_INVALID;
+    if (!state || ((uintptr_t)state & 7u) || ((uintptr_t)block->dev_lr & 7u)) return PIGS_ERR_INVALID;
+    if (!exp_avg || !exp_avg_sq || ((uintptr_t)exp_avg & 15u) || ((uintptr_t)exp_avg_sq & 15u)) return PIGS_ERR_INVALID;
+    if (loss && ((uintptr_t)loss & (loss_dtype == PIGS_F32 ? 3u : 7u))) return PIGS_ERR_INVALID;
+    NetworkAdamStep o{};
+    o.dtype = dtype; o.loss_dtype = loss_dtype; o.block = block; o.state = state;
+    o.exp_avg = exp_avg; o.exp_avg_sq = exp_avg_sq; o.loss = loss;
+    return network_adam_step(o, (hipStream_t)stream);
+}
+
 size_t pigs_advance_scratch_bytes(int64_t N) { return advance_scratch_bytes(N); }
 
 static int advance_sizes_ok(int dtype, int c, int64_t N) {

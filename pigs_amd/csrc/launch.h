@@ -100,6 +100,19 @@ int optim1d_materialize(int dtype, int64_t N, bool tanh_map, double scale, const
                         void* o_means, void* o_cov, void* o_conic, hipStream_t stream);
 int optim1d_step(const OptimStep& o, hipStream_t stream);
 
+// network_adam.hip
+constexpr int NETWORK_ADAM_MAX = PIGS_NETWORK_ADAM_MAX_TENSORS;
+constexpr int NETWORK_ADAM_HEAD = 4;                   // rate_scale, loss_sum, loss_max, loss_count in front of the arrays
+struct NetworkAdamStep {
+    int dtype, loss_dtype;
+    const PigsNetworkAdam* block;
+    double* state;                                     // [4 + 5 S]
+    void *exp_avg, *exp_avg_sq;                        // the flat moments
+    const void* loss;                                  // or null
+};
+inline int network_adam_state_doubles(int tensors) { return NETWORK_ADAM_HEAD + 5 * tensors; }
+int network_adam_step(const NetworkAdamStep& o, hipStream_t stream);
+
 // advance.hip
 struct AdvanceStep {
     int dtype, c, wrap;

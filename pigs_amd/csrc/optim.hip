@@ -26,6 +26,7 @@
 // (test_no_mlp_1d.py:109-111); three groups (means, values, scaling) in slots 0..2 of the same argument block.
 #include <hip/hip_runtime.h>
 
+#include "adam_update.h"
 #include "cov_terms.h"
 #include "launch.h"
 
@@ -116,15 +117,8 @@ struct AdamGroup {
     }
 };
 
-// The same update with its multiply-adds written out.  The d = 1 kernels with and without statistics must agree bit for
-// bit, and under -ffp-contract=fast which of the two products of  b1 m + (1 - b1) g  the compiler contracts is its choice
-// per instantiation (in double it differed between the two); with explicit fma there is no choice left.
-template <typename T>
-__device__ __forceinline__ T adam_update_fma(const AdamGroup<T>& a, T p, T g, T& m, T& v) {
-    m = fma(a.b1, m, a.omb1 * g);
-    v = fma(a.b2, v, (a.omb2 * g) * g);
-    return fma(-a.step_size, m / (sqrt(v) / a.bc2_sqrt + a.eps), p);
-}
+// The same update with its multiply-adds written out is adam_update_fma(adam, p, g, m, v) of adam_update.h: the d = 1
+// kernels with and without statistics must agree bit for bit.
 
 // sum += g, norm += |sum| (of the sum after adding), last = g: one row of a group's statistics
 template <typename T>
