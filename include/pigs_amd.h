@@ -980,6 +980,57 @@ int pigs_advance_backward(int dtype, int c, int64_t N, const void* out_scaling, 
                           const void* g_full_conics, const void* g_penalty, void* g_means, void* g_u, void* g_scaling,
                           void* g_transforms, void* g_deltas, void* stream);
 
+/*
+ * The TEST problem's state terms (additive to ABI 10: the number does not change).  The eight
+ * unweighted terms of Problem.TEST's pde_loss (model_pn.py:851-852), bc_loss (:854-861) and conservation_loss
+ * (:866-876), which read the Gaussians' NEW state and the network's deltas and no sample: three `if torch.any(...)` and
+ * about seventeen boolean indexings there, each with a host wait.  d = 2, c = 1..4, float32 / float64.
+ *
+ * Arrays, row-major: means [N][2] and u [N][c] of the new state (out_means, out_u of pigs_advance_forward), deltas
+ * [N][5 + c] in the network's column order, boundary_mask [N] (one byte per row, nonzero = a FREE Gaussian).
+ * Over the free rows, with F their count, y = means[.][1], dx, dy = deltas[.][0], deltas[.][1], du = deltas[.][5 .. 5 + c),
+ * u0 = u[.][0], and LOW = {y < -wall}, HIGH = {y > wall}, MID = {|y| < wall}, strict compares in the dtype against wall
+ * rounded to it (a row at +-wall or with a NaN height is in no set):
+ *   terms[0]  sum (dy - u0 / drift)^2 / F                  u0 / drift divided in the dtype, drift rounded to it
+ *   terms[1]  sum_LOW sum_c (u - 1)^2 / (|LOW| c)           0 when LOW is empty
+ *   terms[2]  sum_HIGH sum_c (u + 1)^2 / (|HIGH| c)         0 when HIGH is empty
+ *   terms[3]  sum dx^2 / F
+ *   terms[4]  sum [(dx - mean dx)^2 + (dy - mean dy)^2] / (2 F)
+ *   terms[5]  sum (y - mean y)^2 / F
+ *   terms[6]  sum_MID (|u0| - 1)^2 / |MID|                  0 when MID is empty
+ *   terms[7]  sum_MID sum_c du^2 / (|MID| c)                0 when MID is empty
+ * each rounded once to the dtype; with F = 0 the entries 0, 3, 4, 5 are NaN (0 / 0, torch.mean of nothing).  A boundary
+ * row is branched around: its state and deltas (NaN, Inf) reach neither a term nor a gradient.
+ *
+ * pigs_state_loss_forward.  Up to PIGS_STATE_LOSS_ONE_LAUNCH_ROWS rows: ONE launch of one workgroup (256 threads up to
+ *   256 rows, else 1 024 threads of up to four rows each) that makes both passes: it adds F and the sums of dx, dy, y,
+ *   takes K = sum / F as the centre and adds sum (x - K) and sum (x - K)^2 over the rows it kept in registers; the
+ *   spread is sum (x - K)^2 - (sum (x - K))^2 / F, whose second part is a second-order correction.  Above the bound TWO
+ *   launches: workgroups of 256 rows do the same about their own centres and write one record of
+ *   PIGS_STATE_LOSS_RECORD doubles each; one workgroup then moves the records to one common centre and adds them in
+ *   record order.  Accumulators are double, sums go across a wave by shuffles, across waves through LDS in wave order.
+ *   No float atomics: the same inputs give the same bits.
+ * pigs_state_loss_backward, one launch of one thread per Gaussian, from g_terms [8] on the device to g_means [N][2],
+ *   g_u [N][c] and ONE packed g_deltas [N][5 + c] (a NULL one is not written).  The sets, their counts and the means are
+ *   constants: it reads them from the statistics record.  A boundary row's gradients are exact zeros.
+ * scratch: pigs_state_loss_scratch_bytes(N) bytes, 8-byte aligned (0 for N <= 0): PIGS_STATE_LOSS_STATS doubles
+ *   F, |LOW|, |HIGH|, |MID|, mean dx, mean dy, mean y, 0; above the bound also ceil(N / 256) records.
+ * Arguments are checked before any HIP call: a bad dtype or c outside 1..4 is PIGS_ERR_UNSUPPORTED; N <= 0, a wall that
+ *   is negative or not finite, a drift that is zero or not finite, a null array (the backward: all three gradients
+ *   null) or a scratch off 8 bytes is PIGS_ERR_INVALID; a short scratch is PIGS_ERR_WORKSPACE.  Nothing allocates, frees,
+ *   synchronises or waits for another workgroup.
+ */
+#define PIGS_STATE_LOSS_ONE_LAUNCH_ROWS 4096
+#define PIGS_STATE_LOSS_STATS 8
+#define PIGS_STATE_LOSS_RECORD 20
+size_t pigs_state_loss_scratch_bytes(int64_t N);
+int pigs_state_loss_forward(int dtype, int c, int64_t N, double wall, double drift, const void* means, const void* u,
+                            const void* deltas, const uint8_t* boundary_mask, void* scratch, size_t scratch_bytes,
+                            void* terms, void* stream);
+int pigs_state_loss_backward(int dtype, int c, int64_t N, double wall, double drift, const void* means, const void* u,
+                             const void* deltas, const uint8_t* boundary_mask, const void* scratch, const void* g_terms,
+                             void* g_means, void* g_u, void* g_deltas, void* stream);
+
 /* ---- One per-Gaussian tanh network per launch (additive to ABI 10) ----------------------------
  * The three per-Gaussian nets of the dynamics network (model_pn.py:154-174 delta_net, :187-198 input_projection,
  * :203-226 the query / key transforms; nn.Tanh, :425-426): nn.Linear layers with tanh between them and none after the last,

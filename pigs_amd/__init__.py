@@ -24,6 +24,9 @@ Public surface:
                             conservation penalty in two launches, one for the backward (pigs_amd.advance;
                             model_pn.py:270-273, 677-698, 878-882)
     ADVANCE_PENALTY_COLUMNS the names of ``advance_gaussians(...).penalty``'s four entries
+    state_loss_terms        the eight state terms of Problem.TEST's pde, bc and conservation losses in one launch and one
+                            for the backward, no host decision (pigs_amd.state_loss; model_pn.py:851-861, 866-876)
+    STATE_LOSS_COLUMNS      the names of its eight entries
     fused_mlp               one per-Gaussian tanh network (nn.Linear layers with nn.Tanh between them, up to 6 layers
                             of width up to 48) in one launch forward and at most two backward, on the f32 MFMA
                             (pigs_amd.mlp; model_pn.py:154-174, 187-198, 203-226)
@@ -72,6 +75,9 @@ def __getattr__(name):
     if name in ("advance_gaussians", "ADVANCE_PENALTY_COLUMNS"):
         from . import advance
         return getattr(advance, name)
+    if name in ("state_loss_terms", "STATE_LOSS_COLUMNS"):
+        from . import state_loss
+        return getattr(state_loss, name)
     if name in ("fused_mlp", "FusedMLP", "fused_mlp_bank", "FusedMLPBank", "fused_mlp_joined"):
         from . import mlp
         return getattr(mlp, name)

@@ -221,6 +221,13 @@ SIGNATURES = {
     "pigs_advance_forward": (_i, [_i, _i, _i64, _i, ctypes.c_double, ctypes.c_double] + [_vp] * 4 + [_vp, _vp]
                              + [_vp, ctypes.c_size_t] + [_vp] * 9 + [_vp]),
     "pigs_advance_backward": (_i, [_i, _i, _i64] + [_vp] * 3 + [_vp, _vp] + [_vp] * 9 + [_vp] * 5 + [_vp]),
+    # the TEST problem's state terms (additive to ABI 10): wall, drift, means, u, deltas, mask, scratch, terms /
+    # ..., scratch, g_terms, the three gradients
+    "pigs_state_loss_scratch_bytes": (ctypes.c_size_t, [_i64]),
+    "pigs_state_loss_forward": (_i, [_i, _i, _i64, ctypes.c_double, ctypes.c_double] + [_vp] * 3 + [_vp]
+                                + [_vp, ctypes.c_size_t] + [_vp] + [_vp]),
+    "pigs_state_loss_backward": (_i, [_i, _i, _i64, ctypes.c_double, ctypes.c_double] + [_vp] * 3 + [_vp] + [_vp, _vp]
+                                 + [_vp] * 3 + [_vp]),
     # one tanh network per launch (additive to ABI 10): widths, x, weights, biases, y / ..., g_y, scratch, the gradients
     "pigs_mlp_scratch_bytes": (ctypes.c_size_t, [_i64, _i, _ip]),
     "pigs_mlp_forward": (_i, [_i, _i64, _i, _ip, _vp, _vpp, _vpp, _vp, _vp]),

@@ -853,6 +853,45 @@ int pigs_advance_backward(int dtype, int c, int64_t N, const void* out_scaling, 
     return advance_backward(s, (hipStream_t)stream);
 }
 
+size_t pigs_state_loss_scratch_bytes(int64_t N) { return state_loss_scratch_bytes(N); }
+
+static int state_loss_sizes_ok(int dtype, int c, int64_t N, double wall, double drift) {
+    const int rc = advance_sizes_ok(dtype, c, N);
+    if (rc != PIGS_OK) return rc;
+    if (!(wall >= 0.0) || !(wall < 1e300)) return PIGS_ERR_INVALID;            // NaN fails the compare
+    if (!(drift * drift > 0.0) || !(drift * drift < 1e300)) return PIGS_ERR_INVALID;
+    return PIGS_OK;
+}
+
+int pigs_state_loss_forward(int dtype, int c, int64_t N, double wall, double drift, const void* means, const void* u,
+                            const void* deltas, const uint8_t* boundary_mask, void* scratch, size_t scratch_bytes,
+                            void* terms, void* stream) {
+    const int rc = state_loss_sizes_ok(dtype, c, N, wall, drift);
+    if (rc != PIGS_OK) return rc;
+    if (!means || !u || !deltas || !boundary_mask || !terms) return PIGS_ERR_INVALID;
+    if (!scratch || ((uintptr_t)scratch & 7u)) return PIGS_ERR_INVALID;
+    if (scratch_bytes < state_loss_scratch_bytes(N)) return PIGS_ERR_WORKSPACE;
+    StateLossStep s{};
+    s.dtype = dtype; s.c = c; s.N = N; s.wall = wall; s.drift = drift;
+    s.means = means; s.u = u; s.deltas = deltas; s.mask = boundary_mask; s.scratch = scratch; s.terms = terms;
+    return state_loss_forward(s, (hipStream_t)stream);
+}
+
+int pigs_state_loss_backward(int dtype, int c, int64_t N, double wall, double drift, const void* means, const void* u,
+                             const void* deltas, const uint8_t* boundary_mask, const void* scratch, const void* g_terms,
+                             void* g_means, void* g_u, void* g_deltas, void* stream) {
+    const int rc = state_loss_sizes_ok(dtype, c, N, wall, drift);
+    if (rc != PIGS_OK) return rc;
+    if (!means || !u || !deltas || !boundary_mask || !g_terms) return PIGS_ERR_INVALID;
+    if (!scratch || ((uintptr_t)scratch & 7u)) return PIGS_ERR_INVALID;
+    if (!g_means && !g_u && !g_deltas) return PIGS_ERR_INVALID;
+    StateLossStep s{};
+    s.dtype = dtype; s.c = c; s.N = N; s.wall = wall; s.drift = drift;
+    s.means = means; s.u = u; s.deltas = deltas; s.mask = boundary_mask; s.scratch = const_cast<void*>(scratch);
+    s.g_terms = g_terms; s.g_means = g_means; s.g_u = g_u; s.g_deltas = g_deltas;
+    return state_loss_backward(s, (hipStream_t)stream);
+}
+
 size_t pigs_mlp_scratch_bytes(int64_t N, int L, const int* widths) { return mlp_scratch_bytes(N, L, widths); }
 
 static int mlp_sizes_ok(int dtype, int64_t N, int L, const int* widths) {

@@ -130,6 +130,23 @@ size_t advance_scratch_bytes(int64_t N);
 int advance_forward(const AdvanceStep& s, hipStream_t stream);
 int advance_backward(const AdvanceStep& s, hipStream_t stream);
 
+// state_loss.hip
+constexpr int64_t STATE_LOSS_ONE_LAUNCH_ROWS = PIGS_STATE_LOSS_ONE_LAUNCH_ROWS;      // up to here one workgroup, one launch
+struct StateLossStep {
+    int dtype, c;
+    int64_t N;
+    double wall, drift;
+    const void *means, *u, *deltas;      // the NEW state's means [N][2], u [N][c]; deltas [N][5 + c]
+    const uint8_t* mask;
+    void* scratch;                       // the forward writes it, the backward reads its statistics record
+    void* terms;                         // forward: [8]
+    const void* g_terms;                 // backward: the incoming gradient [8]
+    void *g_means, *g_u, *g_deltas;      // backward: null = not wanted
+};
+size_t state_loss_scratch_bytes(int64_t N);
+int state_loss_forward(const StateLossStep& s, hipStream_t stream);
+int state_loss_backward(const StateLossStep& s, hipStream_t stream);
+
 // mlp.hip
 struct MlpStep {
     int64_t N;
