@@ -33,7 +33,7 @@
  *     trace together with order 3 has no fused kernel (PIGS_ERR_UNSUPPORTED: two calls).
  *     The composed outputs have entry points of their own and no mask bit a caller may pass (PIGS_ERR_INVALID):
  *     the library's masks 32, 64, 128, 256 and 512 stand for pigs_residual_*, pigs_residual_terms_*,
- *     pigs_vorticity_*, pigs_residual_coupled_* and pigs_vorticity_residual_*.
+ *     pigs_vorticity_*, pigs_residual_coupled_*, pigs_vorticity_residual_* and pigs_vorticity_fit_*.
  *   - supported: d in {1,2}, c in {1..4}, dtype f32/f64 (binned plan: d=2, f32).
  *   - return value: PIGS_OK or an error code; pigs_status_string() names it.
  */
@@ -359,6 +359,51 @@ int pigs_vorticity_residual_backward(int dtype, int64_t N, int64_t M,
                                      void* g_means, void* g_conics, void* g_values,
                                      void* plan_ws, size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes,
                                      void* stream);
+
+/*
+ * The vorticity residual with a data term as a third column, from the same seven sums in the same launch (additive to
+ * ABI 10; d = 2 and c = 2 are implied).  Everything of pigs_vorticity_residual_* holds, and in addition
+ *     out[m][2] = data_weight (w_now[m] - data[m])
+ * with w_now the vorticity of the CURRENT level (not blended) and data a DEVICE array [M] in the call's dtype -- the
+ * recon_loss of the reference's Navier-Stokes loop (main_pn.py:209-210; data_weight = sqrt(5)) and, with nu = dt =
+ * time_term = 0, the loss of its initialisation fit (test_initialize.py:135-136).  out and gout are [M][3].  The
+ * backward differs in one line: the gradient that arrives at w is gout[m][1] time_term + gout[m][2] data_weight; it
+ * reads neither prev nor data, and there is no gradient wrt data.  A NULL params or a NULL data in the forward is
+ * PIGS_ERR_INVALID, as is a backward with M > 0 and no aux; through a plan float64 is PIGS_ERR_UNSUPPORTED; on a
+ * PIGS_BUILD_FORWARD_ONLY plan the backward writes NaN gradients.
+ */
+typedef struct PigsVorticityFit {
+    double nu, dt, time_term, tau, data_weight;      /* tau: used where tau_pt is NULL */
+    const void* tau_pt;                              /* device field [M] or NULL */
+    const void* data;                                /* device array [M]; the forward reads it */
+} PigsVorticityFit;
+int pigs_vorticity_fit_forward(int dtype, int64_t N, int64_t M,
+                               const void* means, const void* conics, const void* values, const void* samples,
+                               const PigsVorticityFit* params, const void* prev, void* out, void* aux,
+                               void* plan_ws, size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes,
+                               void* stream);
+int pigs_vorticity_fit_backward(int dtype, int64_t N, int64_t M,
+                                const void* means, const void* conics, const void* values, const void* samples,
+                                const PigsVorticityFit* params, const void* gout, const void* aux,
+                                void* g_means, void* g_conics, void* g_values,
+                                void* plan_ws, size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes,
+                                void* stream);
+
+/*
+ * The pixel of an image under every sample point, in one launch (additive to ABI 10): image [H][W] (dtype_image),
+ * samples [M][2] (dtype_samples), out [M] (dtype_image), all on the device and contiguous.  With every operation
+ * rounded once in the samples' dtype, a true division and no contraction,
+ *     tx = (x - lo) / (hi - lo) * W,  ix = clamp(trunc(tx), 0, W - 1)         (ty, iy with H likewise)
+ *     out[m] = image[iy][ix]
+ * -- `((samples + 1) / 2 * res).to(long).clamp(0, res - 1)`, `coords[:, 1] * res + coords[:, 0]` and `torch.take` of the
+ * reference (main_pn.py:206-207, 210) for lo = -1, hi = 1 and a square image, bit for bit.  A non-finite coordinate reads
+ * pixel 0 of its axis.  Checked before any HIP call: a dtype other than PIGS_F32 / PIGS_F64, H or W above 2^24 or more
+ * than 2^31 - 1 blocks of 256 points is PIGS_ERR_UNSUPPORTED; H or W < 1, M < 0, hi <= lo (also after rounding to the
+ * samples' dtype), a non-finite box or a NULL array with M > 0 is PIGS_ERR_INVALID.  M = 0 returns PIGS_OK without a
+ * launch.  Nothing allocates, frees or synchronises.
+ */
+int pigs_grid_lookup(int dtype_image, int dtype_samples, int64_t H, int64_t W, int64_t M, double lo, double hi,
+                     const void* image, const void* samples, void* out, void* stream);
 
 /*
  * The network inputs in ONE launch (additive to ABI 10; d = 2; forward only): the four arrays that the reference's

@@ -4,6 +4,9 @@ Public surface:
     GaussianSampler         drop-in for ``diff_gaussian_sampling.GaussianSampler``
     VORTICITY_COLUMNS       the column names of ``GaussianSampler.vorticity_terms()``
     VORTICITY_RESIDUAL_COLUMNS  the column names of ``GaussianSampler.vorticity_residual()``
+    VORTICITY_FIT_COLUMNS   the column names of ``GaussianSampler.vorticity_residual(data=...)``
+    grid_lookup             the pixel of an image under every sample point in one launch: the data of the reference's
+                            vorticity fits (pigs_amd.lookup; main_pn.py:206-210, test_initialize.py:132-135)
     NETWORK_PDES            the right-hand sides ``GaussianSampler.network_inputs()`` composes
     covariances             fused ``build_covariances`` / ``build_full_covariances`` (gaussians.py:163-193)
     split_gaussians         prune and split / clone Gaussians in HIP with one host read (pigs_amd.refine;
@@ -60,6 +63,12 @@ def __getattr__(name):
     if name == "VORTICITY_RESIDUAL_COLUMNS":
         from .sampler import VORTICITY_RESIDUAL_COLUMNS
         return VORTICITY_RESIDUAL_COLUMNS
+    if name == "VORTICITY_FIT_COLUMNS":
+        from .sampler import VORTICITY_FIT_COLUMNS
+        return VORTICITY_FIT_COLUMNS
+    if name == "grid_lookup":
+        from .lookup import grid_lookup
+        return grid_lookup
     if name == "NETWORK_PDES":
         from .sampler import NETWORK_PDES
         return NETWORK_PDES

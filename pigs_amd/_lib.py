@@ -75,6 +75,15 @@ class PigsVorticityResidual(ctypes.Structure):
 _vorticity_residual_p = ctypes.POINTER(PigsVorticityResidual)
 
 
+class PigsVorticityFit(ctypes.Structure):
+    """struct PigsVorticityFit of include/pigs_amd.h (the vorticity residual's coefficients, the data and its weight)"""
+    _fields_ = [("nu", ctypes.c_double), ("dt", ctypes.c_double), ("time_term", ctypes.c_double), ("tau", ctypes.c_double),
+                ("data_weight", ctypes.c_double), ("tau_pt", _vp), ("data", _vp)]
+
+
+_vorticity_fit_p = ctypes.POINTER(PigsVorticityFit)
+
+
 class PigsNetworkInputs(ctypes.Structure):
     """struct PigsNetworkInputs of include/pigs_amd.h (the right-hand side's kind, nu and the two wave constants)"""
     _fields_ = [("kind", _i), ("nu", ctypes.c_double), ("wave", ctypes.c_double * 2)]
@@ -159,6 +168,13 @@ SIGNATURES = {
                                         + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
     "pigs_vorticity_residual_backward": (_i, [_i, _i64, _i64] + [_vp] * 4 + [_vorticity_residual_p, _vp, _vp] + [_vp] * 3
                                          + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
+    # the vorticity fit (additive to ABI 10): the vorticity residual's arguments, out and gout [M][3]
+    "pigs_vorticity_fit_forward": (_i, [_i, _i64, _i64] + [_vp] * 4 + [_vorticity_fit_p, _vp, _vp, _vp]
+                                   + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
+    "pigs_vorticity_fit_backward": (_i, [_i, _i64, _i64] + [_vp] * 4 + [_vorticity_fit_p, _vp, _vp] + [_vp] * 3
+                                    + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
+    # the image lookup (additive to ABI 10): dtypes, H, W, M, lo, hi, image, samples, out
+    "pigs_grid_lookup": (_i, [_i, _i, _i64, _i64, _i64, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp] + [_vp]),
     # the network inputs (additive to ABI 10; forward only): params, sample_u, sample_ux, sample_uxx, sample_pde
     "pigs_network_inputs_forward": (_i, [_i, _i, _i, _i64, _i64] + [_vp] * 4 + [_network_inputs_p] + [_vp] * 4
                                     + [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),

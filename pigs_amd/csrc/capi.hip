@@ -308,6 +308,31 @@ int pigs_vorticity_residual_backward(int dtype, int64_t N, int64_t M, const void
     return fused_launch(true, a, plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, stream);
 }
 
+// vorticity fit (pair_math.h ORDF): the vorticity residual's two columns and data_weight (w - data), d = 2, c = 2
+int pigs_vorticity_fit_forward(int dtype, int64_t N, int64_t M, const void* means, const void* conics, const void* values,
+                               const void* samples, const PigsVorticityFit* params, const void* prev, void* out, void* aux,
+                               void* plan_ws, size_t plan_ws_bytes, const void* samples_ws, size_t samples_ws_bytes, void* stream) {
+    if (!params || !params->data || (M > 0 && !out)) return PIGS_ERR_INVALID;
+    SampleArgs a = fused_args(MASK_VORT_FIT, dtype, 2, 2, N, M, means, conics, values, samples);
+    a.fit = params;
+    a.target = prev;
+    a.out[0] = out;
+    a.aux = aux;
+    return fused_launch(false, a, plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, stream);
+}
+
+int pigs_vorticity_fit_backward(int dtype, int64_t N, int64_t M, const void* means, const void* conics, const void* values,
+                                const void* samples, const PigsVorticityFit* params, const void* gout, const void* aux,
+                                void* g_means, void* g_conics, void* g_values, void* plan_ws, size_t plan_ws_bytes,
+                                const void* samples_ws, size_t samples_ws_bytes, void* stream) {
+    if (!params || (M > 0 && (!gout || !aux)) || (N > 0 && (!g_means || !g_conics || !g_values))) return PIGS_ERR_INVALID;
+    SampleArgs a = fused_args(MASK_VORT_FIT, dtype, 2, 2, N, M, means, conics, values, samples);
+    a.fit = params;
+    a.aux = const_cast<void*>(aux);
+    fused_gradients(a, gout, g_means, g_conics, g_values);
+    return fused_launch(true, a, plan_ws, plan_ws_bytes, samples_ws, samples_ws_bytes, stream);
+}
+
 // network inputs (pair_math.h ORDI, ORDJ): sample_u, sample_ux, sample_uxx, sample_pde of Model.forward; d = 2, forward only
 int pigs_network_inputs_forward(int dtype, int d, int c, int64_t N, int64_t M, const void* means, const void* conics,
                                 const void* values, const void* samples, const PigsNetworkInputs* params, void* sample_u,

@@ -20,7 +20,7 @@
 namespace pigs {
 
 static_assert(MASK_RESIDUAL == ORDR && MASK_TERMS == ORDG && MASK_VORTICITY == ORDV && MASK_COUPLED == ORDC &&
-                  MASK_VORT_RESIDUAL == ORDN && MASK_NET_INPUTS == ORDI && MASK_NET_INPUTS_NS == ORDJ,
+                  MASK_VORT_RESIDUAL == ORDN && MASK_VORT_FIT == ORDF && MASK_NET_INPUTS == ORDI && MASK_NET_INPUTS_NS == ORDJ,
               "launch.h and pair_math.h name the same fused-output masks");
 
 template <typename T, int D, int C, int MASK, int NW>
@@ -104,6 +104,7 @@ __global__ __launch_bounds__(NW * 64) void dense_backward_kernel(
         else if constexpr (MASK == ORDV) G.load_vorticity(m, G0);
         else if constexpr (MASK == ORDC) G.load_coupled(m, G0, rz);
         else if constexpr (MASK == ORDN) G.load_vorticity_residual(m, G0, rz);
+        else if constexpr (MASK == ORDF) G.load_vorticity_fit(m, G0, rz);
         else G.load(m, G0, G1, G2, G3);
     };
     // the general residual: the two points' wave-uniform values (coefficients, gr, aux) are fetched field by field,
@@ -339,6 +340,7 @@ __global__ __launch_bounds__(256) void dense_backward_staged_kernel(
         else if constexpr (MASK == ORDV) p.G.load_vorticity(m, G0);
         else if constexpr (MASK == ORDC) p.G.load_coupled(m, G0, rz);
         else if constexpr (MASK == ORDN) p.G.load_vorticity_residual(m, G0, rz);
+        else if constexpr (MASK == ORDF) p.G.load_vorticity_fit(m, G0, rz);
         else p.G.load(m, G0, G1, G2, G3);
         pts[threadIdx.x] = p;
     }
@@ -457,6 +459,7 @@ static int dispatch_mask(bool backward, const SampleArgs& a, hipStream_t stream)
     if constexpr (dense_vort_instance(D, C)) {
         switch (mask) {
             PIGS_DENSE_VORT_MASKS(PIGS_CASE)
+            PIGS_DENSE_FIT_MASKS(PIGS_CASE)
             default: break;
         }
     }

@@ -18,7 +18,7 @@ constexpr int fwd_accumulators(int d, int c, int mask) {
     const int nf = d * (d + 1) / 2, n3 = d * (d + 1) * (d + 2) / 6;
     const int m = mask == MASK_TERMS ? 19 : mask == MASK_COUPLED ? 17 : mask;      // u, grad u, trace; u and the trace
     return ((m & 1) ? c : 0) + ((m & 2) ? d * c : 0) + ((m & 4) ? nf * c : (m & 16) ? c : 0) + ((m & 8) ? n3 * c : 0) +
-           ((m & MASK_RESIDUAL) ? c : 0) + ((m == MASK_VORTICITY || m == MASK_VORT_RESIDUAL) ? 7 : 0) +
+           ((m & MASK_RESIDUAL) ? c : 0) + ((m == MASK_VORTICITY || m == MASK_VORT_RESIDUAL || m == MASK_VORT_FIT) ? 7 : 0) +
            (m == MASK_NET_INPUTS ? 5 * c : m == MASK_NET_INPUTS_NS ? 13 : 0);      // u, grad u, u_xx, u_yy; + w_x, w_y, lap w
 }
 

@@ -15,13 +15,14 @@ constexpr int MASK_TERMS = 64;                // the general residual, [M][c] --
 constexpr int MASK_VORTICITY = 128;           // the vorticity terms (d = 2, c = 2), [M][7] -- pigs_vorticity_*
 constexpr int MASK_COUPLED = 256;             // the coupled residual (c >= 2), [M][c] -- pigs_residual_coupled_*
 constexpr int MASK_VORT_RESIDUAL = 512;       // the vorticity residual (d = 2, c = 2), [M][2] -- pigs_vorticity_residual_*
+constexpr int MASK_VORT_FIT = 4096;           // the vorticity residual + its data term, [M][3] -- pigs_vorticity_fit_*
 // the model's sample features (d = 2), [M][c], [M][2c], [M][2c], [M][p] in slots 0..3 -- pigs_network_inputs_forward
 constexpr int MASK_NET_INPUTS = 1024;         // the right-hand sides zero, diffusion, burgers, wave
 constexpr int MASK_NET_INPUTS_NS = 2048;      // Navier-Stokes (c = 2)
 inline bool is_network_inputs(int m) { return m == MASK_NET_INPUTS || m == MASK_NET_INPUTS_NS; }
 inline bool is_fused_output(int m) {
     return m == MASK_RESIDUAL || m == MASK_TERMS || m == MASK_VORTICITY || m == MASK_COUPLED || m == MASK_VORT_RESIDUAL ||
-           is_network_inputs(m);
+           m == MASK_VORT_FIT || is_network_inputs(m);
 }
 inline bool mask_valid(int m) { return m > 0 && m < 32 && !((m & 4) && (m & 16)); }
 inline bool mask_uses_slot(int m, int k) {
@@ -61,13 +62,20 @@ constexpr bool network_instance(int d, int c, int mask) {
     return d == 2 && (mask == MASK_NET_INPUTS || (mask == MASK_NET_INPUTS_NS && c == 2));
 }
 
+// the vorticity fit (d = 2, c = 2: dense_vort_instance): lists of its own, which the forward and the backward switches of
+// dense.hip and plan.hip expand beside PIGS_DENSE_VORT_MASKS / PIGS_BINNED_C2_MASKS
+#define PIGS_DENSE_FIT_MASKS(X) X(4096)
+#define PIGS_BINNED_FIT_MASKS(X) X(4096)
+
 #define PIGS_OR_MASK_IS(MK) || mask == (MK)
 constexpr bool dense_compiled(int d, int c, int mask) {
-    return (false PIGS_PLAIN_MASKS(PIGS_OR_MASK_IS)) || (dense_vort_instance(d, c) && (false PIGS_DENSE_VORT_MASKS(PIGS_OR_MASK_IS))) ||
+    return (false PIGS_PLAIN_MASKS(PIGS_OR_MASK_IS)) ||
+           (dense_vort_instance(d, c) && (false PIGS_DENSE_VORT_MASKS(PIGS_OR_MASK_IS) PIGS_DENSE_FIT_MASKS(PIGS_OR_MASK_IS))) ||
            (dense_coupled_instance(c) && (false PIGS_DENSE_COUPLED_MASKS(PIGS_OR_MASK_IS)));
 }
 constexpr bool binned_compiled(int c, int mask) {
-    return (c == 1 || c == 2) && ((false PIGS_PLAIN_MASKS(PIGS_OR_MASK_IS)) || (c == 2 && (false PIGS_BINNED_C2_MASKS(PIGS_OR_MASK_IS))));
+    return (c == 1 || c == 2) && ((false PIGS_PLAIN_MASKS(PIGS_OR_MASK_IS)) ||
+                                  (c == 2 && (false PIGS_BINNED_C2_MASKS(PIGS_OR_MASK_IS) PIGS_BINNED_FIT_MASKS(PIGS_OR_MASK_IS))));
 }
 constexpr bool fused_first_compiled(int c, int mask) {
     return c == 1 ? (false PIGS_FUSED_FIRST_C1_MASKS(PIGS_OR_MASK_IS)) : c == 2 ? (false PIGS_FUSED_FIRST_C2_MASKS(PIGS_OR_MASK_IS)) : false;

@@ -24,6 +24,7 @@ struct SampleArgs {
     const PigsResidualCoupling* coupling;      // MASK_COUPLED: coefficients, fields, the two matrices
     const PigsVorticityResidual* vort;         // MASK_VORT_RESIDUAL: coefficients, tau field; `target` = prev [M][7] or null,
                                                //   `aux` = [M][4] (the forward writes it, the backward reads it)
+    const PigsVorticityFit* fit;               // MASK_VORT_FIT: the same, and the data [M] with its weight
     const PigsNetworkInputs* net;              // MASK_NET_INPUTS, MASK_NET_INPUTS_NS: the right-hand side's kind and constants;
                                                //   the four arrays leave through out[0..3]
 };

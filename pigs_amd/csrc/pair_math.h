@@ -78,6 +78,13 @@ constexpr int ORDC_AS = ORD0 | ORD2T;
 // backward with the seven incoming gradients formed from gout[m][0..1], the coefficients and that record
 // (Gsym::load_vorticity_residual); prev is not read there.
 constexpr int ORDN = 512;
+// THE VORTICITY FIT (mask == ORDF, alone; D == 2, C == 2): the vorticity residual with the data term of the reference's
+// Navier-Stokes loop and of its initialisation fit (main_pn.py:202-212, test_initialize.py:131-136) as a third column,
+//   out[m][0..1] as for ORDN,   out[m][2] = data_weight (w - data[m])         (w of the CURRENT level, not blended)
+// from the same seven sums; data [M] is a constant.  Its backward is that of ORDN with the gradient that arrives at w
+// g_r time_term + g_f data_weight (Gsym::load_vorticity_fit); neither prev nor data is read there.
+constexpr int ORDF = 4096;
+constexpr bool is_vort_resid(int MASK) { return MASK == ORDN || MASK == ORDF; }
 // THE NETWORK INPUTS (mask == ORDI or ORDJ, alone; D == 2; forward only): the four arrays that the reference's
 // Model.forward hands to its dynamics network (model_pn.py:645-664), each through its own output slot,
 //   o0[m][ch]          = u                                   sample_u    [M][c]
@@ -103,7 +110,7 @@ inline NetIn<T> make_net_in(const ABI& t) {
     return NetIn<T>{t.kind, (T)t.nu, {(T)t.wave[0], (T)t.wave[1]}};
 }
 constexpr int bwd_mask_of(int MASK) {
-    return (MASK == ORDR || MASK == ORDG) ? ORDR_AS : (MASK == ORDV || MASK == ORDN) ? ORDV_AS : MASK == ORDC ? ORDC_AS : MASK;
+    return (MASK == ORDR || MASK == ORDG) ? ORDR_AS : (MASK == ORDV || is_vort_resid(MASK)) ? ORDV_AS : MASK == ORDC ? ORDC_AS : MASK;
 }
 
 template <typename T> struct Terms {
@@ -158,10 +165,25 @@ inline VortResid<T> make_vort_resid(const ABI& t, const void* prev, const void* 
     z.aux = (T*)const_cast<void*>(aux);
     return z;
 }
+// the vorticity fit: the vorticity residual's block, the data and its weight
+template <typename T> struct VortFit : VortResid<T> {
+    const T* data;                                  // [M]; read by the forward alone
+    T data_weight;
+};
+// host side: the block from the C ABI's PigsVorticityFit (include/pigs_amd.h) in the launch's type
+template <typename T, typename ABI>
+inline VortFit<T> make_vort_fit(const ABI& t, const void* prev, const void* aux, bool backward) {
+    VortFit<T> z{};
+    static_cast<VortResid<T>&>(z) = make_vort_resid<T>(t, prev, aux);
+    z.data = backward ? nullptr : (const T*)t.data;
+    z.data_weight = (T)t.data_weight;
+    return z;
+}
 // the coefficient block a kernel compiled for MASK receives
 template <typename T, int MASK>
 using RzOf = std::conditional_t<MASK == ORDG, Terms<T>, std::conditional_t<MASK == ORDC, Coupled<T>,
-             std::conditional_t<MASK == ORDN, VortResid<T>, std::conditional_t<is_net_inputs(MASK), NetIn<T>, Resid<T>>>>>;
+             std::conditional_t<MASK == ORDN, VortResid<T>, std::conditional_t<MASK == ORDF, VortFit<T>,
+             std::conditional_t<is_net_inputs(MASK), NetIn<T>, Resid<T>>>>>>;
 // host side: that block from a launcher's arguments (launch.h's SampleArgs; aux: the forward's output, the backward's
 // input; the target / previous level is read by the forward alone)
 template <typename T, int MASK, typename ARGS>
@@ -172,6 +194,8 @@ inline RzOf<T, MASK> rz_of(const ARGS& a, bool backward) {
         return make_coupled<T>(*a.coupling, backward ? nullptr : a.target);
     } else if constexpr (MASK == ORDN) {
         return make_vort_resid<T>(*a.vort, backward ? nullptr : a.target, a.aux);
+    } else if constexpr (MASK == ORDF) {
+        return make_vort_fit<T>(*a.fit, backward ? nullptr : a.target, a.aux, backward);
     } else if constexpr (is_net_inputs(MASK)) {
         return make_net_in<T>(*a.net);
     } else {
@@ -220,7 +244,7 @@ template <int D, int C, int MASK_> struct FwdLayout {
     static constexpr int O1 = O0 + ((MASK & ORD0) ? C : 0);
     static constexpr int O2 = O1 + ((MASK & ORD1) ? D * C : 0);
     static constexpr int O3 = O2 + ((MASK & ORD2) ? Sym<D>::NF * C : (MASK & ORD2T) ? C : 0);
-    static constexpr int N = O3 + ((MASK & ORD3) ? Sym<D>::N3 * C : 0) + ((MASK & ORDR) ? C : 0) + ((MASK == ORDV || MASK == ORDN) ? NVORT : 0) +
+    static constexpr int N = O3 + ((MASK & ORD3) ? Sym<D>::N3 * C : 0) + ((MASK & ORDR) ? C : 0) + ((MASK == ORDV || is_vort_resid(MASK)) ? NVORT : 0) +
                              (MASK == ORDI ? 5 * C : MASK == ORDJ ? NNETJ : 0);
     // the network inputs (D = 2): u, +sum p_i w, t_xx w, t_yy w per channel; ORDJ: w_x, w_y, lap w behind them
     static constexpr int IU = 0, IP = C, IXX = 3 * C, IYY = 4 * C, IW = 5 * C;
@@ -257,7 +281,7 @@ __device__ __forceinline__ void fwd_accumulate(T* acc, const T* s, const T* mu, 
         fwd_accumulate<T, D, C, ORDC_AS>(acc, s, mu, con, v);
         return;
     }
-    if constexpr (MASK == ORDN) {      // the seven sums of the vorticity terms, their `live` guard included
+    if constexpr (is_vort_resid(MASK)) {      // the seven sums of the vorticity terms, their `live` guard included
         fwd_accumulate<T, D, C, ORDV>(acc, s, mu, con, v);
         return;
     }
@@ -452,7 +476,7 @@ __device__ __forceinline__ void fwd_store(const T* acc, int64_t m, T* __restrict
         }
         return;
     }
-    if constexpr (MASK == ORDN) {
+    if constexpr (is_vort_resid(MASK)) {
         // the composing store: the point's tau and its row of the previous level meet the seven finished sums
         static_assert(D == 2 && C == 2, "the vorticity residual is that of a two-channel field in two dimensions");
         const T tau = rz->tau_pt ? rz->tau_pt[m] : rz->tau;
@@ -466,8 +490,16 @@ __device__ __forceinline__ void fwd_store(const T* acc, int64_t m, T* __restrict
         const T adv = fma_<T>(b[0], b[4], b[1] * b[5]);      // u_b . grad w_b
         const T r = fma_<T>(rz->time_term, acc[3] - pv[3], -rz->dt * fma_<T>(rz->nu, b[6], -adv));
         if constexpr (STREAM) asm volatile("" ::: "memory");      // as for ORDV below: keeps the hint
-        store_out<STREAM>(&o0[m * 2], b[2]);
-        store_out<STREAM>(&o0[m * 2 + 1], r);
+        if constexpr (MASK == ORDF) {
+            // three adjacent words; the point's data word is fetched here, after r, when prev's row is dead
+            const T fit = rz->data_weight * (acc[3] - rz->data[m]);
+            store_out<STREAM>(&o0[m * 3], b[2]);
+            store_out<STREAM>(&o0[m * 3 + 1], r);
+            store_out<STREAM>(&o0[m * 3 + 2], fit);
+        } else {
+            store_out<STREAM>(&o0[m * 2], b[2]);
+            store_out<STREAM>(&o0[m * 2 + 1], r);
+        }
         if (rz->aux) {
             T* ax = rz->aux + m * 4;
             store_out<STREAM>(&ax[0], b[0]);
@@ -762,6 +794,22 @@ template <typename T, int D, int C, int MASK> struct Gsym {
         T gv[NVORT];
         gv[0] = k * ax[2];      gv[1] = k * ax[3];
         gv[2] = gd * tau;       gv[3] = gr * vz.time_term;
+        gv[4] = k * ax[0];      gv[5] = k * ax[1];
+        gv[6] = -k * vz.nu;
+        form_vorticity(gv);
+    }
+    // the same for the vorticity fit's gout [M][3] = (g_d, g_r, g_f): w also receives g_f data_weight.  (Written out a
+    // second time: with the body shared, the ORDN backward kernels no longer compiled to the instructions they had.)
+    __device__ __forceinline__ void load_vorticity_fit(int64_t m, const T* __restrict__ GR, const VortFit<T>& vz) {
+        const T gd = GR[m * 3], gr = GR[m * 3 + 1], gf = GR[m * 3 + 2];
+        const T tau = vz.tau_pt ? vz.tau_pt[m] : vz.tau;
+        T ax[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) ax[q] = vz.aux ? vz.aux[m * 4 + q] : T(0);
+        const T k = gr * vz.dt * tau;
+        T gv[NVORT];
+        gv[0] = k * ax[2];      gv[1] = k * ax[3];
+        gv[2] = gd * tau;       gv[3] = fma_<T>(gf, vz.data_weight, gr * vz.time_term);
         gv[4] = k * ax[0];      gv[5] = k * ax[1];
         gv[6] = -k * vz.nu;
         form_vorticity(gv);

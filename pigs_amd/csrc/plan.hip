@@ -539,12 +539,13 @@ int plan_build(void* ws, size_t ws_bytes, void* sws, size_t sws_bytes, int flags
     return run_build(r, sws, sws_bytes, ws, ws_bytes, means, conics, values, samples, stream);
 }
 
-// a fused output whose coefficient block the caller left out (SampleArgs: terms, coupling, vort)
+// a fused output whose coefficient block the caller left out (SampleArgs: terms, coupling, vort, fit)
 static bool block_missing(int mask, const SampleArgs& a) {
     switch (mask) {
         case ORDG: return !a.terms;
         case ORDC: return !a.coupling;
         case ORDN: return !a.vort;
+        case ORDF: return !a.fit;
         case ORDI:
         case ORDJ: return !a.net;
         default: return false;
@@ -601,6 +602,7 @@ static int plan_forward_c(const PlanView& pv_in, const SamplesView& sv, int mask
     if constexpr (C == 2) {
         switch (mask) {
             PIGS_BINNED_C2_MASKS(PIGS_CASE)
+            PIGS_BINNED_FIT_MASKS(PIGS_CASE)
             default: break;
         }
     }
@@ -657,6 +659,7 @@ static int plan_backward_c(const PlanView& pv_in, const SamplesView& sv, int mas
     if constexpr (C == 2) {      // as in plan_forward_c
         switch (mask) {
             PIGS_BINNED_C2_MASKS(PIGS_CASE)
+            PIGS_BINNED_FIT_MASKS(PIGS_CASE)
             default: break;
         }
     }

@@ -218,6 +218,7 @@ __device__ __forceinline__ void load_tile_point(const SamplesView& sv, uint32_t 
     else if constexpr (MASK == ORDV) G.load_vorticity((int64_t)sp.m, G0p);
     else if constexpr (MASK == ORDC) G.load_coupled((int64_t)sp.m, G0p, rz);
     else if constexpr (MASK == ORDN) G.load_vorticity_residual((int64_t)sp.m, G0p, rz);
+    else if constexpr (MASK == ORDF) G.load_vorticity_fit((int64_t)sp.m, G0p, rz);
     else G.load((int64_t)sp.m, G0p, G1p, G2p, G3p);
     if (!valid) {
 #pragma unroll
@@ -366,6 +367,7 @@ __device__ __forceinline__ void backward_points_helper(const PlanView& pv, const
         else if constexpr (MASK == ORDV) G.load_vorticity((int64_t)sp.m, G0p);
         else if constexpr (MASK == ORDC) G.load_coupled((int64_t)sp.m, G0p, rz);
         else if constexpr (MASK == ORDN) G.load_vorticity_residual((int64_t)sp.m, G0p, rz);
+        else if constexpr (MASK == ORDF) G.load_vorticity_fit((int64_t)sp.m, G0p, rz);
         else G.load((int64_t)sp.m, G0p, G1p, G2p, G3p);
         // The walk in step over the whole wave (round 4): every lane meets its own (point, Gaussian) pair, and a pair's
         // NV sums leave as ONE atomic request -- lane = (pair, value), eight pairs per instruction, each a pair's 32-byte

@@ -426,7 +426,7 @@ std::array<at::Tensor, 3> periodic_images_apply(const at::Tensor& means, const a
 // ---------------------------------------------------------------------------------------------
 // The fused outputs -- residual() in its three forms, vorticity_terms(), vorticity_residual() -- each one launch
 // forward and one backward (pigs_residual_*, pigs_residual_terms_*, pigs_residual_coupled_*, pigs_vorticity_*,
-// pigs_vorticity_residual_*).  ONE node and ONE apply function serve them, told apart by a FusedOp; the node owns its
+// pigs_vorticity_residual_*, pigs_vorticity_fit_*).  ONE node and ONE apply function serve them, told apart by a FusedOp; the node owns its
 // inputs and plan like SampleBackward, plus the operator's coefficient fields and, where the backward reads one, the
 // record `aux` the forward left.
 // ---------------------------------------------------------------------------------------------
@@ -486,7 +486,22 @@ struct VorticityResidualHost {
     }
 };
 
-using FusedParams = std::variant<std::monostate, ResidualCoeffs, TermsHost, CouplingHost, VorticityResidualHost>;
+// the vorticity fit: the vorticity residual's coefficients, the data (which the node so keeps alive) and its weight
+struct VorticityFitHost {
+    VorticityResidualHost resid;
+    at::Tensor data;                                    // [M]: detached, contiguous, in the means' dtype
+    double data_weight = 1;
+    PigsVorticityFit abi() const {
+        PigsVorticityFit t{};
+        t.nu = resid.nu; t.dt = resid.dt; t.time_term = resid.time_term; t.tau = resid.tau;
+        t.data_weight = data_weight;
+        t.tau_pt = ptr(resid.tau_field);
+        t.data = ptr(data);
+        return t;
+    }
+};
+
+using FusedParams = std::variant<std::monostate, ResidualCoeffs, TermsHost, CouplingHost, VorticityResidualHost, VorticityFitHost>;
 
 // what one C call of a fused output receives
 struct FusedLaunch {
@@ -565,6 +580,18 @@ const FusedOp VORTICITY_RESIDUAL{
     [](const FusedParams& p, const FusedLaunch& l) {
         const PigsVorticityResidual t = std::get<VorticityResidualHost>(p).abi();
         return pigs_vorticity_residual_backward(PIGS_HEAD, &t, l.gout, l.aux, PIGS_GRADS, PIGS_TAIL);
+    }};
+// (div_b, r, data_weight (w - data)) as [M, 3]: vorticity_residual(data=...)
+const FusedOp VORTICITY_FIT{
+    "vorticity_residual()", "PigsVorticityFitBackward", "pigs_vorticity_fit_forward", "pigs_vorticity_fit_backward", 3, false,
+    [](const FusedParams&, int64_t M, int64_t, int64_t) { return std::vector<int64_t>{M, 4}; },
+    [](const FusedParams& p, const FusedLaunch& l) {
+        const PigsVorticityFit t = std::get<VorticityFitHost>(p).abi();
+        return pigs_vorticity_fit_forward(PIGS_HEAD, &t, l.side, l.out, l.aux, PIGS_TAIL);
+    },
+    [](const FusedParams& p, const FusedLaunch& l) {
+        const PigsVorticityFit t = std::get<VorticityFitHost>(p).abi();
+        return pigs_vorticity_fit_backward(PIGS_HEAD, &t, l.gout, l.aux, PIGS_GRADS, PIGS_TAIL);
     }};
 #undef PIGS_HEAD
 #undef PIGS_HEAD_DC
@@ -1215,6 +1242,17 @@ struct Core {
         return fused_apply(VORTICITY_RESIDUAL, means, values, conics, samples, t, prev, debug, plan_for(8));
     }
 
+    // the same with the data term as a third column; data: [M], validated, detached, contiguous, in the means' dtype
+    at::Tensor vorticity_fit(double nu, double dt, double time_term, double tau, const c10::optional<at::Tensor>& tau_field,
+                             const c10::optional<at::Tensor>& prev, const at::Tensor& data, double data_weight) {
+        require_inputs();
+        VorticityFitHost t;
+        t.resid.nu = nu; t.resid.dt = dt; t.resid.time_term = time_term; t.resid.tau = tau;
+        if (tau_field.has_value()) t.resid.tau_field = *tau_field;
+        t.data = data; t.data_weight = data_weight;
+        return fused_apply(VORTICITY_FIT, means, values, conics, samples, t, prev, debug, plan_for(8));
+    }
+
     // sample_u, sample_ux, sample_uxx, sample_pde (kind: PIGS_NET_*) as views of one allocation; forward only: no
     // autograd node, and the plan of the bound inputs as it stands (a forward-only one serves); Navier-Stokes takes
     // the order-3 plan where there is one
@@ -1382,7 +1420,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("vorticity_terms", &Core::vorticity_terms)
         .def("vorticity_residual", &Core::vorticity_residual, py::arg("nu"), py::arg("dt"), py::arg("time_term"), py::arg("tau"),
              py::arg("tau_field") = c10::optional<at::Tensor>(), py::arg("prev") = c10::optional<at::Tensor>())
-        // (underscored: tests/test_host_cpu.py pins the set of public core names; the facade's network_inputs() drives it)
+        // (underscored: tests/test_host_cpu.py pins the set of public core names; the facade's vorticity_residual(data=) and
+        // network_inputs() drive them)
+        .def("_vorticity_fit", &Core::vorticity_fit, py::arg("nu"), py::arg("dt"), py::arg("time_term"), py::arg("tau"),
+             py::arg("tau_field"), py::arg("prev"), py::arg("data"), py::arg("data_weight"))
         .def("_network_inputs", &Core::network_inputs, py::arg("kind"), py::arg("nu"), py::arg("wave0"), py::arg("wave1"))
         .def("preprocess_aggregate", &Core::preprocess_aggregate, py::arg("cap") = -1)
         .def("aggregate_neighbors", &Core::aggregate_neighbors)

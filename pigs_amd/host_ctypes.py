@@ -16,6 +16,8 @@ TRACE = 4       # order index of the Hessian's trace (mask bit 16); it travels i
 VORTICITY_COLUMNS = ("u_x", "u_y", "div", "w", "w_x", "w_y", "lap_w")
 # the columns of GaussianSampler.vorticity_residual(): the blended divergence and the vorticity equation's residual
 VORTICITY_RESIDUAL_COLUMNS = ("div", "r")
+# the columns of GaussianSampler.vorticity_residual(data=...): the same two and the weighted data term
+VORTICITY_FIT_COLUMNS = ("div", "r", "fit")
 # the right-hand sides of GaussianSampler.network_inputs(), in the order of the C ABI's PIGS_NET_* codes
 NETWORK_PDES = ("zero", "diffusion", "burgers", "wave", "navier_stokes")
 _NET_WAVE, _NET_NAVIER_STOKES = NETWORK_PDES.index("wave"), NETWORK_PDES.index("navier_stokes")
@@ -518,6 +520,20 @@ class VorticityResidual:
                                           self.tau.data_ptr() if field else None)
 
 
+class VorticityFit(VorticityResidual):
+    """The coefficients of a vorticity_residual(data=...) call: those of :class:`VorticityResidual`, the detached device
+    array ``data`` [M] (which the node so keeps alive; only the forward reads it) and its weight."""
+
+    def __init__(self, nu, dt, time_term, tau, data, data_weight):
+        super().__init__(nu, dt, time_term, tau)
+        self.data, self.data_weight = data, data_weight
+
+    def struct(self):
+        field = isinstance(self.tau, torch.Tensor)
+        return _lib.PigsVorticityFit(self.nu, self.dt, self.time_term, 0.0 if field else self.tau, self.data_weight,
+                                     self.tau.data_ptr() if field else None, self.data.data_ptr())
+
+
 class _ResidualFunction(_FusedFunction):
     """r = a0 u + a1 . grad u + aL lap u - target."""
     op = _FusedOp("residual()", "pigs_residual")
@@ -546,6 +562,13 @@ class _VorticityResidualFunction(_FusedFunction):
     """(div_b, r) of the Navier-Stokes residual as [M, 2]; ``side`` = the previous level's vorticity terms (a constant),
     ``aux`` = the blended u and grad w of the forward, which the backward of the advection term reads."""
     op = _FusedOp("vorticity_residual()", "pigs_vorticity_residual", width=len(VORTICITY_RESIDUAL_COLUMNS), dims=False,
+                  has_target=False, aux_shape=lambda params, M, d, c: (M, 4))
+
+
+class _VorticityFitFunction(_FusedFunction):
+    """(div_b, r, data_weight (w - data)) as [M, 3]: the vorticity residual with the data term from the same sums;
+    ``side`` and ``aux`` as there, the data travels in ``params``."""
+    op = _FusedOp("vorticity_residual()", "pigs_vorticity_fit", width=len(VORTICITY_FIT_COLUMNS), dims=False,
                   has_target=False, aux_shape=lambda params, M, d, c: (M, 4))
 
 
@@ -846,6 +869,10 @@ class SamplerCore:
     def vorticity_residual(self, nu, dt, time_term, tau, tau_field=None, prev=None):
         params = VorticityResidual(nu, dt, time_term, tau if tau_field is None else tau_field)
         return self._fused(_VorticityResidualFunction, 8, prev, params, want_aux=self._needs_backward())
+
+    def _vorticity_fit(self, nu, dt, time_term, tau, tau_field, prev, data, data_weight):
+        params = VorticityFit(nu, dt, time_term, tau if tau_field is None else tau_field, data, data_weight)
+        return self._fused(_VorticityFitFunction, 8, prev, params, want_aux=self._needs_backward())
 
     def _network_inputs(self, kind, nu, wave0, wave1):
         """sample_u, sample_ux, sample_uxx, sample_pde as views of one allocation; forward only, no autograd node."""

@@ -30,8 +30,8 @@ import os
 import torch
 
 from . import _lib, host_ctypes
-from .host_ctypes import (NETWORK_PDES, TRACE, VORTICITY_COLUMNS, VORTICITY_RESIDUAL_COLUMNS, backward_raw,  # noqa: F401
-                          forward_raw, network_pde_width)
+from .host_ctypes import (NETWORK_PDES, TRACE, VORTICITY_COLUMNS, VORTICITY_FIT_COLUMNS,  # noqa: F401
+                          VORTICITY_RESIDUAL_COLUMNS, backward_raw, forward_raw, network_pde_width)
 
 # what GaussianSampler.network_inputs() returns: the four arrays of the reference's Model.forward (model_pn.py:650-664)
 NetworkInputs = collections.namedtuple("NetworkInputs", ("sample_u", "sample_ux", "sample_uxx", "sample_pde"))
@@ -466,7 +466,7 @@ class GaussianSampler:
         INTEGRATION.md has the Navier-Stokes recipe; DESIGN.md 13 the measured times."""
         return self._core.vorticity_terms()
 
-    def vorticity_residual(self, nu, dt, prev=None, tau=1.0, *, time_term=1.0):
+    def vorticity_residual(self, nu, dt, prev=None, tau=1.0, *, time_term=1.0, data=None, data_weight=1.0):
         """Extension of the reference API: the Navier-Stokes residual of the reference's flagship problem (a periodic
         box in the vorticity formulation, ``compute_loss`` for ``Problem.NAVIER_STOKES``: model_pn.py:794-818, 629-631,
         830, 848-849) as ONE tensor [M, 2] with the columns ``pigs_amd.VORTICITY_RESIDUAL_COLUMNS`` = ``(div, r)``, in one
@@ -486,7 +486,16 @@ class GaussianSampler:
         and c = 2 only.  Binned plans run it on the order-3 plan (``q_max_order3``), the backward with the wide cut-off.
         The result is not cached: its arguments vary from call to call.  INTEGRATION.md 3 has the recipe (two calls
         and one line of loss); DESIGN.md 15 the kernels (the step's time against the same loss composed from
-        ``vorticity_terms()`` has not been measured yet: ``tools/bench_vorticity.py`` times the two side by side)."""
+        ``vorticity_terms()`` has not been measured yet: ``tools/bench_vorticity.py`` times the two side by side).
+
+        ``data`` ([M] or [M, 1] on the device; a constant, treated as ``tau`` is) adds the data term of the reference's
+        Navier-Stokes loop (main_pn.py:202-212) from the same sums in the same launch: the result is [M, 3] with the
+        columns ``pigs_amd.VORTICITY_FIT_COLUMNS`` = ``(div, r, fit)``, ``fit = data_weight * (w_now - data)`` with the
+        vorticity of the CURRENT level.  With ``data_weight = sqrt(5)`` the step loss including ``recon_loss`` is
+        ``out.pow(2).mean(0).sum()``; ``vorticity_residual(0.0, 0.0, None, 1.0, time_term=0.0, data=...)`` is the loss
+        of the initialisation fit (test_initialize.py:135-136), its column 1 exact zeros.  ``pigs_amd.grid_lookup``
+        makes ``data`` from an image in one launch.  There is no gradient with respect to ``data``, and the backward
+        does not read it."""
         means, values, conics, samples = self._require_inputs()
         d, c, M = means.shape[1], values.shape[1], samples.shape[0]
         if d != 2 or c != 2:
@@ -505,6 +514,12 @@ class GaussianSampler:
             prev = prev.detach().to(means.dtype).contiguous()
         nu, dt, time_term = float(nu), float(dt), float(time_term)
         field = f_tau if isinstance(f_tau, torch.Tensor) else None
+        if data is not None:
+            if not isinstance(data, torch.Tensor):
+                raise RuntimeError("data must be a tensor on the sampler's device (no CPU fallback)")
+            data = self._residual_field("data", data, 1)
+            return self._core._vorticity_fit(nu, dt, time_term, 0.0 if field is not None else f_tau, field, prev, data,
+                                             float(data_weight))
         return self._core.vorticity_residual(nu, dt, time_term, 0.0 if field is not None else f_tau, field, prev)
 
     def network_inputs(self, pde, nu=0.0, wave=(10.0, 0.1)):
