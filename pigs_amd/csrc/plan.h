@@ -483,6 +483,13 @@ __device__ __forceinline__ void store_through(uint32_t* a, I i, uint32_t v, bool
     if (through) __hip_atomic_store(&a[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     else a[i] = v;
 }
+// ... at a wave-uniform base plus a 32-bit byte offset: `global_store_dword v_off, v_data, s[base:base+1]`, the base in
+// scalar registers and no 64-bit address formed per lane (the forward-only appends of the list launch, plan_lists.h)
+__device__ __forceinline__ void store_through_at(uint32_t* base, uint32_t byte_off, uint32_t v, bool through) {
+    uint32_t* p = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(base) + byte_off);
+    if (through) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    else *p = v;
+}
 
 // ---- grid geometry derived (identically by every thread) from the sample bounding box ----
 

@@ -229,7 +229,7 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
     }
     int sn = 0;
     // one step's accepted survivors of tile t (this lane: sorted index j, wide mask gm, narrow mask gf; zero: none)
-    // appended to the tile's list and its four group lists
+    // appended to the tile's list and its four group lists (full plans: the tile list's entries hold the masks)
     auto append = [&](int t, uint32_t j, uint32_t gm, uint32_t gf) __attribute__((always_inline)) {
         uint32_t* tl = a.tlist + (size_t)(tile0 + (uint32_t)t) * cap;
         uint32_t* gl = a.glist + (size_t)(tile0 + (uint32_t)t) * 4 * cap;
@@ -254,6 +254,25 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
             }
             ng[t][g] += cg;
         }
+    };
+    // A forward-only plan writes no tile list, so nothing needs the masks: one step's accepted survivors of ONE group
+    // go to list g of tile t at once.  pass: this lane's compare; have: this lane holds a survivor of this step, and
+    // live: the ballot of that.  The ballot of a bare compare is the compare's own scalar result, the count comes from
+    // it, the position is v_mbcnt, and one v_add_lshl joins it to the list's place in the block's lists and its running
+    // count, both scalar (v_mbcnt takes the mask from a scalar register, and one instruction reads one: the addend
+    // cannot ride in it): the store takes the block's base in scalar registers and a 32-bit byte offset (16 lists of
+    // cap words).  Groups go to different lists, so their order among each other is free; within a list the entries
+    // keep the survivors' order.  The capacity rule is append's: what would pass cap is counted and not stored.  t
+    // and g are compile-time constants wherever this is called, and the counts are wave-uniform: ng stays in SGPRs.
+    auto append_group = [&](int t, int g, bool pass, bool have, uint64_t live, uint32_t j) __attribute__((always_inline)) {
+        uint32_t* gl = a.glist + (size_t)tile0 * 4 * cap;
+        const uint64_t mg = __ballot(pass) & live;
+        const uint32_t cg = (uint32_t)__builtin_popcountll(mg);
+        const uint32_t first = (uint32_t)(4 * t + g) * cap + ng[t][g];      // (read before the count moves: one register per count)
+        ng[t][g] += cg;       // (no flag: the counts only grow, so goverflow[t] is read off them after the last flush)
+        const bool fits = ng[t][g] <= cap;
+        const uint32_t at = __builtin_amdgcn_mbcnt_hi((uint32_t)(mg >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mg, 0u));
+        if (fits && pass && have) store_through_at(gl, (at + first) << 2, j, through);
     };
     // the tiles' tests on the survivors in LDS, general path: per tile, (A) the survivors that reach the tile's
     // box, compacted (their positions, one byte each would do: 128 survivors), then (B) the four
@@ -285,17 +304,29 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
                 Ellipse e;
                 e.x = A.x; e.y = A.y; e.a = A.z; e.b = A.w; e.c = B.x; e.nb_c = B.y; e.nb_a = B.z;
                 const uint32_t j = __builtin_bit_cast(uint32_t, B.w);
-                uint32_t gm = 0, gf = 0;       // wide (tile list, backward) and narrow (group lists, forward) masks
+                if constexpr (FWD_ONLY) {      // no masks: each group's ballot from its compare, appended at once
+                    const bool in = s0 + lane < sel;
+                    const uint64_t live = __ballot(in);
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float qmin = ellipse_min_q_rect(e, gb[g].x, gb[g].y, gb[g].z, gb[g].w);
-                    if (!FWD_ONLY && !(qmin > pv.q_max)) gm |= 1u << g;
-                    if (!(qmin > a.q_f)) gf |= 1u << g;
+                    for (int g = 0; g < 4; ++g) {
+                        const float qmin = ellipse_min_q_rect(e, gb[g].x, gb[g].y, gb[g].z, gb[g].w);
+                        // (a group without a point has an inverted box, never needed: the ragged last tile alone)
+                        const bool held = (has[t] >> g & 1u) != 0u;      // wave-uniform
+                        append_group(t, g, !(qmin > a.q_f), in && held, held ? live : 0ull, j);
+                    }
+                } else {
+                    uint32_t gm = 0, gf = 0;       // wide (tile list, backward) and narrow (group lists, forward) masks
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const float qmin = ellipse_min_q_rect(e, gb[g].x, gb[g].y, gb[g].z, gb[g].w);
+                        if (!(qmin > pv.q_max)) gm |= 1u << g;
+                        if (!(qmin > a.q_f)) gf |= 1u << g;
+                    }
+                    // a group without a point has an inverted box, never needed: the ragged last tile alone (wave-uniform)
+                    if (has[t] != 15u) { gm &= has[t]; gf &= has[t]; }
+                    if (s0 + lane >= sel) gm = gf = 0u;
+                    append(t, j, gm, gf);
                 }
-                // a group without a point has an inverted box, never needed: the ragged last tile alone (wave-uniform)
-                if (has[t] != 15u) { gm &= has[t]; gf &= has[t]; }
-                if (s0 + lane >= sel) gm = gf = 0u;
-                append(t, j, gm, gf);
             }
             wave_lds_fence();
         }
@@ -313,39 +344,63 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
             const float4 A = lds.sa[k], B = lds.sb[k];
             const uint32_t j = __builtin_bit_cast(uint32_t, B.w);
             const float ea = A.z, ec = B.x, b2 = 2.f * A.w;
-            uint32_t gm = 0, gf = 0;
-            // Loops, not unrolled (rows and columns are wave-uniform): a fraction of the code and of the registers.  A
-            // full plan, whose wave holds more beside the flush, takes the rows two at a time -- the columns' terms
-            // are then formed once per pair, 28 instructions more per step, for 10 registers fewer.
-            constexpr int RP = FWD_ONLY ? NI : 2;           // rows per pass
-#pragma nounroll
-            for (int r0 = 0; r0 < NI; r0 += RP) {
-                AxisTerms Y[RP];
+            if constexpr (FWD_ONLY) {
+                // No masks: the group in column c and row r is list g = (c & 1) + 2 (r & 1) of tile t = 2 (c >> 1) +
+                // (r >> 1) (bit 4 t + g of the masks below), and the compare's own ballot appends its entries.  Rows
+                // and columns unrolled: the running counts are indexed by constants.
+                const uint64_t live = __ballot(have);
+                // (the intervals are read again in every step: hoisted out of this loop, the 16 of them stay in
+                // vector registers across the walk -- 80 -> 86 VGPRs here, scratch in the cells' instantiation)
+                asm volatile("" ::: "memory");
+                AxisTerms Y[NI];
 #pragma unroll
-                for (int rr = 0; rr < RP; ++rr) {
-                    const float4 d = lds.gbox[diagonal(r0 + rr)];
-                    Y[rr] = axis_terms(A.y, ec, b2, B.z, d.y, d.w);
+                for (int r = 0; r < NI; ++r) {
+                    const float4 d = lds.gbox[diagonal(r)];
+                    Y[r] = axis_terms(A.y, ec, b2, B.z, d.y, d.w);
                 }
-#pragma nounroll
+#pragma unroll
                 for (int c = 0; c < NI; ++c) {
                     const float4 d = lds.gbox[diagonal(c)];
                     const AxisTerms X = axis_terms(A.x, ea, b2, B.y, d.x, d.z);
-                    uint32_t wide = 0, narrow = 0;
 #pragma unroll
-                    for (int rr = 0; rr < RP; ++rr) {
-                        const float qmin = min_q_of_terms(X, Y[rr], ea, ec);
-                        const int bit = 4 * (rr >> 1) + 2 * (rr & 1);
-                        if (!FWD_ONLY && !(qmin > pv.q_max)) wide |= 1u << bit;
-                        if (!(qmin > a.q_f)) narrow |= 1u << bit;
+                    for (int r = 0; r < NI; ++r) {
+                        const bool pass = !(min_q_of_terms(X, Y[r], ea, ec) > a.q_f);
+                        append_group(2 * (c >> 1) + (r >> 1), (c & 1) + 2 * (r & 1), pass, have, live, j);
                     }
-                    // group (column c, row r): tile 2 (c >> 1) + (r >> 1), group (c & 1) + 2 (r & 1); r0 is even
-                    const int shift = 8 * (c >> 1) + (c & 1) + 4 * (r0 >> 1);
-                    gm |= wide << shift; gf |= narrow << shift;
                 }
-            }
-            if (!have) gm = gf = 0u;
+            } else {
+                uint32_t gm = 0, gf = 0;
+                // Loops, not unrolled (rows and columns are wave-uniform): a fraction of the code and of the registers.
+                // A full plan's wave holds more beside the flush, so it takes the rows two at a time -- the columns'
+                // terms are then formed once per pair, 28 instructions more per step, for 10 registers fewer.
+#pragma nounroll
+                for (int r0 = 0; r0 < NI; r0 += 2) {
+                    AxisTerms Y[2];
 #pragma unroll
-            for (int t = 0; t < TPW; ++t) append(t, j, gm >> (4 * t) & 15u, gf >> (4 * t) & 15u);
+                    for (int rr = 0; rr < 2; ++rr) {
+                        const float4 d = lds.gbox[diagonal(r0 + rr)];
+                        Y[rr] = axis_terms(A.y, ec, b2, B.z, d.y, d.w);
+                    }
+#pragma nounroll
+                    for (int c = 0; c < NI; ++c) {
+                        const float4 d = lds.gbox[diagonal(c)];
+                        const AxisTerms X = axis_terms(A.x, ea, b2, B.y, d.x, d.z);
+                        uint32_t wide = 0, narrow = 0;
+#pragma unroll
+                        for (int rr = 0; rr < 2; ++rr) {
+                            const float qmin = min_q_of_terms(X, Y[rr], ea, ec);
+                            if (!(qmin > pv.q_max)) wide |= 1u << 2 * rr;
+                            if (!(qmin > a.q_f)) narrow |= 1u << 2 * rr;
+                        }
+                        // group (column c, row r): tile 2 (c >> 1) + (r >> 1), group (c & 1) + 2 (r & 1); r0 is even
+                        const int shift = 8 * (c >> 1) + (c & 1) + 4 * (r0 >> 1);
+                        gm |= wide << shift; gf |= narrow << shift;
+                    }
+                }
+                if (!have) gm = gf = 0u;
+#pragma unroll
+                for (int t = 0; t < TPW; ++t) append(t, j, gm >> (4 * t) & 15u, gf >> (4 * t) & 15u);
+            }
         }
         wave_lds_fence();
         sn = 0;
@@ -366,7 +421,11 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
         // filter and the group tests in two portions, twice the steps of one; a walk that finds them in batches of ~25,
         // four strips of 16 candidates, more often still).
         const int add = __builtin_popcountll(mask);
-        if (sn + add > SURV_CAP) flush();
+        // (forward-only: unlikely, said aloud -- its unrolled flush wants many scalar registers, and without the hint the
+        // walk's own loop counters were the ones kept in lanes of a vector register, 80 VALU instructions per wave;
+        // full plans and the fused launch compile as they did without it)
+        const bool full = sn + add > SURV_CAP;
+        if (FWD_ONLY ? __builtin_expect(full, false) : full) flush();
         if (mask >> lane & 1ull) {
             const Ellipse e = ellipse_of(A, B.x);
             const int k = sn + lanes_below(mask);
@@ -376,6 +435,11 @@ __device__ __forceinline__ void build_block_lists(const ListArgs& a, ListsLds<TP
         sn += add;
     });
     if (sn > 0) flush();
+    if constexpr (FWD_ONLY) {
+        // an append that did not fit left its list's count above cap, and nothing else can: counts only grow
+#pragma unroll
+        for (int t = 0; t < TPW; ++t) goverflow[t] = ng[t][0] > cap || ng[t][1] > cap || ng[t][2] > cap || ng[t][3] > cap;
+    }
 
     // A tile list that does not fit while the four group lists do (64 scattered points of a sparse
     // region share few Gaussians: up to 4 x cap distinct ones) is no reason to give the lists up: the
